@@ -1,7 +1,7 @@
 """
 bench.py -- BASELINE.json metric: MCTS simulations/s (whole job) and self-play steps/s, CartPole & Connect4.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one rank per GPU over RCCL: either the driver launches this file under
 ``python -m torch.distributed.run --nproc-per-node N ...`` or, when started as plain ``python bench.py --gpus N``,
@@ -10,30 +10,35 @@ the script re-executes itself that way (the reference spawns its N self-play wor
 One "step" = one pass of the hot path over one batch of synthetic input: B independent roots, each doing
 initial_inference + num_simulations x {select, recurrent_inference, expand, backpropagate} (one self-play move
 per tree, self_play.py:144-150).  Default workload = BASELINE config C2: CartPole FullyConnectedNetwork, 4096
-trees x 50 simulations per GPU; the same invocation also measures the Connect4 half of the metric (C4: Connect4
-ResNet, 1024 trees x 200 simulations per GPU, the configuration BASELINE.json shards over 8 GPUs) and reports it
-under ``workloads``.  Inputs (stacked observations, legal actions, Dirichlet noise, tie tape, weights) are
+trees x 50 simulations per GPU; with ``--full`` the same invocation also measures the Connect4 half of the metric (C4:
+Connect4 ResNet, 1024 trees x 200 simulations per GPU, the configuration BASELINE.json shards over 8 GPUs) and reports
+it under ``workloads``.  Inputs (stacked observations, legal actions, Dirichlet noise, tie tape, weights) are
 resident in HBM before the timed region; every rank owns an independent shard of trees (weak scaling, no
 data-path collective; RCCL only broadcasts the flat weight buffer, outside the timed region, as the reference's
 weight pull self_play.py:37).
+
+A plain run is the headline figure alone: set-up, W warm-up steps, ONE timed block of exactly K steps, the line.
+``--dump-outputs DIR`` then writes what the last timed step returned (rank 0's shard) as DIR/<name>.npy.  ``--full``
+adds every side measurement below that is marked [full]: they take runs of their own.
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "roofline"      algorithmic tree bytes (SURVEY.md section 8d formula, with the measured mean leaf depth) /
                   HIP-event time of the search launch, vs the HBM peak (residual networks: network FLOPs vs the
                   dense FP32-input MFMA peak)
-  "workloads"     the other BASELINE configurations (C3, C4 = the Connect4 half of the metric, C5), C2 on the reference's
+  "workloads"     [full] the other BASELINE configurations (C3, C4 = the Connect4 half of the metric, C5), C2 on the reference's
                   shipped checkpoint, and the reference's games/gomoku.py / games/atari.py as shipped, measured in this
                   invocation -- compact entries: w workload, v sims/s (median block; min / max beside it), ms per step, B
                   trees, S simulations, L mean leaf depth, k the search kernel (+ its shape), roofline {bound, achieved
                   (TFLOP/s | GB/s), frac, traffic (PMC HBM bytes per step | null), launch_ms}
-  "per_rank" / "single_gpu_reference"   N > 1: every rank's own rate, and rank 0 timed alone just before
-  "selfplay_end_to_end*"  self-play steps/s through the plugin surface (N = 1)
-  "selfplay_actor_loop"   continuous_self_play itself, batched protocol: play_rounds + initial PER priorities (td_steps 50) +
+  "per_rank" / "single_gpu_reference"   N > 1: every rank's own rate, and [full] rank 0 timed alone just before
+  "repeats"       the timed blocks (plain run: 1; [full]: 25 for blocks under 0.1 s, fewer for long ones, the median reported)
+  "selfplay_end_to_end*"  [full] self-play steps/s through the plugin surface (N = 1)
+  "selfplay_actor_loop"   [full] continuous_self_play itself, batched protocol: play_rounds + initial PER priorities (td_steps 50) +
                           save_game of every finished game, in-process storage (N = 1)
-  "observation_stacker"   the path's HBM-bound kernel (mzx_obs_stack, atari geometry) against the HBM peak
-  "cpu_baseline"  kind "reference": the UNMODIFIED reference MCTS(config).run + models.py (oracle/_ref, compiled
-                  from /root/reference by oracle/build_ref.py) on this box's host cores, bounded sample (kind "port": the
-                  CPU oracle oracle/*.py, when the bytecode did not travel).
+  "observation_stacker"   [full] the path's HBM-bound kernel (mzx_obs_stack, atari geometry) against the HBM peak
+  "cpu_baseline"  [full] kind "reference": the UNMODIFIED reference MCTS(config).run + models.py (oracle/_ref, compiled
+                  from the reference tree by oracle/build_ref.py) on up to 15 host cores of this job, bounded sample
+                  (kind "port": the CPU oracle oracle/*.py, when the bytecode did not travel); null in a plain run.
 Weights: the reference constructor's under torch.manual_seed(0) (--weights synthetic = rounds 1-4's).
 N > 1 validates itself: after the RCCL broadcast every rank's flat buffer has rank 0's checksum, and one search on
 rank-independent inputs builds the same trees on every rank -- or the run fails ("collective" in the line).
@@ -105,26 +110,35 @@ WORKLOADS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the main workload (per timed block)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the other workloads, the self-play legs, the observation "
+                         "stacker, the CPU baselines, repeated timed blocks and (N > 1) rank 0 timed alone.  Without it the run "
+                         "times exactly --steps steps of the main workload and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step of the main workload computed (rank 0's "
+                         "shard) as DIR/<name>.npy, float64")
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--also", default=None,
                     help="comma list of further workloads measured in the same invocation and reported under "
-                         "'workloads' (default: c4 when the main workload is c2; 'none' = skip)")
+                         "'workloads' (default: none; with --full, DEFAULT_ALSO when the main workload is c2; 'none' = skip)")
     ap.add_argument("--also-steps", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=None,
-                    help="timed blocks of exactly --steps steps each (default: 25 for blocks shorter than 0.1 s, fewer for "
-                         "long ones); the line's value is the MEDIAN block, min / max are reported beside it")
+                    help="timed blocks of exactly --steps steps each (default: 1; with --full, 25 for blocks shorter than 0.1 s, "
+                         "fewer for long ones); the line's value is the MEDIAN block, min / max are reported beside it")
     ap.add_argument("--trees", type=int, default=None, help="trees per GPU (default: the workload's)")
     ap.add_argument("--mode", default="auto", choices=["auto", "generic", "fused", "fused-v1"],
                     help="fused-v1: first-generation fully connected whole-search kernel (A/B; instrumented builds only)")
     ap.add_argument("--net-mode", default="fused", choices=["fused", "fused-4wave", "per-operator", "streamed"],
                     help="residual networks: fused MFMA engine (default) or one kernel per operator")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall budget of each CPU baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="wall budget of each CPU baseline leg (0 = skip; default: 0, with --full 10)")
     ap.add_argument("--cpu-cores", type=int, default=None)
-    ap.add_argument("--selfplay-moves", type=int, default=32,
+    ap.add_argument("--selfplay-moves", type=int, default=None,
                     help="moves per game of the end-to-end self-play legs (SelfPlay(num_games=B) on the synthetic game; "
-                         "0 = skip); the games of the path's configurations run for hundreds of moves (cartpole: 500)")
+                         "0 = skip; default: 0, with --full 32); the games of the path's configurations run for hundreds "
+                         "of moves (cartpole: 500)")
     ap.add_argument("--weights", default="reference", choices=["reference", "synthetic"],
                     help="reference: torch.manual_seed(0); models.MuZeroNetwork(config) of the UNMODIFIED reference (oracle/_ref "
                          "bytecode; SURVEY.md section 8d); synthetic: mzx.synthetic.fill_state_dict(seed 0), rounds 1-4's weights")
@@ -132,7 +146,15 @@ def parse():
                     help="name=value,... entries of the library's tuning table (include/mzx.h) for this run (A/B measurements)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CI plumbing check on the CPU (gloo + tests/hostcheck); not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    # a plain run does what the headline figure needs and nothing else; --full restores every side measurement
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 10.0 if args.full else 0.0
+    if args.selfplay_moves is None:
+        args.selfplay_moves = 32 if args.full else 0
+    if args.repeats is None and not args.full:
+        args.repeats = 1
+    return args
 
 
 # ----------------------------------------------------------------------------- launch (N > 1)
@@ -381,6 +403,21 @@ def _search_baseline_entry(res, cores, seconds, kind):
     }
 
 
+# spawned CPU-baseline workers at most: with this process, no more than 16 processes that may hold the GPU at once
+MAX_CPU_WORKERS = 15
+
+
+def _host_cores():
+    """Host cores this job may use: the affinity mask, bounded by OMP_NUM_THREADS where the launcher sets it (a shared
+    node's os.cpu_count() is the whole machine's, not this job's)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS") or n))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def cpu_baselines(workload, seconds, cores, kind, weights_kind="reference", c4=False, steps_moves=0):
     """
     The CPU legs BASELINE.md section 3 names, timed on this box's host cores in one pool: `workload`'s MCTS.run (the line's
@@ -389,7 +426,7 @@ def cpu_baselines(workload, seconds, cores, kind, weights_kind="reference", c4=F
     synthetic C2 game and on whole connect4 games).  Baselines only (a large GPU / CPU ratio says nothing about kernel
     quality).  Returns {"cpu_baseline": ..., "cpu_baseline_c4": ..., "cpu_baseline_steps": ...}.
     """
-    cores = cores or min(os.cpu_count() or 1, 64)
+    cores = min(cores or _host_cores(), MAX_CPU_WORKERS)
     worker = _cpu_worker_reference if kind == "reference" else _cpu_worker_port
     jobs = [(worker, [(workload, w, seconds, weights_kind) for w in range(cores)])]
     extra = kind == "reference"
@@ -608,11 +645,25 @@ def _checksum(t):
     return int(w.sum().item()), int((w * (idx % 65521)).sum().item())
 
 
+def dump_outputs(out_dir, out):
+    """What one search step hands its caller (mzx.search.SearchResult: visit counts by action, root values, root predicted
+    values, the per-tree info words), one float64 .npy per array -- every tree of the shard, so two builds compare output
+    for output.  The inputs of a given set of arguments are seeded: identical from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    info = out["info"].cpu().numpy()
+    arrays = {"visit_counts": out["visits"].cpu().numpy(), "root_values": out["root_value"].cpu().numpy(),
+              "root_predicted_values": out["predicted"].cpu().numpy(), "max_tree_depth": info[:, 0],
+              "flags": info[:, 1], "tape_used": info[:, 2], "sum_depth": info[:, 3]}
+    for name, a in arrays.items():
+        numpy.save(os.path.join(out_dir, name + ".npy"), numpy.ascontiguousarray(a, dtype=numpy.float64))
+
+
 # ----------------------------------------------------------------------------- the search workload
-def run_search_workload(env, args, workload, steps, warmup, trees=None, solo_reference=False, compact=False):
+def run_search_workload(env, args, workload, steps, warmup, trees=None, solo_reference=False, compact=False, dump_dir=None):
     """
     Times `steps` passes of the hot path of `workload` on every rank (contract bracket: barrier +
     synchronize on both sides, MAX over ranks).  Returns (rank-0 result dict, cfg, net).
+    dump_dir: rank 0 writes what the last timed step returned to its caller there (dump_outputs).
     """
     from mzx import configs, models, self_play, shared_storage, synthetic
 
@@ -774,6 +825,8 @@ def run_search_workload(env, args, workload, steps, warmup, trees=None, solo_ref
     elapsed, own_elapsed, launch_ms, gathered = blocks[order[len(order) // 2]]
     per_rank = [B * S * steps / t for t in gathered]
     block_rates = [world * B * S * steps / b[0] for b in blocks]
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, sets[(steps - 1) % n_sets][1])
 
     # sanity: the timed work is real (every tree ran S simulations, no flags)
     for _, out, _ in sets[: 0 if tuning.get("rt_dbg") else min(n_sets, max(steps, warmup, 1))]:
@@ -912,11 +965,11 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={env.world}")
     also = args.also
     if also is None:
-        also = DEFAULT_ALSO if (args.workload == DEFAULT_WORKLOAD and not args.dry_run and args.trees is None) else "none"
+        also = DEFAULT_ALSO if (args.full and args.workload == DEFAULT_WORKLOAD and not args.dry_run and args.trees is None) else "none"
     also = [w for w in also.split(",") if w and w != "none"]
 
     line, cfg, net = run_search_workload(env, args, args.workload, args.steps, args.warmup, args.trees,
-                                         solo_reference=True)
+                                         solo_reference=args.full, dump_dir=args.dump_outputs)
     others = []
     c4_net = None
     for w in also:

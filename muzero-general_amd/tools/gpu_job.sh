@@ -5,7 +5,7 @@
 #   rt-first     tests of rt_search_kernel, then connect4 whole steps by shard size on the three routes
 #   c4-shards    connect4 whole steps by shard size (routes: rt_search_kernel, per-simulation launches, rz_search_kernel)
 #   tests        the -m gpu suite + smoke
-#   bench        the default bench line (as the driver runs it) + rocprofv3 kernel stats of the same command
+#   bench        the --full bench line (every side measurement) + rocprofv3 kernel stats of the same command
 #   pmc          PMC passes (separate --pmc runs: FETCH_SIZE, WRITE_SIZE, MFMA-busy) of every default workload's search
 #   final        tests + bench + pmc
 JOB=${1:?job}
@@ -13,7 +13,7 @@ TAG=${2:-$JOB}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-Q="--also none --cpu-seconds 0 --selfplay-moves 0"
+Q="--full --also none --cpu-seconds 0 --selfplay-moves 0"
 
 c4_shards() {   # trees...
   for t in "$@"; do
@@ -36,9 +36,9 @@ run_tests() {
 }
 
 run_bench() {
-  timeout 900 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
+  timeout 900 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
   echo "bench rc $?" >> $OUT/bench_default.err
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench/stats -o run -- python bench.py --cpu-seconds 0 --selfplay-moves 0 > $OUT/rocprof_bench_stats.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench/stats -o run -- python bench.py --full --cpu-seconds 0 --selfplay-moves 0 > $OUT/rocprof_bench_stats.log 2>&1
   python muzero-general_amd/tools/rocprof_summary.py $OUT/bench > $OUT/summary_bench.txt 2>&1
   tail -c 1500 $OUT/bench_default.log
 }
@@ -71,8 +71,8 @@ one() {   # label, bench arguments...: one line per run
 }
 
 case $JOB in
-  bench-only)      # the default bench line as the driver runs it; size of the line
-    timeout 900 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
+  bench-only)      # the --full bench line; size of the line
+    timeout 900 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
     echo "bench rc $?" >> $OUT/bench_default.err
     tail -3 $OUT/bench_default.err
     wc -c $OUT/bench_default.log
@@ -341,7 +341,7 @@ print('cpu', d['cpu_baseline']['value'], d['cpu_baseline']['kind'], d['cpu_basel
     timeout ${MOVE_TEST_S:-300} python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "${MOVE_TESTS:-refilled or batched_shard_of_4096 or whole_game or pipelined_shard}" > $OUT/pytest_move.log 2>&1
     echo "pytest rc $?" >> $OUT/pytest_move.log
     grep -E "passed|failed|^FAILED|^ERROR|Error|rc " $OUT/pytest_move.log | tail -12
-    timeout 400 python bench.py ${MOVE_BENCH_ARGS---also c4 --cpu-seconds 0} > $OUT/bench_selfplay.log 2> $OUT/bench_selfplay.err
+    timeout 400 python bench.py --full ${MOVE_BENCH_ARGS---also c4 --cpu-seconds 0} > $OUT/bench_selfplay.log 2> $OUT/bench_selfplay.err
     echo "bench rc $?" >> $OUT/bench_selfplay.err
     tail -3 $OUT/bench_selfplay.err
     python -c "
@@ -356,8 +356,8 @@ for k in d:
       head -40 $OUT/host_profile_batched.txt
     fi
     ;;
-  last)      # HEAD's evidence in one short call: the default bench line, then smoke + the whole -m gpu suite
-    timeout 300 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
+  last)      # HEAD's evidence in one short call: the --full bench line, then smoke + the whole -m gpu suite
+    timeout 600 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
     echo "bench rc $?" >> $OUT/bench_default.err
     wc -c $OUT/bench_default.log
     run_tests

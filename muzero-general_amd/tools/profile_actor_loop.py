@@ -11,9 +11,9 @@ import bench  # noqa: E402
 
 from mzx import configs, models  # noqa: E402
 
-if len(sys.argv) > 1:      # e.g. "atari gomoku": run these search workloads first, as the default bench line does
+if len(sys.argv) > 1:      # e.g. "atari gomoku": run these search workloads first, as the --full bench line does
     after = sys.argv[1:]
-    sys.argv = ["bench.py"]
+    sys.argv = ["bench.py", "--full"]
     args = bench.parse()
     env = bench.Env(args)
     for w in after:

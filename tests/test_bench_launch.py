@@ -29,7 +29,7 @@ def _run(argv, env_extra=None):
 
 
 def test_bench_self_launches_two_ranks():
-    line = _run(["--gpus", "2", "--dry-run", "--trees", "8", "--steps", "2", "--warmup", "1", "--selfplay-moves", "0",
+    line = _run(["--gpus", "2", "--dry-run", "--full", "--trees", "8", "--steps", "2", "--warmup", "1", "--selfplay-moves", "0",
                  "--also", "c3", "--also-steps", "1"])
     # every workload of a multi-GPU run reports every rank's own time per step (the first real 8-GPU run yields the scaling
     # of the CartPole AND the residual workloads in one go)
@@ -91,3 +91,24 @@ def test_bench_large_shard_workload_labels_what_ran():
     assert cfg["trees_per_gpu"] == 4 and "4 trees x 200 sims" in cfg["workload"] and "9216" not in cfg["workload"]
     assert cfg["search_kernel"] == "one kernel per operator"      # (the test double has no tuned kernels)
     assert line["roofline"]["bound"] == "mfma" and line["roofline"]["traffic"] is None     # PMC entry is for the default shard
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """A plain run is the headline alone: one timed block of exactly --steps steps, no side legs; --dump-outputs writes
+    what the last timed step returned, float64, the same on every run with the same arguments."""
+    argv = ["--dry-run", "--trees", "6", "--steps", "3", "--warmup", "1"]
+    lines = [_run(argv + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["repeats"]["n"] == 1 and line["repeats"]["steps_per_block"] == 3
+        assert line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+        assert "workloads" not in line and not any(k.startswith("selfplay") for k in line)
+    import numpy
+
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in ("visit_counts", "root_values", "root_predicted_values", "max_tree_depth",
+                                                "flags", "tape_used", "sum_depth"))
+    for n in names:
+        a, b = numpy.load(tmp_path / "a" / n), numpy.load(tmp_path / "b" / n)
+        assert a.dtype == numpy.float64 and a.shape[0] == 6 and numpy.array_equal(a, b), n
+    visits = numpy.load(tmp_path / "a" / "visit_counts.npy")
+    assert visits.shape == (6, 2) and (visits.sum(1) == 50).all()
