@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 1
+#define MZX_ABI_VERSION 2
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -334,6 +334,56 @@ typedef struct mzx_tree_dump {
   int32_t* d_child; double* d_prior; double* d_minmax; int32_t* d_n_nodes;
 } mzx_tree_dump;
 int mzx_search_dump(mzx_search* s, const mzx_tree_dump* dump, void* d_arena, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Continued searches: MCTS.run(..., override_root_with=node) (self_play.py:260-361) on a node that already carries
+ * visits and expanded descendants -- a child of the previous move's root (tree reuse) or the same root searched again
+ * (anytime budgets).  Semantics: the reference's, bit for bit:
+ *   - the new tree holds exactly the subtree under the chosen node, renumbered in creation order (increasing old
+ *     canonical index, the new root at 0); the leaf expanded by continued simulation k gets index n_carried + k;
+ *     every carried node keeps visit count, value sum, reward, to_play, its children's priors and its hidden state;
+ *   - a carried non-root node was expanded over the whole action space: the new root has A children in action order;
+ *   - Dirichlet noise (io->d_noise, one value per root child in slot order) is mixed into the children's existing
+ *     priors; MinMaxStats starts empty; max_tree_depth counts from the new root; root_predicted_value is NaN;
+ *   - io->d_to_play must equal the carried root's to_play.
+ *
+ * mzx_search_set_capacity: node slots per tree = max_nodes (>= num_simulations + 1) and the pb_c / sqrt tables for
+ *   visit counts 0 .. max_nodes - 1 (max_nodes entries each, same definition as in mzx_search_config).  Re-plans the
+ *   arena (mzx_search_arena_bytes grows) and forgets what earlier calls left in any arena.  A handle with spare
+ *   capacity runs mzx_search_run on the routes that keep every node's hidden state in the arena (the per-operator path,
+ *   or the streamed row route launch by launch), never on an LDS-resident whole-search kernel.
+ * mzx_search_advance: tree i -> the subtree under root action d_actions[i] (-1: the old root itself), read from the trees
+ *   and hidden states the PRECEDING search call of this handle left in d_src_arena (the arena persists between these
+ *   calls, as for mzx_search_dump), written to d_dst_arena (another arena of the same size).  MZX_ERR_INVALID when that
+ *   call's route does not leave every node's hidden state in d_src_arena (mzx_search_kernel_name names it), or when the
+ *   arenas are the same.  An action that names no expanded child keeps the old root and sets flag 4 in the continued
+ *   search's io->d_info[1].
+ * mzx_search_load: imports B trees built elsewhere (host arrays in canonical order, parents before children, `max_nodes`
+ *   node slots per tree; slot s of the root is root action h_root_actions[i][s], of any other node action s).
+ *   Synchronises the stream.  MZX_ERR_INVALID for an inconsistent tree or one that cannot take num_simulations more.
+ * mzx_search_run_continued: num_simulations simulations on the trees mzx_search_advance / mzx_search_load put into
+ *   d_arena (io->d_observation and io->d_legal_actions are not read).  Reads the carried node counts back (one stream
+ *   synchronisation) and fails with MZX_ERR_INVALID when carried nodes + num_simulations + 1 exceed the capacity or when
+ *   io->d_to_play differs from a carried root's to_play.  On a handle without a network it prepares the roots (noise,
+ *   meta words, MinMaxStats) and returns: the caller drives mzx_search_lockstep_select / _apply / mzx_search_finish.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_tree_load {
+  int32_t max_nodes;               /* node slots per tree in the arrays below */
+  const int32_t* h_visit;          /* [B][max_nodes] */
+  const double* h_value_sum;       /* [B][max_nodes] */
+  const double* h_reward;          /* [B][max_nodes] */
+  const int32_t* h_to_play;        /* [B][max_nodes] */
+  const int32_t* h_parent;         /* [B][max_nodes], -1 for the root */
+  const int32_t* h_child;          /* [B][max_nodes][A] child node of each slot, -1 = not expanded */
+  const double* h_prior;           /* [B][max_nodes][A] prior of each slot */
+  const float* h_hidden;           /* [B][max_nodes][hidden_size] */
+  const int32_t* h_n_nodes;        /* [B] */
+  const int32_t* h_root_actions;   /* [B][A] actions of the root's children in slot order, padded with -1 */
+} mzx_tree_load;
+int mzx_search_set_capacity(mzx_search* s, int32_t max_nodes, const double* h_pb_c_table, const double* h_sqrt_table);
+int mzx_search_advance(mzx_search* s, const int32_t* d_actions, void* d_src_arena, void* d_dst_arena, void* stream);
+int mzx_search_load(mzx_search* s, const mzx_tree_load* trees, void* d_arena, void* stream);
+int mzx_search_run_continued(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_t arena_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Observation pipeline on the device (csrc/mzx_obs.h).

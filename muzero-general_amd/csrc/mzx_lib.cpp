@@ -12,6 +12,7 @@
 #include "mzx_replay.h"
 #include "mzx_rng.h"
 #include "mzx_search.h"
+#include "mzx_tree_carry.h"
 #ifndef MZX_HOSTCHECK
 #include "mzx_fused_fc.h"
 #include "mzx_fused_fc2.h"
@@ -444,14 +445,15 @@ static void search_route_of(const mzx_search* s, int32_t out[8]) {
 #ifndef MZX_HOSTCHECK
   if (!s->net) return;
   int whole = 0;
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true)) {
+  const bool spare = s->max_nodes > 0;
+  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
     const int route = wide_search_route(s);
     out[0] = route == ROUTE_RZ ? 1 : (route == ROUTE_ROWS ? 2 : 3);
     whole = route == ROUTE_RT;
-  } else if ((s->mode & 1) && s->fused_ok == 1) {
+  } else if ((s->mode & 1) && s->fused_ok == 1 && !spare) {
     out[0] = 4;
   } else if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
-    whole = streamed_whole_search(s);
+    whole = !spare && streamed_whole_search(s);
     out[0] = whole ? 3 : 2;
   }
   if (whole) rt_search_shape(s, out + 1);      // out[1 .. 6]
@@ -522,13 +524,15 @@ int mzx_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_
     set_error("mzx_search_run: missing io buffer");
     return MZX_ERR_INVALID;
   }
+  s->hidden_arena = s->carried_arena = nullptr;
+  const bool spare = s->max_nodes > 0;     // a handle with spare node capacity keeps every node's hidden state in the arena
 #ifndef MZX_HOSTCHECK
-  if ((s->mode & 1) && s->fused_ok == 1)
+  if ((s->mode & 1) && s->fused_ok == 1 && !spare)
   {
     s->last_kernel = (s->mode & 16) ? "mzx::fused_fc_search" : "mzx::fc2_search_kernel";
     return (s->mode & 16) ? fused_fc_run(s, io, d_arena, (stream_t)stream) : fc2_run(s, io, d_arena, (stream_t)stream);
   }
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true)) {
+  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
     // a wide network: the tower arithmetic at every shard size (wide_search_route, mzx_row_search.h) -- all simulations in
     // one launch of rt_search_kernel, or the trunks as towers between the row-per-tree kernels
     const int route = wide_search_route(s);
@@ -541,14 +545,19 @@ int mzx_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_
   if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
     s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
     // (renames last_kernel when it runs two half-shards or the whole-search kernel)
-    return search_run_rows(s, io, d_arena, (stream_t)stream, nullptr, false, streamed_whole_search(s));
+    const bool whole = !spare && streamed_whole_search(s);
+    rc = search_run_rows(s, io, d_arena, (stream_t)stream, nullptr, false, whole);
+    if (!rc && !whole) s->hidden_arena = d_arena;
+    return rc;
   }
 #endif
   s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
 #ifndef MZX_HOSTCHECK
   if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
 #endif
-  return search_run_generic(s, io, d_arena, (stream_t)stream);
+  rc = search_run_generic(s, io, d_arena, (stream_t)stream);
+  if (!rc) s->hidden_arena = d_arena;
+  return rc;
 }
 
 int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const float* d_root_hidden,
@@ -563,15 +572,17 @@ int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const floa
   }
   RootOverride ov;
   ov.hidden = d_root_hidden; ov.priors = d_root_priors; ov.reward = d_root_reward;
+  s->hidden_arena = s->carried_arena = nullptr;
+  const bool spare = s->max_nodes > 0;
 #ifndef MZX_HOSTCHECK
   // the simulations run on the kernel mzx_search_run would use: the residual whole-search kernels read the roots from
   // the arena, the fully connected one (second generation) takes them as launch arguments instead of running
   // initial_inference; the first-generation kernel (flag 16, A/B only) stays on the per-operator path here
-  if ((s->mode & 1) && s->fused_ok == 1 && !(s->mode & 16)) {
+  if ((s->mode & 1) && s->fused_ok == 1 && !(s->mode & 16) && !spare) {
     s->last_kernel = "mzx::fc2_search_kernel";
     return fc2_run(s, io, d_arena, (stream_t)stream, &ov);
   }
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true)) {
+  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
     const int route = wide_search_route(s);
     if (route != ROUTE_RZ) {
       s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
@@ -581,11 +592,16 @@ int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const floa
   }
   if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
     s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-    return search_run_rows(s, io, d_arena, (stream_t)stream, &ov, false, streamed_whole_search(s));
+    const bool whole = !spare && streamed_whole_search(s);
+    rc = search_run_rows(s, io, d_arena, (stream_t)stream, &ov, false, whole);
+    if (!rc && !whole) s->hidden_arena = d_arena;
+    return rc;
   }
 #endif
   s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
-  return search_run_generic(s, io, d_arena, (stream_t)stream, &ov);
+  rc = search_run_generic(s, io, d_arena, (stream_t)stream, &ov);
+  if (!rc) s->hidden_arena = d_arena;
+  return rc;
 }
 
 int mzx_search_lockstep_begin(mzx_search* s, const mzx_search_io* io, const double* d_root_priors,
@@ -593,6 +609,8 @@ int mzx_search_lockstep_begin(mzx_search* s, const mzx_search_io* io, const doub
   int rc = check_search_call(s, d_arena, arena_bytes, false);
   if (rc) return rc;
   if (!io || !io->d_legal_actions || !io->d_to_play || !d_root_priors) { set_error("lockstep_begin: missing buffer"); return MZX_ERR_INVALID; }
+  s->carried_arena = nullptr;
+  s->hidden_arena = s->net ? nullptr : d_arena;    // (a handle without a network carries trees alone)
   rc = ensure_tables(s, d_arena, (stream_t)stream);
   if (rc) return rc;
   const ArenaView v = arena_view(s, d_arena);
@@ -645,6 +663,167 @@ int mzx_search_dump(mzx_search* s, const mzx_tree_dump* dump, void* d_arena, voi
   op.arena = v.arena; op.p = v.p; op.d = *dump;
   MZX_TRY_LAUNCH(launch<64>(op, (stream_t)stream));
   return MZX_OK;
+}
+
+// ------------------------------------------------------- continued searches (mzx_tree_carry.h)
+
+int mzx_search_set_capacity(mzx_search* s, int32_t max_nodes, const double* h_pb_c_table, const double* h_sqrt_table) {
+  if (!s || !h_pb_c_table || !h_sqrt_table) { set_error("mzx_search_set_capacity: null argument"); return MZX_ERR_INVALID; }
+  if (max_nodes < s->cfg.num_simulations + 1 || max_nodes > (1 << 24)) {
+    set_error("mzx_search_set_capacity: max_nodes %d must lie in num_simulations + 1 (%d) .. 2^24", max_nodes,
+              s->cfg.num_simulations + 1);
+    return MZX_ERR_INVALID;
+  }
+  std::vector<double> pbc(h_pb_c_table, h_pb_c_table + max_nodes), sq(h_sqrt_table, h_sqrt_table + max_nodes);
+  pbc.push_back(0.0);
+  sq.push_back(0.0);
+  double* old = s->d_tables;
+  const int32_t old_nodes = s->max_nodes;
+  s->h_pbc.swap(pbc);
+  s->h_sqrt.swap(sq);
+  s->max_nodes = max_nodes;
+  search_plan(s);
+  s->d_tables = nullptr;
+  if (int rc = upload_tables(s)) {       // keep the handle as it was
+    s->h_pbc.swap(pbc);
+    s->h_sqrt.swap(sq);
+    s->max_nodes = old_nodes;
+    search_plan(s);
+    s->d_tables = old;
+    return rc;
+  }
+  if (old) device_free(old);
+  s->hidden_arena = s->carried_arena = nullptr;
+  s->rt_plan_key[0] = -1;
+  return MZX_OK;
+}
+
+int mzx_search_advance(mzx_search* s, const int32_t* d_actions, void* d_src_arena, void* d_dst_arena, void* stream) {
+  int rc = check_search_call(s, d_dst_arena, -1, false);
+  if (rc) return rc;
+  if (!d_actions || !d_src_arena) { set_error("mzx_search_advance: null argument"); return MZX_ERR_INVALID; }
+  if (d_src_arena == d_dst_arena) { set_error("mzx_search_advance: the source and destination arenas must differ"); return MZX_ERR_INVALID; }
+  if (s->off_carry < 0) { set_error("mzx_search_advance: the handle has no node capacity for carried trees (mzx_search_set_capacity)"); return MZX_ERR_INVALID; }
+  if (!s->hidden_arena || s->hidden_arena != d_src_arena) {
+    set_error("mzx_search_advance: the last search of this handle did not leave every node's hidden state in d_src_arena "
+              "(route: %s)", s->last_kernel[0] ? s->last_kernel : "none yet");
+    return MZX_ERR_INVALID;
+  }
+  const ArenaView src = arena_view(s, d_src_arena), dst = arena_view(s, d_dst_arena);
+  TreeAdvanceArgs a;
+  a.p = src.p; a.L = s->L;
+  a.src_trees = src.arena.trees; a.dst_trees = dst.arena.trees;
+  a.src_hidden = src.arena.hidden; a.dst_hidden = dst.arena.hidden;
+  a.scratch = (int32_t*)((char*)d_dst_arena + s->off_rowpath);     // 2 N + 2 ints per tree: the row kernels' path store
+  a.actions = d_actions;
+  a.carry = (int32_t*)((char*)d_dst_arena + s->off_carry);
+  MZX_TRY_LAUNCH(tree_advance_launch(a, (stream_t)stream));
+  s->hidden_arena = s->carried_arena = d_dst_arena;
+  return MZX_OK;
+}
+
+int mzx_search_load(mzx_search* s, const mzx_tree_load* h, void* d_arena, void* stream) {
+  int rc = check_search_call(s, d_arena, -1, false);
+  if (rc) return rc;
+  if (!h || !h->h_visit || !h->h_value_sum || !h->h_reward || !h->h_to_play || !h->h_parent || !h->h_child || !h->h_prior ||
+      !h->h_n_nodes || !h->h_root_actions || (s->p.hidden_size > 0 && !h->h_hidden)) {
+    set_error("mzx_search_load: missing array");
+    return MZX_ERR_INVALID;
+  }
+  if (s->off_carry < 0) { set_error("mzx_search_load: the handle has no node capacity for carried trees (mzx_search_set_capacity)"); return MZX_ERR_INVALID; }
+  const int B = s->p.num_trees, N = s->p.num_nodes, M = h->max_nodes;
+  const int64_t Hf = s->p.hidden_size;
+  if (M < 1) { set_error("mzx_search_load: max_nodes must be positive"); return MZX_ERR_INVALID; }
+  std::vector<char> image((size_t)s->L.tree_bytes * B);
+  std::vector<int32_t> carry((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    const int nn = h->h_n_nodes[b];
+    if (nn < 1 || nn > M || nn + s->p.num_sims + 1 > N) {
+      set_error("mzx_search_load: tree %d has %d nodes; %d node slots given, capacity %d for %d more simulations", b, nn, M, N,
+                s->p.num_sims);
+      return MZX_ERR_INVALID;
+    }
+    TreeRef t;
+    t.base = image.data() + (size_t)b * s->L.tree_bytes;
+    t.L = s->L;
+    if (pack_loaded_tree(t, s->p, *h, b)) {
+      set_error("mzx_search_load: tree %d is not a canonical-order tree this handle can continue (parents before children, "
+                "child links matching parents, visit counts + num_simulations below the capacity)", b);
+      return MZX_ERR_INVALID;
+    }
+    carry[2 * b] = nn;
+    carry[2 * b + 1] = t.to_play(0);
+  }
+  const ArenaView v = arena_view(s, d_arena);
+  const stream_t st = (stream_t)stream;
+  MZX_TRY_LAUNCH(copy_h2d(v.arena.trees, image.data(), image.size(), st));
+  MZX_TRY_LAUNCH(copy_h2d((char*)d_arena + s->off_carry, carry.data(), carry.size() * sizeof(int32_t), st));
+  if (Hf > 0) {
+    for (int b = 0; b < B; ++b)
+      MZX_TRY_LAUNCH(copy_h2d(v.arena.hidden + (int64_t)b * N * Hf, h->h_hidden + (int64_t)b * M * Hf,
+                              sizeof(float) * Hf * h->h_n_nodes[b], st));
+  }
+  MZX_TRY_LAUNCH(stream_sync(st));      // (the host image is released on return)
+  s->hidden_arena = s->carried_arena = d_arena;
+  return MZX_OK;
+}
+
+int mzx_search_run_continued(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_t arena_bytes, void* stream) {
+  int rc = check_search_call(s, d_arena, arena_bytes, false);
+  if (rc) return rc;
+  const bool with_net = s->net != nullptr;
+  if (with_net && !s->net->d_flat) { set_error("search needs a network with bound weights"); return MZX_ERR_INVALID; }
+  if (!io || !io->d_to_play || (with_net && (!io->d_tape || !io->d_visit_counts || !io->d_root_value || !io->d_info))) {
+    set_error("mzx_search_run_continued: missing io buffer");
+    return MZX_ERR_INVALID;
+  }
+  if (!s->carried_arena || s->carried_arena != d_arena) {
+    set_error("mzx_search_run_continued: d_arena holds no carried trees (mzx_search_advance / mzx_search_load of this handle "
+              "put them there; a search call since then used them up)");
+    return MZX_ERR_INVALID;
+  }
+  const int B = s->p.num_trees, N = s->p.num_nodes, S = s->p.num_sims;
+  const stream_t st = (stream_t)stream;
+  std::vector<int32_t> carry((size_t)2 * B), tp((size_t)B);
+  MZX_TRY_LAUNCH(copy_d2h(carry.data(), (char*)d_arena + s->off_carry, carry.size() * sizeof(int32_t), st));
+  MZX_TRY_LAUNCH(copy_d2h(tp.data(), io->d_to_play, tp.size() * sizeof(int32_t), st));
+  MZX_TRY_LAUNCH(stream_sync(st));
+  for (int b = 0; b < B; ++b) {
+    if (carry[2 * b] + S + 1 > N) {
+      set_error("mzx_search_run_continued: tree %d carries %d nodes; with %d simulations it needs %d node slots, the handle has %d "
+                "(mzx_search_set_capacity)", b, carry[2 * b], S, carry[2 * b] + S + 1, N);
+      return MZX_ERR_INVALID;
+    }
+    if (carry[2 * b + 1] != tp[b]) {
+      set_error("mzx_search_run_continued: to_play %d of tree %d differs from its carried root's to_play %d", tp[b], b, carry[2 * b + 1]);
+      return MZX_ERR_INVALID;
+    }
+  }
+  const ArenaView v = arena_view(s, d_arena);
+  ContinueRootOp cr;
+  cr.arena = v.arena; cr.p = v.p; cr.noise = io->d_noise; cr.root_predicted_value = io->d_root_predicted_value;
+  MZX_TRY_LAUNCH(launch<64>(cr, st));
+  s->carried_arena = nullptr;
+  s->hidden_arena = d_arena;
+  if (!with_net) return MZX_OK;     // lock-step handle: the caller drives the simulations
+  s->hidden_arena = nullptr;
+#ifndef MZX_HOSTCHECK
+  // the streamed row route launch by launch (its arena holds every node's hidden state); every other network: the
+  // per-operator path (the whole-search kernels keep nodes in LDS and do not take carried trees)
+  if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
+    s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
+    rc = search_run_rows(s, io, d_arena, st, nullptr, false, false, true);
+    if (!rc) s->hidden_arena = d_arena;
+    return rc;
+  }
+#endif
+  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
+#ifndef MZX_HOSTCHECK
+  if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
+#endif
+  rc = search_run_generic(s, io, d_arena, st, nullptr, true);
+  if (!rc) s->hidden_arena = d_arena;
+  return rc;
 }
 
 // ------------------------------------------------------- observation pipeline

@@ -31,7 +31,7 @@ struct RowSearchArgs {
   const float* value;    // [B][F] logits of recurrent_inference
   const float* reward;   // [B][F]
   const float* policy;   // [B][A]
-  int32_t sim;           // simulations finished so far (= visit count of the root)
+  int32_t sim;           // simulations finished so far (= visit count of the root); -1: read the root's visit count (continued searches)
 };
 
 constexpr int ROWSEL_INTS = 64;
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(64) row_select_kernel(const RowSearchArgs a) {
   TreeRef t;
   t.base = a.trees + (size_t)tree * a.L.tree_bytes;
   t.L = a.L;
-  row_select_body<AW>(a.p, t, a.tape + (size_t)tree * a.p.tape_words, a.sim, sub, row, a.rowsel + (size_t)tree * ROWSEL_INTS,
+  row_select_body<AW>(a.p, t, a.tape + (size_t)tree * a.p.tape_words, a.sim >= 0 ? a.sim : t.visit(0), sub, row, a.rowsel + (size_t)tree * ROWSEL_INTS,
                       a.sel_parent + tree, a.sel_action + tree, a.sel_leaf + tree, a.rowpath + (size_t)tree * (a.p.num_nodes + 1));
 }
 
@@ -246,8 +246,9 @@ __global__ void __launch_bounds__(64) wave_select_kernel(const RowSearchArgs a) 
   load_state(t, st);
   int2* path = a.rowpath + (size_t)tree * (a.p.num_nodes + 1);
   const uint32_t* tape = a.tape + (size_t)tree * a.p.tape_words;
-  const RowSel sel = (a.p.num_actions <= 128) ? wave_select_wide<2>(t, a.p, tape, lane, a.sim, st, path)
-                                              : wave_select_wide<4>(t, a.p, tape, lane, a.sim, st, path);
+  const int sim = a.sim >= 0 ? a.sim : t.visit(0);
+  const RowSel sel = (a.p.num_actions <= 128) ? wave_select_wide<2>(t, a.p, tape, lane, sim, st, path)
+                                              : wave_select_wide<4>(t, a.p, tape, lane, sim, st, path);
   int32_t* rs = a.rowsel + (size_t)tree * ROWSEL_INTS;
   if (lane < FUSED_ROW) { rs[16 + 3 * lane] = sel.my_node; rs[17 + 3 * lane] = sel.my_parent; rs[18 + 3 * lane] = sel.my_pslot; }
   if (lane == 0) {
@@ -321,8 +322,11 @@ inline int wide_search_route(const mzx_search* s) {
   return streamed_whole_search(s) ? ROUTE_RT : ROUTE_ROWS;
 }
 
+// continued = true: the trees in the arena are carried trees whose roots ContinueRootOp prepared (mzx_tree_carry.h):
+// no initial_inference, no root expansion, and the walks read the root's visit count from the tree.
 inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream,
-                   const RootOverride* ov = nullptr, bool force_streamed = false, bool whole_search = false) {
+                   const RootOverride* ov = nullptr, bool force_streamed = false, bool whole_search = false,
+                   bool continued = false) {
   const ArenaView v = arena_view(s, d_arena);
   mzx_net* net = s->net;
   const int B = s->p.num_trees;
@@ -339,7 +343,7 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
   NetBuffers nb;
   nb.in = io->d_observation; nb.action = nullptr; nb.hidden = ix_init ? v.arena.hidden : v.dense_out;
   nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
-  if (!ov) {
+  if (!ov && !continued) {
     rc = run_network(net, false, nb, B, stream, ix_init ? &ix : nullptr);
     if (rc) return rc;
   }
@@ -350,8 +354,8 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
   ri.ext_priors = ov ? ov->priors : nullptr; ri.ext_root_reward = ov ? ov->reward : nullptr;
   ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
   ri.root_predicted_value = io->d_root_predicted_value;
-  MZX_TRY_LAUNCH(launch<64>(ri, stream));
-  if (ov || !ix_init) {
+  if (!continued) MZX_TRY_LAUNCH(launch<64>(ri, stream));
+  if (!continued && (ov || !ix_init)) {
     HiddenMoveOp mv;
     mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
     mv.dense = ov ? const_cast<float*>(ov->hidden) : v.dense_out; mv.node = nullptr; mv.to_arena = 1;
@@ -430,7 +434,7 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
     for (int k = 0; k < s->p.num_sims; ++k) {
       for (int h = 0; h < parts; ++h) {
         RowSearchArgs& a = as[h];
-        a.sim = k;
+        a.sim = continued ? -1 : k;
         MZX_TRY_LAUNCH(aw == 0 ? row_search_step<0>(a, streams[h]) : aw == 4 ? row_search_step<4>(a, streams[h]) : row_search_step<16>(a, streams[h]));
         const int nrc = run_network(net, true, nbs[h], count[h], streams[h], &ixs[h]);
         if (nrc) return nrc;

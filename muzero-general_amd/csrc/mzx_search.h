@@ -20,6 +20,7 @@ struct mzx_search {
   // arena carve (byte offsets)
   int64_t off_tables = 0, off_trees = 0, off_hidden = 0, off_dense_in = 0, off_dense_out = 0;
   int64_t off_value = 0, off_reward = 0, off_policy = 0, off_sel = 0, off_rowsel = 0, off_rowpath = 0, off_ws = 0, arena_bytes = 0;
+  int64_t off_carry = -1;   // carried node counts (handles with spare node capacity only)
   int64_t ws_floats = 0;
   // pbc[N+1] then sqrt[N+1] on the device: owned by the handle (uploaded once at create), NOT carved from the
   // caller's arena -- an arena may be cleared, freed or re-allocated at the same address between calls
@@ -38,6 +39,12 @@ struct mzx_search {
   // and reused by every move's search; owned by the handle
   mutable std::shared_ptr<void> rt_plan_cache;
   mutable int64_t rt_plan_key[4] = {-1, -1, -1, -1};
+  // continued searches (mzx_tree_carry.h): node slots per tree set by mzx_search_set_capacity (0: num_simulations + 1);
+  // the arena whose trees + hidden states of every node the last call left complete (null: none, e.g. after a
+  // whole-search kernel), and the arena mzx_search_advance / mzx_search_load last carried trees into
+  int32_t max_nodes = 0;
+  const void* hidden_arena = nullptr;
+  const void* carried_arena = nullptr;
 };
 
 namespace mzx {
@@ -46,7 +53,8 @@ inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
 
 inline void search_plan(mzx_search* s) {
   const mzx_search_config& c = s->cfg;
-  const int B = c.num_trees, N = c.num_simulations + 1, A = c.action_space_size;
+  const int B = c.num_trees, A = c.action_space_size;
+  const int N = s->max_nodes > c.num_simulations + 1 ? s->max_nodes : c.num_simulations + 1;
   const int F = 2 * c.support_size + 1;
   const int64_t Hf = s->net ? s->net->hidden_size : 0;
   s->L = TreeLayout::make(N, A);
@@ -69,6 +77,9 @@ inline void search_plan(mzx_search* s) {
   s->off_rowpath = o;   o += align256(int64_t(8) * B * (N + 1));   // ... and the whole path of a walk, (node, slot taken) per depth: paths beyond a row's 16 lanes
   s->ws_floats = s->net ? net_ws_per_sample(s->net) * (int64_t)B : 0;
   s->off_ws = o;        o += align256(int64_t(4) * s->ws_floats);
+  if (s->max_nodes > 0) {
+    s->off_carry = o;   o += align256(int64_t(8) * B);            // [B][2]: nodes carried, to_play of the carried root
+  }
   s->arena_bytes = o;
 }
 
@@ -140,8 +151,10 @@ struct RootOverride {
 };
 
 // Generic path: one kernel per operator (any network configuration).
+// continued = true: the trees in the arena are carried trees whose roots ContinueRootOp prepared (mzx_tree_carry.h):
+// no initial_inference, no root expansion.
 inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream,
-                              const RootOverride* ov = nullptr) {
+                              const RootOverride* ov = nullptr, bool continued = false) {
   const ArenaView v = arena_view(s, d_arena);
   mzx_net* net = s->net;
   const int B = s->p.num_trees;
@@ -157,7 +170,7 @@ inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_ar
   NetBuffers nb;
   nb.in = io->d_observation; nb.action = nullptr; nb.hidden = ix_init ? v.arena.hidden : v.dense_out;
   nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
-  if (!ov) {
+  if (!ov && !continued) {
     rc = run_network(net, false, nb, B, stream, ix_init ? &ix : nullptr);
     if (rc) return rc;
   }
@@ -167,11 +180,11 @@ inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_ar
   ri.ext_priors = ov ? ov->priors : nullptr; ri.ext_root_reward = ov ? ov->reward : nullptr;
   ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
   ri.root_predicted_value = io->d_root_predicted_value;
-  MZX_TRY_LAUNCH(launch<64>(ri, stream));
+  if (!continued) MZX_TRY_LAUNCH(launch<64>(ri, stream));
 
   HiddenMoveOp mv;
   mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
-  if (ov || !ix_init) {
+  if (!continued && (ov || !ix_init)) {
     mv.dense = ov ? const_cast<float*>(ov->hidden) : v.dense_out; mv.node = nullptr; mv.to_arena = 1;
     MZX_TRY_LAUNCH(launch<256>(mv, stream));
   }

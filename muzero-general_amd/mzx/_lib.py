@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 1
+ABI_VERSION = 2
 MOVE_NO_SYNC = 1
 
 c_i32, c_i64, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
@@ -92,6 +92,15 @@ class TreeDump(ctypes.Structure):
     ]
 
 
+class TreeLoad(ctypes.Structure):
+    """``mzx_tree_load``: host arrays of B canonical-order trees imported by mzx_search_load."""
+    _fields_ = [
+        ("max_nodes", c_i32), ("h_visit", c_vp), ("h_value_sum", c_vp), ("h_reward", c_vp), ("h_to_play", c_vp),
+        ("h_parent", c_vp), ("h_child", c_vp), ("h_prior", c_vp), ("h_hidden", c_vp), ("h_n_nodes", c_vp),
+        ("h_root_actions", c_vp),
+    ]
+
+
 class ObsLayout(ctypes.Structure):
     _fields_ = [
         ("channels", c_i32), ("height", c_i32), ("width", c_i32), ("stacked_observations", c_i32),
@@ -151,6 +160,10 @@ PROTOTYPES = {
     "mzx_search_lockstep_apply": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_search_finish": (ctypes.c_int, [c_vp, ctypes.POINTER(SearchIO), c_vp, c_vp]),
     "mzx_search_dump": (ctypes.c_int, [c_vp, ctypes.POINTER(TreeDump), c_vp, c_vp]),
+    "mzx_search_set_capacity": (ctypes.c_int, [c_vp, c_i32, ctypes.POINTER(c_f64), ctypes.POINTER(c_f64)]),
+    "mzx_search_advance": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_search_load": (ctypes.c_int, [c_vp, ctypes.POINTER(TreeLoad), c_vp, c_vp]),
+    "mzx_search_run_continued": (ctypes.c_int, [c_vp, ctypes.POINTER(SearchIO), c_vp, c_i64, c_vp]),
     "mzx_obs_stacked_floats": (c_i64, [ctypes.POINTER(ObsLayout)]),
     "mzx_obs_stack": (ctypes.c_int, [ctypes.POINTER(ObsLayout), c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_support_to_scalar": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),

@@ -83,7 +83,7 @@ class BatchedMCTS:
 
     fused_move = True     # A/B switch of the tests: False = the separate calls (root_draws, _launch, advance, numpy select)
 
-    def __init__(self, config, model, max_trees, num_simulations=None, mode=None):
+    def __init__(self, config, model, max_trees, num_simulations=None, mode=None, max_carried_nodes=0):
         _validate(config)
         self.config = config
         self.model = model
@@ -101,6 +101,19 @@ class BatchedMCTS:
         self._arena = None
         self._mode = mode
         self._buffers = {}
+        # continued searches (continue_search / run_from_trees): node slots per tree = num_simulations + 1 + carried nodes
+        self.max_carried_nodes = int(max_carried_nodes)
+        if self.max_carried_nodes < 0:
+            raise ValueError("max_carried_nodes must be >= 0")
+        self.num_nodes = n + self.max_carried_nodes
+        if self.max_carried_nodes:
+            m = self.num_nodes
+            self._cap_pbc = (ctypes.c_double * m)(
+                *[math.log((k + config.pb_c_base + 1) / config.pb_c_base) + config.pb_c_init for k in range(m)]
+            )
+            self._cap_sqrt = (ctypes.c_double * m)(*[math.sqrt(k) for k in range(m)])
+        self._arena_alt = None     # the second arena of continue_search (the carried trees are copied across)
+        self._carry = None         # what the last search of the max_trees-independent handle left: see _note_searched
 
     def __del__(self):
         try:
@@ -130,6 +143,8 @@ class BatchedMCTS:
             lib.check(lib.mzx_search_create(ctypes.byref(c), net, ctypes.byref(h)))
             if self._mode is not None:
                 lib.check(lib.mzx_search_set_mode(h, int(self._mode)))
+            if self.max_carried_nodes:
+                lib.check(lib.mzx_search_set_capacity(h, self.num_nodes, self._cap_pbc, self._cap_sqrt))
             self._handles[key] = h
         return self._handles[key]
 
@@ -151,7 +166,7 @@ class BatchedMCTS:
         dict of numpy arrays visit [B][N], value_sum, reward, to_play, parent, child [B][N][A],
         prior, minmax [B][2], n_nodes [B].  With the fused kernel this needs mode flag 2.
         """
-        be, lib, B, N, A = self.backend, self.backend.lib, num_trees, self.num_simulations + 1, self.A
+        be, lib, B, N, A = self.backend, self.backend.lib, num_trees, self.num_nodes, self.A
         t = dict(
             visit=be.zeros((B, N), torch.int32), value_sum=be.zeros((B, N), torch.float64),
             reward=be.zeros((B, N), torch.float64), to_play=be.zeros((B, N), torch.int32),
@@ -222,16 +237,16 @@ class BatchedMCTS:
             raise ValueError("override_root_with: hidden_state does not match the network's encoded state")
         return self.run(None, legal, to_play, add_exploration_noise, rngs, _override=override)
 
-    def node_graph(self, num_trees, i, root_actions):
+    def node_graph(self, num_trees, i, root_actions, _trees=None):
         """
         Tree i of the last ``run`` as reference ``Node`` objects (self_play.py:433-476): children dicts keyed
         by action, visit_count / value_sum / prior / reward / to_play / hidden_state ([1, *hidden_shape]
         device tensor) per node -- what diagnose_model.py:145-192 walks.  Needs the per-operator engine
         (mode 0), whose arena holds every node's hidden state in canonical order.
         """
-        t = self.export_trees(num_trees)
+        t = self.export_trees(num_trees) if _trees is None else _trees     # (_trees: one export for many trees)
         off = self.arena_offsets(num_trees)
-        N, A, Hf = self.num_simulations + 1, self.A, self.model.hidden_size
+        N, A, Hf = self.num_nodes, self.A, self.model.hidden_size
         hid = self.arena(num_trees)[off["hidden"]: off["hidden"] + num_trees * N * Hf * 4].view(torch.float32)
         hid = hid.view(num_trees, N, Hf)[i].clone()
         n_nodes = int(t["n_nodes"][i])
@@ -239,6 +254,7 @@ class BatchedMCTS:
 
         def build(n, prior):
             node = Node(prior)
+            node.canonical_index = n       # creation order (run_from_trees keeps it when the graph comes back)
             node.visit_count = int(t["visit"][i, n])
             node.value_sum = float(t["value_sum"][i, n])
             node.to_play = int(t["to_play"][i, n])
@@ -261,6 +277,169 @@ class BatchedMCTS:
                 else:
                     nodes[n].children[a] = Node(prior)
         return root
+
+    # ---- continued searches: MCTS.run(..., override_root_with=node) on nodes that already carry visits and descendants
+    def _note_searched(self, B, root_actions, visits):
+        """The trees of the last search of handle(B) are in the arena, complete: a continue_search may start from them."""
+        self._carry = dict(B=B, root_actions=[list(a) for a in root_actions], visits=numpy.array(visits, copy=True))
+
+    def _require_capacity(self):
+        if not self.max_carried_nodes:
+            raise ValueError("continued searches need BatchedMCTS(..., max_carried_nodes=...) > 0")
+
+    def _root_draws(self, root_n, add_exploration_noise, rngs):
+        """Dirichlet noise over the root's children, then the tie-break tape, from each tree's stream (as ``run``)."""
+        B, A, alpha = len(root_n), self.A, self.config.root_dirichlet_alpha
+        assert len(rngs) == B
+        noise = numpy.zeros((B, A), numpy.float64) if add_exploration_noise else None
+        tape = numpy.zeros((B, TAPE_WORDS), numpy.uint32)
+        states = []
+        for i in range(B):
+            if add_exploration_noise:
+                noise[i, : root_n[i]] = rngs[i].dirichlet([alpha] * int(root_n[i]))
+            states.append(rngs[i].get_state())
+            tape[i] = rngs[i].randint(0, 2 ** 32, size=TAPE_WORDS, dtype=numpy.uint32)
+        return noise, tape, states
+
+    def _run_continued(self, B, root_actions, to_play, noise, tape, states, rngs):
+        """mzx_search_run_continued on the carried trees of the arena; the result record of ``run``."""
+        be, lib, A = self.backend, self.backend.lib, self.A
+        dev = lambda a, dt: torch.as_tensor(numpy.ascontiguousarray(a)).to(dt).to(be.device)
+        t_tp = dev(numpy.asarray(to_play, numpy.int32), torch.int32)
+        t_noise = None if noise is None else dev(noise, torch.float64)
+        t_tape = dev(tape.view(numpy.int32), torch.int32)
+        out = dict(visits=be.zeros((B, A), torch.int32), root_value=be.zeros((B,), torch.float64),
+                   predicted=be.zeros((B,), torch.float64), info=be.zeros((B, 4), torch.int32))
+        io = _lib.SearchIO(None, None, be.ptr(t_tp), be.ptr(t_noise), be.ptr(t_tape), be.ptr(out["visits"]),
+                           be.ptr(out["root_value"]), be.ptr(out["predicted"]), be.ptr(out["info"]))
+        arena = self._arena
+        lib.check(lib.mzx_search_run_continued(self.handle(B), ctypes.byref(io), be.ptr(arena), arena.numel(), be.stream()))
+        res = {k: v.cpu().numpy() for k, v in out.items()}
+        info = res["info"]
+        for i in range(B):      # rewind, then consume exactly what the device consumed
+            rngs[i].set_state(states[i])
+            if info[i, 2]:
+                rngs[i].randint(0, 2 ** 32, size=int(info[i, 2]), dtype=numpy.uint32)
+        if (info[:, 1] != 0).any():
+            self._carry = None
+            bad = numpy.nonzero(info[:, 1])[0][:8]
+            raise _lib.MzxError(f"continued search flagged trees {bad} (flags {set(info[:, 1])}): 1 = tie-break tape "
+                                f"exhausted ({TAPE_WORDS} words; continued searches are not re-run), 4 = not an expanded child")
+        result = SearchResult(res["visits"], res["root_value"], [None] * B, info, [list(a) for a in root_actions])
+        self._note_searched(B, root_actions, res["visits"])
+        return result
+
+    def continue_search(self, actions, to_play, add_exploration_noise, rngs):
+        """
+        MCTS.run(model, None, _, to_play_i, add_exploration_noise, override_root_with=old_root_i.children[actions[i]])
+        (self_play.py:260-361) for the B trees the last ``run`` / ``continue_search`` / ``run_from_trees`` of this engine
+        left on the device; ``actions[i] = -1`` searches old root i itself again.  The chosen subtree is carried on the
+        device (``mzx_search_advance``): visits, values, priors and hidden states stay, ``num_simulations`` more
+        simulations follow (Dirichlet noise over the carried root's children, fresh MinMaxStats).  Returns a
+        ``SearchResult`` (``root_predicted_values`` are None, as in the reference); ``export_trees`` / ``node_graph``
+        read the continued trees.  rngs: B numpy RandomState-like objects.
+        """
+        self._require_capacity()
+        B = len(actions)
+        c = self._carry
+        if c is None or c["B"] != B:
+            raise ValueError("continue_search: no searched trees of this shard size to continue (run them first)")
+        A = self.A
+        acts = numpy.asarray(actions, numpy.int32).reshape(B)
+        root_actions = []
+        for i, a in enumerate(acts.tolist()):
+            if a < 0:
+                root_actions.append(c["root_actions"][i])
+                continue
+            if a not in c["root_actions"][i] or c["visits"][i, a] == 0:
+                raise ValueError(f"continue_search: action {a} of tree {i} is not an expanded child of its root")
+            root_actions.append(list(range(A)))
+        root_n = [len(r) for r in root_actions]
+        noise, tape, states = self._root_draws(root_n, add_exploration_noise, rngs)
+        be = self.backend
+        if self._arena_alt is None or self._arena_alt.numel() != self._arena.numel():
+            self._arena_alt = be.zeros((self._arena.numel(),), torch.uint8)
+        t_act = torch.as_tensor(acts).to(be.device)
+        self._carry = None
+        lib = be.lib
+        lib.check(lib.mzx_search_advance(self.handle(B), be.ptr(t_act), be.ptr(self._arena), be.ptr(self._arena_alt),
+                                         be.stream()))
+        self._arena, self._arena_alt = self._arena_alt, self._arena
+        return self._run_continued(B, root_actions, to_play, noise, tape, states, rngs)
+
+    def run_from_trees(self, roots, to_play, add_exploration_noise, rngs):
+        """
+        MCTS.run(..., override_root_with=root) (self_play.py:260-361) for B expanded reference ``Node`` graphs that may
+        already carry visits and expanded descendants: the graphs are flattened on the host (hidden states from
+        ``node.hidden_state``), loaded (``mzx_search_load``) and searched ``num_simulations`` more times; each given
+        root is then updated in place with the searched tree, as ``MCTS.run`` does for a fresh override.  Node order:
+        the ``canonical_index`` ``node_graph`` records, else depth first in action order (the statistics do not depend
+        on it).  Returns the ``SearchResult``.
+        """
+        self._require_capacity()
+        B, A, M, Hf = len(roots), self.A, self.num_nodes, self.model.hidden_size
+        arr = dict(visit=numpy.zeros((B, M), numpy.int32), value_sum=numpy.zeros((B, M)), reward=numpy.zeros((B, M)),
+                   to_play=numpy.full((B, M), -1, numpy.int32), parent=numpy.full((B, M), -1, numpy.int32),
+                   child=numpy.full((B, M, A), -1, numpy.int32), prior=numpy.zeros((B, M, A)),
+                   hidden=numpy.zeros((B, M, Hf), numpy.float32), n_nodes=numpy.zeros(B, numpy.int32),
+                   root_actions=numpy.full((B, A), -1, numpy.int32))
+        root_actions = []
+        for i, root in enumerate(roots):
+            if not root.expanded() or root.hidden_state is None:
+                raise ValueError("run_from_trees: every root must be an expanded Node with a hidden_state")
+            if root.to_play != to_play[i]:
+                raise ValueError("run_from_trees: root.to_play must equal the to_play argument")
+            nodes = self._flatten(root)
+            if len(nodes) + self.num_simulations + 1 > M:
+                raise ValueError(f"run_from_trees: tree {i} has {len(nodes)} nodes; the engine holds "
+                                 f"{M - self.num_simulations - 1} carried nodes (max_carried_nodes)")
+            index = {id(n): k for k, n in enumerate(nodes)}
+            acts = list(root.children.keys())
+            root_actions.append(acts)
+            arr["root_actions"][i, : len(acts)] = acts
+            arr["n_nodes"][i] = len(nodes)
+            for k, n in enumerate(nodes):
+                arr["visit"][i, k], arr["value_sum"][i, k] = n.visit_count, n.value_sum
+                arr["reward"][i, k], arr["to_play"][i, k] = n.reward, n.to_play
+                arr["hidden"][i, k] = n.hidden_state.detach().reshape(-1).to("cpu", torch.float32).numpy()
+                for slot, (a, ch) in enumerate(n.children.items()):
+                    s = slot if k == 0 else a
+                    arr["prior"][i, k, s] = ch.prior
+                    if ch.expanded():
+                        arr["child"][i, k, s] = index[id(ch)]
+                        arr["parent"][i, index[id(ch)]] = k
+        ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+        h = _lib.TreeLoad(M, *[ptr(arr[k]) for k in ("visit", "value_sum", "reward", "to_play", "parent", "child", "prior",
+                                                      "hidden", "n_nodes", "root_actions")])
+        be = self.backend
+        arena = self.arena(B)
+        self._carry = None
+        be.lib.check(be.lib.mzx_search_load(self.handle(B), ctypes.byref(h), be.ptr(arena), be.stream()))
+        noise, tape, states = self._root_draws([len(r) for r in root_actions], add_exploration_noise, rngs)
+        res = self._run_continued(B, root_actions, to_play, noise, tape, states, rngs)
+        trees = self.export_trees(B)
+        for i, root in enumerate(roots):      # the reference searches the given objects in place
+            searched = self.node_graph(B, i, root_actions[i], _trees=trees)
+            searched.hidden_state = root.hidden_state
+            root.__dict__.update(searched.__dict__)
+        return res
+
+    def _flatten(self, root):
+        """Expanded nodes of a Node graph, parents before children (see run_from_trees)."""
+        nodes, stack = [], [root]
+        while stack:
+            n = stack.pop()
+            if not n.expanded():
+                continue
+            if n.hidden_state is None:
+                raise ValueError("run_from_trees: every expanded node needs its hidden_state")
+            nodes.append(n)
+            stack.extend(reversed(list(n.children.values())))
+        if all(hasattr(n, "canonical_index") for n in nodes):
+            nodes.sort(key=lambda n: n.canonical_index)
+            if nodes[0] is not root:
+                raise ValueError("run_from_trees: canonical_index of the root must be the smallest")
+        return nodes
 
     def _staging(self, B, tape_words, obs_floats, with_noise):
         """
@@ -510,6 +689,9 @@ class BatchedMCTS:
             v2, r2, p2, i2 = self._launch(len(redo), sub_obs, legal[redo], to_play[redo],
                                           None if noise is None else noise[redo], long_tape, words, ov)
             visits[redo], root_values[redo], predicted[redo], info[redo] = v2, r2, p2, i2
+        self._carry = None      # (the re-runs used the arena at other shard sizes: the trees of this run are gone)
+        if words == TAPE_WORDS:
+            self._note_searched(B, [list(legal[i, : int((legal[i] >= 0).sum())]) for i in range(B)], visits)
         result = SearchResult(visits, root_values, predicted, info,
                               legal_actions if isinstance(legal_actions, numpy.ndarray) else
                               (shared if shared is not None else [list(a) for a in legal_actions]))
