@@ -295,7 +295,7 @@ int mzx_search_fused_supported(const mzx_search* s);
  * whole-search kernels a configuration is routed to is decided per launch (network family, board size, LDS fit). */
 const char* mzx_search_kernel_name(const mzx_search* s);
 int mzx_search_set_mode(mzx_search* s, int32_t mode);
-/* What the NEXT mzx_search_run of this handle would launch (host-side, no GPU): out[0] = 0 the generic path, 1
+/* What the NEXT mzx_search_run (or mzx_search_run_continued) of this handle would launch (host-side, no GPU): out[0] = 0 the generic path, 1
  * mzx::rz_search_kernel or one of its small-board siblings, 2 per-simulation launches around the streamed engine, 3
  * mzx::rt_search_kernel (every simulation in one launch, csrc/mzx_tower_search.inc), 4 the fully connected whole-search
  * kernel; for 3: out[1..6] = {trees per workgroup, row tiles per wave, workgroups, workgroups per CU, LDS bytes, threads per
@@ -350,8 +350,10 @@ int mzx_search_dump(mzx_search* s, const mzx_tree_dump* dump, void* d_arena, voi
  * mzx_search_set_capacity: node slots per tree = max_nodes (>= num_simulations + 1) and the pb_c / sqrt tables for
  *   visit counts 0 .. max_nodes - 1 (max_nodes entries each, same definition as in mzx_search_config).  Re-plans the
  *   arena (mzx_search_arena_bytes grows) and forgets what earlier calls left in any arena.  A handle with spare
- *   capacity runs mzx_search_run on the routes that keep every node's hidden state in the arena (the per-operator path,
- *   or the streamed row route launch by launch), never on an LDS-resident whole-search kernel.
+ *   capacity runs mzx_search_run and mzx_search_run_continued on the same route (mzx_search_route reports it), one that
+ *   leaves every node's hidden state in the arena: the fully connected whole-search kernel where its LDS plan holds the
+ *   capacity (route 4; it then exports every search), the tower whole-search kernel (3) or the streamed row route (2)
+ *   where a fresh search takes them, else the per-operator path (0) -- never the LDS-resident residual kernels (1).
  * mzx_search_advance: tree i -> the subtree under root action d_actions[i] (-1: the old root itself), read from the trees
  *   and hidden states the PRECEDING search call of this handle left in d_src_arena (the arena persists between these
  *   calls, as for mzx_search_dump), written to d_dst_arena (another arena of the same size).  MZX_ERR_INVALID when that
@@ -364,7 +366,8 @@ int mzx_search_dump(mzx_search* s, const mzx_tree_dump* dump, void* d_arena, voi
  * mzx_search_run_continued: num_simulations simulations on the trees mzx_search_advance / mzx_search_load put into
  *   d_arena (io->d_observation and io->d_legal_actions are not read).  Reads the carried node counts back (one stream
  *   synchronisation) and fails with MZX_ERR_INVALID when carried nodes + num_simulations + 1 exceed the capacity or when
- *   io->d_to_play differs from a carried root's to_play.  On a handle without a network it prepares the roots (noise,
+ *   io->d_to_play differs from a carried root's to_play.  The simulations run where a fresh search of the handle runs
+ *   (see mzx_search_set_capacity); mzx_search_kernel_name names the kernel.  On a handle without a network it prepares the roots (noise,
  *   meta words, MinMaxStats) and returns: the caller drives mzx_search_lockstep_select / _apply / mzx_search_finish.
  * ------------------------------------------------------------------------- */
 typedef struct mzx_tree_load {

@@ -376,7 +376,40 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
   wave_sync();
 }
 
-template <class Net, int AW, bool PROFILE>
+// Arena tree (TreeLayout) -> the slot / node records above in LDS: a root RootInitOp left alone (the residual whole-search
+// kernel, mzx_resnet_search.h), or a carried tree ContinueRootOp prepared (fc2_search_kernel's continued searches).  The
+// cached prior score of every slot is recomputed at its node's visit count with prior_score -- the operations of the
+// refresh after back-propagation, hence the bits a tree grown in LDS would hold.  Called by the 16-lane row of the tree.
+template <int RW>
+__device__ __forceinline__ void fc2_from_arena(const Fc2Tree& FT, Fc2Row& rst, const TreeRef& t, int sub) {
+  const int nn = t.meta(TM_N_NODES), rootn = t.meta(TM_ROOT_N);
+  for (int n = sub; n < nn; n += FUSED_ROW) {
+    Fc2Node r;
+    r.value_sum = t.value_sum(n); r.reward = t.reward(n); r.visit = t.visit(n); r.to_play = t.to_play(n);
+    r.parent = t.parent(n); r.parent_slot = t.parent_slot(n);
+    FT.nodes[n] = r;
+    const int nc = (n == 0) ? rootn : FT.A;
+    for (int s2 = 0; s2 < RW; ++s2) {
+      Fc2Slot q;
+      const bool in = s2 < nc;
+      q.prior = in ? t.prior(n, s2) : 0.0; q.q = in ? t.slot_q(n, s2) : 0.0;
+      q.n = in ? t.slot_visit(n, s2) : 0; q.child = in ? t.child(n, s2) : -1;
+      q.ps = in ? prior_score(FT.pbc[r.visit], FT.sqt[r.visit], q.n, FT.inv_y[q.n + 1], q.prior) : -MZX_INF;
+      FT.slots[n * RW + s2] = q;
+    }
+  }
+  if (sub < RW) FT.roota[sub] = (sub < rootn) ? t.root_action(sub) : -1;
+  if (sub == 0) { FT.path[0] = make_int2(0, -1); FT.mm[0] = t.mm_min(); FT.mm[1] = t.mm_max(); }
+  rst.n_nodes = nn; rst.tape_pos = t.meta(TM_TAPE_POS); rst.flags = t.meta(TM_FLAGS); rst.ties = t.meta(TM_TIE_DRAWS);
+  rst.max_depth = t.meta(TM_MAX_DEPTH); rst.sum_depth = t.meta(TM_SUM_DEPTH); rst.root_n = rootn;
+  rst.root_to_play = t.to_play(0);
+}
+
+// CONT: a continued search (mzx_tree_carry.h) -- each tree comes from the arena (f.export_trees / f.export_hidden, where
+// mzx_search_advance / mzx_search_load put it and ContinueRootOp prepared its root) instead of initial_inference and root
+// expansion; continued simulation k expands node n_carried + k, the root's N is its visit count from the tree, and the
+// grown tree goes back to the same place.  CONT = false is the fresh search, unchanged.
+template <class Net, int AW, bool PROFILE, bool CONT = false>
 __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -425,8 +458,25 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
   int32_t n_nodes = 1, tape_pos = 0, flags = 0, ties = 0, max_depth = 0, sum_depth = 0, root_n = 0, root_to_play = 0;
   MZX_PROF(0)
 
+  // ---- a carried tree: node and slot records (prior scores recomputed), MinMaxStats, root actions and counters, and
+  // the hidden state of every node, arena -> LDS
+  if constexpr (CONT) {
+    Fc2Tree FT;
+    FT.slots = slots; FT.nodes = nodes; FT.path = path; FT.roota = roota; FT.mm = mm;
+    FT.pbc = pbc; FT.sqt = sqt; FT.inv_y = inv_y; FT.A = A;
+    TreeRef t;
+    t.base = a.f.export_trees + (size_t)tree * a.f.L.tree_bytes;
+    t.L = a.f.L;
+    Fc2Row rst;
+    fc2_from_arena<AW>(FT, rst, t, sub);
+    n_nodes = rst.n_nodes; tape_pos = rst.tape_pos; flags = rst.flags; ties = rst.ties; max_depth = rst.max_depth;
+    sum_depth = rst.sum_depth; root_n = rst.root_n; root_to_play = rst.root_to_play;
+    const float* hd = a.f.export_hidden + (size_t)tree * NN * E;
+    for (int i = sub; i < n_nodes * E; i += FUSED_ROW) hidden[i] = hd[i];
+    wave_sync();
+  }
   // ---- initial_inference (models.py:172-190) + root expansion (self_play.py:286-314, :467-476)
-  {
+  if constexpr (!CONT) {
     NetOut o;
     const bool given = a.ov_hidden != nullptr;       // (launch-uniform) the caller's roots: no initial_inference
     if (!given) net.initial(a.f.io.d_observation + (size_t)tree * a.f.in_size, hidden, scr, sub, o);
@@ -594,29 +644,38 @@ inline Fc2Plan fc2_plan(const mzx_search* s, bool allow_small = true) {
   return P;
 }
 
-template <class Net, int AW, bool PROFILE>
+template <class Net, int AW, bool PROFILE, bool CONT = false>
 inline int fc2_launch(const Fc2Plan& P, unsigned grid, stream_t stream) {
   static std::atomic<uint64_t> lds_attr_done{0};   // per instantiation, one bit per device
-  if (const int ae = allow_large_lds((const void*)fc2_search_kernel<Net, AW, PROFILE>, FUSED_LDS_BUDGET, lds_attr_done)) {
+  if (const int ae = allow_large_lds((const void*)fc2_search_kernel<Net, AW, PROFILE, CONT>, FUSED_LDS_BUDGET, lds_attr_done)) {
     set_error("hipFuncSetAttribute: %s", runtime_error_string(ae));
     return MZX_ERR_RUNTIME;
   }
-  hipLaunchKernelGGL((fc2_search_kernel<Net, AW, PROFILE>), dim3(grid), dim3(P.args.f.trees_per_block * FUSED_ROW),
+  hipLaunchKernelGGL((fc2_search_kernel<Net, AW, PROFILE, CONT>), dim3(grid), dim3(P.args.f.trees_per_block * FUSED_ROW),
                      (size_t)P.lds_bytes, stream, P.args);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("fused kernel launch failed: %s", hipGetErrorString(e)); return MZX_ERR_RUNTIME; }
   return MZX_OK;
 }
 
-template <class Net, bool PROFILE>
+template <class Net, bool PROFILE, bool CONT = false>
 inline int fc2_launch_aw(const Fc2Plan& P, unsigned grid, stream_t stream) {
-  if (P.aw == 2) return fc2_launch<Net, 2, PROFILE>(P, grid, stream);
-  if (P.aw == 4) return fc2_launch<Net, 4, PROFILE>(P, grid, stream);
-  return fc2_launch<Net, 16, PROFILE>(P, grid, stream);
+  if (P.aw == 2) return fc2_launch<Net, 2, PROFILE, CONT>(P, grid, stream);
+  if (P.aw == 4) return fc2_launch<Net, 4, PROFILE, CONT>(P, grid, stream);
+  return fc2_launch<Net, 16, PROFILE, CONT>(P, grid, stream);
 }
 
+// Whether fc2_search_kernel takes the searches of this handle at its node capacity (num_nodes: num_simulations + 1, or
+// what mzx_search_set_capacity set): the per-tree slabs, the pb_c / sqrt tables and the reciprocal table are all sized by
+// it.  A capacity whose smallest workgroup (four trees) exceeds FUSED_LDS_BUDGET leaves the handle on the per-operator path.
+inline bool fc2_fits(const mzx_search* s) { return fc2_plan(s, !(s->mode & 4)).ok != 0; }
+
 // mode bits: 1 = fused, 2 = export trees to the arena, 4 = force LdsNet, 8 = cycle-profile build
-inline int fc2_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const RootOverride* ov = nullptr) {
+// Handles with spare node capacity (mzx_search_set_capacity) always export, hidden states included: mzx_search_advance
+// carries the trees from there.  continued = true: the arena holds carried trees ContinueRootOp prepared; the kernel
+// imports them (CONT instantiation) and writes the grown trees back (no profile build).
+inline int fc2_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const RootOverride* ov = nullptr,
+                   bool continued = false) {
   Fc2Plan P = fc2_plan(s, !(s->mode & 4));
   if (!P.ok) { set_error("fused search kernel does not support this configuration"); return MZX_ERR_INVALID; }
   int rc = ensure_tables(s, d_arena, stream);
@@ -625,14 +684,16 @@ inline int fc2_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream
   P.args.f.flat = s->net->d_flat;
   P.args.f.tables = s->d_tables;
   P.args.f.io = *io;
-  const bool profile = (s->mode & 8) != 0 && s->ws_floats * 4 >= int64_t(s->p.num_trees) * FUSED_PROF_WORDS * 4;
-  if (s->mode & 2) {
+  const bool profile = !continued && (s->mode & 8) != 0 && s->ws_floats * 4 >= int64_t(s->p.num_trees) * FUSED_PROF_WORDS * 4;
+  if ((s->mode & 2) || s->max_nodes > 0 || continued) {
     P.args.f.export_trees = (char*)d_arena + s->off_trees;
     P.args.f.export_hidden = (float*)((char*)d_arena + s->off_hidden);
   }
   if (profile) P.args.f.prof = (uint32_t*)((char*)d_arena + s->off_ws);
   const int tpb = P.args.f.trees_per_block;
   const unsigned grid = (unsigned)((s->p.num_trees + tpb - 1) / tpb);
+  if (continued)
+    return P.small ? fc2_launch<SmallNetCartpole, 2, false, true>(P, grid, stream) : fc2_launch_aw<LdsNet, false, true>(P, grid, stream);
   if (P.small)   // SmallNetCartpole has A = 2
     return profile ? fc2_launch<SmallNetCartpole, 2, true>(P, grid, stream)
                    : fc2_launch<SmallNetCartpole, 2, false>(P, grid, stream);

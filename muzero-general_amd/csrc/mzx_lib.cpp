@@ -440,23 +440,45 @@ int mzx_tuning_get(const char* name, int32_t* value, int32_t* dflt) {
 const char* mzx_tuning_name(int32_t index) { return (index >= 0 && index < TUNE_COUNT) ? tuning_table()[index].name : nullptr; }
 const char* mzx_tuning_help(int32_t index) { return (index >= 0 && index < TUNE_COUNT) ? tuning_table()[index].what : nullptr; }
 
+// The one route decision of a search on this handle: mzx_search_run and mzx_search_run_continued launch what it names,
+// mzx_search_route reports it.  A handle with spare node capacity (mzx_search_set_capacity) takes only kernels that leave
+// every node's hidden state in the arena for mzx_search_advance and that take carried trees: fc2_search_kernel where its
+// LDS plan fits the capacity (it exports every search), rt_search_kernel and the streamed row route (the node store), or
+// the per-operator path.  The LDS-resident residual kernels (rz_*) and the first-generation fully connected kernel (flag 16)
+// do not; such a handle runs the per-operator path instead.
+enum SearchPath { PATH_GENERIC = 0, PATH_RZ, PATH_ROWS, PATH_RT, PATH_FC2, PATH_FUSED_FC };
+struct SearchChoice {
+  int path = PATH_GENERIC;
+  bool force_streamed = false;   // a network the LDS-resident engine would run: the streamed engine for this search
+};
+
+static SearchChoice search_choice(const mzx_search* s) {
+  SearchChoice c;
+#ifndef MZX_HOSTCHECK
+  if (!s->net || !(s->mode & 1)) return c;
+  const bool spare = s->max_nodes > 0;
+  if (s->fused_ok == 1 && !spare) { c.path = (s->mode & 16) ? PATH_FUSED_FC : PATH_FC2; return c; }
+  if (s->fused_ok == 1 && !(s->mode & 16) && fc2_fits(s)) { c.path = PATH_FC2; return c; }
+  if (s->fused_ok == 2 && rz_enabled(s->net, true)) {
+    // a wide network: the tower arithmetic at every shard size (wide_search_route, mzx_row_search.h) -- all simulations in
+    // one launch of rt_search_kernel, or the trunks as towers between the row-per-tree kernels
+    const int route = wide_search_route(s);
+    if (route != ROUTE_RZ) { c.path = route == ROUTE_RT ? PATH_RT : PATH_ROWS; c.force_streamed = true; return c; }
+    if (!spare) { c.path = PATH_RZ; return c; }
+  }
+  if (rb_enabled(s->net, true) && row_search_supported(s->p)) c.path = streamed_whole_search(s) ? PATH_RT : PATH_ROWS;
+#else
+  (void)s;
+#endif
+  return c;
+}
+
 static void search_route_of(const mzx_search* s, int32_t out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = 0;
 #ifndef MZX_HOSTCHECK
-  if (!s->net) return;
-  int whole = 0;
-  const bool spare = s->max_nodes > 0;
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
-    const int route = wide_search_route(s);
-    out[0] = route == ROUTE_RZ ? 1 : (route == ROUTE_ROWS ? 2 : 3);
-    whole = route == ROUTE_RT;
-  } else if ((s->mode & 1) && s->fused_ok == 1 && !spare) {
-    out[0] = 4;
-  } else if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
-    whole = !spare && streamed_whole_search(s);
-    out[0] = whole ? 3 : 2;
-  }
-  if (whole) rt_search_shape(s, out + 1);      // out[1 .. 6]
+  static const int32_t code[] = {0, 1, 2, 3, 4, 4};   // indexed by SearchPath
+  out[0] = code[search_choice(s).path];
+  if (out[0] == 3) rt_search_shape(s, out + 1);      // out[1 .. 6]
   if (out[0] == 2) {
     const int first = rb_split_first(s->net, s->p.num_trees, tune(TUNE_ROW_SPLIT_MIN));
     out[6] = first > 0 ? first : s->p.num_trees;
@@ -516,6 +538,48 @@ static int check_search_call(const mzx_search* s, const void* d_arena, int64_t a
   return MZX_OK;
 }
 
+#ifndef MZX_HOSTCHECK
+static const char* const ROWS_KERNELS = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
+#endif
+
+// The simulations of mzx_search_run (continued = false) or mzx_search_run_continued (the arena holds carried trees whose
+// roots ContinueRootOp prepared) on the route search_choice names; records the kernel and whether the arena now holds every
+// node's hidden state (mzx_search_advance).
+static int search_simulate(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued) {
+  int rc = MZX_OK;
+#ifndef MZX_HOSTCHECK
+  const SearchChoice c = search_choice(s);
+  switch (c.path) {
+    case PATH_FUSED_FC:
+      s->last_kernel = "mzx::fused_fc_search";
+      return fused_fc_run(s, io, d_arena, stream);
+    case PATH_FC2:
+      s->last_kernel = "mzx::fc2_search_kernel";
+      rc = fc2_run(s, io, d_arena, stream, nullptr, continued);
+      if (!rc && s->max_nodes > 0) s->hidden_arena = d_arena;      // (handles with spare capacity always export)
+      return rc;
+    case PATH_RZ:
+      return rz_search_run(s, io, d_arena, stream);
+    case PATH_ROWS:
+    case PATH_RT:
+      // (search_run_rows renames last_kernel when it runs two half-shards or the whole-search kernel)
+      s->last_kernel = ROWS_KERNELS;
+      rc = search_run_rows(s, io, d_arena, stream, nullptr, c.force_streamed, c.path == PATH_RT, continued);
+      if (!rc) s->hidden_arena = d_arena;
+      return rc;
+    default:
+      break;
+  }
+#endif
+  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
+#ifndef MZX_HOSTCHECK
+  if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
+#endif
+  rc = search_run_generic(s, io, d_arena, stream, nullptr, continued);
+  if (!rc) s->hidden_arena = d_arena;
+  return rc;
+}
+
 int mzx_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_t arena_bytes, void* stream) {
   int rc = check_search_call(s, d_arena, arena_bytes, true);
   if (rc) return rc;
@@ -525,39 +589,7 @@ int mzx_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_
     return MZX_ERR_INVALID;
   }
   s->hidden_arena = s->carried_arena = nullptr;
-  const bool spare = s->max_nodes > 0;     // a handle with spare node capacity keeps every node's hidden state in the arena
-#ifndef MZX_HOSTCHECK
-  if ((s->mode & 1) && s->fused_ok == 1 && !spare)
-  {
-    s->last_kernel = (s->mode & 16) ? "mzx::fused_fc_search" : "mzx::fc2_search_kernel";
-    return (s->mode & 16) ? fused_fc_run(s, io, d_arena, (stream_t)stream) : fc2_run(s, io, d_arena, (stream_t)stream);
-  }
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
-    // a wide network: the tower arithmetic at every shard size (wide_search_route, mzx_row_search.h) -- all simulations in
-    // one launch of rt_search_kernel, or the trunks as towers between the row-per-tree kernels
-    const int route = wide_search_route(s);
-    if (route != ROUTE_RZ) {
-      s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-      return search_run_rows(s, io, d_arena, (stream_t)stream, nullptr, true, route == ROUTE_RT);
-    }
-    return rz_search_run(s, io, d_arena, (stream_t)stream);
-  }
-  if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
-    s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-    // (renames last_kernel when it runs two half-shards or the whole-search kernel)
-    const bool whole = !spare && streamed_whole_search(s);
-    rc = search_run_rows(s, io, d_arena, (stream_t)stream, nullptr, false, whole);
-    if (!rc && !whole) s->hidden_arena = d_arena;
-    return rc;
-  }
-#endif
-  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
-#ifndef MZX_HOSTCHECK
-  if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
-#endif
-  rc = search_run_generic(s, io, d_arena, (stream_t)stream);
-  if (!rc) s->hidden_arena = d_arena;
-  return rc;
+  return search_simulate(s, io, d_arena, (stream_t)stream, false);
 }
 
 int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const float* d_root_hidden,
@@ -807,23 +839,9 @@ int mzx_search_run_continued(mzx_search* s, const mzx_search_io* io, void* d_are
   s->hidden_arena = d_arena;
   if (!with_net) return MZX_OK;     // lock-step handle: the caller drives the simulations
   s->hidden_arena = nullptr;
-#ifndef MZX_HOSTCHECK
-  // the streamed row route launch by launch (its arena holds every node's hidden state); every other network: the
-  // per-operator path (the whole-search kernels keep nodes in LDS and do not take carried trees)
-  if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
-    s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-    rc = search_run_rows(s, io, d_arena, st, nullptr, false, false, true);
-    if (!rc) s->hidden_arena = d_arena;
-    return rc;
-  }
-#endif
-  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
-#ifndef MZX_HOSTCHECK
-  if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
-#endif
-  rc = search_run_generic(s, io, d_arena, st, nullptr, true);
-  if (!rc) s->hidden_arena = d_arena;
-  return rc;
+  // the route of a fresh search on this handle (search_choice): fc2_search_kernel / rt_search_kernel import the carried
+  // trees, the streamed row route and the per-operator path walk them in the arena
+  return search_simulate(s, io, d_arena, st, true);
 }
 
 // ------------------------------------------------------- observation pipeline

@@ -177,33 +177,8 @@ __host__ __device__ inline int64_t rz_trec_tree_floats(int N, int AW) {
 }
 inline int64_t rz_trec_extra_floats(int N) { return 2 * (int64_t)(N + 2); }   // refined-reciprocal table
 
-// Arena tree (TreeLayout, as RootInitOp left it: normally the root alone) -> the slot / node records of
-// mzx_fused_fc2.h in LDS, and back (what FinalizeOp and mzx_search_dump read).  Called by the 16-lane row of the tree.
-template <int RW>
-__device__ __forceinline__ void fc2_from_arena(const Fc2Tree& FT, Fc2Row& rst, const TreeRef& t, int sub) {
-  const int nn = t.meta(TM_N_NODES), rootn = t.meta(TM_ROOT_N);
-  for (int n = sub; n < nn; n += FUSED_ROW) {
-    Fc2Node r;
-    r.value_sum = t.value_sum(n); r.reward = t.reward(n); r.visit = t.visit(n); r.to_play = t.to_play(n);
-    r.parent = t.parent(n); r.parent_slot = t.parent_slot(n);
-    FT.nodes[n] = r;
-    const int nc = (n == 0) ? rootn : FT.A;
-    for (int s2 = 0; s2 < RW; ++s2) {
-      Fc2Slot q;
-      const bool in = s2 < nc;
-      q.prior = in ? t.prior(n, s2) : 0.0; q.q = in ? t.slot_q(n, s2) : 0.0;
-      q.n = in ? t.slot_visit(n, s2) : 0; q.child = in ? t.child(n, s2) : -1;
-      q.ps = in ? prior_score(FT.pbc[r.visit], FT.sqt[r.visit], q.n, FT.inv_y[q.n + 1], q.prior) : -MZX_INF;
-      FT.slots[n * RW + s2] = q;
-    }
-  }
-  if (sub < RW) FT.roota[sub] = (sub < rootn) ? t.root_action(sub) : -1;
-  if (sub == 0) { FT.path[0] = make_int2(0, -1); FT.mm[0] = t.mm_min(); FT.mm[1] = t.mm_max(); }
-  rst.n_nodes = nn; rst.tape_pos = t.meta(TM_TAPE_POS); rst.flags = t.meta(TM_FLAGS); rst.ties = t.meta(TM_TIE_DRAWS);
-  rst.max_depth = t.meta(TM_MAX_DEPTH); rst.sum_depth = t.meta(TM_SUM_DEPTH); rst.root_n = rootn;
-  rst.root_to_play = t.to_play(0);
-}
-
+// LDS records -> the arena tree (what FinalizeOp and mzx_search_dump read); fc2_from_arena (mzx_fused_fc2.h) is the
+// inverse.  Called by the 16-lane row of the tree.
 template <int RW>
 __device__ __forceinline__ void fc2_to_arena(const Fc2Tree& FT, const Fc2Row& rst, const TreeRef& t, int sub) {
   for (int n = sub; n < rst.n_nodes; n += FUSED_ROW) {

@@ -44,7 +44,9 @@ inline bool row_search_supported(const SearchParams& p) { return p.num_actions <
 // workgroups per CU, LDS bytes, threads per workgroup}, zeros when the kernel does not take the search.
 bool rt_search_supported(const mzx_search* s);
 void rt_search_shape(const mzx_search* s, int32_t out[6]);
-int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream);
+// continued = true: carried trees (mzx_tree_carry.h) -- every walk reads the root's visit count from its tree, and each tree's
+// next leaf is its own node count (carried counts differ from tree to tree).
+int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued = false);
 
 // One selection walk of tree `t` by its 16-lane row (self_play.py:325-334): the walk's result for the network
 // (parent node, action, leaf) and the row's share of the path -- 64 ints at `rs`: SelCtx (5), action, then (node, parent,
@@ -364,7 +366,7 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
   // ---- the simulations, all of them in one launch (rt_search_kernel, mzx_tower_search.inc) ...
   if (whole_search) {
     s->last_kernel = "mzx::rt_search_kernel";
-    rc = rt_search_simulations(s, io, d_arena, stream);
+    rc = rt_search_simulations(s, io, d_arena, stream, continued);
     if (rc) return rc;
     return search_finish(s, io, d_arena, stream);
   }

@@ -86,7 +86,7 @@ struct RtSearchArgs {
   float* hidden;           // arena node store [num_trees][num_nodes][hidden_size], NCHW per node
   const float* flat;
   const float* der;
-  int32_t num_sims, sim0, batch;
+  int32_t num_sims, sim0, batch;   // sim0 = -1: continued search, the root's visit count is read from its tree
   int32_t dbg;             // timing experiments (tuning "rt_dbg", never set in production; results are WRONG with any bit set): 1 skip the
                            // K loops, 2 skip the epilogues, 4 skip select / expand, 8 skip staging and tails, 16 skip the head MLPs
   int32_t C, H, W, PH, PW, Cs, cchunks, T, rows, mtiles;
@@ -248,7 +248,8 @@ rt_search_kernel(const RtSearchArgs sa) {
     if constexpr (MT >= MZX_OPAQUE_MIN_MT) asm volatile("" : "+v"(ts.base));
     // ---- selection (self_play.py:325-334)
     if (row_valid && !(sa.dbg & 4))
-      row_select_body<AW>(p, ts, tape, sa.sim0 + sim, sub, row_in_wave, rs, sel_parent + row, sel_action + row, sel_leaf + row);
+      row_select_body<AW>(p, ts, tape, sa.sim0 >= 0 ? sa.sim0 + sim : ts.visit(0), sub, row_in_wave, rs, sel_parent + row,
+                          sel_action + row, sel_leaf + row);
     RT_STAMP(0);
     __syncthreads();
     RT_STAMP(1);
@@ -926,7 +927,7 @@ void rt_search_shape(const mzx_search* s, int32_t out[6]) {
 }
 
 // The simulations of a search whose roots are in the arena (RootInitOp done, root states in the node store).
-int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream) {
+int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued) {
   RtPlan P = rt_plan(s);
   if (!P.ok) { set_error("tower whole-search kernel: configuration not supported"); return MZX_ERR_INVALID; }
   const mzx_net* net = s->net;
@@ -936,7 +937,7 @@ int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena,
   a.p = v.p; a.L = s->L;
   a.trees = v.arena.trees; a.tape = io->d_tape; a.hidden = v.arena.hidden;
   a.flat = net->d_flat; a.der = net->d_derived;
-  a.num_sims = s->p.num_sims; a.sim0 = 0; a.batch = s->p.num_trees;
+  a.num_sims = s->p.num_sims; a.sim0 = continued ? -1 : 0; a.batch = s->p.num_trees;
   a.magic_hw = rt_magic(a.H * a.W); a.magic_w = rt_magic(a.W); a.magic_rows = rt_magic(16 * a.mtiles);
   a.magic_chw = rt_magic(a.C * a.H * a.W); a.magic_c = rt_magic(a.C);
   RbTowerShape sh;

@@ -164,7 +164,8 @@ class BatchedMCTS:
         """
         Canonical-order copy of the trees of the last ``run`` (diagnose tooling / parity tests):
         dict of numpy arrays visit [B][N], value_sum, reward, to_play, parent, child [B][N][A],
-        prior, minmax [B][2], n_nodes [B].  With the fused kernel this needs mode flag 2.
+        prior, minmax [B][2], n_nodes [B].  With the fused kernel this needs mode flag 2 (or max_carried_nodes > 0: such
+        an engine's searches always leave their trees in the arena).
         """
         be, lib, B, N, A = self.backend, self.backend.lib, num_trees, self.num_nodes, self.A
         t = dict(
