@@ -47,6 +47,13 @@ constexpr int FUSED_MAX_WIDTH = 64;    // widest layer LdsNet handles
 constexpr int FUSED_SCRATCH = 5 * FUSED_MAX_WIDTH;  // floats of per-tree exchange scratch
 constexpr int FUSED_PROF_WORDS = 16;
 
+// Lanes of a tree's 16-lane row that hold child slots in the row kernels' instantiations: 4 or 16 when the actions and the
+// support's bins fit one row's registers, 0 = the wide forms (several slots / bins per lane).
+inline int row_action_lanes(const SearchParams& p) {
+  const bool wide = p.num_actions > FUSED_ROW || 2 * p.support_size + 1 > 2 * FUSED_ROW;
+  return wide ? 0 : (p.num_actions <= 4 ? 4 : 16);
+}
+
 struct FusedMlp {
   int32_t n;                                 // number of Linear layers
   int32_t sizes[MZX_MAX_LAYERS + 2];         // widths, sizes[0] = input (incl. one-hot block)
@@ -1058,7 +1065,12 @@ inline int fused_launch_aw(const FusedPlan& P, unsigned grid, stream_t stream) {
 #endif  // MZX_EXPERIMENT
 
 // mode bits: 1 = fused, 2 = export trees to the arena, 4 = force LdsNet, 8 = cycle-profile build
-inline int fused_fc_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream) {
+// Fresh searches only: the kernel runs its own initial_inference and neither takes given roots nor carried trees.
+inline int fused_fc_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
+  if (start.kind != SearchStart::FRESH) {
+    set_error("the first-generation fully connected kernel (mode flag 16) runs fresh searches only");
+    return MZX_ERR_INVALID;
+  }
 #ifndef MZX_EXPERIMENT
   (void)io; (void)d_arena; (void)stream; (void)s;
   set_error("the first-generation fully connected kernel (mode flag 16) is built into instrumented libraries only (-DMZX_EXPERIMENT)");
@@ -1066,7 +1078,7 @@ inline int fused_fc_run(mzx_search* s, const mzx_search_io* io, void* d_arena, s
 #else
   FusedPlan P = fused_plan(s, !(s->mode & 4));
   if (!P.ok) { set_error("fused search kernel does not support this configuration"); return MZX_ERR_INVALID; }
-  int rc = ensure_tables(s, d_arena, stream);
+  int rc = ensure_tables(s);
   if (rc) return rc;
   P.args.flat = s->net->d_flat;
   P.args.tables = s->d_tables;

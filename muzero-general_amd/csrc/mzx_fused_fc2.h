@@ -672,15 +672,18 @@ inline bool fc2_fits(const mzx_search* s) { return fc2_plan(s, !(s->mode & 4)).o
 
 // mode bits: 1 = fused, 2 = export trees to the arena, 4 = force LdsNet, 8 = cycle-profile build
 // Handles with spare node capacity (mzx_search_set_capacity) always export, hidden states included: mzx_search_advance
-// carries the trees from there.  continued = true: the arena holds carried trees ContinueRootOp prepared; the kernel
-// imports them (CONT instantiation) and writes the grown trees back (no profile build).
-inline int fc2_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const RootOverride* ov = nullptr,
-                   bool continued = false) {
+// carries the trees from there.  OVERRIDE: the given roots go in as launch arguments instead of initial_inference.
+// CONTINUED: the arena holds carried trees ContinueRootOp prepared; the kernel imports them (CONT instantiation) and writes
+// the grown trees back (no profile build).
+inline int fc2_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
   Fc2Plan P = fc2_plan(s, !(s->mode & 4));
   if (!P.ok) { set_error("fused search kernel does not support this configuration"); return MZX_ERR_INVALID; }
-  int rc = ensure_tables(s, d_arena, stream);
+  int rc = ensure_tables(s);
   if (rc) return rc;
-  if (ov) { P.args.ov_hidden = ov->hidden; P.args.ov_priors = ov->priors; P.args.ov_reward = ov->reward; }
+  const bool continued = start.kind == SearchStart::CONTINUED;
+  if (start.kind == SearchStart::OVERRIDE) {
+    P.args.ov_hidden = start.ov.hidden; P.args.ov_priors = start.ov.priors; P.args.ov_reward = start.ov.reward;
+  }
   P.args.f.flat = s->net->d_flat;
   P.args.f.tables = s->d_tables;
   P.args.f.io = *io;

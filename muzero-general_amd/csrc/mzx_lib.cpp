@@ -440,35 +440,44 @@ int mzx_tuning_get(const char* name, int32_t* value, int32_t* dflt) {
 const char* mzx_tuning_name(int32_t index) { return (index >= 0 && index < TUNE_COUNT) ? tuning_table()[index].name : nullptr; }
 const char* mzx_tuning_help(int32_t index) { return (index >= 0 && index < TUNE_COUNT) ? tuning_table()[index].what : nullptr; }
 
-// The one route decision of a search on this handle: mzx_search_run and mzx_search_run_continued launch what it names,
-// mzx_search_route reports it.  A handle with spare node capacity (mzx_search_set_capacity) takes only kernels that leave
-// every node's hidden state in the arena for mzx_search_advance and that take carried trees: fc2_search_kernel where its
-// LDS plan fits the capacity (it exports every search), rt_search_kernel and the streamed row route (the node store), or
-// the per-operator path.  The LDS-resident residual kernels (rz_*) and the first-generation fully connected kernel (flag 16)
-// do not; such a handle runs the per-operator path instead.
-enum SearchPath { PATH_GENERIC = 0, PATH_RZ, PATH_ROWS, PATH_RT, PATH_FC2, PATH_FUSED_FC };
-struct SearchChoice {
-  int path = PATH_GENERIC;
-  bool force_streamed = false;   // a network the LDS-resident engine would run: the streamed engine for this search
-};
-
-static SearchChoice search_choice(const mzx_search* s) {
+// The one route decision of a search on this handle, for its three entries: mzx_search_run (FRESH), mzx_search_run_from_roots
+// (OVERRIDE) and mzx_search_run_continued (CONTINUED) launch what it names (search_simulate), mzx_search_route reports the
+// FRESH one.  A handle with spare node capacity (mzx_search_set_capacity) takes only kernels that leave every node's hidden
+// state in the arena for mzx_search_advance and that take carried trees: fc2_search_kernel where its LDS plan fits the
+// capacity (it exports every search), rt_search_kernel and the streamed row route (the node store), or the per-operator path.
+// The LDS-resident residual kernels (rz_*) and the first-generation fully connected kernel (flag 16) do not; such a handle
+// runs the per-operator path instead.
+// A CONTINUED search takes the route of a FRESH one.  An OVERRIDE search does not in every case: the rules marked "from roots"
+// keep what mzx_search_run_from_roots chose while it had an if-chain of its own (tests/test_gpu_route_table.py pins them);
+// whether such a search should follow the fresh route is a decision to take on purpose, not made here.
+static SearchChoice search_choice(const mzx_search* s, SearchStart::Kind kind) {
   SearchChoice c;
 #ifndef MZX_HOSTCHECK
   if (!s->net || !(s->mode & 1)) return c;
   const bool spare = s->max_nodes > 0;
-  if (s->fused_ok == 1 && !spare) { c.path = (s->mode & 16) ? PATH_FUSED_FC : PATH_FC2; return c; }
-  if (s->fused_ok == 1 && !(s->mode & 16) && fc2_fits(s)) { c.path = PATH_FC2; return c; }
-  if (s->fused_ok == 2 && rz_enabled(s->net, true)) {
+  const bool from_roots = kind == SearchStart::OVERRIDE;
+  if (s->fused_ok == 1 && !spare) {
+    if (!(s->mode & 16)) { c.path = PATH_FC2; return c; }
+    // from roots: the first-generation kernel (flag 16, experiment builds) takes no given roots -- the per-operator path
+    if (!from_roots) { c.path = PATH_FUSED_FC; return c; }
+  }
+  // from roots: never fc2_search_kernel on a spare-capacity handle -- the per-operator path
+  if (s->fused_ok == 1 && spare && !from_roots && !(s->mode & 16) && fc2_fits(s)) { c.path = PATH_FC2; return c; }
+  // from roots: a spare-capacity handle skips the wide-network rule -- the row route below only when the network handle's own
+  // mode selects the streamed engine, else the per-operator path (the LDS-resident engine's arithmetic)
+  if (s->fused_ok == 2 && rz_enabled(s->net, true) && !(from_roots && spare)) {
     // a wide network: the tower arithmetic at every shard size (wide_search_route, mzx_row_search.h) -- all simulations in
     // one launch of rt_search_kernel, or the trunks as towers between the row-per-tree kernels
     const int route = wide_search_route(s);
     if (route != ROUTE_RZ) { c.path = route == ROUTE_RT ? PATH_RT : PATH_ROWS; c.force_streamed = true; return c; }
     if (!spare) { c.path = PATH_RZ; return c; }
   }
-  if (rb_enabled(s->net, true) && row_search_supported(s->p)) c.path = streamed_whole_search(s) ? PATH_RT : PATH_ROWS;
+  if (rb_enabled(s->net, true) && row_search_supported(s->p)) {
+    // from roots: launch by launch on a spare-capacity handle, also where the fresh search takes rt_search_kernel
+    c.path = !(from_roots && spare) && streamed_whole_search(s) ? PATH_RT : PATH_ROWS;
+  }
 #else
-  (void)s;
+  (void)s; (void)kind;
 #endif
   return c;
 }
@@ -477,7 +486,7 @@ static void search_route_of(const mzx_search* s, int32_t out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = 0;
 #ifndef MZX_HOSTCHECK
   static const int32_t code[] = {0, 1, 2, 3, 4, 4};   // indexed by SearchPath
-  out[0] = code[search_choice(s).path];
+  out[0] = code[search_choice(s, SearchStart::FRESH).path];
   if (out[0] == 3) rt_search_shape(s, out + 1);      // out[1 .. 6]
   if (out[0] == 2) {
     const int first = rb_split_first(s->net, s->p.num_trees, tune(TUNE_ROW_SPLIT_MIN));
@@ -538,45 +547,41 @@ static int check_search_call(const mzx_search* s, const void* d_arena, int64_t a
   return MZX_OK;
 }
 
-#ifndef MZX_HOSTCHECK
-static const char* const ROWS_KERNELS = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-#endif
-
-// The simulations of mzx_search_run (continued = false) or mzx_search_run_continued (the arena holds carried trees whose
-// roots ContinueRootOp prepared) on the route search_choice names; records the kernel and whether the arena now holds every
-// node's hidden state (mzx_search_advance).
-static int search_simulate(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued) {
+// The simulations of a search whose roots arrive as `start` says, on the route search_choice names.  The one place that
+// records the kernel (the drivers refine it where they decide: rz_search_run among its three kernels, search_run_rows when
+// it runs two half-shards) and whether the arena now holds every node's hidden state (mzx_search_advance).
+static int search_simulate(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
+  const SearchChoice c = search_choice(s, start.kind);
   int rc = MZX_OK;
-#ifndef MZX_HOSTCHECK
-  const SearchChoice c = search_choice(s);
   switch (c.path) {
+#ifndef MZX_HOSTCHECK
     case PATH_FUSED_FC:
-      s->last_kernel = "mzx::fused_fc_search";
-      return fused_fc_run(s, io, d_arena, stream);
+      s->last_kernel = KERNEL_FUSED_FC;
+      rc = fused_fc_run(s, io, d_arena, stream, start);
+      break;
     case PATH_FC2:
-      s->last_kernel = "mzx::fc2_search_kernel";
-      rc = fc2_run(s, io, d_arena, stream, nullptr, continued);
-      if (!rc && s->max_nodes > 0) s->hidden_arena = d_arena;      // (handles with spare capacity always export)
-      return rc;
+      s->last_kernel = KERNEL_FC2;
+      rc = fc2_run(s, io, d_arena, stream, start);
+      break;
     case PATH_RZ:
-      return rz_search_run(s, io, d_arena, stream);
+      rc = rz_search_run(s, io, d_arena, stream, start);
+      break;
     case PATH_ROWS:
     case PATH_RT:
-      // (search_run_rows renames last_kernel when it runs two half-shards or the whole-search kernel)
-      s->last_kernel = ROWS_KERNELS;
-      rc = search_run_rows(s, io, d_arena, stream, nullptr, c.force_streamed, c.path == PATH_RT, continued);
-      if (!rc) s->hidden_arena = d_arena;
-      return rc;
+      s->last_kernel = c.path == PATH_RT ? KERNEL_RT : KERNEL_ROWS;
+      rc = search_run_rows(s, io, d_arena, stream, start, c.force_streamed, c.path == PATH_RT);
+      break;
+#endif
     default:
+      // from roots: the plain name, also where the network runs on the streamed engine
+      s->last_kernel = start.kind != SearchStart::OVERRIDE && rb_enabled(s->net, true) ? KERNEL_GENERIC_STREAMED : KERNEL_GENERIC;
+      rc = search_run_generic(s, io, d_arena, stream, start);
       break;
   }
-#endif
-  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
-#ifndef MZX_HOSTCHECK
-  if (rb_enabled(s->net, true)) s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between one-thread-per-tree kernels";
-#endif
-  rc = search_run_generic(s, io, d_arena, stream, nullptr, continued);
-  if (!rc) s->hidden_arena = d_arena;
+  // the per-operator path, the row route and rt_search_kernel keep every node's hidden state in the arena's store;
+  // fc2_search_kernel exports it for handles with spare capacity; the other whole-search kernels keep it in LDS
+  const bool leaves_hidden = c.path == PATH_GENERIC || c.path == PATH_ROWS || c.path == PATH_RT || (c.path == PATH_FC2 && s->max_nodes > 0);
+  if (!rc && leaves_hidden) s->hidden_arena = d_arena;
   return rc;
 }
 
@@ -589,7 +594,7 @@ int mzx_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, int64_
     return MZX_ERR_INVALID;
   }
   s->hidden_arena = s->carried_arena = nullptr;
-  return search_simulate(s, io, d_arena, (stream_t)stream, false);
+  return search_simulate(s, io, d_arena, (stream_t)stream, SearchStart{});
 }
 
 int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const float* d_root_hidden,
@@ -602,38 +607,8 @@ int mzx_search_run_from_roots(mzx_search* s, const mzx_search_io* io, const floa
     set_error("mzx_search_run_from_roots: missing buffer");
     return MZX_ERR_INVALID;
   }
-  RootOverride ov;
-  ov.hidden = d_root_hidden; ov.priors = d_root_priors; ov.reward = d_root_reward;
   s->hidden_arena = s->carried_arena = nullptr;
-  const bool spare = s->max_nodes > 0;
-#ifndef MZX_HOSTCHECK
-  // the simulations run on the kernel mzx_search_run would use: the residual whole-search kernels read the roots from
-  // the arena, the fully connected one (second generation) takes them as launch arguments instead of running
-  // initial_inference; the first-generation kernel (flag 16, A/B only) stays on the per-operator path here
-  if ((s->mode & 1) && s->fused_ok == 1 && !(s->mode & 16) && !spare) {
-    s->last_kernel = "mzx::fc2_search_kernel";
-    return fc2_run(s, io, d_arena, (stream_t)stream, &ov);
-  }
-  if ((s->mode & 1) && s->fused_ok == 2 && rz_enabled(s->net, true) && !spare) {
-    const int route = wide_search_route(s);
-    if (route != ROUTE_RZ) {
-      s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-      return search_run_rows(s, io, d_arena, (stream_t)stream, &ov, true, route == ROUTE_RT);
-    }
-    return rz_search_run(s, io, d_arena, (stream_t)stream, &ov);
-  }
-  if ((s->mode & 1) && rb_enabled(s->net, true) && row_search_supported(s->p)) {
-    s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
-    const bool whole = !spare && streamed_whole_search(s);
-    rc = search_run_rows(s, io, d_arena, (stream_t)stream, &ov, false, whole);
-    if (!rc && !whole) s->hidden_arena = d_arena;
-    return rc;
-  }
-#endif
-  s->last_kernel = "one kernel per step of a simulation (select / network / expand + back-propagate)";
-  rc = search_run_generic(s, io, d_arena, (stream_t)stream, &ov);
-  if (!rc) s->hidden_arena = d_arena;
-  return rc;
+  return search_simulate(s, io, d_arena, (stream_t)stream, SearchStart{SearchStart::OVERRIDE, {d_root_hidden, d_root_priors, d_root_reward}});
 }
 
 int mzx_search_lockstep_begin(mzx_search* s, const mzx_search_io* io, const double* d_root_priors,
@@ -643,7 +618,7 @@ int mzx_search_lockstep_begin(mzx_search* s, const mzx_search_io* io, const doub
   if (!io || !io->d_legal_actions || !io->d_to_play || !d_root_priors) { set_error("lockstep_begin: missing buffer"); return MZX_ERR_INVALID; }
   s->carried_arena = nullptr;
   s->hidden_arena = s->net ? nullptr : d_arena;    // (a handle without a network carries trees alone)
-  rc = ensure_tables(s, d_arena, (stream_t)stream);
+  rc = ensure_tables(s);
   if (rc) return rc;
   const ArenaView v = arena_view(s, d_arena);
   RootInitOp ri;
@@ -841,7 +816,7 @@ int mzx_search_run_continued(mzx_search* s, const mzx_search_io* io, void* d_are
   s->hidden_arena = nullptr;
   // the route of a fresh search on this handle (search_choice): fc2_search_kernel / rt_search_kernel import the carried
   // trees, the streamed row route and the per-operator path walk them in the arena
-  return search_simulate(s, io, d_arena, st, true);
+  return search_simulate(s, io, d_arena, st, SearchStart{SearchStart::CONTINUED});
 }
 
 // ------------------------------------------------------- observation pipeline

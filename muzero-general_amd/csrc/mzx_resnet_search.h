@@ -394,8 +394,7 @@ inline int rz_search_launch_k(const RzSearchArgs& sa, unsigned grid, size_t lds_
 
 template <bool WLDS, int NW, int MM>
 inline int rz_search_launch_aw(const RzSearchArgs& sa, unsigned grid, size_t lds, stream_t stream) {
-  const bool wide = sa.p.num_actions > FUSED_ROW || 2 * sa.p.support_size + 1 > 2 * FUSED_ROW;
-  if (wide) return rz_search_launch_k<WLDS, NW, 0, MM>(sa, grid, lds, stream);
+  if (row_action_lanes(sa.p) == 0) return rz_search_launch_k<WLDS, NW, 0, MM>(sa, grid, lds, stream);
   if constexpr (NW == 4 && MM == 3) {   // record-form LDS trees: the small-network kernels (tree side 14-18 % of a simulation)
     if (sa.tree_lds == 2)
       return sa.p.num_actions <= 4 ? rz_search_launch_k<WLDS, NW, 4, MM, true>(sa, grid, lds, stream)
@@ -422,40 +421,20 @@ inline bool rz_search_supported(const mzx_search* s) {
   return 4 * (rz_lds_floats(net->rz.g, R, 1, false) + rz_search_extra_floats(s->p)) <= RZ_LDS_BUDGET;
 }
 
-// MCTS.run for B roots, residual network: root by the generic kernels, all simulations in one launch.
-inline int rz_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream,
-                   const RootOverride* ov = nullptr) {
+// MCTS.run for B roots, residual network: root by the generic kernels (fresh, or the caller's roots), all simulations in one
+// launch.  The LDS-resident kernels start every walk at simulation 0: they do not take carried trees.  Names the kernel it
+// launched in s->last_kernel.
+inline int rz_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
+  if (start.kind == SearchStart::CONTINUED) {
+    set_error("the LDS-resident residual search kernels do not continue carried trees");
+    return MZX_ERR_INVALID;
+  }
   const ArenaView v = arena_view(s, d_arena);
   mzx_net* net = s->net;
   const int B = s->p.num_trees;
-  int rc = ensure_tables(s, d_arena, stream);
-  if (rc) return rc;
-
   // ---- root: initial_inference (hidden state -> arena node 0) + root expansion
-  const bool ix_init = rz_enabled(net, false);
-  NetIndex ix;
-  ix.in_nodes = 1; ix.out_nodes = s->p.num_nodes;
-  NetBuffers nb;
-  nb.in = io->d_observation; nb.action = nullptr; nb.hidden = ix_init ? v.arena.hidden : v.dense_out;
-  nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
-  if (!ov) {
-    rc = run_network(net, false, nb, B, stream, ix_init ? &ix : nullptr);
-    if (rc) return rc;
-  }
-  // roots the caller expanded itself (MCTS.run(..., override_root_with=root), self_play.py:275-277): their priors /
-  // reward / hidden state replace initial_inference, the simulations run on the same kernel
-  RootInitOp ri;
-  ri.arena = v.arena; ri.p = v.p; ri.value_logits = v.value; ri.policy_logits = v.policy;
-  ri.ext_priors = ov ? ov->priors : nullptr; ri.ext_root_reward = ov ? ov->reward : nullptr;
-  ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
-  ri.root_predicted_value = io->d_root_predicted_value;
-  MZX_TRY_LAUNCH(launch<64>(ri, stream));
-  if (ov || !ix_init) {
-    HiddenMoveOp mv;
-    mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
-    mv.dense = ov ? const_cast<float*>(ov->hidden) : v.dense_out; mv.node = nullptr; mv.to_arena = 1;
-    MZX_TRY_LAUNCH(launch<256>(mv, stream));
-  }
+  int rc = search_prepare_roots(s, io, d_arena, stream, start, &run_network, rz_enabled(net, false));
+  if (rc) return rc;
 
   // ---- every simulation, one launch
   if (s->p.num_sims > 0) {
@@ -507,13 +486,13 @@ inline int rz_search_run(mzx_search* s, const mzx_search_io* io, void* d_arena, 
         wa.s.sim0 = 0;
         wa.s.prof = ((s->mode & 8) && s->ws_floats >= (int64_t)wgrid * 8) ? (uint32_t*)((char*)d_arena + s->off_ws) : nullptr;
         wa.s.tree_lds = 2;
-        s->last_kernel = wave_k ? "mzx::rz_wave_search_kernel" : "mzx::rz_tile_search_kernel";
+        s->last_kernel = wave_k ? KERNEL_RZ_WAVE : KERNEL_RZ_TILE;
         rc = wave_k ? rz_wave_launch(wa, wgrid, wlds, stream) : rz_tile_launch(wa, wgrid, wlds, stream);
         if (rc) return rc;
         return search_finish(s, io, d_arena, stream);
       }
     }
-    s->last_kernel = "mzx::rz_search_kernel";
+    s->last_kernel = KERNEL_RZ;
     RzSearchArgs sa;
     sa.net = L.a;
     sa.p = v.p;

@@ -44,9 +44,9 @@ inline bool row_search_supported(const SearchParams& p) { return p.num_actions <
 // workgroups per CU, LDS bytes, threads per workgroup}, zeros when the kernel does not take the search.
 bool rt_search_supported(const mzx_search* s);
 void rt_search_shape(const mzx_search* s, int32_t out[6]);
-// continued = true: carried trees (mzx_tree_carry.h) -- every walk reads the root's visit count from its tree, and each tree's
+// A CONTINUED start: carried trees (mzx_tree_carry.h) -- every walk reads the root's visit count from its tree, and each tree's
 // next leaf is its own node count (carried counts differ from tree to tree).
-int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued = false);
+int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start);
 
 // One selection walk of tree `t` by its 16-lane row (self_play.py:325-334): the walk's result for the network
 // (parent node, action, leaf) and the row's share of the path -- 64 ints at `rs`: SelCtx (5), action, then (node, parent,
@@ -324,49 +324,24 @@ inline int wide_search_route(const mzx_search* s) {
   return streamed_whole_search(s) ? ROUTE_RT : ROUTE_ROWS;
 }
 
-// continued = true: the trees in the arena are carried trees whose roots ContinueRootOp prepared (mzx_tree_carry.h):
-// no initial_inference, no root expansion, and the walks read the root's visit count from the tree.
-inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream,
-                   const RootOverride* ov = nullptr, bool force_streamed = false, bool whole_search = false,
-                   bool continued = false) {
+// force_streamed: the network would run on the LDS-resident engine by default; this search runs it on the streamed one
+// without touching the network handle's mode.  whole_search: rt_search_kernel instead of the per-simulation launches
+// (SearchChoice carries both).  Renames s->last_kernel when it runs two half-shards.
+inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start,
+                           bool force_streamed, bool whole_search) {
   const ArenaView v = arena_view(s, d_arena);
   mzx_net* net = s->net;
   const int B = s->p.num_trees;
-  int rc = ensure_tables(s, d_arena, stream);
+  const NetworkRunner run_network = !force_streamed ? &mzx::run_network :
+      +[](const mzx_net* n, bool recurrent, const NetBuffers& b, int batch, stream_t st, const NetIndex* ixp) {
+        return rb_run_program(n, recurrent, b, batch, st, ixp);
+      };
+  int rc = search_prepare_roots(s, io, d_arena, stream, start, run_network,
+                                force_streamed || rz_enabled(net, false) || rb_enabled(net, false));
   if (rc) return rc;
-  // (force_streamed: the network would run on the LDS-resident engine by default; this search runs it on the streamed
-  // one -- row_search_preferred -- without touching the network handle's mode)
-  auto run_network = [&](mzx_net* n, bool recurrent, const NetBuffers& b, int batch, stream_t st, const NetIndex* ixp) {
-    return force_streamed ? rb_run_program(n, recurrent, b, batch, st, ixp) : mzx::run_network(n, recurrent, b, batch, st, ixp);
-  };
-  const bool ix_init = force_streamed || rz_enabled(net, false) || rb_enabled(net, false);
-  NetIndex ix;
-  ix.in_nodes = 1; ix.out_nodes = s->p.num_nodes;
-  NetBuffers nb;
-  nb.in = io->d_observation; nb.action = nullptr; nb.hidden = ix_init ? v.arena.hidden : v.dense_out;
-  nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
-  if (!ov && !continued) {
-    rc = run_network(net, false, nb, B, stream, ix_init ? &ix : nullptr);
-    if (rc) return rc;
-  }
-  // roots the caller expanded itself (MCTS.run(..., override_root_with=root), self_play.py:275-277): their priors /
-  // reward / hidden state replace initial_inference, the simulations run on the same kernel
-  RootInitOp ri;
-  ri.arena = v.arena; ri.p = v.p; ri.value_logits = v.value; ri.policy_logits = v.policy;
-  ri.ext_priors = ov ? ov->priors : nullptr; ri.ext_root_reward = ov ? ov->reward : nullptr;
-  ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
-  ri.root_predicted_value = io->d_root_predicted_value;
-  if (!continued) MZX_TRY_LAUNCH(launch<64>(ri, stream));
-  if (!continued && (ov || !ix_init)) {
-    HiddenMoveOp mv;
-    mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
-    mv.dense = ov ? const_cast<float*>(ov->hidden) : v.dense_out; mv.node = nullptr; mv.to_arena = 1;
-    MZX_TRY_LAUNCH(launch<256>(mv, stream));
-  }
   // ---- the simulations, all of them in one launch (rt_search_kernel, mzx_tower_search.inc) ...
   if (whole_search) {
-    s->last_kernel = "mzx::rt_search_kernel";
-    rc = rt_search_simulations(s, io, d_arena, stream, continued);
+    rc = rt_search_simulations(s, io, d_arena, stream, start);
     if (rc) return rc;
     return search_finish(s, io, d_arena, stream);
   }
@@ -397,10 +372,8 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
     }
     if (s->side_stream) parts = 2;
   }
-  if (parts == 2)
-    s->last_kernel = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel, two half-shards on two streams";
-  const bool wide = s->p.num_actions > FUSED_ROW || 2 * s->p.support_size + 1 > 2 * FUSED_ROW;
-  const int aw = wide ? 0 : (s->p.num_actions <= 4 ? 4 : 16);
+  if (parts == 2) s->last_kernel = KERNEL_ROWS_SPLIT;
+  const int aw = row_action_lanes(s->p);
   const int F = 2 * s->p.support_size + 1, A = s->p.num_actions;
   const int64_t node_floats = (int64_t)s->p.num_nodes * s->p.hidden_size;
   RowSearchArgs as[2];
@@ -436,7 +409,7 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
     for (int k = 0; k < s->p.num_sims; ++k) {
       for (int h = 0; h < parts; ++h) {
         RowSearchArgs& a = as[h];
-        a.sim = continued ? -1 : k;
+        a.sim = start.kind == SearchStart::CONTINUED ? -1 : k;
         MZX_TRY_LAUNCH(aw == 0 ? row_search_step<0>(a, streams[h]) : aw == 4 ? row_search_step<4>(a, streams[h]) : row_search_step<16>(a, streams[h]));
         const int nrc = run_network(net, true, nbs[h], count[h], streams[h], &ixs[h]);
         if (nrc) return nrc;

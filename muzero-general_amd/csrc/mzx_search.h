@@ -5,6 +5,9 @@
 // Reference: MCTS.run, /root/reference/self_play.py:260-361 -- the body of one
 // simulation (:319-355) becomes select -> gather hidden -> recurrent_inference
 // -> expand+backpropagate -> scatter hidden, each over all B trees at once.
+//
+// SearchStart says how the roots of a search arrive (fresh / given by the caller / carried trees); every host driver
+// takes one, and search_prepare_roots is the root preparation the drivers with an arena-resident root share.
 #pragma once
 #include <memory>
 #include <vector>
@@ -128,7 +131,7 @@ inline int upload_tables(mzx_search* s) {
   MZX_TRY_LAUNCH(copy_h2d_blocking(s->d_tables + n, s->h_sqrt.data(), sizeof(double) * n));
   return MZX_OK;
 }
-inline int ensure_tables(mzx_search* s, void*, stream_t) {
+inline int ensure_tables(const mzx_search* s) {
   if (!s->d_tables) { set_error("search handle has no device tables"); return MZX_ERR_RUNTIME; }
   return MZX_OK;
 }
@@ -150,45 +153,92 @@ struct RootOverride {
   const double* reward;   // [B]
 };
 
+// Where the roots of a search come from.  FRESH: initial_inference on the observations (mzx_search_run); OVERRIDE: the
+// caller's roots (mzx_search_run_from_roots); CONTINUED: the trees in the arena are carried trees whose roots
+// ContinueRootOp prepared (mzx_search_run_continued, mzx_tree_carry.h) -- no initial_inference, no root expansion, and a
+// walk reads the root's visit count from its tree.
+struct SearchStart {
+  enum Kind { FRESH, OVERRIDE, CONTINUED } kind = FRESH;
+  RootOverride ov{};   // OVERRIDE only
+};
+
+// The routes of a search (search_choice in mzx_lib.cpp decides, search_simulate launches) and the names
+// mzx_search_kernel_name reports for them -- each string once; tests match them.
+enum SearchPath { PATH_GENERIC = 0, PATH_RZ, PATH_ROWS, PATH_RT, PATH_FC2, PATH_FUSED_FC };
+struct SearchChoice {
+  int path = PATH_GENERIC;
+  bool force_streamed = false;   // a network the LDS-resident engine would run: the streamed engine for this search
+};
+#define MZX_STREAMED_BETWEEN "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between "
+constexpr const char* KERNEL_GENERIC = "one kernel per step of a simulation (select / network / expand + back-propagate)";
+constexpr const char* KERNEL_GENERIC_STREAMED = MZX_STREAMED_BETWEEN "one-thread-per-tree kernels";
+#define MZX_ROW_KERNELS MZX_STREAMED_BETWEEN "mzx::row_select_kernel / mzx::row_expand_backprop_kernel"
+constexpr const char* KERNEL_ROWS = MZX_ROW_KERNELS;
+constexpr const char* KERNEL_ROWS_SPLIT = MZX_ROW_KERNELS ", two half-shards on two streams";
+#undef MZX_ROW_KERNELS
+#undef MZX_STREAMED_BETWEEN
+constexpr const char* KERNEL_RT = "mzx::rt_search_kernel";
+constexpr const char* KERNEL_FC2 = "mzx::fc2_search_kernel";
+constexpr const char* KERNEL_FUSED_FC = "mzx::fused_fc_search";
+constexpr const char* KERNEL_RZ = "mzx::rz_search_kernel";            // PATH_RZ: rz_search_run picks one of these three
+constexpr const char* KERNEL_RZ_WAVE = "mzx::rz_wave_search_kernel";
+constexpr const char* KERNEL_RZ_TILE = "mzx::rz_tile_search_kernel";
+
+// initial_inference of a driver: run_network, or the streamed engine forced (search_run_rows)
+using NetworkRunner = int (*)(const mzx_net*, bool, const NetBuffers&, int, stream_t, const NetIndex*);
+
+// The roots of a search whose trees live in the arena (the per-operator path, the row route, the residual whole-search
+// kernels): the table check, then
+//   FRESH      initial_inference, RootInitOp from its logits, and HiddenMoveOp from the dense staging buffer unless the
+//              engine wrote node 0 of the arena's store [B][N][Hf] itself (writes_node0: it takes a NetIndex);
+//   OVERRIDE   no network: RootInitOp from the given priors / rewards, HiddenMoveOp from the given hidden states;
+//   CONTINUED  nothing more.
+inline int search_prepare_roots(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start,
+                                NetworkRunner run, bool writes_node0) {
+  if (int rc = ensure_tables(s)) return rc;
+  if (start.kind == SearchStart::CONTINUED) return MZX_OK;
+  const ArenaView v = arena_view(s, d_arena);
+  const bool fresh = start.kind == SearchStart::FRESH;
+  const int B = s->p.num_trees;
+  if (fresh) {
+    NetIndex ix;
+    ix.in_nodes = 1; ix.out_nodes = s->p.num_nodes;   // dense observation in, node 0 out
+    NetBuffers nb;
+    nb.in = io->d_observation; nb.action = nullptr; nb.hidden = writes_node0 ? v.arena.hidden : v.dense_out;
+    nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
+    if (int rc = run(s->net, false, nb, B, stream, writes_node0 ? &ix : nullptr)) return rc;
+  }
+  RootInitOp ri;
+  ri.arena = v.arena; ri.p = v.p; ri.value_logits = v.value; ri.policy_logits = v.policy;
+  ri.ext_priors = fresh ? nullptr : start.ov.priors; ri.ext_root_reward = fresh ? nullptr : start.ov.reward;
+  ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
+  ri.root_predicted_value = io->d_root_predicted_value;
+  MZX_TRY_LAUNCH(launch<64>(ri, stream));
+  if (!fresh || !writes_node0) {
+    HiddenMoveOp mv;
+    mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
+    mv.dense = fresh ? v.dense_out : const_cast<float*>(start.ov.hidden); mv.node = nullptr; mv.to_arena = 1;
+    MZX_TRY_LAUNCH(launch<256>(mv, stream));
+  }
+  return MZX_OK;
+}
+
 // Generic path: one kernel per operator (any network configuration).
-// continued = true: the trees in the arena are carried trees whose roots ContinueRootOp prepared (mzx_tree_carry.h):
-// no initial_inference, no root expansion.
-inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream,
-                              const RootOverride* ov = nullptr, bool continued = false) {
+inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
   const ArenaView v = arena_view(s, d_arena);
   mzx_net* net = s->net;
   const int B = s->p.num_trees;
-  int rc = ensure_tables(s, d_arena, stream);
-  if (rc) return rc;
-
   // With the fused network engine the per-node hidden states are read from / written to the arena
   // store [B][N][Hf] directly (NetIndex); the per-operator engine goes through dense staging copies.
   const bool ix_init = rz_enabled(net, false) || rb_enabled(net, false), ix_rec = rz_enabled(net, true) || rb_enabled(net, true);
+  int rc = search_prepare_roots(s, io, d_arena, stream, start, &run_network, ix_init);
+  if (rc) return rc;
+
   NetIndex ix;
-  ix.in_nodes = 1; ix.out_nodes = s->p.num_nodes;   // root: dense observation in, node 0 out
-
   NetBuffers nb;
-  nb.in = io->d_observation; nb.action = nullptr; nb.hidden = ix_init ? v.arena.hidden : v.dense_out;
   nb.value = v.value; nb.reward = v.reward; nb.policy = v.policy; nb.workspace = v.ws;
-  if (!ov && !continued) {
-    rc = run_network(net, false, nb, B, stream, ix_init ? &ix : nullptr);
-    if (rc) return rc;
-  }
-
-  RootInitOp ri;
-  ri.arena = v.arena; ri.p = v.p; ri.value_logits = v.value; ri.policy_logits = v.policy;
-  ri.ext_priors = ov ? ov->priors : nullptr; ri.ext_root_reward = ov ? ov->reward : nullptr;
-  ri.legal = io->d_legal_actions; ri.to_play = io->d_to_play; ri.noise = io->d_noise;
-  ri.root_predicted_value = io->d_root_predicted_value;
-  if (!continued) MZX_TRY_LAUNCH(launch<64>(ri, stream));
-
   HiddenMoveOp mv;
   mv.arena = v.arena; mv.num_trees = B; mv.num_nodes = s->p.num_nodes; mv.hidden_size = s->p.hidden_size;
-  if (!continued && (ov || !ix_init)) {
-    mv.dense = ov ? const_cast<float*>(ov->hidden) : v.dense_out; mv.node = nullptr; mv.to_arena = 1;
-    MZX_TRY_LAUNCH(launch<256>(mv, stream));
-  }
-
   SelectOp sel;
   sel.arena = v.arena; sel.p = v.p; sel.tape = io->d_tape;
   sel.sel_parent = v.sel_parent; sel.sel_action = v.sel_action; sel.sel_leaf = v.sel_leaf;

@@ -927,7 +927,7 @@ void rt_search_shape(const mzx_search* s, int32_t out[6]) {
 }
 
 // The simulations of a search whose roots are in the arena (RootInitOp done, root states in the node store).
-int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, bool continued) {
+int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena, stream_t stream, const SearchStart& start) {
   RtPlan P = rt_plan(s);
   if (!P.ok) { set_error("tower whole-search kernel: configuration not supported"); return MZX_ERR_INVALID; }
   const mzx_net* net = s->net;
@@ -937,14 +937,14 @@ int rt_search_simulations(mzx_search* s, const mzx_search_io* io, void* d_arena,
   a.p = v.p; a.L = s->L;
   a.trees = v.arena.trees; a.tape = io->d_tape; a.hidden = v.arena.hidden;
   a.flat = net->d_flat; a.der = net->d_derived;
-  a.num_sims = s->p.num_sims; a.sim0 = continued ? -1 : 0; a.batch = s->p.num_trees;
+  a.num_sims = s->p.num_sims; a.sim0 = start.kind == SearchStart::CONTINUED ? -1 : 0; a.batch = s->p.num_trees;
   a.magic_hw = rt_magic(a.H * a.W); a.magic_w = rt_magic(a.W); a.magic_rows = rt_magic(16 * a.mtiles);
   a.magic_chw = rt_magic(a.C * a.H * a.W); a.magic_c = rt_magic(a.C);
   RbTowerShape sh;
   rt_grid(R.towers[0], P.T, P.waves, sh);
   rt_fill_tower(net, R.towers[0], sh, a.tw[0]);
   rt_fill_tower(net, R.towers[1], sh, a.tw[1]);
-  const bool wide = s->p.num_actions > FUSED_ROW || 2 * s->p.support_size + 1 > 2 * FUSED_ROW;
+  const bool wide = row_action_lanes(s->p) == 0;
   // (a last row group of MT - 1 tiles: the instantiation whose short waves skip the tile that is not there)
   const bool short_group = tune(TUNE_RT_SHORT) != 0 && sh.WM >= 2 && sh.MT >= 2 && sh.mtiles - (sh.WM - 1) * sh.MT == sh.MT - 1;
   RtSearchFn fn = rt_pick(P.MT, wide, s->p.num_actions, short_group);
