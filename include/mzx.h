@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 2
+#define MZX_ABI_VERSION 3
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -512,6 +512,56 @@ int mzx_selfplay_select(mzx_rng* r, const mzx_move* m, const int32_t* n_legal, c
 int mzx_replay_priorities(const double* d_root_values, const double* d_rewards, const int32_t* d_to_play, int32_t num_games,
                           int32_t moves, int32_t td_steps, const double* d_discount_pow, double per_alpha, double* d_targets,
                           float* d_priorities, float* d_game_priority, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Device-resident replay store (mzx.replay.DeviceGameStore; csrc/mzx_replay.h, csrc/mzx_obs.h): finished games stay in
+ * HBM and ReplayBuffer.get_batch (replay_buffer.py:70-138) assembles the trainer's tensors there.  Stateless like the
+ * entries above: the caller owns the pool, every pointer is a device pointer.
+ * Pool: a game of T searched positions starts at pool row `base` and owns rows base .. base + T, one row per history
+ * index (root_values / child_visits / values use the first T of them).  The caller keeps 0 <= base, base + T < rows.
+ * The Python store allocates the rows circularly and bounds the buffer in POSITIONS besides replay_buffer_size in games
+ * (the one deliberate difference from the reference: the oldest games leave store and stock buffer alike when a new game
+ * does not fit); mzx.replay.trainer_tensors(batch, device) binds the outputs to a trainer (trainer.py:140-153).
+ * mzx_replay_values: compute_target_value (:230-262) of every position of num_games games (d_base[g], d_len[g] = T) into
+ *   pool->d_values, bit for bit (the arithmetic of mzx_replay_priorities; d_discount_pow [td_steps + 1] as there).  One
+ *   launch for all the games an ingest or a reanalyse update touched.
+ * mzx_replay_batch: sample n is position d_pos[n] (0 <= pos <= T) of the game (d_base[n], d_len[n]).
+ *   d_observation [n][channels * (stacked + 1) + stacked][height][width] f32 = get_stacked_observations(pos, stacked, A)
+ *     after torch.tensor(...).float(), the values of mzx_obs_stack; NULL skips the gather.
+ *   targets, make_target (:264-303) for unroll step u = 0 .. num_unroll_steps: d_value / d_reward [n][U + 1] f64,
+ *     d_policy [n][U + 1][A] f64, d_action [n][U + 1] i64 -- inside the game the stored entries; at index T value 0, the
+ *     stored reward and action, the uniform policy 1 / A; past T zeros, 1 / A and d_absorbing_actions[n][u], the actions the
+ *     CALLER drew (numpy.random.choice(action_space), :301; entries of other steps are not read) --, d_gradient_scale
+ *     [n][U + 1] i64 = min(U, T + 1 - pos) (:103-111).  d_value == NULL skips the targets (then only the gather runs).
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_replay_pool {
+  const float* d_frames;           /* [rows][channels][height][width] */
+  const int32_t* d_actions;        /* [rows] action_history */
+  const double* d_rewards;         /* [rows] reward_history */
+  const int32_t* d_to_play;        /* [rows] to_play_history */
+  const double* d_root_values;     /* [rows] root_values, or the reanalysed values */
+  const double* d_child_visits;    /* [rows][action_space_size] */
+  double* d_values;                /* [rows] derived: mzx_replay_values */
+  int64_t rows;
+  int32_t channels, height, width; /* config.observation_shape */
+  int32_t action_space_size;       /* len(config.action_space) */
+} mzx_replay_pool;
+typedef struct mzx_replay_batch_io {
+  const int64_t* d_base;           /* [num_samples] */
+  const int32_t* d_len;            /* [num_samples] T */
+  const int32_t* d_pos;            /* [num_samples] */
+  const int32_t* d_absorbing_actions; /* [num_samples][num_unroll_steps + 1] */
+  int32_t num_samples, num_unroll_steps, stacked_observations, reserved;
+  float* d_observation;
+  double* d_value;
+  double* d_reward;
+  double* d_policy;
+  int64_t* d_action;
+  int64_t* d_gradient_scale;
+} mzx_replay_batch_io;
+int mzx_replay_values(const mzx_replay_pool* pool, const int64_t* d_base, const int32_t* d_len, int32_t num_games,
+                      int32_t td_steps, const double* d_discount_pow, void* stream);
+int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of

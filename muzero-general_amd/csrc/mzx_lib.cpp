@@ -1211,6 +1211,80 @@ int mzx_replay_priorities(const double* d_root_values, const double* d_rewards, 
   return MZX_OK;
 }
 
+// ------------------------------------------------------------- device-resident replay store: values + batches
+
+int mzx_replay_values(const mzx_replay_pool* pool, const int64_t* d_base, const int32_t* d_len, int32_t num_games,
+                      int32_t td_steps, const double* d_discount_pow, void* stream) {
+  if (!pool) { set_error("mzx_replay_values: null pool"); return MZX_ERR_INVALID; }
+  if (num_games < 0 || td_steps < 0) { set_error("mzx_replay_values: negative argument"); return MZX_ERR_INVALID; }
+  if (num_games == 0) return MZX_OK;
+  if (!pool->d_root_values || !pool->d_rewards || !pool->d_to_play || !pool->d_values || !d_base || !d_len || !d_discount_pow) {
+    set_error("mzx_replay_values: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  ReplayValuesOp op;
+  op.root_values = pool->d_root_values; op.rewards = pool->d_rewards; op.to_play = pool->d_to_play;
+  op.discount_pow = d_discount_pow; op.values = pool->d_values; op.base = d_base; op.len = d_len;
+  op.num_games = num_games; op.td_steps = td_steps;
+  MZX_TRY_LAUNCH(launch<64>(op, (stream_t)stream));
+  return MZX_OK;
+}
+
+extern "C++" {
+template <int VEC>
+static int replay_obs_launch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, stream_t stream) {
+  ReplayObsOp<VEC> op;
+  op.frames = pool->d_frames; op.actions = pool->d_actions; op.base = io->d_base; op.pos = io->d_pos; op.out = io->d_observation;
+  op.C = pool->channels; op.hwv = pool->height * pool->width / VEC; op.k = io->stacked_observations;
+  op.A = pool->action_space_size; op.n_out = io->num_samples;
+  op.c_out = pool->channels * (io->stacked_observations + 1) + io->stacked_observations;
+  op.pieces = (op.hwv + 64 * OBS_UNROLL - 1) / (64 * OBS_UNROLL);
+  if ((int64_t)op.n_out * op.c_out * op.pieces >= (int64_t)1 << 26) {   // 32-bit group index; split the call
+    set_error("mzx_replay_batch: %d samples x %d planes exceed one launch; gather in smaller batches", op.n_out, op.c_out);
+    return MZX_ERR_INVALID;
+  }
+  MZX_TRY_LAUNCH(launch<256>(op, stream));
+  return MZX_OK;
+}
+}  // extern "C++"
+
+int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream) {
+  if (!pool || !io) { set_error("mzx_replay_batch: null argument"); return MZX_ERR_INVALID; }
+  if (io->num_samples < 0 || io->num_unroll_steps < 0 || io->stacked_observations < 0) {
+    set_error("mzx_replay_batch: negative argument");
+    return MZX_ERR_INVALID;
+  }
+  if (pool->action_space_size <= 0) { set_error("mzx_replay_batch: action_space_size must be positive"); return MZX_ERR_INVALID; }
+  if (io->num_samples == 0) return MZX_OK;
+  if (!io->d_base || !io->d_len || !io->d_pos) { set_error("mzx_replay_batch: missing sample arrays"); return MZX_ERR_INVALID; }
+  if (io->d_observation) {
+    if (pool->channels < 1 || pool->height < 1 || pool->width < 1 ||
+        (int64_t)pool->channels * (io->stacked_observations + 1) + io->stacked_observations >= (1 << 20)) {
+      set_error("mzx_replay_batch: invalid observation shape %d x %d x %d", pool->channels, pool->height, pool->width);
+      return MZX_ERR_INVALID;
+    }
+    if (!pool->d_frames || (io->stacked_observations > 0 && !pool->d_actions)) { set_error("mzx_replay_batch: missing pool frames / actions"); return MZX_ERR_INVALID; }
+    const bool vec = (pool->height * pool->width) % 4 == 0 && ((uintptr_t)pool->d_frames % 16) == 0 &&
+                     ((uintptr_t)io->d_observation % 16) == 0;
+    const int rc = vec ? replay_obs_launch<4>(pool, io, (stream_t)stream) : replay_obs_launch<1>(pool, io, (stream_t)stream);
+    if (rc) return rc;
+  }
+  if (io->d_value) {
+    if (!io->d_reward || !io->d_policy || !io->d_action || !io->d_gradient_scale || !io->d_absorbing_actions || !pool->d_actions ||
+        !pool->d_rewards || !pool->d_child_visits || !pool->d_values) {
+      set_error("mzx_replay_batch: missing target buffer");
+      return MZX_ERR_INVALID;
+    }
+    ReplayTargetsOp op;
+    op.actions = pool->d_actions; op.rewards = pool->d_rewards; op.child_visits = pool->d_child_visits; op.values = pool->d_values;
+    op.base = io->d_base; op.len = io->d_len; op.pos = io->d_pos; op.absorbing = io->d_absorbing_actions;
+    op.value = io->d_value; op.reward = io->d_reward; op.policy = io->d_policy; op.action = io->d_action;
+    op.gradient_scale = io->d_gradient_scale; op.n = io->num_samples; op.U = io->num_unroll_steps; op.A = pool->action_space_size;
+    MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
+  }
+  return MZX_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------- natively stepped games + the round loop of a shard

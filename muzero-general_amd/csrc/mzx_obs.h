@@ -26,9 +26,36 @@ namespace mzx {
 // Work split: one wavefront-sized group of 64 elements moves one 4 KB piece (UNROLL x 64 vectors) of
 // one output plane, so the (sample, plane) decode -- four 32-bit divisions -- is shared by UNROLL
 // 16-byte moves per thread and every load / store instruction of a wave covers 1 KB contiguous.
+constexpr int OBS_UNROLL = 4;
+
+// One lane's share of a piece: copies from `src`, or writes `fill` where the plane has no source.
+template <int VEC>
+MZX_HD inline void obs_move_piece(const float* src, float fill, float* dst, uint32_t piece, uint32_t lane, int32_t hwv) {
+  for (int u = 0; u < OBS_UNROLL; ++u) {
+    const uint32_t p = piece * (64u * OBS_UNROLL) + (uint32_t)u * 64u + lane;
+    if (p >= (uint32_t)hwv) break;
+    if (VEC == 4) {
+#ifdef MZX_HOSTCHECK
+      struct alignas(16) F4 { float x, y, z, w; };
+      F4 v = {fill, fill, fill, fill};
+      if (src) v = *(const F4*)(src + (int64_t)p * 4);
+      *(F4*)(dst + (int64_t)p * 4) = v;
+#else
+      // streamed once in, once out: non-temporal 16-byte accesses keep the frames from displacing each other in L2
+      typedef float v4 __attribute__((ext_vector_type(4)));
+      v4 v = {fill, fill, fill, fill};
+      if (src) v = __builtin_nontemporal_load((const v4*)(src + (int64_t)p * 4));
+      __builtin_nontemporal_store(v, (v4*)(dst + (int64_t)p * 4));
+#endif
+    } else {
+      dst[p] = src ? src[p] : fill;
+    }
+  }
+}
+
 template <int VEC>
 struct ObsStackOp {
-  static constexpr int UNROLL = 4;
+  static constexpr int UNROLL = OBS_UNROLL;
   const float* frames;
   const int32_t* actions;
   const int32_t* game;   // nullable
@@ -63,27 +90,44 @@ struct ObsStackOp {
         }
       }
     }
-    float* dst = out + (int64_t)plane * plane_floats;
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t p = piece * (64u * UNROLL) + (uint32_t)u * 64u + lane;
-      if (p >= (uint32_t)hwv) break;
-      if (VEC == 4) {
-#ifdef MZX_HOSTCHECK
-        struct alignas(16) F4 { float x, y, z, w; };
-        F4 v = {fill, fill, fill, fill};
-        if (src) v = *(const F4*)(src + (int64_t)p * 4);
-        *(F4*)(dst + (int64_t)p * 4) = v;
-#else
-        // streamed once in, once out: non-temporal 16-byte accesses keep the frames from displacing each other in L2
-        typedef float v4 __attribute__((ext_vector_type(4)));
-        v4 v = {fill, fill, fill, fill};
-        if (src) v = __builtin_nontemporal_load((const v4*)(src + (int64_t)p * 4));
-        __builtin_nontemporal_store(v, (v4*)(dst + (int64_t)p * 4));
-#endif
-      } else {
-        dst[p] = src ? src[p] : fill;
+    obs_move_piece<VEC>(src, fill, out + (int64_t)plane * plane_floats, piece, lane, hwv);
+  }
+};
+
+// The same stacked input gathered out of the RAGGED replay pool (csrc/mzx_replay.h; mzx.replay.DeviceGameStore): sample n
+// is history index pos[n] of the game whose rows start at base[n] -- frames [rows][C][H][W], actions [rows] --, so a
+// source plane is addressed by the pool row base + index: no ring, no common game stride.  Values and work split are
+// ObsStackOp's.  The 33 frame groups of one sample are shared with its neighbours in time (and with the samples of the
+// same game in a batch), so the loads mostly hit L2; the launch is bound by its writes.
+template <int VEC>
+struct ReplayObsOp {
+  const float* frames;
+  const int32_t* actions;
+  const int64_t* base;   // [n_out]
+  const int32_t* pos;    // [n_out]
+  float* out;
+  int32_t C, hwv /* H*W / VEC */, k, A, n_out, c_out, pieces /* per plane */;
+
+  MZX_HD size_t size() const { return (size_t)n_out * c_out * pieces * 64; }
+  MZX_HD void operator()(size_t i) const {
+    const uint32_t lane = (uint32_t)i & 63u, grp = (uint32_t)(i >> 6);
+    const uint32_t plane = grp / (uint32_t)pieces, piece = grp % (uint32_t)pieces;
+    const int c = (int)(plane % (uint32_t)c_out), n = (int)(plane / (uint32_t)c_out);
+    const int t = pos[n];
+    const int64_t row = base[n] + t;
+    const int64_t plane_floats = (int64_t)hwv * VEC;
+    const float* src = nullptr;
+    float fill = 0.f;
+    if (c < C) {
+      src = frames + (row * C + c) * plane_floats;
+    } else {
+      const int j = (c - C) / (C + 1), r = (c - C) % (C + 1);
+      if (t - 1 - j >= 0) {                 // history index t - 1 - j; before the game: zeros
+        if (r < C) src = frames + ((row - 1 - j) * C + r) * plane_floats;
+        else fill = (float)((double)actions[row - j] / (double)A);      // action_history[t - j]
       }
     }
+    obs_move_piece<VEC>(src, fill, out + (int64_t)plane * plane_floats, piece, lane, hwv);
   }
 };
 

@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 2
+ABI_VERSION = 3
 MOVE_NO_SYNC = 1
 
 c_i32, c_i64, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
@@ -108,6 +108,24 @@ class ObsLayout(ctypes.Structure):
     ]
 
 
+class ReplayPool(ctypes.Structure):
+    """``mzx_replay_pool``: the column pointers of a device-resident replay store (mzx.replay.DeviceGameStore)."""
+    _fields_ = [
+        ("d_frames", c_vp), ("d_actions", c_vp), ("d_rewards", c_vp), ("d_to_play", c_vp), ("d_root_values", c_vp),
+        ("d_child_visits", c_vp), ("d_values", c_vp), ("rows", c_i64), ("channels", c_i32), ("height", c_i32),
+        ("width", c_i32), ("action_space_size", c_i32),
+    ]
+
+
+class ReplayBatchIO(ctypes.Structure):
+    """``mzx_replay_batch_io``: the samples and output tensors of one mzx_replay_batch call."""
+    _fields_ = [
+        ("d_base", c_vp), ("d_len", c_vp), ("d_pos", c_vp), ("d_absorbing_actions", c_vp), ("num_samples", c_i32),
+        ("num_unroll_steps", c_i32), ("stacked_observations", c_i32), ("reserved", c_i32), ("d_observation", c_vp),
+        ("d_value", c_vp), ("d_reward", c_vp), ("d_policy", c_vp), ("d_action", c_vp), ("d_gradient_scale", c_vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/mzx.h declares
 PROTOTYPES = {
     "mzx_abi_version": (ctypes.c_int, []),
@@ -180,6 +198,8 @@ PROTOTYPES = {
     "mzx_rng_choice_weighted": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "mzx_selfplay_search": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_i64, c_vp]),
     "mzx_replay_priorities": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_replay_values": (ctypes.c_int, [ctypes.POINTER(ReplayPool), c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mzx_replay_batch": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplayBatchIO), c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

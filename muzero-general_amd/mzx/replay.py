@@ -13,13 +13,18 @@ operation over all positions) and stores them on the ``GameHistory``; ``save_gam
 (replay_buffer.py:306-373): same constructor and ``reanalyse(replay_buffer, shared_storage)`` loop, with the
 per-game work -- stacked observations of every position, one batched ``initial_inference``, value decode --
 on the device (``mzx.observations.stack_history`` + the network kernels + ``mzx_support_to_scalar``).
+
+``DeviceGameStore`` keeps finished games in HBM (a ragged pool, csrc/mzx_replay.h) so that ``ReplayBuffer(...,
+device_store=store).get_batch()`` assembles the trainer's tensors on the device (``mzx_replay_batch``): the draws stay
+numpy's, in the reference's order, and only fill index arrays.  ``trainer_tensors`` is the binding line of a trainer.
 """
+import ctypes
 import time
 
 import numpy
 import torch
 
-from . import models, observations
+from . import _lib, models, observations
 from .history import gc_paused
 
 
@@ -226,6 +231,226 @@ def fill_initial_priorities_many(histories, config, backend=None):
     return filled
 
 
+class StoreFull(RuntimeError):
+    """The pool of a ``DeviceGameStore`` has no contiguous room for the game(s): release older games first."""
+
+
+class DeviceGameStore:
+    """
+    Finished games resident on the device, for ``ReplayBuffer(..., device_store=...)`` and ``Reanalyse``.
+
+    One RAGGED pool of ``max_positions`` rows (include/mzx.h ``mzx_replay_pool``): a game of T searched positions takes
+    T + 1 contiguous rows -- one per history index -- of the columns frames [C][H][W] fp32, actions i32, rewards f64,
+    to_play i32, root_values f64 (the reanalysed values when the history carries them, as ``n_step_values`` reads them),
+    child_visits [A] f64 and the derived n-step ``values`` f64 (``mzx_replay_values``: compute_target_value bit for bit).
+    The allocator is circular because the stock buffer only ever evicts its oldest game (replay_buffer.py:58-61): a new
+    game goes to the head, wraps to row 0 when the room up to the end of the pool is too short, and the rows of the
+    oldest resident games are what a release gives back.  ``games`` maps game_id -> (base, T) in allocation order.
+    A game is uploaded ONCE (``add`` / ``add_many``); batches are gathered from the pool (``batch``, ``stacked``).
+    """
+
+    def __init__(self, config, backend, max_positions):
+        self.config, self.backend = config, backend
+        self.shape = tuple(int(v) for v in config.observation_shape)
+        if len(self.shape) != 3 or min(self.shape) < 1:
+            raise ValueError("observation_shape must be (channels, height, width)")
+        self.A = len(config.action_space)
+        self.k = int(config.stacked_observations)
+        self.rows = int(max_positions)
+        if self.rows < 1 or self.A < 1:
+            raise ValueError("max_positions and the action space must be positive")
+        z = backend.zeros
+        self.frames = z((self.rows,) + self.shape, torch.float32)
+        self.actions, self.to_play = z((self.rows,), torch.int32), z((self.rows,), torch.int32)
+        self.rewards, self.root_values, self.values = (z((self.rows,), torch.float64) for _ in range(3))
+        self.child_visits = z((self.rows, self.A), torch.float64)
+        self.sample_shape = (self.shape[0] * (self.k + 1) + self.k,) + self.shape[1:]
+        pool = self.pool = _lib.ReplayPool()
+        pool.d_frames, pool.d_actions, pool.d_rewards = self.frames.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr()
+        pool.d_to_play, pool.d_root_values = self.to_play.data_ptr(), self.root_values.data_ptr()
+        pool.d_child_visits, pool.d_values = self.child_visits.data_ptr(), self.values.data_ptr()
+        pool.rows, pool.action_space_size = self.rows, self.A
+        pool.channels, pool.height, pool.width = self.shape
+        td = int(config.td_steps)
+        self._discount_pow = self._up(numpy.array([config.discount ** i for i in range(td + 1)], dtype=numpy.float64))
+        self.games = {}       # game_id -> (base, T), oldest allocation first
+        self._head = 0        # next free row
+
+    def __contains__(self, game_id):
+        return game_id in self.games
+
+    def __len__(self):
+        return len(self.games)
+
+    def _up(self, array):
+        return torch.from_numpy(array).to(self.backend.device, non_blocking=True)
+
+    # ---- allocator
+    def _find(self, n, head, tail):
+        """Base of n contiguous free rows given the head and the base of the oldest resident game (None: empty), or None."""
+        if n > self.rows:
+            return None
+        if tail is None:
+            return 0
+        if head > tail:                     # free: [head, rows) and [0, tail)
+            if self.rows - head >= n:
+                return head
+            return 0 if tail >= n else None
+        return head if tail - head >= n else None      # wrapped (or full): free is [head, tail)
+
+    def _place(self, lengths):
+        """Bases for games of the given T, allocated in order; raises StoreFull and leaves the store as it was."""
+        head = self._head
+        tail = next(iter(self.games.values()))[0] if self.games else None
+        bases = []
+        for T in lengths:
+            base = self._find(T + 1, head, tail)
+            if base is None:
+                raise StoreFull(f"no room for a game of {T} positions in a pool of {self.rows} rows")
+            bases.append(base)
+            head = base + T + 1
+            if tail is None:
+                tail = base
+        self._head = head
+        return bases
+
+    def drop(self, game_id):
+        """Release a game's rows.  Rows come back when every OLDER game has been released too (the tail moves on)."""
+        del self.games[game_id]
+
+    # ---- ingest
+    def _columns(self, gh):
+        T = len(gh.root_values)
+        if not (len(gh.observation_history) == len(gh.action_history) == len(gh.reward_history) == len(gh.to_play_history) == T + 1):
+            raise ValueError("not a finished game: the histories must have len(root_values) + 1 entries")
+        roots = gh.root_values if gh.reanalysed_predicted_root_values is None else gh.reanalysed_predicted_root_values
+        visits = numpy.zeros((T + 1, self.A), numpy.float64)
+        if T:
+            visits[:T] = numpy.array(gh.child_visits, dtype=numpy.float64).reshape(T, self.A)
+        return (numpy.array([int(a) for a in gh.action_history], dtype=numpy.int32),
+                numpy.array([float(r) for r in gh.reward_history], dtype=numpy.float64),
+                numpy.array([int(p) for p in gh.to_play_history], dtype=numpy.int32),
+                numpy.array([float(v) for v in roots] + [0.0], dtype=numpy.float64), visits)
+
+    def _run_values(self, entries):
+        be, lib = self.backend, self.backend.lib
+        base = self._up(numpy.array([b for b, _ in entries], dtype=numpy.int64))
+        length = self._up(numpy.array([T for _, T in entries], dtype=numpy.int32))
+        lib.check(lib.mzx_replay_values(ctypes.byref(self.pool), be.ptr(base), be.ptr(length), len(entries),
+                                        int(self.config.td_steps), be.ptr(self._discount_pow), be.stream()))
+
+    def add(self, game_id, game_history):
+        self.add_many([(game_id, game_history)])
+
+    def add_many(self, items):
+        """
+        Ingest the games [(game_id, game_history), ...] of one hand-off: per contiguous run of rows ONE upload per column
+        (two runs when the allocation wraps), then ONE values launch for all of them.  Raises StoreFull -- with the store
+        unchanged -- when they do not fit.
+        """
+        items = list(items)
+        if not items:
+            return
+        for game_id, _ in items:
+            if game_id in self.games:
+                raise ValueError(f"game {game_id} is already resident")
+        columns = [self._columns(gh) for _, gh in items]
+        lengths = [len(gh.root_values) for _, gh in items]
+        bases = self._place(lengths)
+        for (game_id, _), base, T in zip(items, bases, lengths):
+            self.games[game_id] = (base, T)
+        pool_columns = (self.actions, self.rewards, self.to_play, self.root_values, self.child_visits)
+        lo = 0
+        while lo < len(items):
+            hi = lo + 1
+            while hi < len(items) and bases[hi] == bases[hi - 1] + lengths[hi - 1] + 1:
+                hi += 1
+            b0, b1 = bases[lo], bases[hi - 1] + lengths[hi - 1] + 1
+            for c, column in enumerate(pool_columns):
+                column[b0:b1].copy_(self._up(numpy.concatenate([columns[i][c] for i in range(lo, hi)])))
+            if (b1 - b0) * int(numpy.prod(self.shape)) < (1 << 22):      # small frames: one upload for the run
+                frames = numpy.array([numpy.asarray(o) for i in range(lo, hi) for o in items[i][1].observation_history])
+                self.frames[b0:b1].copy_(observations._frames_to_device(self.backend, frames.reshape((b1 - b0,) + self.shape)))
+            else:                                                         # whole games through the pinned staging block
+                for i in range(lo, hi):
+                    self.frames[bases[i]:bases[i] + lengths[i] + 1].copy_(
+                        observations._history_to_device(self.backend, items[i][1].observation_history, self.shape))
+            lo = hi
+        self._run_values(list(zip(bases, lengths)))
+
+    def update(self, game_id, game_history):
+        """Reanalyse's update_game_history (replay_buffer.py:197-203): new root values, the n-step values recomputed."""
+        base, T = self.games[game_id]
+        if len(game_history.root_values) != T:
+            raise ValueError("update: the game's length changed")
+        roots = (game_history.root_values if game_history.reanalysed_predicted_root_values is None
+                 else game_history.reanalysed_predicted_root_values)
+        if T:
+            self.root_values[base:base + T].copy_(self._up(numpy.array([float(v) for v in roots], dtype=numpy.float64)))
+            self._run_values([(base, T)])
+
+    # ---- gathers
+    def batch(self, game_ids, positions, absorbing_actions=None, num_unroll_steps=None, observations=True, targets=True):
+        """
+        ``mzx_replay_batch`` for the samples (game_ids[n], positions[n]): returns (observation [n, C', H, W] fp32 or None,
+        (value, reward [n, U + 1] f64, policy [n, U + 1, A] f64, action, gradient_scale [n, U + 1] i64) or None) as
+        device tensors.  ``absorbing_actions`` [n, U + 1]: the actions drawn for steps past the end of a game.
+        """
+        be, lib = self.backend, self.backend.lib
+        n = len(game_ids)
+        entries = [self.games[g] for g in game_ids]
+        base = numpy.array([b for b, _ in entries], dtype=numpy.int64)
+        length = numpy.array([T for _, T in entries], dtype=numpy.int32)
+        pos = numpy.ascontiguousarray(positions, dtype=numpy.int32).reshape(n)
+        if n and (pos.min() < 0 or (pos > length).any()):
+            raise ValueError("position outside its game")
+        io = _lib.ReplayBatchIO()
+        keep = [self._up(base), self._up(length), self._up(pos)]
+        io.d_base, io.d_len, io.d_pos = (t.data_ptr() for t in keep)
+        io.num_samples, io.stacked_observations = n, self.k
+        obs = out = None
+        if observations:
+            obs = be.empty((n,) + self.sample_shape, torch.float32)
+            io.d_observation = obs.data_ptr()
+        if targets:
+            U = int(self.config.num_unroll_steps if num_unroll_steps is None else num_unroll_steps)
+            tape = numpy.zeros((n, U + 1), numpy.int32) if absorbing_actions is None else numpy.ascontiguousarray(
+                absorbing_actions, dtype=numpy.int32).reshape(n, U + 1)
+            keep.append(self._up(tape))
+            value, reward = be.empty((n, U + 1), torch.float64), be.empty((n, U + 1), torch.float64)
+            policy = be.empty((n, U + 1, self.A), torch.float64)
+            action, scale = be.empty((n, U + 1), torch.int64), be.empty((n, U + 1), torch.int64)
+            io.num_unroll_steps, io.d_absorbing_actions = U, keep[-1].data_ptr()
+            io.d_value, io.d_reward, io.d_policy = value.data_ptr(), reward.data_ptr(), policy.data_ptr()
+            io.d_action, io.d_gradient_scale = action.data_ptr(), scale.data_ptr()
+            out = (value, reward, policy, action, scale)
+        if n:
+            lib.check(lib.mzx_replay_batch(ctypes.byref(self.pool), ctypes.byref(io), be.stream()))
+        return obs, out
+
+    def stacked(self, game_id, count=None):
+        """get_stacked_observations(i, k, A) for i = 0 .. count-1 (default: every searched position) of a resident game."""
+        T = self.games[game_id][1]
+        count = T if count is None else int(count)
+        return self.batch([game_id] * count, numpy.arange(count), targets=False)[0]
+
+
+def trainer_tensors(batch, device):
+    """
+    The tensors ``Trainer.update_weights`` builds from a batch (trainer.py:140-153) -- observation fp32, action int64
+    [batch, U + 1, 1], target value / reward / policy fp32, PER weight fp32 (None without PER), gradient scale fp32 -- from
+    the second element of ``get_batch()``'s result, whether it holds device tensors (a buffer with a ``device_store``) or
+    the host lists / arrays of the stock path.
+    """
+    def t(x):
+        return x if torch.is_tensor(x) else torch.tensor(numpy.array(x))
+
+    observation, action, value, reward, policy, weight, scale = batch
+    return (t(observation).float().to(device), t(action).long().to(device).unsqueeze(-1), t(value).float().to(device),
+            t(reward).float().to(device), t(policy).float().to(device),
+            None if weight is None else t(weight).float().to(device), t(scale).float().to(device))
+
+
 def _stock_replay_buffer_class():
     """
     The user's own ``ReplayBuffer`` (the reference's replay_buffer.py:11-303, importable wherever its trainer runs):
@@ -271,18 +496,55 @@ class ReplayBuffer:
     two side by side).  The tensors come back as numpy arrays instead of nested lists (``trainer.py:55-75`` feeds
     them to ``torch.tensor`` either way).  Attributes (``buffer``, ``num_played_games``, ``total_samples``, ...)
     read through to the stock object.
+
+    ``device_store`` (a ``DeviceGameStore``; opt-in, nothing changes without it): the games also live on the device --
+    ``save_game`` / ``update_game_history`` / the stock eviction keep the store in step, the games of an
+    ``initial_buffer`` are ingested -- and ``get_batch`` returns DEVICE tensors: the draws below only fill index arrays
+    and the tape of absorbing-step actions, one ``mzx_replay_batch`` call gathers observations and targets from the pool
+    (same tuple, ``index_batch`` stays a host list; ``trainer_tensors`` binds it to a trainer).  The one deliberate
+    difference from the reference: the pool adds a capacity bound in POSITIONS to ``replay_buffer_size`` in games.  When
+    a new game does not fit after the rows of already evicted games are released, the oldest games leave both the
+    store and the stock buffer (the stock buffer's own eviction statements, replay_buffer.py:59-61).
     """
 
-    def __init__(self, initial_checkpoint, initial_buffer, config, stock=None):
+    def __init__(self, initial_checkpoint, initial_buffer, config, stock=None, device_store=None):
         factory = _plain_class(stock) if stock is not None else _stock_replay_buffer_class()
         # a class (also the one behind a ray.remote ActorClass) is instantiated; anything that already has the buffer's
         # methods is taken as the instance to wrap
         built = factory(initial_checkpoint, initial_buffer, config) if isinstance(factory, type) else factory
         object.__setattr__(self, "_stock", built)
         object.__setattr__(self, "_arrays", {})   # game_id -> (game_history, per-game numpy views); dropped when the game changes or leaves
+        object.__setattr__(self, "_store", device_store)
+        if device_store is not None:
+            self._store_sync(list(self._stock.buffer.items()))
+
+    @property
+    def device_store(self):
+        return self._store
+
+    def _store_sync(self, new_games):
+        """Games the stock buffer no longer holds leave the store; ``new_games`` enter it, the oldest games making room."""
+        store, stock = self._store, self._stock
+        for game_id in [g for g in store.games if g not in stock.buffer]:
+            store.drop(game_id)
+        new_games = [(g, h) for g, h in new_games if g in stock.buffer]
+        while new_games:
+            try:
+                return store.add_many(new_games)
+            except StoreFull:
+                if len(stock.buffer) <= 1:
+                    raise
+            # the capacity bound in positions: the stock buffer's eviction (replay_buffer.py:59-61), applied once more
+            del_id = stock.num_played_games - len(stock.buffer)
+            stock.total_samples -= len(stock.buffer[del_id].root_values)
+            del stock.buffer[del_id]
+            self._arrays.pop(del_id, None)
+            if del_id in store:
+                store.drop(del_id)
+            new_games = [(g, h) for g, h in new_games if g != del_id]
 
     def __getattr__(self, name):
-        if name in ("_stock", "_arrays"):
+        if name in ("_stock", "_arrays", "_store"):
             raise AttributeError(name)
         return getattr(self._stock, name)
 
@@ -315,7 +577,11 @@ class ReplayBuffer:
 
     def save_game(self, game_history, shared_storage=None):
         fill_initial_priorities(game_history, self._stock.config)    # no-op for games it does not cover
+        if self._store is not None and len(game_history.root_values) + 1 > self._store.rows:
+            raise StoreFull(f"a game of {len(game_history.root_values)} positions exceeds the device store's {self._store.rows} rows")
         out = self._stock.save_game(game_history, shared_storage)
+        if self._store is not None:
+            self._store_sync([(self._stock.num_played_games - 1, game_history)])
         if self._arrays and self._stock.buffer:                      # evicted games take their cached arrays along
             oldest = next(iter(self._stock.buffer))                  # game ids only grow (replay_buffer.py:53-62)
             for game_id in [g for g in self._arrays if g < oldest]:
@@ -324,7 +590,10 @@ class ReplayBuffer:
 
     def update_game_history(self, game_id, game_history):
         self._arrays.pop(game_id, None)          # reanalysed root values change the n-step targets
-        return self._stock.update_game_history(game_id, game_history)
+        out = self._stock.update_game_history(game_id, game_history)
+        if self._store is not None and game_id in self._store and self._stock.buffer.get(game_id) is game_history:
+            self._store.update(game_id, game_history)
+        return out
 
     # ---- position draw
     def _sample_position_fast(self, game_history):
@@ -385,7 +654,32 @@ class ReplayBuffer:
                 actions[k] = space[numpy.random.randint(0, len(space))]    # == numpy.random.choice(space), same draw
         return values, rewards, policies, actions
 
+    def _get_batch_device(self):
+        """get_batch with a device store: the same draws in the same order, the tensors gathered by mzx_replay_batch."""
+        cfg, store = self._stock.config, self._store
+        U, space = cfg.num_unroll_steps, cfg.action_space
+        n = cfg.batch_size
+        total_samples = self._stock.total_samples
+        index_batch, weight_batch = [], [] if cfg.PER else None
+        tape = numpy.zeros((n, U + 1), numpy.int32)
+        for i, (game_id, game_history, game_prob) in enumerate(self._stock.sample_n_games(n)):
+            game_pos, pos_prob = self._sample_position_fast(game_history)
+            index_batch.append([game_id, game_pos])
+            for k in range(max(0, len(game_history.root_values) + 1 - game_pos), U + 1):     # absorbing steps (:301)
+                tape[i, k] = space[numpy.random.randint(0, len(space))]    # == numpy.random.choice(space), same draw
+            if cfg.PER:
+                weight_batch.append(1 / (total_samples * game_prob * pos_prob))
+        if cfg.PER:
+            weight_batch = numpy.array(weight_batch, dtype="float32") / max(weight_batch)
+            weight_batch = torch.from_numpy(weight_batch).to(store.backend.device, non_blocking=True)
+        observation_batch, (value_batch, reward_batch, policy_batch, action_batch, gradient_scale_batch) = store.batch(
+            [g for g, _ in index_batch], [p for _, p in index_batch], tape, U)
+        return (index_batch, (observation_batch, action_batch, value_batch, reward_batch, policy_batch, weight_batch,
+                              gradient_scale_batch))
+
     def get_batch(self):
+        if self._store is not None:
+            return self._get_batch_device()
         cfg = self._stock.config
         U, A = cfg.num_unroll_steps, len(cfg.action_space)
         n = cfg.batch_size
@@ -429,8 +723,11 @@ class Reanalyse:
     latest network.  ``reanalyse_game`` is the per-game step (new, reusable); ``reanalyse`` the worker loop.
     """
 
-    def __init__(self, initial_checkpoint, config, _backend=None):
+    def __init__(self, initial_checkpoint, config, _backend=None, device_store=None):
         self.config = config
+        # a DeviceGameStore (default: the replay buffer's own, when ``reanalyse`` is handed a local buffer that has one):
+        # games resident in it are stacked from the pool instead of being uploaded again
+        self.device_store = device_store
         # Fix random generator seed (replay_buffer.py:318-319)
         numpy.random.seed(self.config.seed)
         torch.manual_seed(self.config.seed)
@@ -440,12 +737,20 @@ class Reanalyse:
         self.model.eval()
         self.num_reanalysed_games = initial_checkpoint["num_reanalysed_games"]
 
-    def reanalyse_game(self, game_history):
-        """replay_buffer.py:343-367: float32 array [len(root_values)] of decoded root values under the current weights."""
+    def reanalyse_game(self, game_history, game_id=None):
+        """
+        replay_buffer.py:343-367: float32 array [len(root_values)] of decoded root values under the current weights.
+        With ``game_id`` of a game resident in ``device_store`` the stacked observations are gathered from the pool
+        (samples (game, 0 .. T-1) of ``mzx_replay_batch``) -- same planes, nothing uploaded.
+        """
         n = len(game_history.root_values)
         backend = self.model.backend
-        stacked = observations.stack_history(backend, self.config, game_history.observation_history,
-                                             game_history.action_history, count=n)
+        store = self.device_store
+        if store is not None and game_id is not None and game_id in store and store.games[game_id][1] == n:
+            stacked = store.stacked(game_id, n)
+        else:
+            stacked = observations.stack_history(backend, self.config, game_history.observation_history,
+                                                 game_history.action_history, count=n)
         if n == 0:
             return numpy.zeros((0,), numpy.float32)
         value_logits = self.model.initial_inference(stacked)[0]
@@ -456,12 +761,14 @@ class Reanalyse:
         get = lambda key: _remote(shared_storage.get_info, key)
         while get("num_played_games") < 1:
             time.sleep(0.1)
+        if self.device_store is None and isinstance(replay_buffer, ReplayBuffer):
+            self.device_store = replay_buffer.device_store
         while get("training_step") < self.config.training_steps and not get("terminate"):
             self.model.set_weights(get("weights"))
             game_id, game_history, _ = _remote(replay_buffer.sample_game, force_uniform=True)
             # Use the last model to provide a fresher, stable n-step value (See paper appendix Reanalyze)
             if self.config.use_last_model_value:
-                game_history.reanalysed_predicted_root_values = self.reanalyse_game(game_history)
+                game_history.reanalysed_predicted_root_values = self.reanalyse_game(game_history, game_id)
             _remote(replay_buffer.update_game_history, game_id, game_history)
             self.num_reanalysed_games += 1
             _remote(shared_storage.set_info, "num_reanalysed_games", self.num_reanalysed_games)
