@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 3
+#define MZX_ABI_VERSION 4
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -525,6 +525,16 @@ int mzx_replay_priorities(const double* d_root_values, const double* d_rewards, 
  * mzx_replay_values: compute_target_value (:230-262) of every position of num_games games (d_base[g], d_len[g] = T) into
  *   pool->d_values, bit for bit (the arithmetic of mzx_replay_priorities; d_discount_pow [td_steps + 1] as there).  One
  *   launch for all the games an ingest or a reanalyse update touched.
+ * mzx_replay_positions: the reanalyse sweep's sample list, built on the device.  The positions of num_games games, in the
+ *   order given, form one flat sequence of total_positions = sum(d_len) entries; d_first [num_games] i64 is the exclusive
+ *   prefix of d_len (both totals computed by the CALLER: O(games) host work per sweep, nothing per position).  Entry e of
+ *   the window [first, first + count) becomes d_sample_base / d_sample_len / d_sample_pos [count] -- the three arrays
+ *   mzx_replay_batch_io takes; games of T = 0 contribute no entry.  A window that runs past total_positions is refused.
+ * mzx_replay_reanalyse_write: Reanalyse's value decode (replay_buffer.py:361-367) of a chunk of such samples, written in
+ *   place.  d_value_logits [num_samples][2 * support_size + 1] f32 -> d_out [num_samples] f32, the bits of
+ *   mzx_support_to_scalar, and d_root_values[d_sample_base[n] + d_sample_pos[n]] = (double)d_out[n] -- the binary64 the
+ *   per-game update uploads.  d_root_values is the pool's root_values column, passed writable (the pool holds it const);
+ *   mzx_replay_values afterwards refreshes the n-step targets of the games touched.  One launch.
  * mzx_replay_batch: sample n is position d_pos[n] (0 <= pos <= T) of the game (d_base[n], d_len[n]).
  *   d_observation [n][channels * (stacked + 1) + stacked][height][width] f32 = get_stacked_observations(pos, stacked, A)
  *     after torch.tensor(...).float(), the values of mzx_obs_stack; NULL skips the gather.
@@ -561,6 +571,11 @@ typedef struct mzx_replay_batch_io {
 } mzx_replay_batch_io;
 int mzx_replay_values(const mzx_replay_pool* pool, const int64_t* d_base, const int32_t* d_len, int32_t num_games,
                       int32_t td_steps, const double* d_discount_pow, void* stream);
+int mzx_replay_positions(const int64_t* d_base, const int32_t* d_len, const int64_t* d_first, int32_t num_games,
+                         int64_t total_positions, int64_t first, int32_t count, int64_t* d_sample_base, int32_t* d_sample_len,
+                         int32_t* d_sample_pos, void* stream);
+int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples, int32_t support_size, const int64_t* d_sample_base,
+                               const int32_t* d_sample_pos, float* d_out, double* d_root_values, void* stream);
 int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *

@@ -1230,6 +1230,42 @@ int mzx_replay_values(const mzx_replay_pool* pool, const int64_t* d_base, const 
   return MZX_OK;
 }
 
+int mzx_replay_positions(const int64_t* d_base, const int32_t* d_len, const int64_t* d_first, int32_t num_games,
+                         int64_t total_positions, int64_t first, int32_t count, int64_t* d_sample_base, int32_t* d_sample_len,
+                         int32_t* d_sample_pos, void* stream) {
+  if (num_games < 0 || total_positions < 0 || first < 0 || count < 0) { set_error("mzx_replay_positions: negative argument"); return MZX_ERR_INVALID; }
+  if (first + (int64_t)count > total_positions) {
+    set_error("mzx_replay_positions: window [%lld, %lld) runs past the last of %lld positions", (long long)first,
+              (long long)(first + count), (long long)total_positions);
+    return MZX_ERR_INVALID;
+  }
+  if (count == 0) return MZX_OK;
+  if (!d_base || !d_len || !d_first || !d_sample_base || !d_sample_len || !d_sample_pos) {
+    set_error("mzx_replay_positions: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  ReplayPositionsOp op;
+  op.base = d_base; op.len = d_len; op.first = d_first; op.sample_base = d_sample_base; op.sample_len = d_sample_len;
+  op.sample_pos = d_sample_pos; op.first_position = first; op.num_games = num_games; op.count = count;
+  MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples, int32_t support_size, const int64_t* d_sample_base,
+                               const int32_t* d_sample_pos, float* d_out, double* d_root_values, void* stream) {
+  if (num_samples < 0 || support_size < 0) { set_error("mzx_replay_reanalyse_write: negative argument"); return MZX_ERR_INVALID; }
+  if (num_samples == 0) return MZX_OK;
+  if (!d_value_logits || !d_sample_base || !d_sample_pos || !d_out || !d_root_values) {
+    set_error("mzx_replay_reanalyse_write: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  ReplayReanalyseOp op;
+  op.logits = d_value_logits; op.sample_base = d_sample_base; op.sample_pos = d_sample_pos; op.out = d_out;
+  op.root_values = d_root_values; op.n = num_samples; op.support_size = support_size;
+  MZX_TRY_LAUNCH(launch<64>(op, (stream_t)stream));
+  return MZX_OK;
+}
+
 extern "C++" {
 template <int VEC>
 static int replay_obs_launch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, stream_t stream) {

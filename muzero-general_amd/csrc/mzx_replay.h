@@ -1,6 +1,7 @@
 // mzx_replay.h -- hand-off of finished games to the replay buffer: the INITIAL prioritised-replay priorities of a
 // shard's games on the device, and the device-resident replay store (second half of the file):
-// n-step values of ragged games and make_target for a training batch.
+// n-step values of ragged games, make_target for a training batch, and the reanalyse sweep (the positions of ragged games
+// as a sample list, the decoded values of a chunk written into the pool).
 //
 // Reference: ReplayBuffer.save_game, /root/reference/replay_buffer.py:39-51 -- for every position i of a game
 //     priority_i = |root_value_i - compute_target_value(game, i)| ** PER_alpha        (numpy.float64, then float32)
@@ -19,6 +20,7 @@
 // float32 rounding boundary (probability ~1e-9 per position); tests compare the float32 priorities bit for bit.
 #pragma once
 #include "mzx_platform.h"
+#include "mzx_tree.h"
 
 namespace mzx {
 
@@ -153,6 +155,53 @@ struct ReplayTargetsOp {
     action[e] = idx <= T ? actions[row] : absorbing[e];
     const int left = T + 1 - p;      // len(action_history) - game_pos
     gradient_scale[e] = U < left ? U : left;
+  }
+};
+
+// The reanalyse sweep (DeviceGameStore.reanalyse): the positions of G ragged games, flattened in game order, as the sample
+// list mzx_replay_batch_io takes -- element e is flat position `first_position + e`; `first` [G] is the exclusive prefix
+// of `len` (the caller's only per-sweep host work is O(games)).  The game of a flat position is the LAST g with
+// first[g] <= position: games of T == 0 share their first with the next game and are passed over.
+struct ReplayPositionsOp {
+  const int64_t* base;          // [num_games]
+  const int32_t* len;           // [num_games] T
+  const int64_t* first;         // [num_games] exclusive prefix of len
+  int64_t* sample_base;         // [count]
+  int32_t* sample_len;          // [count]
+  int32_t* sample_pos;          // [count]
+  int64_t first_position;
+  int32_t num_games, count;
+
+  MZX_HD size_t size() const { return (size_t)count; }
+  MZX_HD void operator()(size_t e) const {
+    const int64_t p = first_position + (int64_t)e;
+    int lo = 0, hi = num_games - 1;      // first[lo] <= p always (first[0] == 0)
+    while (lo < hi) {
+      const int mid = lo + (hi - lo + 1) / 2;
+      if (first[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    sample_base[e] = base[lo];
+    sample_len[e] = len[lo];
+    sample_pos[e] = (int32_t)(p - first[lo]);
+  }
+};
+
+// Value logits [n][2 * support_size + 1] of a chunk of such samples -> the decoded root values (SupportToScalarOp's
+// function: the float32 bits of mzx_support_to_scalar) into out [n] and, widened to binary64 -- what float(v) of the
+// downloaded float32 uploads on the per-game path --, into the pool's root_values row of every sample.
+struct ReplayReanalyseOp {
+  const float* logits;
+  const int64_t* sample_base;   // [n]
+  const int32_t* sample_pos;    // [n]
+  float* out;                   // [n]
+  double* root_values;          // the pool column
+  int32_t n, support_size;
+
+  MZX_HD size_t size() const { return (size_t)n; }
+  MZX_HD void operator()(size_t e) const {
+    const float v = support_to_scalar(logits + (int64_t)e * (2 * support_size + 1), support_size);
+    out[e] = v;
+    root_values[sample_base[e] + sample_pos[e]] = (double)v;
   }
 };
 

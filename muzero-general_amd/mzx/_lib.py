@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 3
+ABI_VERSION = 4
 MOVE_NO_SYNC = 1
 
 c_i32, c_i64, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
@@ -199,6 +199,8 @@ PROTOTYPES = {
     "mzx_selfplay_search": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_i64, c_vp]),
     "mzx_replay_priorities": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_values": (ctypes.c_int, [ctypes.POINTER(ReplayPool), c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mzx_replay_positions": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_replay_reanalyse_write": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_batch": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplayBatchIO), c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),

@@ -17,6 +17,8 @@ on the device (``mzx.observations.stack_history`` + the network kernels + ``mzx_
 ``DeviceGameStore`` keeps finished games in HBM (a ragged pool, csrc/mzx_replay.h) so that ``ReplayBuffer(...,
 device_store=store).get_batch()`` assembles the trainer's tensors on the device (``mzx_replay_batch``): the draws stay
 numpy's, in the reference's order, and only fill index arrays.  ``trainer_tensors`` is the binding line of a trainer.
+``DeviceGameStore.reanalyse`` / ``Reanalyse.reanalyse_store`` re-evaluate every resident game in a sweep: a handful of
+launches per chunk of positions, the decoded values written straight into the pool (opt-in: ``config.reanalyse_sweep``).
 """
 import ctypes
 import time
@@ -26,6 +28,12 @@ import torch
 
 from . import _lib, models, observations
 from .history import gc_paused
+
+# DeviceGameStore.reanalyse: the stacked observations of one chunk of positions stay within this many bytes (the network's
+# activations scale with the same count), and within the 64-lane groups one mzx_replay_batch gather accepts
+# (csrc/mzx_lib.cpp replay_obs_launch)
+REANALYSE_CHUNK_BYTES = 512 << 20
+REPLAY_GATHER_GROUPS = 1 << 26
 
 
 def n_step_values(game_history, config):
@@ -434,6 +442,66 @@ class DeviceGameStore:
         count = T if count is None else int(count)
         return self.batch([game_id] * count, numpy.arange(count), targets=False)[0]
 
+    # ---- reanalyse sweep
+    def reanalyse_chunk_limit(self):
+        """Positions one ``mzx_replay_batch`` gather accepts (the scalar path's piece count: the smaller bound)."""
+        pieces = -(-self.shape[1] * self.shape[2] // 256)
+        return max(1, (REPLAY_GATHER_GROUPS - 1) // (self.sample_shape[0] * pieces))
+
+    def reanalyse_chunk_positions(self):
+        """Default chunk of ``reanalyse``: REANALYSE_CHUNK_BYTES of stacked observations, within one gather launch."""
+        sample_bytes = 4 * int(numpy.prod(self.sample_shape))
+        return max(1, min(REANALYSE_CHUNK_BYTES // sample_bytes, self.reanalyse_chunk_limit()))
+
+    def reanalyse(self, model, game_ids=None, chunk_positions=None):
+        """
+        Reanalyse (replay_buffer.py:343-367) as a SWEEP over resident games -- every one in allocation order, or
+        ``game_ids`` --: their positions form one flat sequence that is evaluated under ``model``'s current weights in
+        chunks of ``chunk_positions`` (default ``reanalyse_chunk_positions()``), whatever the games' lengths.  Per chunk, on
+        the backend's stream: ``mzx_replay_positions`` (the chunk's samples, built on the device), ``mzx_replay_batch`` with
+        the observation pointer only, ``model.initial_inference``, ``mzx_replay_reanalyse_write`` (decode, the float32 into
+        the sweep's output, its binary64 into the pool's root_values).  Then ONE ``mzx_replay_values`` launch for the games
+        swept and ONE download.  Returns {game_id: float32 array [T]} (views of that download) -- what ``reanalyse_game``
+        returns per game; the pool is left as ``update`` with those arrays would leave it.  An unknown game raises KeyError;
+        no other column is touched.  Host work per sweep is O(games): nothing is built or uploaded per position.
+        """
+        be, lib = self.backend, self.backend.lib
+        ids = list(dict.fromkeys(self.games if game_ids is None else game_ids))
+        entries = [self.games[g] for g in ids]
+        if not ids:
+            return {}
+        lengths = numpy.array([T for _, T in entries], dtype=numpy.int64)
+        first = numpy.concatenate([[0], numpy.cumsum(lengths)[:-1]]).astype(numpy.int64)
+        total = int(lengths.sum())
+        if total == 0:
+            return {g: numpy.zeros((0,), numpy.float32) for g in ids}
+        chunk = self.reanalyse_chunk_positions() if chunk_positions is None else int(chunk_positions)
+        if chunk < 1:
+            raise ValueError("chunk_positions must be positive")
+        chunk = min(chunk, total, self.reanalyse_chunk_limit())
+        G = len(ids)
+        d_base = self._up(numpy.array([b for b, _ in entries], dtype=numpy.int64))
+        d_len, d_first = self._up(lengths.astype(numpy.int32)), self._up(first)
+        s_base, s_len, s_pos = be.empty((chunk,), torch.int64), be.empty((chunk,), torch.int32), be.empty((chunk,), torch.int32)
+        obs = be.empty((chunk,) + self.sample_shape, torch.float32)
+        out = be.empty((total,), torch.float32)
+        io = _lib.ReplayBatchIO()
+        io.d_base, io.d_len, io.d_pos, io.d_observation = s_base.data_ptr(), s_len.data_ptr(), s_pos.data_ptr(), obs.data_ptr()
+        io.stacked_observations = self.k
+        support = int(self.config.support_size)
+        for lo in range(0, total, chunk):
+            n = min(chunk, total - lo)
+            lib.check(lib.mzx_replay_positions(be.ptr(d_base), be.ptr(d_len), be.ptr(d_first), G, total, lo, n, be.ptr(s_base),
+                                               be.ptr(s_len), be.ptr(s_pos), be.stream()))
+            io.num_samples = n
+            lib.check(lib.mzx_replay_batch(ctypes.byref(self.pool), ctypes.byref(io), be.stream()))
+            value_logits = model.initial_inference(obs[:n])[0]
+            lib.check(lib.mzx_replay_reanalyse_write(be.ptr(value_logits), n, support, be.ptr(s_base), be.ptr(s_pos),
+                                                     be.ptr(out[lo:lo + n]), be.ptr(self.root_values), be.stream()))
+        self._run_values([e for e in entries if e[1] > 0])
+        host = out.cpu().numpy()
+        return {g: host[f:f + T] for g, f, T in zip(ids, first.tolist(), lengths.tolist())}
+
 
 def trainer_tensors(batch, device):
     """
@@ -757,14 +825,46 @@ class Reanalyse:
         values = models.support_to_scalar(value_logits, self.config.support_size, _backend=backend)
         return torch.squeeze(values).detach().cpu().numpy()
 
+    def reanalyse_store(self, replay_buffer, game_ids=None):
+        """
+        The sweep as a worker step (``DeviceGameStore.reanalyse`` under the current weights): every game of the buffer's
+        device store that the stock buffer still holds -- or those of ``game_ids`` -- gets its float32 array [T] as
+        ``reanalysed_predicted_root_values`` (what ``reanalyse_game`` would assign), its cached host arrays are dropped and
+        it counts in ``num_reanalysed_games``; the pool's root values and n-step values are already refreshed in place.  A
+        game the stock buffer has evicted is passed over.  Needs an in-process ``ReplayBuffer`` with a device store (device
+        pointers do not cross processes).  Returns the number of games refreshed.
+        """
+        store = replay_buffer.device_store if isinstance(replay_buffer, ReplayBuffer) else None
+        if store is None:
+            raise ValueError("reanalyse_store needs an in-process mzx.replay.ReplayBuffer with a device_store")
+        buffer = replay_buffer.buffer
+        ids = [g for g in (store.games if game_ids is None else game_ids) if g in buffer or g not in store]
+        done = 0
+        for game_id, values in store.reanalyse(self.model, ids).items():
+            game_history = buffer.get(game_id)
+            if game_history is None or len(game_history.root_values) != len(values):
+                continue
+            game_history.reanalysed_predicted_root_values = values
+            replay_buffer._arrays.pop(game_id, None)      # reanalysed root values change the n-step targets
+            done += 1
+        self.num_reanalysed_games += done
+        return done
+
     def reanalyse(self, replay_buffer, shared_storage):
         get = lambda key: _remote(shared_storage.get_info, key)
         while get("num_played_games") < 1:
             time.sleep(0.1)
         if self.device_store is None and isinstance(replay_buffer, ReplayBuffer):
             self.device_store = replay_buffer.device_store
+        # opt-in (config.reanalyse_sweep): every resident game per iteration instead of one drawn game
+        sweep = (getattr(self.config, "reanalyse_sweep", False) and isinstance(replay_buffer, ReplayBuffer)
+                 and replay_buffer.device_store is not None)
         while get("training_step") < self.config.training_steps and not get("terminate"):
             self.model.set_weights(get("weights"))
+            if sweep and self.config.use_last_model_value:
+                self.reanalyse_store(replay_buffer)
+                _remote(shared_storage.set_info, "num_reanalysed_games", self.num_reanalysed_games)
+                continue
             game_id, game_history, _ = _remote(replay_buffer.sample_game, force_uniform=True)
             # Use the last model to provide a fresher, stable n-step value (See paper appendix Reanalyze)
             if self.config.use_last_model_value:
