@@ -256,8 +256,9 @@ def bits(a):
     return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.int64)
 
 
-def assert_tree_equal(got, i, tree, A):
-    """Tree i of a lock-step / engine dump against an oracle Tree, bit for bit (statistics, links, priors, min-max)."""
+def assert_tree_equal(got, i, tree, A, flags=0):
+    """Tree i of a lock-step / engine dump against an oracle Tree, bit for bit (statistics, links, priors, min-max);
+    `flags`: the status word the tree must report (4 = TF_BAD_CARRY: the advance kept the old root)."""
     n = len(tree.visit)
     assert got["n_nodes"][i] == n, (i, got["n_nodes"][i], n)
     assert numpy.array_equal(got["visit"][i, :n], tree.visit), i
@@ -277,4 +278,4 @@ def assert_tree_equal(got, i, tree, A):
     if "visits" in got:
         assert numpy.array_equal(got["visits"][i], want), i
         assert got["root_value"][i] == tree.node_value(0), i
-        assert got["info"][i, 0] == tree.max_depth and got["info"][i, 1] == 0, i
+        assert got["info"][i, 0] == tree.max_depth and got["info"][i, 1] == flags, i

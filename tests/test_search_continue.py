@@ -77,10 +77,53 @@ def test_helper_equals_live_reference(game, noise, which):
 
 # ---------------------------------------------------------------- the serial ABI against the helper
 
-def _carry_case(backend, game, B, S, rounds, noise, ties=False, legal_cut=0, pick=None, seed=0):
-    cfg = configs.BY_NAME[game](num_simulations=S)
-    A = len(cfg.action_space)
-    legal = [list(cfg.action_space)[legal_cut:] for _ in range(B)]
+def _config(game, S):
+    """A named game (configs.BY_NAME) or a factory of a config that takes num_simulations."""
+    return configs.BY_NAME[game](num_simulations=S) if isinstance(game, str) else game(num_simulations=S)
+
+
+def wide32(**kw):
+    """32 actions on a 4 x 8 board, two players: several child slots per lane in the device kernels."""
+    return configs.connect4(observation_shape=(3, 4, 8), action_space=list(range(32)), **kw)
+
+
+def ragged_legal(A, B, seed):
+    """Per-tree legal sets as tests/test_gpu_tower_search.py draws them; tree 0 keeps a single action."""
+    rs = numpy.random.RandomState(seed)
+    legal = [sorted(rs.choice(A, size=rs.randint(1, A + 1), replace=False).tolist()) for _ in range(B)]
+    legal[0] = legal[0][:1]
+    return legal
+
+
+def _expanded(t):
+    """(node index, visits, action) of the expanded children of the root of oracle tree t."""
+    return [(c, t.visit[c], a) for a, c in zip(t.actions[0], t.child[0]) if c >= 0]
+
+
+def pick_alternating(r, i, t):
+    """The old root again and an expanded child in the same shard and round: the trees alternate between them in pairs (trees
+    0, 1, 4, 5, ... start with the root: root again on its restricted legal set, then a child, then that child again as a
+    root), so that with tree i starting as player i % P both players meet both kinds; the child is the most visited one
+    or, for odd i, the least visited expanded one."""
+    if (r + i // 2) % 2 == 0:
+        return -1
+    seen = [(v, a) for _, v, a in _expanded(t)]
+    return (max(seen) if i % 2 == 0 else min(seen, key=lambda x: (x[0], -x[1])))[1]
+
+
+def pick_late_child(r, i, t):
+    """The old root for three rounds, then its expanded child with the largest node index (the youngest subtree)."""
+    return -1 if r < 3 else max(_expanded(t))[2]
+
+
+def _carry_case(backend, game, B, S, rounds, noise, ties=False, legal_cut=0, pick=None, seed=0, ragged=False,
+                mixed_to_play=False, log=None):
+    """ragged: per-tree legal sets (ragged_legal); mixed_to_play: tree i starts with player i % P; log: a list that gets,
+    per round, the chosen actions, the old node index of every new root and the node counts carried (oracle trees)."""
+    cfg = _config(game, S)
+    A, P = len(cfg.action_space), len(cfg.players)
+    legal = ragged_legal(A, B, seed + 7) if ragged else [list(cfg.action_space)[legal_cut:] for _ in range(B)]
+    tp0 = [i % P if mixed_to_play else 0 for i in range(B)]
     cap = (rounds + 1) * S + 1 + 1
     ls = co.LockstepCarry(backend, cfg, B, S, cap)
     count = (rounds + 1) * S + 1
@@ -88,15 +131,19 @@ def _carry_case(backend, game, B, S, rounds, noise, ties=False, legal_cut=0, pic
     ora_rngs = [numpy.random.RandomState(seed + 100 + i) for i in range(B)]
     dev_ev = [co.ReplayValues(seed + i, count, A, ties) for i in range(B)]
     ora_ev = [co.ReplayValues(seed + i, count, A, ties) for i in range(B)]
-    trees = [mo.run_search(cfg, ora_ev[i], None, legal[i], 0, noise, ora_rngs[i]) for i in range(B)]
-    got = ls.fresh(legal, numpy.zeros(B, numpy.int32), noise, dev_rngs, dev_ev)
+    trees = [mo.run_search(cfg, ora_ev[i], None, legal[i], tp0[i], noise, ora_rngs[i]) for i in range(B)]
+    got = ls.fresh(legal, numpy.array(tp0, numpy.int32), noise, dev_rngs, dev_ev)
     for i in range(B):
         co.assert_tree_equal(got, i, trees[i], A)
     pick = pick or (lambda r, i, t: -1 if (r + i) % 3 == 2 else max(
         (a for s, a in enumerate(t.actions[0]) if t.child[0][s] >= 0), key=lambda a: t.visit[t.child[0][t.actions[0].index(a)]]))
     for r in range(rounds):
         acts = [pick(r, i, trees[i]) for i in range(B)]
+        chosen = [0 if a < 0 else t.child[0][t.actions[0].index(a)] for a, t in zip(acts, trees)]
         trees = [co.carry(trees[i], cfg, acts[i]) for i in range(B)]
+        if log is not None:
+            log.append(dict(acts=acts, chosen=chosen, carried=[len(t.visit) for t in trees], legal_n=[len(a) for a in legal],
+                            root_n=[len(t.actions[0]) for t in trees], to_play=[t.to_play[0] for t in trees]))
         assert ls.advance(acts) == 0, backend.lib.mzx_last_error()
         for i in range(B):
             co.continue_search(cfg, ora_ev[i], trees[i], trees[i].to_play[0], noise, ora_rngs[i])
@@ -122,6 +169,109 @@ def test_hostcheck_root_again_keeps_legal_children(backend):
     trees = _carry_case(backend, "tictactoe", 4, 10, 2, True, legal_cut=4, pick=lambda r, i, t: -1)
     for t in trees:
         assert len(t.actions[0]) == 5 and t.visit[0] == 30 and len(t.visit) == 31
+
+
+def assert_root_shapes(log, A, P, B):
+    """What a ragged, alternating chain has to contain to be worth its name (read off the oracle trees)."""
+    first = log[0]
+    assert len(set(first["legal_n"])) > 1                                                     # ragged sets
+    assert any(n == 1 and a < 0 for n, a in zip(first["root_n"], first["acts"]))              # a single-action root, again
+    assert all(any(a < 0 for a in r["acts"]) and any(a >= 0 for a in r["acts"]) for r in log)     # both kinds, every round
+    # root again on a restricted root, then its child (a full root), then that root again
+    assert any(log[0]["acts"][i] < 0 and log[0]["root_n"][i] < A and log[1]["acts"][i] >= 0 and log[2]["acts"][i] < 0
+               for i in range(B))
+
+
+CHAINS = [("cartpole", True, False), ("lunarlander", True, False), ("tictactoe", True, True), (wide32, False, True),
+          ("gomoku", True, False)]
+
+
+@pytest.mark.parametrize("game,noise,ties", CHAINS, ids=lambda v: getattr(v, "__name__", str(v)))
+def test_hostcheck_ragged_roots_mixed_players_equal_helper(backend, game, noise, ties):
+    """Ragged legal sets (a single-action root among them), tree i starting with player i % P, and a pick that searches
+    the old root again in some trees and moves to an expanded child in others, in the same shard and round: the slot ->
+    action map of a restricted root survives a = -1, is replaced by the whole action space under a child, and the noise
+    covers exactly the root's own slots.  Action spaces 2, 4, 9, 32 and 121."""
+    B, S = 8, 10
+    cfg = _config(game, S)
+    log = []
+    trees = _carry_case(backend, game, B, S, 3, noise, ties, pick=pick_alternating, seed=5, ragged=True, mixed_to_play=True,
+                        log=log)
+    assert_root_shapes(log, len(cfg.action_space), len(cfg.players), B)
+    P = len(cfg.players)
+    for r in log:      # both players at roots searched again and at new roots, in every round
+        assert len({p for p, a in zip(r["to_play"], r["acts"]) if a < 0}) == P, r
+        assert len({p for p, a in zip(r["to_play"], r["acts"]) if a >= 0}) == P, r
+
+
+LATE = [(wide32, True), ("gomoku", False)]
+
+
+@pytest.mark.parametrize("game,ties", LATE, ids=lambda v: getattr(v, "__name__", str(v)))
+def test_hostcheck_carry_starts_past_the_first_chunk(backend, game, ties):
+    """A new root whose old node index is >= 64: tree_advance_kernel's membership loop starts at `c & ~63`, past chunk 0,
+    and the trees that keep their root carry more than 64 nodes (two chunks).  3 S + 1 nodes never reach 64 at S <= 20, so
+    this chain alone has a fourth round: three times the old root (21, 41, 61, 81 nodes), then its youngest expanded child."""
+    log = []
+    _carry_case(backend, game, 6, 20, 4, True, ties, pick=lambda r, i, t: -1 if i % 2 else pick_late_child(r, i, t), seed=9,
+                ragged=True, mixed_to_play=True, log=log)
+    assert max(log[3]["chosen"]) >= 64, log[3]["chosen"]
+    assert max(log[3]["carried"]) > 64
+
+
+def _bad_carry_actions(d, legal, A):
+    """Per tree of a fresh dump: (action, kind) with kind 0 = a legal action whose child was never expanded, 1 = an action
+    outside the root's legal set, 2 = an expanded child -- each kind in every third tree."""
+    out = []
+    for i, acts in enumerate(legal):
+        child = d["child"][i, 0]
+        never = [a for s, a in enumerate(acts) if child[s] < 0]
+        illegal = [a for a in range(A) if a not in acts]
+        valid = [a for s, a in enumerate(acts) if child[s] > 0]
+        kind = i % 3
+        assert never and illegal and valid, (i, acts)
+        out.append(((never[-1], illegal[0], valid[-1])[kind], kind))
+    return out
+
+
+def bad_carry_lockstep(backend, game, B, S, seed=0):
+    """TF_BAD_CARRY through the C ABI: mzx_search_advance with actions that name no expanded child (the library's host
+    guard lives in BatchedMCTS.continue_search, not here).  carry_root reports them, the old root is kept, carry_meta sets
+    flag 4, ContinueRootOp preserves it, the simulations run on the old root and mzx_search_finish reports it: info word 1
+    is 4 exactly on those trees, which equal what a = -1 yields under the oracle helper; the valid trees equal the helper."""
+    cfg = _config(game, S)
+    A, P = len(cfg.action_space), len(cfg.players)
+    rs = numpy.random.RandomState(seed + 3)
+    legal = [sorted(rs.choice(A, size=rs.randint(S + 1, A), replace=False).tolist()) for _ in range(B)]     # S < |legal| < A
+    tp0 = [i % P for i in range(B)]
+    ls = co.LockstepCarry(backend, cfg, B, S, 2 * S + 2)
+    dev_rngs = [numpy.random.RandomState(seed + 40 + i) for i in range(B)]
+    ora_rngs = [numpy.random.RandomState(seed + 40 + i) for i in range(B)]
+    dev_ev = [co.ReplayValues(seed + i, 2 * S + 1, A) for i in range(B)]
+    ora_ev = [co.ReplayValues(seed + i, 2 * S + 1, A) for i in range(B)]
+    trees = [mo.run_search(cfg, ora_ev[i], None, legal[i], tp0[i], True, ora_rngs[i]) for i in range(B)]
+    got = ls.fresh(legal, numpy.array(tp0, numpy.int32), True, dev_rngs, dev_ev)
+    picks = _bad_carry_actions(got, legal, A)
+    assert {k for _, k in picks} == {0, 1, 2}
+    assert ls.advance([a for a, _ in picks]) == 0, backend.lib.mzx_last_error()
+    trees = [co.carry(trees[i], cfg, a if kind == 2 else -1) for i, (a, kind) in enumerate(picks)]
+    for i in range(B):
+        co.continue_search(cfg, ora_ev[i], trees[i], trees[i].to_play[0], True, ora_rngs[i])
+    got = ls.cont([len(t.actions[0]) for t in trees], numpy.array([t.to_play[0] for t in trees], numpy.int32), True,
+                  dev_rngs, dev_ev)
+    want = numpy.array([0 if kind == 2 else 4 for _, kind in picks])
+    assert numpy.array_equal(got["info"][:, 1], want), got["info"][:, 1]
+    for i, (a, kind) in enumerate(picks):
+        co.assert_tree_equal(got, i, trees[i], A, flags=int(want[i]))
+        if kind != 2:
+            assert len(trees[i].actions[0]) == len(legal[i]) and got["n_nodes"][i] == 2 * S + 1     # the old root, whole
+        assert numpy.array_equal(dev_rngs[i].get_state()[1], ora_rngs[i].get_state()[1])
+    ls.close()
+
+
+@pytest.mark.parametrize("game", ["tictactoe", "lunarlander"])
+def test_hostcheck_bad_carry_keeps_the_old_root_and_flags_it(backend, game):
+    bad_carry_lockstep(backend, game, 9, 3 if game == "tictactoe" else 2)
 
 
 def test_hostcheck_refusals(backend):
