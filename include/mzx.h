@@ -579,6 +579,52 @@ int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples,
 int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The loss head of the trainer (mzx.trainer; csrc/mzx_trainer.h): what Trainer.update_weights computes between the
+ * network's logits and loss.backward() (trainer.py:161-258).  Stateless; every pointer is a device pointer, fp32.
+ * mzx_scalar_to_support = models.scalar_to_support (models.py:669-689) of `rows` scalars -> d_out [rows][2 * support_size
+ *   + 1], bit for bit (at most two non-zeros per row; the fused entry below derives the same pair in registers).
+ * mzx_trainer_loss, for B = batch samples, steps = num_unroll_steps + 1, W = 2 * support_size + 1, A = num_actions:
+ *   in:  d_value_logits / d_reward_logits [steps][B][W], d_policy_logits [steps][B][A] -- STEP-MAJOR, what
+ *        torch.stack(list_of_steps, 0) yields --, d_target_value / d_target_reward [B][steps] (scalars),
+ *        d_target_policy [B][steps][A] (used as given: rows need not sum to 1), d_gradient_scale [B][steps],
+ *        d_weight [B] (the PER weights; NULL when PER is off).
+ *   out: d_losses [4] = loss, mean value loss, mean reward loss, mean policy loss (the four numbers update_weights logs):
+ *          loss = mean_b(w_b * (value_loss_weight * sum_i vl + sum_{i>=1} rl + sum_i pl)), l = sum_j -t_j * log_softmax(x)_j;
+ *        d_priorities [B][steps] = float32(|support_to_scalar(value logits) - target value|) ** per_alpha, the prediction
+ *          with the bits of mzx_support_to_scalar;
+ *        d_grad_value / d_grad_reward / d_grad_policy, shaped like the logits: d loss / d logit
+ *          = (w_b / B) * c_head * g_{b,i} * (softmax(x)_j * sum_j t_j - t_j), c_head = value_loss_weight for the value head,
+ *          g_{b,0} = 1, g_{b,i} = 1 / gradient_scale[b][i] (the register_hook lines :225-233; not part of the loss value);
+ *          the reward rows of step 0 are written as zeros.  All three NULL: evaluation only.
+ *   d_scratch: mzx_trainer_loss_scratch_bytes(batch, steps) bytes, 16-byte aligned.
+ *   Two launches (the rows; the batch means in a fixed order), no atomics: the same bits on every run.  MZX_ERR_INVALID
+ *   -- before anything is launched -- for batch / steps / num_actions < 1, support_size < 0, a missing required pointer,
+ *   gradient pointers given in part, or a short scratch buffer.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_trainer_loss_io {
+  const float* d_value_logits;
+  const float* d_reward_logits;
+  const float* d_policy_logits;
+  const float* d_target_value;
+  const float* d_target_reward;
+  const float* d_target_policy;
+  const float* d_gradient_scale;
+  const float* d_weight;           /* nullable */
+  int32_t batch, steps, support_size, num_actions;
+  double value_loss_weight, per_alpha;
+  float* d_losses;
+  float* d_priorities;
+  float* d_grad_value;             /* the three gradients: all or none */
+  float* d_grad_reward;
+  float* d_grad_policy;
+  void* d_scratch;
+  int64_t scratch_bytes;
+} mzx_trainer_loss_io;
+int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream);
+int64_t mzx_trainer_loss_scratch_bytes(int32_t batch, int32_t steps);
+int mzx_trainer_loss(const mzx_trainer_loss_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of
  * games/abstract_game.py:9-105 -- reset / step / legal_actions / to_play -- for num_games games at once, so that a
  * self-play shard need not return to the interpreter per move (mzx_selfplay_rounds below).  kind: "synthetic" (the

@@ -12,6 +12,7 @@
 #include "mzx_replay.h"
 #include "mzx_rng.h"
 #include "mzx_search.h"
+#include "mzx_trainer.h"
 #include "mzx_tree_carry.h"
 #ifndef MZX_HOSTCHECK
 #include "mzx_fused_fc.h"
@@ -1318,6 +1319,66 @@ int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io,
     op.gradient_scale = io->d_gradient_scale; op.n = io->num_samples; op.U = io->num_unroll_steps; op.A = pool->action_space_size;
     MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
   }
+  return MZX_OK;
+}
+
+// ------------------------------------------------------------- the trainer's loss head (csrc/mzx_trainer.h)
+
+int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream) {
+  if (rows < 0 || support_size < 0) { set_error("scalar_to_support: negative argument"); return MZX_ERR_INVALID; }
+  if (rows == 0) return MZX_OK;
+  if (!d_x || !d_out) { set_error("scalar_to_support: missing buffer"); return MZX_ERR_INVALID; }
+  ScalarToSupportOp op;
+  op.x = d_x; op.out = d_out; op.rows = rows; op.support_size = support_size;
+  MZX_TRY_LAUNCH(launch<64>(op, (stream_t)stream));
+  return MZX_OK;
+}
+
+int64_t mzx_trainer_loss_scratch_bytes(int32_t batch, int32_t steps) {
+  if (batch < 1 || steps < 1) return 0;
+  return (int64_t)sizeof(TrainerLossRow) * batch * steps;
+}
+
+int mzx_trainer_loss(const mzx_trainer_loss_io* io, void* stream) {
+  if (!io) { set_error("mzx_trainer_loss: null argument"); return MZX_ERR_INVALID; }
+  if (io->batch < 1 || io->steps < 1 || io->num_actions < 1 || io->support_size < 0) {
+    set_error("mzx_trainer_loss: batch %d, steps %d, num_actions %d must be positive, support_size %d not negative", io->batch,
+              io->steps, io->num_actions, io->support_size);
+    return MZX_ERR_INVALID;
+  }
+  if (!io->d_value_logits || !io->d_reward_logits || !io->d_policy_logits || !io->d_target_value || !io->d_target_reward ||
+      !io->d_target_policy || !io->d_gradient_scale || !io->d_losses || !io->d_priorities || !io->d_scratch) {
+    set_error("mzx_trainer_loss: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  const int given = (io->d_grad_value != nullptr) + (io->d_grad_reward != nullptr) + (io->d_grad_policy != nullptr);
+  if (given != 0 && given != 3) { set_error("mzx_trainer_loss: the three gradient buffers go together"); return MZX_ERR_INVALID; }
+  const int64_t rows = (int64_t)io->batch * io->steps;
+  if (io->scratch_bytes < mzx_trainer_loss_scratch_bytes(io->batch, io->steps) || ((uintptr_t)io->d_scratch % 16) != 0) {
+    set_error("mzx_trainer_loss: scratch needs %lld bytes, 16-byte aligned", (long long)mzx_trainer_loss_scratch_bytes(io->batch, io->steps));
+    return MZX_ERR_INVALID;
+  }
+  if (rows >= ((int64_t)1 << 31)) { set_error("mzx_trainer_loss: batch x steps exceeds one launch"); return MZX_ERR_INVALID; }
+  TrainerLossParams p;
+  p.value_logits = io->d_value_logits; p.reward_logits = io->d_reward_logits; p.policy_logits = io->d_policy_logits;
+  p.target_value = io->d_target_value; p.target_reward = io->d_target_reward; p.target_policy = io->d_target_policy;
+  p.gradient_scale = io->d_gradient_scale; p.weight = io->d_weight; p.priorities = io->d_priorities;
+  p.grad_value = io->d_grad_value; p.grad_reward = io->d_grad_reward; p.grad_policy = io->d_grad_policy;
+  p.scratch = (TrainerLossRow*)io->d_scratch; p.losses = io->d_losses;
+  p.batch = io->batch; p.steps = io->steps; p.support_size = io->support_size; p.num_actions = io->num_actions;
+  p.value_loss_weight = (float)io->value_loss_weight; p.per_alpha = (float)io->per_alpha;
+#ifdef MZX_HOSTCHECK
+  TrainerLossRowOp rows_op; rows_op.p = p;
+  MZX_TRY_LAUNCH(launch<64>(rows_op, (stream_t)stream));
+  TrainerFinishOp finish; finish.p = p;
+  MZX_TRY_LAUNCH(launch<64>(finish, (stream_t)stream));
+#else
+  const unsigned grid = (unsigned)((rows + TRAINER_WAVES - 1) / TRAINER_WAVES);
+  hipLaunchKernelGGL(trainer_loss_kernel, dim3(grid), dim3(64 * TRAINER_WAVES), 0, (stream_t)stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+  hipLaunchKernelGGL(trainer_finish_kernel, dim3(1), dim3(TRAINER_FINISH_BLOCK), 0, (stream_t)stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+#endif
   return MZX_OK;
 }
 

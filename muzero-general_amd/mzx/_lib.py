@@ -126,6 +126,17 @@ class ReplayBatchIO(ctypes.Structure):
     ]
 
 
+class TrainerLossIO(ctypes.Structure):
+    """``mzx_trainer_loss_io``: the inputs and outputs of one mzx_trainer_loss call (mzx.trainer)."""
+    _fields_ = [
+        ("d_value_logits", c_vp), ("d_reward_logits", c_vp), ("d_policy_logits", c_vp), ("d_target_value", c_vp),
+        ("d_target_reward", c_vp), ("d_target_policy", c_vp), ("d_gradient_scale", c_vp), ("d_weight", c_vp),
+        ("batch", c_i32), ("steps", c_i32), ("support_size", c_i32), ("num_actions", c_i32),
+        ("value_loss_weight", c_f64), ("per_alpha", c_f64), ("d_losses", c_vp), ("d_priorities", c_vp),
+        ("d_grad_value", c_vp), ("d_grad_reward", c_vp), ("d_grad_policy", c_vp), ("d_scratch", c_vp), ("scratch_bytes", c_i64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/mzx.h declares
 PROTOTYPES = {
     "mzx_abi_version": (ctypes.c_int, []),
@@ -202,6 +213,9 @@ PROTOTYPES = {
     "mzx_replay_positions": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_reanalyse_write": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_batch": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplayBatchIO), c_vp]),
+    "mzx_scalar_to_support": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mzx_trainer_loss_scratch_bytes": (c_i64, [c_i32, c_i32]),
+    "mzx_trainer_loss": (ctypes.c_int, [ctypes.POINTER(TrainerLossIO), c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

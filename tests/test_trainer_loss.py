@@ -1,0 +1,204 @@
+"""
+The loss head of the trainer (mzx.trainer, mzx_trainer_loss, mzx_scalar_to_support) on the serial test double of the ABI,
+against tests/golden/trainer_loss.npz -- the unmodified reference's own results in float32 and binary64
+(muzero-general_amd/tools/make_trainer_loss_golden.py) -- and, where the reference tree is present, against it live.
+"""
+import ctypes
+
+import numpy
+import pytest
+import torch
+
+import hostcheck
+import trainer_loss_cases as cases
+from mzx import _lib, trainer
+from oracle import ref_shim
+
+
+@pytest.fixture(scope="module")
+def be():
+    return hostcheck.backend()
+
+
+@pytest.fixture(scope="module")
+def gold(golden_dir):
+    return cases.golden(golden_dir)
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=lambda c: c["name"])
+def test_scalar_to_support_rows_bit_for_bit(be, gold, case):
+    x = cases.inputs(case)
+    for key in ("value", "reward"):
+        rows = trainer.scalar_to_support(torch.from_numpy(x[f"target_{key}"]), case["S"], backend=be).numpy()
+        want = gold[f"{case['name']}/f32_support_{key}"]
+        assert rows.shape == want.shape and rows.dtype == numpy.float32
+        assert numpy.array_equal(rows.view(numpy.int32), want.view(numpy.int32))
+        assert (numpy.count_nonzero(rows, axis=-1) <= 2).all()
+
+
+@pytest.mark.reference
+@pytest.mark.parametrize("case", cases.CASES, ids=lambda c: c["name"])
+def test_scalar_to_support_live(be, case):
+    ref_models, _ = ref_shim.load()
+    rs = numpy.random.RandomState(case["seed"] + 100)
+    x = numpy.concatenate([rs.standard_normal(500) * 30, rs.standard_normal(500), [0.0, -0.0, 1e4, -1e4, 1e-30, 3e38]])
+    x = torch.tensor(x.reshape(2, -1), dtype=torch.float32)
+    with cases.ieee_sqrt():
+        want = ref_models.scalar_to_support(x, case["S"]).numpy()
+    rows = trainer.scalar_to_support(x, case["S"], backend=be).numpy()
+    assert numpy.array_equal(rows.view(numpy.int32), want.view(numpy.int32))
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=lambda c: c["name"])
+def test_loss_gradients_priorities(be, gold, case):
+    x, got = cases.check_case(be, case, gold)
+    # evaluation only (no gradient buffers): loss and priorities unchanged
+    plain = cases.run_abi(be, case, x, grads=False)
+    for key in ("loss", "value_loss", "reward_loss", "policy_loss", "priorities"):
+        assert numpy.array_equal(numpy.asarray(plain[key]), numpy.asarray(got[key])), key
+
+
+def _tensors(x, device="cpu"):
+    t = lambda a: None if a is None else torch.from_numpy(a).to(device)
+    return {k: t(v) for k, v in x.items()}
+
+
+def test_autograd_contract(be, gold):
+    case = cases.CASES[1]
+    cfg = cases.config_of(case)
+    x = cases.inputs(case)
+    t = _tensors(x)
+    direct = cases.run_abi(be, case, x)
+
+    def lists():      # the reference's shape: per-step tensors, value / reward with a trailing singleton
+        v = [a.clone().unsqueeze(-1).requires_grad_() for a in t["value"]]
+        r = [a.clone().unsqueeze(-1).requires_grad_() for a in t["reward"]]
+        p = [a.clone().requires_grad_() for a in t["policy"]]
+        return v, r, p
+
+    def call(v, r, p):
+        return trainer.muzero_loss(v, r, p, t["target_value"], t["target_reward"], t["target_policy"], t["weight"],
+                                   t["gradient_scale"], cfg, backend=be)
+
+    v, r, p = lists()
+    loss, value_loss, reward_loss, policy_loss, priorities = call(v, r, p)
+    assert loss.dim() == 0 and loss.grad_fn is not None
+    for m in (value_loss, reward_loss, policy_loss, priorities):
+        assert not m.requires_grad
+    assert priorities.shape == (case["B"], case["steps"]) and priorities.dtype == torch.float32
+    assert numpy.array_equal(priorities.numpy(), direct["priorities"]) and loss.item() == direct["loss"]
+    assert (value_loss.item(), reward_loss.item(), policy_loss.item()) == (direct["value_loss"], direct["reward_loss"],
+                                                                          direct["policy_loss"])
+    loss.backward()
+    for i in range(case["steps"]):
+        assert numpy.array_equal(v[i].grad.squeeze(-1).numpy(), direct["grad_value"][i])
+        assert numpy.array_equal(r[i].grad.squeeze(-1).numpy(), direct["grad_reward"][i])
+        assert numpy.array_equal(p[i].grad.numpy(), direct["grad_policy"][i])
+    assert not r[0].grad.any()                                         # the reward logits of step 0: exact zeros
+    # grad_output = 2 doubles every gradient
+    v2, r2, p2 = lists()
+    call(v2, r2, p2)[0].backward(torch.tensor(2.0))
+    for a, b in zip(v + r + p, v2 + r2 + p2):
+        assert numpy.array_equal(b.grad.numpy(), 2 * a.grad.numpy())
+    # stacked, non-contiguous, binary64 inputs: made contiguous float32; the gradient comes back in the input's dtype
+    sv = t["value"].double().transpose(0, 1).contiguous().transpose(0, 1).requires_grad_()
+    out = trainer.muzero_loss(sv, t["reward"], t["policy"], t["target_value"].double(), t["target_reward"], t["target_policy"],
+                              t["weight"], t["gradient_scale"], cfg, backend=be)
+    assert out[0].item() == direct["loss"]
+    out[0].backward()
+    assert sv.grad.dtype == torch.float64 and numpy.array_equal(sv.grad.float().numpy(), direct["grad_value"])
+    # no second derivative
+    v3, r3, p3 = lists()
+    with pytest.raises(NotImplementedError):
+        torch.autograd.grad(call(v3, r3, p3)[0], v3[0], create_graph=True)
+    # no logit requires a gradient: evaluation only, same numbers
+    with torch.no_grad():
+        again = call(*lists())
+    assert again[0].item() == direct["loss"] and numpy.array_equal(again[4].numpy(), direct["priorities"])
+
+
+def test_no_cpu_path_in_the_product():
+    if torch.cuda.is_available():
+        pytest.skip("checks the no-GPU failure mode")
+    with pytest.raises(_lib.MzxError):
+        trainer.scalar_to_support(torch.zeros(1, 1), 3)
+
+
+@pytest.mark.parametrize("case", [cases.CASES[1], cases.CASES[2]], ids=lambda c: c["name"])
+def test_update_weights_two_sgd_steps(be, case):
+    cfg = cases.config_of(case)
+    torch.manual_seed(5)
+    ours = cases.TinyModel(6, 8, case["S"], case["A"])
+    theirs = cases.TinyModel(6, 8, case["S"], case["A"])
+    theirs.load_state_dict(ours.state_dict())
+    opt_ours, opt_theirs = torch.optim.SGD(ours.parameters(), lr=1.0), torch.optim.SGD(theirs.parameters(), lr=1.0)
+    for step in range(2):
+        batch = cases.training_batch(case, seed=3 + step)
+        got = trainer.update_weights(ours, opt_ours, batch, cfg, backend=be)
+        want = cases.torch_update_weights(theirs, opt_theirs, batch, cfg)
+        assert isinstance(got[0], numpy.ndarray) and got[0].dtype == numpy.float32 and got[0].shape == want[0].shape
+        assert all(type(v) is float for v in got[1:])
+        # lr = 1: a parameter moves by its gradient, a sum of logit gradients (each within the gradient gate) times
+        # activations bounded by 1 (tanh) over batch x steps rows
+        gate = 4 * cases.GRAD_ERROR_FLOOR * case["B"] * case["steps"]
+        for (name, a), b in zip(ours.named_parameters(), theirs.parameters()):
+            err = (a - b).abs().max().item()
+            print(f"{case['name']} step {step} {name}: {err:.3e} (gate {gate:.3e})")
+            assert err <= gate, name
+        # |a ** alpha - b ** alpha| <= |a - b| ** alpha for alpha <= 1, and the decoded values agree within their gate
+        assert numpy.abs(got[0] - want[0]).max() <= cases.DECODED_SCALAR_GATE ** cfg.PER_alpha
+        assert numpy.allclose(got[1:], want[1:], rtol=1e-5, atol=cases.LOSS_ERROR_FLOOR)
+
+
+def _io(be, case, x, keep):
+    up = lambda a: None if a is None else torch.from_numpy(numpy.ascontiguousarray(a))
+    t = {k: up(v) for k, v in x.items()}
+    B, steps = case["B"], case["steps"]
+    t["losses"], t["priorities"] = torch.full((4,), 7.0), torch.full((B, steps), 7.0)
+    t["gv"], t["gr"], t["gp"] = (torch.full_like(t[k], 7.0) for k in ("value", "reward", "policy"))
+    nbytes = int(be.lib.mzx_trainer_loss_scratch_bytes(B, steps))
+    t["scratch"] = torch.zeros(nbytes // 4)
+    keep.append(t)
+    io = _lib.TrainerLossIO()
+    io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (t[k].data_ptr() for k in ("value", "reward", "policy"))
+    io.d_target_value, io.d_target_reward, io.d_target_policy = (t[k].data_ptr() for k in ("target_value", "target_reward",
+                                                                                             "target_policy"))
+    io.d_gradient_scale, io.d_weight = t["gradient_scale"].data_ptr(), t["weight"].data_ptr()
+    io.batch, io.steps, io.support_size, io.num_actions = B, steps, case["S"], case["A"]
+    io.value_loss_weight, io.per_alpha = case["vlw"], case["alpha"]
+    io.d_losses, io.d_priorities = t["losses"].data_ptr(), t["priorities"].data_ptr()
+    io.d_grad_value, io.d_grad_reward, io.d_grad_policy = t["gv"].data_ptr(), t["gr"].data_ptr(), t["gp"].data_ptr()
+    io.d_scratch, io.scratch_bytes = t["scratch"].data_ptr(), nbytes
+    return io, t
+
+
+REQUIRED = ("d_value_logits", "d_reward_logits", "d_policy_logits", "d_target_value", "d_target_reward", "d_target_policy",
+            "d_gradient_scale", "d_losses", "d_priorities", "d_scratch")
+BAD = ([(f, None) for f in REQUIRED] + [("batch", 0), ("batch", -1), ("steps", 0), ("num_actions", 0), ("support_size", -1),
+                                         ("d_grad_reward", None), ("scratch_bytes", 8)])
+
+
+@pytest.mark.parametrize("field,value", BAD, ids=[f"{f}={v}" for f, v in BAD])
+def test_abi_refusals(be, field, value):
+    case, keep = cases.CASES[1], []
+    io, t = _io(be, case, cases.inputs(case), keep)
+    setattr(io, field, value)
+    assert be.lib.mzx_trainer_loss(ctypes.byref(io), None) == -1        # MZX_ERR_INVALID
+    assert be.lib.mzx_last_error()
+    for key in ("losses", "priorities", "gv", "gr", "gp"):
+        assert (t[key] == 7.0).all(), key
+    io, t = _io(be, case, cases.inputs(case), keep)                     # (and the untouched struct is accepted)
+    assert be.lib.mzx_trainer_loss(ctypes.byref(io), None) == 0 and not (t["losses"] == 7.0).any()
+
+
+def test_abi_refusals_scalar_to_support(be):
+    out = torch.full((2, 3), 7.0)
+    x = torch.zeros(2)
+    lib = be.lib
+    assert lib.mzx_trainer_loss(None, None) == -1
+    assert lib.mzx_scalar_to_support(be.ptr(x), -1, 1, be.ptr(out), None) == -1
+    assert lib.mzx_scalar_to_support(be.ptr(x), 2, -1, be.ptr(out), None) == -1
+    assert lib.mzx_scalar_to_support(None, 2, 1, be.ptr(out), None) == -1
+    assert lib.mzx_scalar_to_support(be.ptr(x), 2, 1, None, None) == -1
+    assert (out == 7.0).all()
+    assert lib.mzx_trainer_loss_scratch_bytes(0, 3) == 0 and lib.mzx_trainer_loss_scratch_bytes(5, 3) >= 5 * 3 * 12
