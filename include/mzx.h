@@ -579,6 +579,78 @@ int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples,
 int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Prioritised sampling and priority feedback for the store above (csrc/mzx_replay.h): the PER priorities live in the pool
+ * too, batches are DRAWN on the device and the trainer's new priorities are scattered back there, so get_batch, the loss
+ * head and update_priorities are launches on one stream.  Stateless like the entries above: the caller owns every array
+ * of mzx_replay_sampler, every pointer is a device pointer, and the argument checks return MZX_ERR_INVALID before
+ * anything is launched.
+ * State: d_priorities f32 [rows] -- row base + i the priority of position i < T, the padding row base + T 0 --; d_owner
+ *   i32 [rows], scratch of the scatter, -1 everywhere between calls; a table of `slots` games, slot = game_id % slots:
+ *   d_slot_game i64 (-1: empty), d_slot_base i64, d_slot_len i32 (T), d_slot_priority f32 (the maximum of the game's
+ *   priorities: game_priority), d_slot_sum f64 (their sum).  A slot whose rows do not lie inside the pool is never followed.
+ *   A priority counts with its float32 value widened to binary64; a non-finite or non-positive one counts as 0.
+ *   Workspace: d_tile_prefix f64 [2 * ceil(slots / 256)], d_raw f64 [raw_capacity >= num_samples] (PER only).
+ * mzx_replay_sampler_refresh: d_slot_priority (max) and d_slot_sum (binary64 sum) of the n slots listed in d_slots (i32),
+ *   recomputed from d_priorities; an empty slot gets 0 / 0.  One launch.
+ * mzx_replay_sample: num_samples draws of the reference's two-level distribution (replay_buffer.py:166-202): game by
+ *   game_priority, position by priorities; both uniform when per == 0.
+ *   Uniforms: Philox4x32-10, key = (seed lo, seed hi), counter = (sample index, call_counter lo, call_counter hi, block).
+ *     Block 0 with words w0..w3: u_game = ((w0 << 21) | (w1 >> 11)) * 2^-53, u_pos the same from w2, w3.  d_uniforms f64
+ *     [num_samples][2] (nullable) replaces the two.  Blocks 1, 2, ... supply one word per unroll step: absorbing step u takes
+ *     index = mulhi(word_u, num_actions) -- no rejection step: bias at most num_actions / 2^32 -- and the action
+ *     d_action_space[index] (i32 [num_actions]; NULL: the identity).
+ *   Game level: slot weight w_s = (double)slot_priority with per, else 1, for a resident game of T > 0; 0 otherwise.
+ *     S = sum w_s, C_s the inclusive prefix in slot order, t = u_game * S: the smallest s with C_s > t.  If rounding leaves
+ *     none, the last slot of positive weight.  Position level with per: the same rule over the T priorities, total P =
+ *     slot_sum; without: pos = min(T - 1, floor(u_pos * T)).  A level whose total is 0 is drawn uniformly (every live game
+ *     with w = 1, S = their number; every position with p = 1, P = T).  No draw leaves the table or its game whatever the
+ *     priorities hold.  Sums are binary64 in a fixed association (tiles / chunks of 256): the same bits on every run.
+ *   Outputs: d_base / d_len / d_pos / d_absorbing_actions [num_samples][num_unroll_steps + 1] -- the arrays
+ *     mzx_replay_batch_io takes; the whole tape row is written: the drawn action at the steps past the end of the game, 0
+ *     elsewhere --, d_game_id i64 [num_samples] (-1 with base 0, T 0 when no game is live), and with per d_weight f32
+ *     [num_samples]: raw = 1.0 / (((double)total_samples * (w_s / S)) * (p_i / P)), weight = (float)(raw / max raw), all
+ *     in binary64 (the reference divides by the maximum in float32: this opt-in path defines its own rounding).  A sample
+ *     drawn while no game is live, and every sample when total_samples <= 0, gets the weight 0 (never NaN).
+ *   Launches: tile sums, tile prefix, draw (a wavefront per sample), and with per the weight finish.
+ * mzx_replay_update_priorities (replay_buffer.py:205-228): sample i writes d_new[i][k] to position d_pos[i] + k for
+ *   k < min(steps, T - pos), provided d_slot_game[d_game_id[i] % slots] == d_game_id[i] (otherwise the game has left the
+ *   buffer and the sample is passed over).  Where windows overlap the highest sample index wins, as in the reference's
+ *   sequential loop: a claim pass (integer atomic max of i into d_owner), a write pass (stores where the claim is its
+ *   own, puts -1 back), then slot_priority / slot_sum of the games touched.  Deterministic; three launches.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_replay_sampler {
+  float* d_priorities;             /* [rows] */
+  int32_t* d_owner;                /* [rows] */
+  const int64_t* d_slot_game;      /* [slots] */
+  const int64_t* d_slot_base;      /* [slots] */
+  const int32_t* d_slot_len;       /* [slots] */
+  float* d_slot_priority;          /* [slots] */
+  double* d_slot_sum;              /* [slots] */
+  int64_t rows;
+  int32_t slots, reserved;
+  double* d_tile_prefix;           /* workspace [2 * ceil(slots / 256)] */
+  double* d_raw;                   /* workspace [raw_capacity] */
+  int64_t raw_capacity;
+} mzx_replay_sampler;
+typedef struct mzx_replay_sample_io {
+  uint64_t seed, call_counter;
+  int64_t total_samples;
+  int32_t num_samples, per, num_unroll_steps, num_actions;
+  const int32_t* d_action_space;   /* nullable */
+  const double* d_uniforms;        /* nullable */
+  int64_t* d_base;
+  int32_t* d_len;
+  int32_t* d_pos;
+  int32_t* d_absorbing_actions;
+  int64_t* d_game_id;
+  float* d_weight;                 /* required with per, ignored without */
+} mzx_replay_sample_io;
+int mzx_replay_sampler_refresh(const mzx_replay_sampler* sampler, const int32_t* d_slots, int32_t n, void* stream);
+int mzx_replay_sample(const mzx_replay_sampler* sampler, const mzx_replay_sample_io* io, void* stream);
+int mzx_replay_update_priorities(const mzx_replay_sampler* sampler, const float* d_new, const int64_t* d_game_id,
+                                 const int32_t* d_pos, int32_t n, int32_t steps, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The loss head of the trainer (mzx.trainer; csrc/mzx_trainer.h): what Trainer.update_weights computes between the
  * network's logits and loss.backward() (trainer.py:161-258).  Stateless; every pointer is a device pointer, fp32.
  * mzx_scalar_to_support = models.scalar_to_support (models.py:669-689) of `rows` scalars -> d_out [rows][2 * support_size

@@ -1322,6 +1322,116 @@ int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io,
   return MZX_OK;
 }
 
+// ------------------------------------------------------------- device replay store: prioritised draws + priority feedback
+
+static int replay_sampler_table(const char* who, const mzx_replay_sampler* sampler, ReplaySamplerTable* t) {
+  if (!sampler) { set_error("%s: null sampler", who); return MZX_ERR_INVALID; }
+  if (sampler->rows < 1 || sampler->slots < 1) { set_error("%s: rows and slots must be positive", who); return MZX_ERR_INVALID; }
+  if (!sampler->d_priorities || !sampler->d_owner || !sampler->d_slot_game || !sampler->d_slot_base || !sampler->d_slot_len ||
+      !sampler->d_slot_priority || !sampler->d_slot_sum) {
+    set_error("%s: missing sampler column", who);
+    return MZX_ERR_INVALID;
+  }
+  t->priorities = sampler->d_priorities; t->owner = sampler->d_owner; t->slot_game = sampler->d_slot_game;
+  t->slot_base = sampler->d_slot_base; t->slot_len = sampler->d_slot_len; t->slot_priority = sampler->d_slot_priority;
+  t->slot_sum = sampler->d_slot_sum; t->rows = sampler->rows; t->slots = sampler->slots;
+  return MZX_OK;
+}
+
+static int replay_refresh_launch(const ReplayRefreshParams& p, stream_t stream) {
+#ifdef MZX_HOSTCHECK
+  ReplayRefreshOp op; op.p = p;
+  MZX_TRY_LAUNCH(launch<64>(op, stream));
+#else
+  const unsigned grid = (unsigned)(((int64_t)p.n + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
+  hipLaunchKernelGGL(replay_refresh_kernel, dim3(grid), dim3(64 * SAMPLER_WAVES), 0, stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+#endif
+  return MZX_OK;
+}
+
+int mzx_replay_sampler_refresh(const mzx_replay_sampler* sampler, const int32_t* d_slots, int32_t n, void* stream) {
+  ReplayRefreshParams p;
+  const int rc = replay_sampler_table("mzx_replay_sampler_refresh", sampler, &p.t);
+  if (rc) return rc;
+  if (n < 0) { set_error("mzx_replay_sampler_refresh: negative count"); return MZX_ERR_INVALID; }
+  if (n == 0) return MZX_OK;
+  if (!d_slots) { set_error("mzx_replay_sampler_refresh: missing slot list"); return MZX_ERR_INVALID; }
+  p.slot_list = d_slots; p.game_ids = nullptr; p.n = n;
+  return replay_refresh_launch(p, (stream_t)stream);
+}
+
+int mzx_replay_sample(const mzx_replay_sampler* sampler, const mzx_replay_sample_io* io, void* stream) {
+  ReplayDrawParams p;
+  const int rc = replay_sampler_table("mzx_replay_sample", sampler, &p.t);
+  if (rc) return rc;
+  if (!io) { set_error("mzx_replay_sample: null io"); return MZX_ERR_INVALID; }
+  if (io->num_samples < 0 || io->num_unroll_steps < 0 || io->num_actions < 1) {
+    set_error("mzx_replay_sample: num_samples %d and num_unroll_steps %d must not be negative, num_actions %d positive",
+              io->num_samples, io->num_unroll_steps, io->num_actions);
+    return MZX_ERR_INVALID;
+  }
+  if (!io->d_base || !io->d_len || !io->d_pos || !io->d_absorbing_actions || !io->d_game_id || (io->per && !io->d_weight)) {
+    set_error("mzx_replay_sample: missing output");
+    return MZX_ERR_INVALID;
+  }
+  if (!sampler->d_tile_prefix || (io->per && (!sampler->d_raw || sampler->raw_capacity < io->num_samples))) {
+    set_error("mzx_replay_sample: workspace missing or short (%lld raw entries for %d samples)", (long long)sampler->raw_capacity,
+              io->num_samples);
+    return MZX_ERR_INVALID;
+  }
+  if (io->num_samples == 0) return MZX_OK;
+  p.tile_prefix = sampler->d_tile_prefix; p.raw = sampler->d_raw; p.action_space = io->d_action_space; p.uniforms = io->d_uniforms;
+  p.out_base = io->d_base; p.out_len = io->d_len; p.out_pos = io->d_pos; p.out_tape = io->d_absorbing_actions;
+  p.out_game = io->d_game_id; p.out_weight = io->d_weight; p.seed = io->seed; p.call_counter = io->call_counter;
+  p.total_samples = io->total_samples; p.n = io->num_samples; p.per = io->per ? 1 : 0; p.U = io->num_unroll_steps;
+  p.A = io->num_actions; p.tiles = (sampler->slots + SAMPLER_TILE - 1) / SAMPLER_TILE;
+#ifdef MZX_HOSTCHECK
+  ReplayTileSumOp sums; sums.p = p;
+  MZX_TRY_LAUNCH(launch<64>(sums, (stream_t)stream));
+  ReplayTilePrefixOp prefix; prefix.p = p;
+  MZX_TRY_LAUNCH(launch<64>(prefix, (stream_t)stream));
+  ReplayDrawOp draw; draw.p = p;
+  MZX_TRY_LAUNCH(launch<64>(draw, (stream_t)stream));
+  if (p.per) {
+    ReplayWeightFinishOp finish; finish.p = p;
+    MZX_TRY_LAUNCH(launch<64>(finish, (stream_t)stream));
+  }
+#else
+  const unsigned tile_grid = (unsigned)((p.tiles + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
+  hipLaunchKernelGGL(replay_tile_sum_kernel, dim3(tile_grid), dim3(64 * SAMPLER_WAVES), 0, (stream_t)stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+  hipLaunchKernelGGL(replay_tile_prefix_kernel, dim3(1), dim3(128), 0, (stream_t)stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+  const unsigned grid = (unsigned)(((int64_t)p.n + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
+  hipLaunchKernelGGL(replay_draw_kernel, dim3(grid), dim3(64 * SAMPLER_WAVES), 0, (stream_t)stream, p);
+  MZX_TRY_LAUNCH((int)hipGetLastError());
+  if (p.per) {
+    hipLaunchKernelGGL(replay_weight_finish_kernel, dim3(1), dim3(SAMPLER_FINISH_BLOCK), 0, (stream_t)stream, p);
+    MZX_TRY_LAUNCH((int)hipGetLastError());
+  }
+#endif
+  return MZX_OK;
+}
+
+int mzx_replay_update_priorities(const mzx_replay_sampler* sampler, const float* d_new, const int64_t* d_game_id,
+                                 const int32_t* d_pos, int32_t n, int32_t steps, void* stream) {
+  ReplayClaimOp op;
+  const int rc = replay_sampler_table("mzx_replay_update_priorities", sampler, &op.t);
+  if (rc) return rc;
+  if (n < 0 || steps < 1) { set_error("mzx_replay_update_priorities: n %d must not be negative, steps %d positive", n, steps); return MZX_ERR_INVALID; }
+  if (n == 0) return MZX_OK;
+  if (!d_new || !d_game_id || !d_pos) { set_error("mzx_replay_update_priorities: missing buffer"); return MZX_ERR_INVALID; }
+  op.fresh = d_new; op.game_id = d_game_id; op.pos = d_pos; op.n = n; op.steps = steps;
+  op.write = 0;
+  MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
+  op.write = 1;
+  MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
+  ReplayRefreshParams p;
+  p.t = op.t; p.slot_list = nullptr; p.game_ids = d_game_id; p.n = n;
+  return replay_refresh_launch(p, (stream_t)stream);
+}
+
 // ------------------------------------------------------------- the trainer's loss head (csrc/mzx_trainer.h)
 
 int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream) {

@@ -205,4 +205,491 @@ struct ReplayReanalyseOp {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Prioritised sampling and priority feedback on the device (mzx_replay_sampler, include/mzx.h): the store also holds the
+// PER priorities -- `priorities` f32 [rows], row base + i the priority of position i < T, the padding row base + T 0 -- and
+// a table of `slots` games, slot = game_id % slots: slot_game i64 (-1: empty), slot_base i64, slot_len i32, slot_priority
+// f32 (the maximum of the game's priorities: game_priority), slot_sum f64 (their sum).
+//
+// The draw (mzx_replay_sample) is the reference's two-level one -- game by game_priority, position by priorities,
+// replay_buffer.py:166-202 -- stated over a counter-based generator so that sample i of call c is a pure function of
+// (seed, c, i): Philox4x32-10, key = the halves of the seed, counter = (i, c lo, c hi, block).  Block 0 gives the two
+// uniforms (53 bits each), blocks 1, 2, ... one word per unroll step for the absorbing actions.
+// A weight is the float32 priority widened to binary64; a non-finite or non-positive one counts as 0.  At each level the
+// target is t = u * total and the draw is the smallest index whose inclusive prefix exceeds t (strictly), where the
+// prefix is accumulated in binary64: slots in tiles of 256 (per-tile sums, a prefix over the tiles, a scan inside the
+// chosen tile), positions in chunks of 256 with a running carry.  If rounding leaves no such index the last index of
+// positive weight is taken; a level whose total is 0 is drawn uniformly (over live games / over the T positions).
+// Importance weight: raw = 1 / ((total_samples * (w_s / S)) * (p_i / P)), weight = float32(raw / max raw) -- binary64
+// throughout (the reference divides by the maximum in float32: this opt-in path defines its own rounding); a sample drawn
+// while no game is live, and every sample when total_samples <= 0, gets the weight 0.
+//
+// Product build: wave-cooperative kernels (a wavefront per refreshed game / per tile / per sample).  tests/hostcheck build:
+// serial functors of the same definition.  The sums of one build are always taken in the same association, so a run
+// repeats bit for bit; the two builds associate differently and agree exactly wherever the sums are exact.
+constexpr int SAMPLER_TILE = 256;
+
+MZX_HD inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// 53 random bits -> [0, 1): ((hi << 21) | (lo >> 11)) * 2^-53
+MZX_HD inline double sampler_u53(uint32_t hi, uint32_t lo) {
+  return (double)(((uint64_t)hi << 21) | (uint64_t)(lo >> 11)) * (1.0 / 9007199254740992.0);
+}
+MZX_HD inline double sampler_weight(float p) { return (p > 0.0f && p <= 3.402823466e+38f) ? (double)p : 0.0; }
+
+struct ReplaySamplerTable {
+  float* priorities;            // [rows]
+  int32_t* owner;               // [rows] scratch of the scatter: -1 between calls
+  const int64_t* slot_game;     // [slots]
+  const int64_t* slot_base;
+  const int32_t* slot_len;
+  float* slot_priority;
+  double* slot_sum;
+  int64_t rows;
+  int32_t slots;
+
+  // a slot whose game lies inside the pool (an entry that does not is never followed)
+  MZX_HD bool resident(int s) const {
+    const int64_t b = slot_base[s];
+    const int64_t T = slot_len[s];
+    return slot_game[s] >= 0 && b >= 0 && T >= 0 && b + T < rows;
+  }
+  // kind 0: game_priority; kind 1: 1 for every game that has a position
+  MZX_HD double weight(int s, int kind) const {
+    if (s >= slots || !resident(s) || slot_len[s] < 1) return 0.0;
+    return kind == 0 ? sampler_weight(slot_priority[s]) : 1.0;
+  }
+  MZX_HD int slot_of(int64_t game_id) const {
+    if (game_id < 0) return -1;
+    const int s = (int)(game_id % slots);
+    return slot_game[s] == game_id && resident(s) ? s : -1;
+  }
+};
+
+struct ReplayRefreshParams {
+  ReplaySamplerTable t;
+  const int32_t* slot_list;     // [n], or
+  const int64_t* game_ids;      // [n]: the slots of these games; one that left the table is passed over
+  int32_t n;
+  MZX_HD int slot(size_t e) const {
+    if (!slot_list) return t.slot_of(game_ids[e]);
+    const int s = slot_list[e];
+    return s >= 0 && s < t.slots ? s : -1;
+  }
+};
+
+struct ReplayDrawParams {
+  ReplaySamplerTable t;
+  double* tile_prefix;          // [2][tiles] inclusive prefix of the tile sums: kind 0, then kind 1
+  double* raw;                  // [n] (per only)
+  const int32_t* action_space;  // [A] nullable: the identity
+  const double* uniforms;       // [n][2] nullable
+  int64_t* out_base;
+  int32_t* out_len;
+  int32_t* out_pos;
+  int32_t* out_tape;            // [n][U + 1]
+  int64_t* out_game;
+  float* out_weight;            // [n] (per only)
+  uint64_t seed, call_counter;
+  int64_t total_samples;
+  int32_t n, per, U, A, tiles;
+
+  MZX_HD void block(int i, uint32_t j, uint32_t w[4]) const {
+    philox4x32_10((uint32_t)i, (uint32_t)call_counter, (uint32_t)(call_counter >> 32), j, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  }
+  MZX_HD void uniform_pair(int i, double& u_game, double& u_pos) const {
+    if (uniforms) {
+      u_game = uniforms[2 * (size_t)i];
+      u_pos = uniforms[2 * (size_t)i + 1];
+      return;
+    }
+    uint32_t w[4];
+    block(i, 0, w);
+    u_game = sampler_u53(w[0], w[1]);
+    u_pos = sampler_u53(w[2], w[3]);
+  }
+  // kind of the game level: the priorities, or every live game alike (PER off, or no positive priority anywhere)
+  MZX_HD int kind() const { return per && tile_prefix[tiles - 1] > 0.0 ? 0 : 1; }
+  // the tile of target t: the first whose inclusive prefix exceeds it, else the first that reaches the total
+  MZX_HD int pick_tile(const double* I, double t) const {
+    int lo = 0, hi = tiles;
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if (I[mid] > t) hi = mid; else lo = mid + 1;
+    }
+    if (lo < tiles) return lo;
+    const double S = I[tiles - 1];
+    lo = 0; hi = tiles - 1;
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if (I[mid] >= S) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  }
+  MZX_HD int uniform_position(double u, int T) const {
+    const double f = floor(u * (double)T);
+    return f >= 0.0 ? (f < (double)T ? (int)f : T - 1) : 0;
+  }
+  // absorbing action of unroll step u of sample i: mulhi(word, A) into the action space
+  MZX_HD int32_t absorbing_action(int i, int u) const {
+    uint32_t w[4];
+    block(i, 1u + (uint32_t)(u >> 2), w);
+    const int32_t index = (int32_t)(((uint64_t)w[u & 3] * (uint64_t)(uint32_t)A) >> 32);
+    return action_space ? action_space[index] : index;
+  }
+  MZX_HD void write_sample(int i, int slot, int pos, double w_s, double S, double p_i, double P) const {
+    out_base[i] = slot >= 0 ? t.slot_base[slot] : 0;
+    out_len[i] = slot >= 0 ? t.slot_len[slot] : 0;
+    out_pos[i] = pos;
+    out_game[i] = slot >= 0 ? t.slot_game[slot] : -1;
+    if (per) raw[i] = slot >= 0 && total_samples > 0 ? 1.0 / (((double)total_samples * (w_s / S)) * (p_i / P)) : 0.0;
+  }
+};
+
+// The scatter (update_priorities, replay_buffer.py:205-228): sample i writes new[i][k] to position pos_i + k < T of its
+// game when the game still holds its slot.  The reference's loop lets the LAST sample win where windows overlap: a claim
+// pass takes the integer maximum of i per row (an atomic max: its result does not depend on the order), the write pass
+// stores where the claim is its own and puts -1 back.
+struct ReplayClaimOp {
+  ReplaySamplerTable t;
+  const float* fresh;           // [n][steps]
+  const int64_t* game_id;       // [n]
+  const int32_t* pos;           // [n]
+  int32_t n, steps, write;
+
+  MZX_HD size_t size() const { return (size_t)n * steps; }
+  MZX_HD void operator()(size_t e) const {
+    const int i = (int)(e / (size_t)steps), k = (int)(e % (size_t)steps);
+    const int s = t.slot_of(game_id[i]);
+    if (s < 0) return;
+    const int64_t p = (int64_t)pos[i] + k;
+    if (pos[i] < 0 || p >= t.slot_len[s]) return;
+    const int64_t row = t.slot_base[s] + p;
+    if (!write) {
+#ifdef MZX_HOSTCHECK
+      if (t.owner[row] < i) t.owner[row] = i;
+#else
+      atomicMax(t.owner + row, i);
+#endif
+    } else if (t.owner[row] == i) {
+      t.priorities[row] = fresh[e];
+      t.owner[row] = -1;
+    }
+  }
+};
+
+#ifdef MZX_HOSTCHECK
+
+struct ReplayRefreshOp {
+  ReplayRefreshParams p;
+  MZX_HD size_t size() const { return (size_t)p.n; }
+  MZX_HD void operator()(size_t e) const {
+    const int s = p.slot(e);
+    if (s < 0) return;
+    float m = -(float)MZX_INF;
+    double sum = 0.0;
+    const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
+    const float* pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
+    for (int i = 0; i < T; ++i) {
+      if (pr[i] > m) m = pr[i];
+      sum = sum + sampler_weight(pr[i]);
+    }
+    p.t.slot_priority[s] = T ? m : 0.0f;
+    p.t.slot_sum[s] = sum;
+  }
+};
+
+struct ReplayTileSumOp {
+  ReplayDrawParams p;
+  MZX_HD size_t size() const { return (size_t)p.tiles; }
+  MZX_HD void operator()(size_t k) const {
+    for (int kind = 0; kind < 2; ++kind) {
+      double sum = 0.0;
+      for (int j = 0; j < SAMPLER_TILE; ++j) sum = sum + p.t.weight((int)k * SAMPLER_TILE + j, kind);
+      p.tile_prefix[(size_t)kind * p.tiles + k] = sum;
+    }
+  }
+};
+
+struct ReplayTilePrefixOp {
+  ReplayDrawParams p;
+  MZX_HD size_t size() const { return 2; }
+  MZX_HD void operator()(size_t kind) const {
+    double* I = p.tile_prefix + kind * (size_t)p.tiles;
+    for (int k = 1; k < p.tiles; ++k) I[k] = I[k - 1] + I[k];
+  }
+};
+
+struct ReplayDrawOp {
+  ReplayDrawParams p;
+  MZX_HD size_t size() const { return (size_t)p.n; }
+
+  // first index of [0, count) with carry + prefix > t and a positive weight (-1: none); last: the last positive one
+  template <class W>
+  static int pick(const W& weight, int count, double carry, double t, int& last, double& total) {
+    double run = 0.0;
+    int first = -1;
+    last = -1;
+    for (int j = 0; j < count; ++j) {
+      const double w = weight(j);
+      run = run + w;
+      if (w > 0.0) {
+        last = j;
+        if (first < 0 && carry + run > t) first = j;
+      }
+    }
+    total = run;
+    return first;
+  }
+
+  MZX_HD void operator()(size_t e) const {
+    const int i = (int)e;
+    double u_game, u_pos;
+    p.uniform_pair(i, u_game, u_pos);
+    const int kind = p.kind();
+    const double* I = p.tile_prefix + (size_t)kind * p.tiles;
+    const double S = I[p.tiles - 1];
+    int slot = -1, last;
+    double total;
+    if (S > 0.0) {
+      const double t = u_game * S;
+      const int k = p.pick_tile(I, t);
+      auto w = [&](int j) { return p.t.weight(k * SAMPLER_TILE + j, kind); };
+      int j = pick(w, SAMPLER_TILE, k ? I[k - 1] : 0.0, t, last, total);
+      if (j < 0) j = last;
+      if (j >= 0) slot = k * SAMPLER_TILE + j;
+      for (int k2 = p.tiles - 1; k2 >= 0 && slot < 0; --k2) {      // (a table whose prefix misled the search: its last live slot)
+        auto w2 = [&](int j2) { return p.t.weight(k2 * SAMPLER_TILE + j2, kind); };
+        pick(w2, SAMPLER_TILE, 0.0, 0.0, last, total);
+        if (last >= 0) slot = k2 * SAMPLER_TILE + last;
+      }
+    }
+    const int T = slot >= 0 ? p.t.slot_len[slot] : 0;
+    const float* pr = p.t.priorities + (slot >= 0 ? p.t.slot_base[slot] : 0);
+    int pos = -1;
+    double p_i = 1.0, P = (double)T;
+    const double sum = slot >= 0 ? p.t.slot_sum[slot] : 0.0;
+    if (p.per && sum > 0.0 && sum <= 1.7976931348623157e308) {
+      const double t = u_pos * sum;
+      double carry = 0.0;
+      int seen = -1;
+      for (int c0 = 0; c0 < T && pos < 0; c0 += SAMPLER_TILE) {
+        auto w = [&](int j) { return c0 + j < T ? sampler_weight(pr[c0 + j]) : 0.0; };
+        const int j = pick(w, SAMPLER_TILE, carry, t, last, total);
+        if (last >= 0) seen = c0 + last;
+        if (j >= 0) pos = c0 + j;
+        carry = carry + total;
+      }
+      if (pos < 0) pos = seen;
+      if (pos >= 0) {
+        p_i = sampler_weight(pr[pos]);
+        P = sum;
+      }
+    }
+    if (pos < 0) pos = T > 0 ? p.uniform_position(u_pos, T) : 0;
+    p.write_sample(i, slot, pos, slot >= 0 ? p.t.weight(slot, kind) : 0.0, S, p_i, P);
+    for (int u = 0; u <= p.U; ++u) p.out_tape[(size_t)i * (p.U + 1) + u] = u >= T + 1 - pos ? p.absorbing_action(i, u) : 0;
+  }
+};
+
+struct ReplayWeightFinishOp {
+  ReplayDrawParams p;
+  MZX_HD size_t size() const { return 1; }
+  MZX_HD void operator()(size_t) const {
+    double m = -MZX_INF;
+    for (int i = 0; i < p.n; ++i) if (p.raw[i] > m) m = p.raw[i];
+    for (int i = 0; i < p.n; ++i) p.out_weight[i] = m > 0.0 ? (float)(p.raw[i] / m) : 0.0f;
+  }
+};
+
+#else
+
+constexpr int SAMPLER_WAVES = 4;          // wavefronts (games, tiles, samples) per workgroup
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_refresh_kernel(const ReplayRefreshParams p) {
+  const int lane = threadIdx.x & 63;
+  const size_t e = (size_t)blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
+  if (e >= (size_t)p.n) return;                                   // (whole waves leave: no barrier below)
+  const int s = p.slot(e);
+  if (s < 0) return;
+  const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
+  const float* __restrict__ pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
+  float m = -(float)MZX_INF;
+  double sum = 0.0;
+  for (int i = lane; i < T; i += 64) {
+    const float v = pr[i];
+    if (v > m) m = v;
+    sum = sum + sampler_weight(v);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float other = __shfl_xor(m, o, 64);
+    if (other > m) m = other;
+  }
+  sum = wave_sum_f64(sum);
+  if (lane == 0) {
+    p.t.slot_priority[s] = T ? m : 0.0f;
+    p.t.slot_sum[s] = sum;
+  }
+}
+
+// the sums of both kinds of weight over a tile of 256 slots: four slots per lane, a butterfly over the lanes
+__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_tile_sum_kernel(const ReplayDrawParams p) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
+  if (k >= p.tiles) return;
+  double a = 0.0, b = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int s = k * SAMPLER_TILE + 4 * lane + j;
+    a = a + p.t.weight(s, 0);
+    b = b + p.t.weight(s, 1);
+  }
+  a = wave_sum_f64(a);
+  b = wave_sum_f64(b);
+  if (lane == 0) {
+    p.tile_prefix[k] = a;
+    p.tile_prefix[(size_t)p.tiles + k] = b;
+  }
+}
+
+// inclusive scan over the 64 lanes (lane l ends with v_0 + ... + v_l in a fixed association)
+__device__ __forceinline__ double wave_scan_f64(double v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double below = __shfl_up(v, o, 64);
+    if (lane >= o) v = below + v;
+  }
+  return v;
+}
+
+// the tile sums -> their inclusive prefix, in place: one workgroup, a wavefront per kind, 64 tiles per step with a carry
+__global__ void __launch_bounds__(128) replay_tile_prefix_kernel(const ReplayDrawParams p) {
+  const int lane = threadIdx.x & 63;
+  double* I = p.tile_prefix + (size_t)(threadIdx.x >> 6) * p.tiles;
+  double carry = 0.0;
+  for (int k0 = 0; k0 < p.tiles; k0 += 64) {
+    const int k = k0 + lane;
+    const double v = wave_scan_f64(k < p.tiles ? I[k] : 0.0, lane);
+    if (k < p.tiles) I[k] = carry + v;
+    carry = carry + __shfl(v, 63, 64);
+  }
+}
+
+// One level of a draw over 256 weights, four per lane (lane l holds indices 4l .. 4l + 3): the first index whose
+// carry + inclusive prefix exceeds t and whose weight is positive (-1: none), `last` the last index of positive weight
+// (-1: none), `total` the sum of the 256.  The same value in every lane.
+__device__ __forceinline__ int wave_pick(const double w[4], double carry, double t, int lane, int& last, double& total) {
+  const double l0 = w[0], l1 = l0 + w[1], l2 = l1 + w[2], l3 = l2 + w[3];
+  const double incl = wave_scan_f64(l3, lane);
+  double below = __shfl_up(incl, 1, 64);
+  if (lane == 0) below = 0.0;
+  total = __shfl(incl, 63, 64);
+  int first = -1, tail = -1;
+  if (w[3] > 0.0 && carry + (below + l3) > t) first = 3;
+  if (w[2] > 0.0 && carry + (below + l2) > t) first = 2;
+  if (w[1] > 0.0 && carry + (below + l1) > t) first = 1;
+  if (w[0] > 0.0 && carry + (below + l0) > t) first = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) if (w[j] > 0.0) tail = j;
+  const uint64_t has_first = __ballot(first >= 0), has_tail = __ballot(tail >= 0);
+  const int tail_lane = has_tail ? 63 - __clzll((long long)has_tail) : 0;
+  const int first_lane = has_first ? __ffsll((long long)has_first) - 1 : 0;
+  const int tail_j = __shfl(tail, tail_lane, 64), first_j = __shfl(first, first_lane, 64);
+  last = has_tail ? 4 * tail_lane + tail_j : -1;
+  return has_first ? 4 * first_lane + first_j : -1;
+}
+
+__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_draw_kernel(const ReplayDrawParams p) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
+  if (i >= p.n) return;                                             // (whole waves leave: no barrier below)
+  double u_game = 0.0, u_pos = 0.0;
+  if (lane == 0) p.uniform_pair(i, u_game, u_pos);                  // lane 0's Philox block, broadcast
+  u_game = __shfl(u_game, 0, 64);
+  u_pos = __shfl(u_pos, 0, 64);
+
+  const int kind = p.kind();
+  const double* __restrict__ I = p.tile_prefix + (size_t)kind * p.tiles;
+  const double S = I[p.tiles - 1];
+  int slot = -1, last;
+  double total, w[4];
+  if (S > 0.0) {
+    const double t = u_game * S;
+    const int k = p.pick_tile(I, t);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = p.t.weight(k * SAMPLER_TILE + 4 * lane + j, kind);
+    int j = wave_pick(w, k ? I[k - 1] : 0.0, t, lane, last, total);
+    if (j < 0) j = last;
+    if (j >= 0) slot = k * SAMPLER_TILE + j;
+    for (int k2 = p.tiles - 1; k2 >= 0 && slot < 0; --k2) {          // (a table whose prefix misled the search: its last live slot)
+#pragma unroll
+      for (int j2 = 0; j2 < 4; ++j2) w[j2] = p.t.weight(k2 * SAMPLER_TILE + 4 * lane + j2, kind);
+      wave_pick(w, 0.0, 0.0, lane, last, total);
+      if (last >= 0) slot = k2 * SAMPLER_TILE + last;
+    }
+  }
+  const int T = slot >= 0 ? p.t.slot_len[slot] : 0;
+  const float* __restrict__ pr = p.t.priorities + (slot >= 0 ? p.t.slot_base[slot] : 0);
+  int pos = -1;
+  double p_i = 1.0, P = (double)T;
+  const double sum = slot >= 0 ? p.t.slot_sum[slot] : 0.0;
+  if (p.per && sum > 0.0 && sum <= 1.7976931348623157e308) {
+    const double t = u_pos * sum;
+    double carry = 0.0;
+    int seen = -1;
+    for (int c0 = 0; c0 < T && pos < 0; c0 += SAMPLER_TILE) {        // (pos is the same in every lane)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int idx = c0 + 4 * lane + j;
+        w[j] = idx < T ? sampler_weight(pr[idx]) : 0.0;
+      }
+      const int j = wave_pick(w, carry, t, lane, last, total);
+      if (last >= 0) seen = c0 + last;
+      if (j >= 0) pos = c0 + j;
+      carry = carry + total;
+    }
+    if (pos < 0) pos = seen;
+    if (pos >= 0) {
+      p_i = sampler_weight(pr[pos]);
+      P = sum;
+    }
+  }
+  if (pos < 0) pos = T > 0 ? p.uniform_position(u_pos, T) : 0;
+  if (lane == 0) p.write_sample(i, slot, pos, slot >= 0 ? p.t.weight(slot, kind) : 0.0, S, p_i, P);
+  for (int u = lane; u <= p.U; u += 64) p.out_tape[(size_t)i * (p.U + 1) + u] = u >= T + 1 - pos ? p.absorbing_action(i, u) : 0;
+}
+
+// weight = float32(raw / max raw): one workgroup
+constexpr int SAMPLER_FINISH_BLOCK = 256;
+__global__ void __launch_bounds__(SAMPLER_FINISH_BLOCK) replay_weight_finish_kernel(const ReplayDrawParams p) {
+  __shared__ double part[SAMPLER_FINISH_BLOCK];
+  const int t = threadIdx.x;
+  double m = -MZX_INF;
+  for (int i = t; i < p.n; i += SAMPLER_FINISH_BLOCK) if (p.raw[i] > m) m = p.raw[i];
+  part[t] = m;
+  __syncthreads();
+  for (int o = SAMPLER_FINISH_BLOCK / 2; o >= 1; o >>= 1) {
+    if (t < o && part[t + o] > part[t]) part[t] = part[t + o];
+    __syncthreads();
+  }
+  m = part[0];
+  for (int i = t; i < p.n; i += SAMPLER_FINISH_BLOCK) p.out_weight[i] = m > 0.0 ? (float)(p.raw[i] / m) : 0.0f;
+}
+
+#endif  // MZX_HOSTCHECK
+
 }  // namespace mzx

@@ -126,6 +126,25 @@ class ReplayBatchIO(ctypes.Structure):
     ]
 
 
+class ReplaySampler(ctypes.Structure):
+    """``mzx_replay_sampler``: the priority column, the game table and the workspace of the device-side sampler."""
+    _fields_ = [
+        ("d_priorities", c_vp), ("d_owner", c_vp), ("d_slot_game", c_vp), ("d_slot_base", c_vp), ("d_slot_len", c_vp),
+        ("d_slot_priority", c_vp), ("d_slot_sum", c_vp), ("rows", c_i64), ("slots", c_i32), ("reserved", c_i32),
+        ("d_tile_prefix", c_vp), ("d_raw", c_vp), ("raw_capacity", c_i64),
+    ]
+
+
+class ReplaySampleIO(ctypes.Structure):
+    """``mzx_replay_sample_io``: the scalars, optional inputs and outputs of one mzx_replay_sample call."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("call_counter", ctypes.c_uint64), ("total_samples", c_i64), ("num_samples", c_i32),
+        ("per", c_i32), ("num_unroll_steps", c_i32), ("num_actions", c_i32), ("d_action_space", c_vp), ("d_uniforms", c_vp),
+        ("d_base", c_vp), ("d_len", c_vp), ("d_pos", c_vp), ("d_absorbing_actions", c_vp), ("d_game_id", c_vp),
+        ("d_weight", c_vp),
+    ]
+
+
 class TrainerLossIO(ctypes.Structure):
     """``mzx_trainer_loss_io``: the inputs and outputs of one mzx_trainer_loss call (mzx.trainer)."""
     _fields_ = [
@@ -213,6 +232,9 @@ PROTOTYPES = {
     "mzx_replay_positions": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_reanalyse_write": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_batch": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplayBatchIO), c_vp]),
+    "mzx_replay_sampler_refresh": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_i32, c_vp]),
+    "mzx_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), ctypes.POINTER(ReplaySampleIO), c_vp]),
+    "mzx_replay_update_priorities": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mzx_scalar_to_support": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_trainer_loss_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "mzx_trainer_loss": (ctypes.c_int, [ctypes.POINTER(TrainerLossIO), c_vp]),

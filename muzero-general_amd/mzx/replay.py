@@ -19,6 +19,9 @@ device_store=store).get_batch()`` assembles the trainer's tensors on the device 
 numpy's, in the reference's order, and only fill index arrays.  ``trainer_tensors`` is the binding line of a trainer.
 ``DeviceGameStore.reanalyse`` / ``Reanalyse.reanalyse_store`` re-evaluate every resident game in a sweep: a handful of
 launches per chunk of positions, the decoded values written straight into the pool (opt-in: ``config.reanalyse_sweep``).
+A store built with ``max_games`` also holds the PER priorities and a game table: ``ReplayBuffer(..., device_sampler=True)``
+then DRAWS the batch on the device (``mzx_replay_sample``, a counter-based generator -- not numpy's draws, hence opt-in)
+and scatters the trainer's priorities back there (``mzx_replay_update_priorities``).
 """
 import ctypes
 import time
@@ -255,9 +258,21 @@ class DeviceGameStore:
     game goes to the head, wraps to row 0 when the room up to the end of the pool is too short, and the rows of the
     oldest resident games are what a release gives back.  ``games`` maps game_id -> (base, T) in allocation order.
     A game is uploaded ONCE (``add`` / ``add_many``); batches are gathered from the pool (``batch``, ``stacked``).
+
+    ``max_games`` (a sensible value: ``config.replay_buffer_size``) adds the state of the device-side sampler
+    (include/mzx.h ``mzx_replay_sampler``): ``priorities`` f32 [rows] (row base + i: position i; the padding row stays 0),
+    ``owner`` i32 [rows] (scratch of the scatter, -1 between calls) and a table of ``max_games`` slots, slot = game_id %
+    max_games -- ``slot_game`` (-1: empty), ``slot_base``, ``slot_len``, ``slot_priority`` (the game's largest priority)
+    and ``slot_sum`` (their binary64 sum).  Game ids only grow and the stock buffer holds a contiguous range of them, so
+    a buffer of at most ``max_games`` games never collides; a game whose slot is held by a resident game raises
+    ``StoreFull``.  ``add_many`` uploads ``game_history.priorities`` (nothing with PER off: the columns stay 0) and
+    refreshes the slots of the ingested games in one launch; ``drop`` empties the slot; slot changes are batched on the
+    host and flushed with one small upload before the next launch that reads the table; ``update`` leaves priorities
+    alone.  ``sample`` / ``update_priorities`` / ``priorities_of`` are the sampler's surface.  Without ``max_games`` none
+    of this is allocated.
     """
 
-    def __init__(self, config, backend, max_positions):
+    def __init__(self, config, backend, max_positions, max_games=None):
         self.config, self.backend = config, backend
         self.shape = tuple(int(v) for v in config.observation_shape)
         if len(self.shape) != 3 or min(self.shape) < 1:
@@ -282,7 +297,32 @@ class DeviceGameStore:
         td = int(config.td_steps)
         self._discount_pow = self._up(numpy.array([config.discount ** i for i in range(td + 1)], dtype=numpy.float64))
         self.games = {}       # game_id -> (base, T), oldest allocation first
+        self._with_positions = 0      # resident games of T > 0 (what the sampler can draw from)
         self._head = 0        # next free row
+        self.max_games = None if max_games is None else int(max_games)
+        self.sampler = None
+        if self.max_games is not None:
+            if self.max_games < 1:
+                raise ValueError("max_games must be positive")
+            slots = self.max_games
+            self.priorities, self.owner = z((self.rows,), torch.float32), torch.full((self.rows,), -1, dtype=torch.int32,
+                                                                                   device=backend.device)
+            self.slot_game = torch.full((slots,), -1, dtype=torch.int64, device=backend.device)
+            self.slot_base, self.slot_len = z((slots,), torch.int64), z((slots,), torch.int32)
+            self.slot_priority, self.slot_sum = z((slots,), torch.float32), z((slots,), torch.float64)
+            self._tile_prefix = z((2 * -(-slots // 256),), torch.float64)
+            self._raw = z((1,), torch.float64)
+            self._slot_owner = {}      # slot -> game_id of the resident game (host mirror of slot_game)
+            self._slot_dirty = {}      # slot -> (game_id, base, T) not yet uploaded
+            space = [int(a) for a in config.action_space]
+            self._action_space = None if space == list(range(self.A)) else self._up(numpy.array(space, dtype=numpy.int32))
+            sampler = self.sampler = _lib.ReplaySampler()
+            sampler.d_priorities, sampler.d_owner = self.priorities.data_ptr(), self.owner.data_ptr()
+            sampler.d_slot_game, sampler.d_slot_base, sampler.d_slot_len = (self.slot_game.data_ptr(), self.slot_base.data_ptr(),
+                                                                            self.slot_len.data_ptr())
+            sampler.d_slot_priority, sampler.d_slot_sum = self.slot_priority.data_ptr(), self.slot_sum.data_ptr()
+            sampler.rows, sampler.slots = self.rows, slots
+            sampler.d_tile_prefix, sampler.d_raw, sampler.raw_capacity = self._tile_prefix.data_ptr(), self._raw.data_ptr(), 1
 
     def __contains__(self, game_id):
         return game_id in self.games
@@ -324,7 +364,12 @@ class DeviceGameStore:
 
     def drop(self, game_id):
         """Release a game's rows.  Rows come back when every OLDER game has been released too (the tail moves on)."""
+        self._with_positions -= self.games[game_id][1] > 0
         del self.games[game_id]
+        if self.sampler is not None:
+            slot = game_id % self.max_games
+            del self._slot_owner[slot]
+            self._slot_dirty[slot] = (-1, 0, 0)
 
     # ---- ingest
     def _columns(self, gh):
@@ -364,9 +409,20 @@ class DeviceGameStore:
                 raise ValueError(f"game {game_id} is already resident")
         columns = [self._columns(gh) for _, gh in items]
         lengths = [len(gh.root_values) for _, gh in items]
+        if self.sampler is not None:
+            priorities = [self._priority_rows(gh, T) for (_, gh), T in zip(items, lengths)]
+            taken = dict(self._slot_owner)
+            for game_id, _ in items:
+                if taken.setdefault(game_id % self.max_games, game_id) != game_id:
+                    raise StoreFull(f"slot {game_id % self.max_games} of game {game_id} is held by resident game "
+                                    f"{taken[game_id % self.max_games]} ({self.max_games} slots)")
         bases = self._place(lengths)
         for (game_id, _), base, T in zip(items, bases, lengths):
             self.games[game_id] = (base, T)
+            self._with_positions += T > 0
+            if self.sampler is not None:
+                self._slot_owner[game_id % self.max_games] = game_id
+                self._slot_dirty[game_id % self.max_games] = (game_id, base, T)
         pool_columns = (self.actions, self.rewards, self.to_play, self.root_values, self.child_visits)
         lo = 0
         while lo < len(items):
@@ -376,6 +432,8 @@ class DeviceGameStore:
             b0, b1 = bases[lo], bases[hi - 1] + lengths[hi - 1] + 1
             for c, column in enumerate(pool_columns):
                 column[b0:b1].copy_(self._up(numpy.concatenate([columns[i][c] for i in range(lo, hi)])))
+            if self.sampler is not None and self.config.PER:
+                self.priorities[b0:b1].copy_(self._up(numpy.concatenate([priorities[i] for i in range(lo, hi)])))
             if (b1 - b0) * int(numpy.prod(self.shape)) < (1 << 22):      # small frames: one upload for the run
                 frames = numpy.array([numpy.asarray(o) for i in range(lo, hi) for o in items[i][1].observation_history])
                 self.frames[b0:b1].copy_(observations._frames_to_device(self.backend, frames.reshape((b1 - b0,) + self.shape)))
@@ -385,6 +443,107 @@ class DeviceGameStore:
                         observations._history_to_device(self.backend, items[i][1].observation_history, self.shape))
             lo = hi
         self._run_values(list(zip(bases, lengths)))
+        if self.sampler is not None:
+            self._flush_slots()
+            slots = self._up(numpy.array([g % self.max_games for g, _ in items], dtype=numpy.int32))
+            be, lib = self.backend, self.backend.lib
+            lib.check(lib.mzx_replay_sampler_refresh(ctypes.byref(self.sampler), be.ptr(slots), len(items), be.stream()))
+
+    # ---- the sampler's state
+    def _priority_rows(self, gh, T):
+        """The T + 1 rows of the priority column of a game: its float32 priorities and the padding 0 (zeros with PER off)."""
+        rows = numpy.zeros(T + 1, numpy.float32)
+        if self.config.PER and T:
+            if gh.priorities is None or len(gh.priorities) != T:
+                raise ValueError("with PER a game enters the store with its priorities (fill_initial_priorities before save_game)")
+            rows[:T] = numpy.asarray(gh.priorities, dtype=numpy.float32)
+        return rows
+
+    def _need_sampler(self):
+        if self.sampler is None:
+            raise ValueError("this DeviceGameStore was built without max_games: it has no sampler state")
+
+    def _flush_slots(self):
+        """The slot changes since the last flush, as ONE upload ([k][4] i64: slot, game, base, T) scattered into the table."""
+        if not self._slot_dirty:
+            return
+        packed = self._up(numpy.array([(s,) + v for s, v in self._slot_dirty.items()], dtype=numpy.int64))
+        self._slot_dirty = {}
+        index = packed[:, 0]
+        self.slot_game.index_copy_(0, index, packed[:, 1])
+        self.slot_base.index_copy_(0, index, packed[:, 2])
+        self.slot_len.index_copy_(0, index, packed[:, 3].to(torch.int32))
+
+    def priorities_of(self, game_id):
+        """(priorities float32 [T], game_priority float32) of a resident game, downloaded."""
+        self._need_sampler()
+        base, T = self.games[game_id]
+        self._flush_slots()
+        return (self.priorities[base:base + T].cpu().numpy(),
+                numpy.float32(self.slot_priority[game_id % self.max_games].cpu().numpy()))
+
+    def sample(self, n, seed, call_counter, total_samples, per, num_unroll_steps=None, uniforms=None):
+        """
+        ``mzx_replay_sample``: n draws of the two-level distribution (include/mzx.h) as device tensors ``(base i64 [n], len
+        i32 [n], pos i32 [n], absorbing_actions i32 [n, U + 1], game_id i64 [n], weight f32 [n] or None without per)``
+        -- the first four are what ``mzx_replay_batch`` takes.  A pure function of the store's state and ``(seed,
+        call_counter)``; ``uniforms`` (f64 [n, 2], host or device) replaces the generator's two uniforms per sample.
+        Nothing is downloaded and nothing synchronises.  Raises ValueError when no game with a position is resident.
+        """
+        self._need_sampler()
+        be, lib = self.backend, self.backend.lib
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        if not self._with_positions:
+            raise ValueError("no game with a position is resident: nothing to draw from")
+        self._flush_slots()
+        U = int(self.config.num_unroll_steps if num_unroll_steps is None else num_unroll_steps)
+        per = bool(per)
+        if per and self._raw.numel() < n:
+            self._raw = be.empty((n,), torch.float64)
+            self.sampler.d_raw, self.sampler.raw_capacity = self._raw.data_ptr(), n
+        base, game_id = be.empty((n,), torch.int64), be.empty((n,), torch.int64)
+        length, pos = be.empty((n,), torch.int32), be.empty((n,), torch.int32)
+        tape = be.empty((n, U + 1), torch.int32)
+        weight = be.empty((n,), torch.float32) if per else None
+        io = _lib.ReplaySampleIO()
+        io.seed, io.call_counter = int(seed) & (2 ** 64 - 1), int(call_counter) & (2 ** 64 - 1)
+        io.total_samples, io.num_samples, io.per, io.num_unroll_steps, io.num_actions = int(total_samples), n, int(per), U, self.A
+        io.d_action_space = None if self._action_space is None else self._action_space.data_ptr()
+        if uniforms is not None:
+            if not torch.is_tensor(uniforms):
+                uniforms = torch.from_numpy(numpy.ascontiguousarray(uniforms, dtype=numpy.float64))
+            uniforms = uniforms.to(be.device, torch.float64).contiguous()
+            if tuple(uniforms.shape) != (n, 2):
+                raise ValueError("uniforms must be [n, 2]")
+            io.d_uniforms = uniforms.data_ptr()
+        io.d_base, io.d_len, io.d_pos, io.d_absorbing_actions = base.data_ptr(), length.data_ptr(), pos.data_ptr(), tape.data_ptr()
+        io.d_game_id = game_id.data_ptr()
+        io.d_weight = None if weight is None else weight.data_ptr()
+        lib.check(lib.mzx_replay_sample(ctypes.byref(self.sampler), ctypes.byref(io), be.stream()))
+        return base, length, pos, tape, game_id, weight
+
+    def update_priorities(self, new, game_id, pos):
+        """
+        ``mzx_replay_update_priorities`` (update_priorities, replay_buffer.py:205-228): ``new`` [n, steps] float32 (device
+        tensor or array), ``game_id`` i64 [n] / ``pos`` i32 [n] as ``sample`` returned them (or host arrays).  A game that
+        has left the store is passed over; where windows overlap the highest sample index wins.
+        """
+        self._need_sampler()
+        be, lib = self.backend, self.backend.lib
+        dev = lambda x, dtype: (x if torch.is_tensor(x) else torch.from_numpy(numpy.ascontiguousarray(x))).detach().to(
+            be.device, dtype).contiguous()
+        new = dev(new, torch.float32)
+        if new.dim() != 2:
+            raise ValueError("priorities must be [n, steps]")
+        game_id, pos = dev(game_id, torch.int64).reshape(-1), dev(pos, torch.int32).reshape(-1)
+        n, steps = new.shape
+        if game_id.numel() != n or pos.numel() != n:
+            raise ValueError("one (game_id, position) per row of priorities")
+        self._flush_slots()
+        lib.check(lib.mzx_replay_update_priorities(ctypes.byref(self.sampler), be.ptr(new), be.ptr(game_id), be.ptr(pos), n, steps,
+                                                   be.stream()))
 
     def update(self, game_id, game_history):
         """Reanalyse's update_game_history (replay_buffer.py:197-203): new root values, the n-step values recomputed."""
@@ -412,8 +571,23 @@ class DeviceGameStore:
         pos = numpy.ascontiguousarray(positions, dtype=numpy.int32).reshape(n)
         if n and (pos.min() < 0 or (pos > length).any()):
             raise ValueError("position outside its game")
+        U = int(self.config.num_unroll_steps if num_unroll_steps is None else num_unroll_steps)
+        tape = None
+        if targets:
+            tape = self._up(numpy.zeros((n, U + 1), numpy.int32) if absorbing_actions is None else numpy.ascontiguousarray(
+                absorbing_actions, dtype=numpy.int32).reshape(n, U + 1))
+        return self.gather(self._up(base), self._up(length), self._up(pos), tape, U, observations, targets)
+
+    def gather(self, base, length, pos, tape=None, num_unroll_steps=None, observations=True, targets=True):
+        """``batch`` for samples that are already device arrays (base i64 / len i32 / pos i32 [n], tape i32 [n, U + 1]):
+        what ``sample`` returns goes in unchanged, no host copy in between.  Without a tape the absorbing steps take action 0."""
+        be, lib = self.backend, self.backend.lib
+        n = int(base.shape[0])
+        if targets and tape is None:
+            U = int(self.config.num_unroll_steps if num_unroll_steps is None else num_unroll_steps)
+            tape = be.zeros((n, U + 1), torch.int32)
         io = _lib.ReplayBatchIO()
-        keep = [self._up(base), self._up(length), self._up(pos)]
+        keep = [base, length, pos]
         io.d_base, io.d_len, io.d_pos = (t.data_ptr() for t in keep)
         io.num_samples, io.stacked_observations = n, self.k
         obs = out = None
@@ -422,9 +596,7 @@ class DeviceGameStore:
             io.d_observation = obs.data_ptr()
         if targets:
             U = int(self.config.num_unroll_steps if num_unroll_steps is None else num_unroll_steps)
-            tape = numpy.zeros((n, U + 1), numpy.int32) if absorbing_actions is None else numpy.ascontiguousarray(
-                absorbing_actions, dtype=numpy.int32).reshape(n, U + 1)
-            keep.append(self._up(tape))
+            keep.append(tape)
             value, reward = be.empty((n, U + 1), torch.float64), be.empty((n, U + 1), torch.float64)
             policy = be.empty((n, U + 1, self.A), torch.float64)
             action, scale = be.empty((n, U + 1), torch.int64), be.empty((n, U + 1), torch.int64)
@@ -519,6 +691,32 @@ def trainer_tensors(batch, device):
             None if weight is None else t(weight).float().to(device), t(scale).float().to(device))
 
 
+class DeviceIndexBatch:
+    """
+    ``index_batch`` of a ``get_batch()`` drawn on the device: the two device tensors ``game_id`` (i64 [n]) and ``pos`` (i32
+    [n]).  ``ReplayBuffer.update_priorities`` takes it as it is -- nothing leaves the device.  Iterating, indexing or
+    ``tolist()`` downloads ONCE and yields the reference's ``[[game_id, pos], ...]``.
+    """
+
+    def __init__(self, game_id, pos):
+        self.game_id, self.pos = game_id, pos
+        self._host = None
+
+    def tolist(self):
+        if self._host is None:
+            self._host = [[int(g), int(p)] for g, p in zip(self.game_id.cpu().tolist(), self.pos.cpu().tolist())]
+        return self._host
+
+    def __len__(self):
+        return int(self.game_id.shape[0])
+
+    def __iter__(self):
+        return iter(self.tolist())
+
+    def __getitem__(self, i):
+        return self.tolist()[i]
+
+
 def _stock_replay_buffer_class():
     """
     The user's own ``ReplayBuffer`` (the reference's replay_buffer.py:11-303, importable wherever its trainer runs):
@@ -573,9 +771,20 @@ class ReplayBuffer:
     difference from the reference: the pool adds a capacity bound in POSITIONS to ``replay_buffer_size`` in games.  When
     a new game does not fit after the rows of already evicted games are released, the oldest games leave both the
     store and the stock buffer (the stock buffer's own eviction statements, replay_buffer.py:59-61).
+
+    ``device_sampler=True`` (opt-in on top of a store built with ``max_games``; ValueError otherwise): the DRAWS move to
+    the device too.  ``get_batch`` calls ``store.sample`` -- seed ``config.seed``, a counter that advances by one per call;
+    the reference's two-level distribution over a counter-based generator, so the batches are not numpy's -- and gathers
+    from the sampled arrays with no host copy in between; ``index_batch`` is a ``DeviceIndexBatch``.
+    ``update_priorities(priorities, index_info)`` with such an index runs the device scatter (``priorities``: a device
+    tensor or an array); with a host list it stays the stock method.  With the sampler on, the DEVICE columns are
+    authoritative: ``priorities`` / ``game_priority`` of the host ``GameHistory`` objects go stale until
+    ``sync_priorities()`` writes them back (do that before pickling the buffer for a checkpoint).
     """
 
-    def __init__(self, initial_checkpoint, initial_buffer, config, stock=None, device_store=None):
+    def __init__(self, initial_checkpoint, initial_buffer, config, stock=None, device_store=None, device_sampler=False):
+        if device_sampler and (device_store is None or device_store.sampler is None):
+            raise ValueError("device_sampler=True needs a device_store built with max_games")
         factory = _plain_class(stock) if stock is not None else _stock_replay_buffer_class()
         # a class (also the one behind a ray.remote ActorClass) is instantiated; anything that already has the buffer's
         # methods is taken as the instance to wrap
@@ -583,6 +792,8 @@ class ReplayBuffer:
         object.__setattr__(self, "_stock", built)
         object.__setattr__(self, "_arrays", {})   # game_id -> (game_history, per-game numpy views); dropped when the game changes or leaves
         object.__setattr__(self, "_store", device_store)
+        object.__setattr__(self, "_sampler", bool(device_sampler))
+        object.__setattr__(self, "_sample_calls", 0)
         if device_store is not None:
             self._store_sync(list(self._stock.buffer.items()))
 
@@ -612,7 +823,7 @@ class ReplayBuffer:
             new_games = [(g, h) for g, h in new_games if g != del_id]
 
     def __getattr__(self, name):
-        if name in ("_stock", "_arrays", "_store"):
+        if name in ("_stock", "_arrays", "_store", "_sampler", "_sample_calls"):
             raise AttributeError(name)
         return getattr(self._stock, name)
 
@@ -629,7 +840,26 @@ class ReplayBuffer:
         return self._stock.get_buffer()
 
     def update_priorities(self, priorities, index_info):
+        if isinstance(index_info, DeviceIndexBatch):
+            if self._store is None or self._store.sampler is None:
+                raise ValueError("a DeviceIndexBatch belongs to a buffer with a device sampler")
+            return self._store.update_priorities(priorities, index_info.game_id, index_info.pos)
         return self._stock.update_priorities(priorities, index_info)
+
+    def sync_priorities(self):
+        """The device priorities and game priorities written back into the resident ``GameHistory`` objects (for
+        checkpoints: the reference pickles the buffer).  One download of the two columns; a no-op with PER off."""
+        store = self._store
+        if store is None or store.sampler is None or not self._stock.config.PER:
+            return
+        store._flush_slots()
+        priorities, top = store.priorities.cpu().numpy(), store.slot_priority.cpu().numpy()
+        for game_id, game_history in self._stock.buffer.items():
+            if game_id in store:
+                base, T = store.games[game_id]
+                if T:
+                    game_history.priorities = priorities[base:base + T].copy()
+                    game_history.game_priority = top[game_id % store.max_games]
 
     def sample_game(self, force_uniform=False):
         return self._stock.sample_game(force_uniform)
@@ -745,7 +975,21 @@ class ReplayBuffer:
         return (index_batch, (observation_batch, action_batch, value_batch, reward_batch, policy_batch, weight_batch,
                               gradient_scale_batch))
 
+    def _get_batch_sampled(self):
+        """get_batch with the device sampler: draw, gather -- launches on the backend's stream, nothing per sample here."""
+        cfg, store = self._stock.config, self._store
+        call = self._sample_calls
+        self._sample_calls = call + 1
+        base, length, pos, tape, game_id, weight_batch = store.sample(
+            cfg.batch_size, cfg.seed, call, self._stock.total_samples, cfg.PER, cfg.num_unroll_steps)
+        observation_batch, (value_batch, reward_batch, policy_batch, action_batch, gradient_scale_batch) = store.gather(
+            base, length, pos, tape, cfg.num_unroll_steps)
+        return (DeviceIndexBatch(game_id, pos), (observation_batch, action_batch, value_batch, reward_batch, policy_batch,
+                                                 weight_batch, gradient_scale_batch))
+
     def get_batch(self):
+        if self._sampler:
+            return self._get_batch_sampled()
         if self._store is not None:
             return self._get_batch_device()
         cfg = self._stock.config

@@ -14,7 +14,9 @@ optimizer and ``loss.backward()`` stay the caller's, the network's forward and b
         target_value, target_reward, target_policy, weight_batch, gradient_scale_batch, config)
     loss.backward()
 
-``update_weights(model, optimizer, batch, config)`` is ``Trainer.update_weights`` with ``self`` unbound.  Like the rest
+``update_weights(model, optimizer, batch, config)`` is ``Trainer.update_weights`` with ``self`` unbound;
+``train_step(model, optimizer, replay_buffer, config)`` is the whole step on the device: batch drawn by the replay
+store's sampler, priorities scattered back into it, no download.  Like the rest
 of the package there is no CPU execution path: without the library or a GPU the calls raise as ``default_backend()`` does.
 """
 import ctypes
@@ -154,6 +156,15 @@ def update_weights(model, optimizer, batch, config, backend=None):
     reference's tuple ``(priorities float32 numpy [batch, K + 1], loss, value_loss, reward_loss, policy_loss)`` after ONE
     download -- ``ReplayBuffer.update_priorities`` takes the array unchanged.  The caller advances ``training_step``.
     """
+    packed, batch_size = _sgd_step(model, optimizer, batch, config, backend)
+    host = packed.cpu().numpy()
+    priorities = host[4:].reshape(batch_size, -1)
+    return priorities, float(host[0]), float(host[1]), float(host[2]), float(host[3])
+
+
+def _sgd_step(model, optimizer, batch, config, backend):
+    """The prediction loop, ``muzero_loss`` and one optimizer step of ``update_weights``: (packed [4 + B * steps] on the
+    device -- the four losses, then the priorities --, B).  Nothing is downloaded."""
     device = next(model.parameters()).device
     (observation_batch, action_batch, target_value, target_reward, target_policy, weight_batch,
      gradient_scale_batch) = replay.trainer_tensors(batch, device)
@@ -174,7 +185,19 @@ def update_weights(model, optimizer, batch, config, backend=None):
     optimizer.zero_grad()
     loss.backward()
     optimizer.step()
+    return packed, target_value.shape[0]
 
-    host = packed.cpu().numpy()
-    priorities = host[4:].reshape(target_value.shape[0], -1)
-    return priorities, float(host[0]), float(host[1]), float(host[2]), float(host[3])
+
+def train_step(model, optimizer, replay_buffer, config, backend=None):
+    """
+    One training step as a chain of launches: ``replay_buffer.get_batch()`` (a ``mzx.replay.ReplayBuffer`` with
+    ``device_sampler=True``: the batch is drawn and gathered on the device) -> the prediction loop, ``muzero_loss`` and the
+    optimizer step of ``update_weights`` -> with PER ``replay_buffer.update_priorities(device priorities, index_batch)``
+    (the device scatter).  Returns the four losses ``(loss, value_loss, reward_loss, policy_loss)`` as ONE packed device
+    tensor [4]; nothing is downloaded and nothing synchronises.  The caller advances ``training_step``.
+    """
+    index_batch, batch = replay_buffer.get_batch()
+    packed, batch_size = _sgd_step(model, optimizer, batch, config, backend)
+    if config.PER:
+        replay_buffer.update_priorities(packed[4:].view(batch_size, -1), index_batch)
+    return packed[:4]
