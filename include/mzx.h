@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 4
+#define MZX_ABI_VERSION 5
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -695,6 +695,51 @@ typedef struct mzx_trainer_loss_io {
 int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream);
 int64_t mzx_trainer_loss_scratch_bytes(int32_t batch, int32_t steps);
 int mzx_trainer_loss(const mzx_trainer_loss_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * One training step of a FULLY CONNECTED network up to and including loss.backward() (csrc/mzx_train_fc.h):
+ * Trainer.update_weights (trainer.py:168-262) for MuZeroFullyConnectedNetwork (models.py:80-195) -- the unrolled forward
+ * pass, the loss head (the launches of mzx_trainer_loss) and back-propagation through time -- as five launches on one
+ * stream, no atomics: the same bits on every run.  B = batch, steps = num_unroll_steps + 1 (steps = 1: no dynamics, the
+ * gradients of the dynamics and reward networks are exactly zero); support size and action count are the network's.
+ *   in:  d_flat [num_params] the weights in the mzx_net_tensor_info layout (need not be the buffer bound by
+ *        mzx_net_set_weights), d_observation [B][input_size], d_action int32 [B][steps] (column 0 unused), and the targets,
+ *        gradient scales, PER weights (nullable) and scalars of mzx_trainer_loss_io, with the same meaning.
+ *   out: d_grad_flat [num_params] = d loss / d parameter in the layout of d_flat, OVERWRITTEN; d_losses [4] and
+ *        d_priorities [B][steps] as mzx_trainer_loss writes them; d_value_logits / d_reward_logits [steps][B][2 S + 1],
+ *        d_policy_logits [steps][B][A] (step-major; each optional; the reward rows of step 0 are the constant log-one-hot:
+ *        0 at the centre, -inf elsewhere).
+ *   min / max of the state normalisation hand their gradient to the selected element, the lowest index on an exact tie.
+ *   d_scratch: mzx_train_fc_scratch_bytes(net, batch, steps) bytes, 16-byte aligned (sized for all three logit outputs
+ *   absent).
+ * mzx_train_fc_supported: 1 when the kernels run this network at this shape, 0 otherwise (residual networks; weights plus
+ * per-wave activations beyond the 160 KiB of LDS of a workgroup).  mzx_train_fc_step returns MZX_ERR_INVALID -- before
+ * anything is launched -- for batch / steps < 1, a missing required pointer, a short or misaligned scratch buffer or an
+ * unsupported network.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_train_fc_io {
+  const float* d_flat;
+  const float* d_observation;
+  const int32_t* d_action;
+  const float* d_target_value;
+  const float* d_target_reward;
+  const float* d_target_policy;
+  const float* d_gradient_scale;
+  const float* d_weight;           /* nullable */
+  int32_t batch, steps;
+  double value_loss_weight, per_alpha;
+  float* d_grad_flat;
+  float* d_losses;
+  float* d_priorities;
+  float* d_value_logits;           /* nullable */
+  float* d_reward_logits;          /* nullable */
+  float* d_policy_logits;          /* nullable */
+  void* d_scratch;
+  int64_t scratch_bytes;
+} mzx_train_fc_io;
+int mzx_train_fc_supported(const mzx_net* net, int32_t batch, int32_t steps);
+int64_t mzx_train_fc_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps);
+int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of

@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 4
+ABI_VERSION = 5
 MOVE_NO_SYNC = 1
 
 c_i32, c_i64, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
@@ -156,6 +156,17 @@ class TrainerLossIO(ctypes.Structure):
     ]
 
 
+class TrainFcIO(ctypes.Structure):
+    """``mzx_train_fc_io``: the inputs and outputs of one mzx_train_fc_step call (mzx.trainer)."""
+    _fields_ = [
+        ("d_flat", c_vp), ("d_observation", c_vp), ("d_action", c_vp), ("d_target_value", c_vp), ("d_target_reward", c_vp),
+        ("d_target_policy", c_vp), ("d_gradient_scale", c_vp), ("d_weight", c_vp), ("batch", c_i32), ("steps", c_i32),
+        ("value_loss_weight", c_f64), ("per_alpha", c_f64), ("d_grad_flat", c_vp), ("d_losses", c_vp), ("d_priorities", c_vp),
+        ("d_value_logits", c_vp), ("d_reward_logits", c_vp), ("d_policy_logits", c_vp), ("d_scratch", c_vp),
+        ("scratch_bytes", c_i64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/mzx.h declares
 PROTOTYPES = {
     "mzx_abi_version": (ctypes.c_int, []),
@@ -238,6 +249,9 @@ PROTOTYPES = {
     "mzx_scalar_to_support": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_trainer_loss_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "mzx_trainer_loss": (ctypes.c_int, [ctypes.POINTER(TrainerLossIO), c_vp]),
+    "mzx_train_fc_supported": (ctypes.c_int, [c_vp, c_i32, c_i32]),
+    "mzx_train_fc_scratch_bytes": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_train_fc_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TrainFcIO), c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

@@ -10,7 +10,11 @@ Same names, arguments and return conventions as /root/reference/models.py:
   dict_to_cpu, support_to_scalar       models.py:44-53, :645-666
 All arithmetic runs in the gfx950 kernels behind include/mzx.h; this module only
 owns device buffers (torch tensors) and the flat weight buffer that RCCL
-broadcasts.  Training-only pieces (scalar_to_support, autograd) are out of scope.
+broadcasts.  Training: ``parameters()`` yields that buffer as ONE leaf parameter, so a
+torch optimizer updates the weights self-play searches on; for fully connected networks
+``mzx.trainer.update_weights`` / ``train_step`` fill its ``.grad`` with one
+``mzx_train_fc_step`` call (csrc/mzx_train_fc.h).  There is no autograd graph through
+``initial_inference`` / ``recurrent_inference``; residual networks train through torch.
 """
 import collections
 import ctypes
@@ -227,6 +231,7 @@ class HipNetwork:
             self.input_shape = (self.input_size,)
             self.hidden_shape = (self.hidden_size,)
         self._flat = self.backend.zeros((self.num_params,), torch.float32)
+        self._param = torch.nn.Parameter(self._flat, requires_grad=True)   # the same storage, as an optimizer's leaf
         self._derived = self.backend.zeros((lib.mzx_net_derived_floats(handle),), torch.float32)
         self._workspace = None
         self._ws_batch = 0
@@ -256,7 +261,14 @@ class HipNetwork:
         return self
 
     def parameters(self):
-        yield self._flat  # self_play.py:284 only reads next(model.parameters()).device
+        """The flat weight buffer as ONE ``torch.nn.Parameter`` (it shares ``flat_weights()``'s storage).  Adam and SGD
+        are elementwise and the reference applies weight decay to every tensor, so an optimizer over this parameter
+        makes the reference's per-tensor update.  Call ``refresh_derived()`` after a step."""
+        yield self._param
+
+    def train_fc_supported(self, batch, steps):
+        """Whether ``mzx_train_fc_step`` runs this network at ``batch`` samples x ``steps`` (= num_unroll_steps + 1)."""
+        return bool(self.backend.lib.mzx_train_fc_supported(self.handle, int(batch), int(steps)))
 
     def state_dict(self):
         out = collections.OrderedDict()

@@ -18,12 +18,19 @@ optimizer and ``loss.backward()`` stay the caller's, the network's forward and b
 ``train_step(model, optimizer, replay_buffer, config)`` is the whole step on the device: batch drawn by the replay
 store's sampler, priorities scattered back into it, no download.  Like the rest
 of the package there is no CPU execution path: without the library or a GPU the calls raise as ``default_backend()`` does.
+
+With a ``mzx.models.HipNetwork`` of a fully connected configuration as ``model`` the network is the library's too: the
+prediction loop, the loss head and ``loss.backward()`` are ONE ``mzx_train_fc_step`` call (csrc/mzx_train_fc.h, five
+launches) that writes ``.grad`` of the network's flat parameter; ``optimizer.step()`` then updates the very buffer self-play
+searches on and RCCL broadcasts.  ``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
+convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """
+import collections
 import ctypes
 
 import torch
 
-from . import _lib, replay
+from . import _lib, models, replay
 
 
 def _backend(backend):
@@ -155,6 +162,9 @@ def update_weights(model, optimizer, batch, config, backend=None):
     the reference's, the 0.5 hook on the hidden state included; the loss head is ``muzero_loss``.  Returns the
     reference's tuple ``(priorities float32 numpy [batch, K + 1], loss, value_loss, reward_loss, policy_loss)`` after ONE
     download -- ``ReplayBuffer.update_priorities`` takes the array unchanged.  The caller advances ``training_step``.
+    A ``HipNetwork`` (fully connected) takes the native path: ``mzx_train_fc_step`` writes the gradient of its flat
+    parameter, then ``optimizer.step()`` and ``model.refresh_derived()``; one the kernels do not run raises
+    ``NotImplementedError``.
     """
     packed, batch_size = _sgd_step(model, optimizer, batch, config, backend)
     host = packed.cpu().numpy()
@@ -165,6 +175,11 @@ def update_weights(model, optimizer, batch, config, backend=None):
 def _sgd_step(model, optimizer, batch, config, backend):
     """The prediction loop, ``muzero_loss`` and one optimizer step of ``update_weights``: (packed [4 + B * steps] on the
     device -- the four losses, then the priorities --, B).  Nothing is downloaded."""
+    if isinstance(model, models.HipNetwork):
+        packed = train_fc_gradients(model, batch, config)
+        optimizer.step()
+        model.refresh_derived()
+        return packed, len(batch[2])
     device = next(model.parameters()).device
     (observation_batch, action_batch, target_value, target_reward, target_policy, weight_batch,
      gradient_scale_batch) = replay.trainer_tensors(batch, device)
@@ -186,6 +201,126 @@ def _sgd_step(model, optimizer, batch, config, backend):
     loss.backward()
     optimizer.step()
     return packed, target_value.shape[0]
+
+
+def train_fc_gradients(model, batch, config, logits=None):
+    """
+    ``Trainer.update_weights`` lines 168-262 -- the unrolled predictions, the loss and ``loss.backward()`` -- for a fully
+    connected ``HipNetwork`` as one ``mzx_train_fc_step`` call on the network's backend and torch's current stream.
+    ``.grad`` of ``next(model.parameters())`` is OVERWRITTEN with d loss / d parameter (allocated once, then reused: no
+    ``zero_grad()`` is needed).  Returns the packed device tensor [4 + B * steps]: loss, value / reward / policy loss
+    means, then the priorities.  ``logits``: an optional dict that receives the step-major ``value`` / ``reward`` /
+    ``policy`` logits.  Nothing synchronises.
+    """
+    be, lib = model.backend, model.backend.lib
+    (observation, action, target_value, target_reward, target_policy, weight,
+     scale) = replay.trainer_tensors(batch, be.device)
+    if not config.PER:
+        weight = None
+    batch_size, steps = target_value.shape
+    if not lib.mzx_train_fc_supported(model.handle, batch_size, steps):
+        limit = ("residual networks train through torch (fully connected networks only)" if model._cfg.network != 0 else
+                 "its weights and per-wave activations exceed the 160 KiB LDS budget of the training kernels")
+        raise NotImplementedError(f"mzx_train_fc_step does not run this network at batch {batch_size} x {steps} steps: {limit}")
+    observation = observation.reshape(batch_size, -1).contiguous()
+    actions = model.action_space_size
+    if (observation.shape[1] != model.input_size or action.numel() != batch_size * steps
+            or target_reward.shape != (batch_size, steps) or scale.shape != (batch_size, steps)
+            or target_policy.shape != (batch_size, steps, actions) or (weight is not None and weight.shape != (batch_size,))):
+        raise ValueError(f"batch: expected observation [batch, {model.input_size}], action / value / reward / gradient scale "
+                         f"[batch, steps], policy [batch, steps, {actions}], weight [batch]")
+    action = action.reshape(batch_size, steps).to(torch.int32).contiguous()
+    tensors = [t.contiguous() for t in (target_value, target_reward, target_policy, scale)]
+    param = next(model.parameters())
+    if param.grad is None:
+        param.grad = torch.zeros_like(model.flat_weights())
+    packed = be.empty((4 + batch_size * steps,), torch.float32)
+    scratch_bytes = int(lib.mzx_train_fc_scratch_bytes(model.handle, batch_size, steps))
+    scratch = be.empty((scratch_bytes // 4,), torch.float32)
+    io = _lib.TrainFcIO()
+    io.d_flat, io.d_observation, io.d_action = model.flat_weights().data_ptr(), observation.data_ptr(), action.data_ptr()
+    io.d_target_value, io.d_target_reward, io.d_target_policy, io.d_gradient_scale = (t.data_ptr() for t in tensors)
+    io.d_weight = None if weight is None else weight.contiguous().data_ptr()
+    io.batch, io.steps = batch_size, steps
+    io.value_loss_weight, io.per_alpha = float(config.value_loss_weight), float(config.PER_alpha)
+    io.d_grad_flat, io.d_losses, io.d_priorities = param.grad.data_ptr(), packed.data_ptr(), packed[4:].data_ptr()
+    if logits is not None:
+        width = model.full_support_size
+        logits["value"], logits["reward"] = (be.empty((steps, batch_size, width), torch.float32) for _ in range(2))
+        logits["policy"] = be.empty((steps, batch_size, actions), torch.float32)
+        io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (logits[k].data_ptr() for k in ("value", "reward", "policy"))
+    io.d_scratch, io.scratch_bytes = scratch.data_ptr(), scratch_bytes
+    lib.check(lib.mzx_train_fc_step(model.handle, ctypes.byref(io), be.stream()))
+    return packed
+
+
+def update_lr(optimizer, config, training_step):
+    """``Trainer.update_lr`` (trainer.py:275-283) with ``self`` unbound."""
+    lr = config.lr_init * config.lr_decay_rate ** (training_step / config.lr_decay_steps)
+    for param_group in optimizer.param_groups:
+        param_group["lr"] = lr
+
+
+def _tensor_table(net):
+    """(key, offset, numel, shape) of every tensor of the flat buffer (``mzx_net_tensor_info``)."""
+    return list(net._tensors)
+
+
+def optimizer_state(optimizer, net):
+    """
+    ``optimizer.state_dict()`` of an optimizer over ``net.parameters()`` (one flat parameter) in the form the reference's
+    optimizer over ``models.MuZeroNetwork(config).parameters()`` has (trainer.py:46-67, ``copy.deepcopy(optimizer.
+    state_dict())`` in a checkpoint): parameter i is tensor i of ``mzx_net_tensor_info`` (the order of the reference's
+    ``parameters()``), every flat state tensor (``momentum_buffer``, ``exp_avg``, ``exp_avg_sq``, ...) is cut into
+    per-tensor pieces of the parameter's shape (on the CPU), scalars and 0-d tensors (``step``) are repeated.
+    """
+    table = _tensor_table(net)
+    flat = optimizer.state_dict()
+    state = {}
+    for index, entry in flat["state"].items():
+        if index != 0:
+            raise ValueError("optimizer_state: the optimizer must hold the network's one flat parameter")
+        for i, (_, off, numel, shape) in enumerate(table):
+            state[i] = {k: (v[off:off + numel].reshape(shape).detach().cpu().clone()
+                            if torch.is_tensor(v) and v.dim() == 1 and v.numel() == net.num_params
+                            else (v.detach().cpu().clone() if torch.is_tensor(v) else v)) for k, v in entry.items()}
+    groups = []
+    for group in flat["param_groups"]:
+        group = dict(group)
+        group["params"] = list(range(len(table)))
+        groups.append(group)
+    return {"state": state, "param_groups": groups}
+
+
+def load_optimizer_state(optimizer, net, state_dict):
+    """The inverse of ``optimizer_state``: load a reference-format optimizer ``state_dict`` (per parameter) into an
+    optimizer over ``net.parameters()``."""
+    table = _tensor_table(net)
+    device = net.flat_weights().device
+    per_param = state_dict["state"]
+    flat_state = {}
+    if per_param:
+        if sorted(per_param) != list(range(len(table))):
+            raise ValueError(f"load_optimizer_state: expected state for parameters 0 .. {len(table) - 1}")
+        entry = collections.OrderedDict()
+        for key, first in per_param[0].items():
+            if torch.is_tensor(first) and tuple(first.shape) == tuple(table[0][3]) and first.dim() > 0:
+                joined = torch.empty(net.num_params, dtype=first.dtype, device=device)
+                for i, (_, off, numel, shape) in enumerate(table):
+                    piece = per_param[i][key]
+                    if tuple(piece.shape) != tuple(shape):
+                        raise ValueError(f"load_optimizer_state: {key} of parameter {i} has shape {tuple(piece.shape)}, expected {shape}")
+                    joined[off:off + numel] = piece.reshape(-1).to(device)
+                entry[key] = joined
+            else:
+                entry[key] = first.clone() if torch.is_tensor(first) else first
+        flat_state[0] = entry
+    groups = []
+    for group in state_dict["param_groups"]:
+        group = dict(group)
+        group["params"] = [0]
+        groups.append(group)
+    optimizer.load_state_dict({"state": flat_state, "param_groups": groups})
 
 
 def train_step(model, optimizer, replay_buffer, config, backend=None):
