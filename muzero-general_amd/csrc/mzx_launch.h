@@ -4,6 +4,10 @@
 // for dense operators, 64-thread (one wavefront) blocks for per-tree operators
 // so that B trees spread over B/64 compute units instead of B/256.
 // tests/hostcheck: a serial loop (test infrastructure only).
+//
+// Wave bodies (mzx_wave.h) go through launch_waves: one work item per wavefront, WAVES items per workgroup, the body called
+// as body(item, lane); one-workgroup bodies through launch_block, called as body(thread).  tests/hostcheck: the serial loop
+// with lane 0 / the one call with thread 0.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -22,6 +26,19 @@ template <int BLOCK, class Op>
 inline int launch(const Op& op, stream_t) {
   const size_t n = op.size();
   for (size_t i = 0; i < n; ++i) op(i);
+  return 0;
+}
+
+template <int WAVES, class Body>
+inline int launch_waves(const Body& body, stream_t) {
+  const size_t n = body.size();
+  for (size_t e = 0; e < n; ++e) body(e, 0);
+  return 0;
+}
+
+template <int BLOCK, class Body>
+inline int launch_block(const Body& body, stream_t) {
+  body(0);
   return 0;
 }
 
@@ -76,6 +93,32 @@ inline int launch(const Op& op, stream_t stream) {
   if (n == 0) return 0;
   const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
   hipLaunchKernelGGL((op_kernel<BLOCK, Op>), dim3(grid), dim3(BLOCK), 0, stream, op, n);
+  return (int)hipGetLastError();
+}
+
+template <int WAVES, class Body>
+__global__ void __launch_bounds__(64 * WAVES) wave_kernel(const Body body) {
+  const size_t e = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (e < body.size()) body(e, (int)(threadIdx.x & 63));      // (whole waves leave: a wave body has no workgroup barrier)
+}
+
+template <int WAVES, class Body>
+inline int launch_waves(const Body& body, stream_t stream) {
+  const size_t n = body.size();
+  if (n == 0) return 0;
+  const unsigned grid = (unsigned)((n + WAVES - 1) / WAVES);
+  hipLaunchKernelGGL((wave_kernel<WAVES, Body>), dim3(grid), dim3(64 * WAVES), 0, stream, body);
+  return (int)hipGetLastError();
+}
+
+template <int BLOCK, class Body>
+__global__ void __launch_bounds__(BLOCK) block_kernel(const Body body) {
+  body((int)threadIdx.x);
+}
+
+template <int BLOCK, class Body>
+inline int launch_block(const Body& body, stream_t stream) {
+  hipLaunchKernelGGL((block_kernel<BLOCK, Body>), dim3(1), dim3(BLOCK), 0, stream, body);
   return (int)hipGetLastError();
 }
 

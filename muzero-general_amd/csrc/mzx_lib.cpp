@@ -1339,18 +1339,6 @@ static int replay_sampler_table(const char* who, const mzx_replay_sampler* sampl
   return MZX_OK;
 }
 
-static int replay_refresh_launch(const ReplayRefreshParams& p, stream_t stream) {
-#ifdef MZX_HOSTCHECK
-  ReplayRefreshOp op; op.p = p;
-  MZX_TRY_LAUNCH(launch<64>(op, stream));
-#else
-  const unsigned grid = (unsigned)(((int64_t)p.n + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
-  hipLaunchKernelGGL(replay_refresh_kernel, dim3(grid), dim3(64 * SAMPLER_WAVES), 0, stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-#endif
-  return MZX_OK;
-}
-
 int mzx_replay_sampler_refresh(const mzx_replay_sampler* sampler, const int32_t* d_slots, int32_t n, void* stream) {
   ReplayRefreshParams p;
   const int rc = replay_sampler_table("mzx_replay_sampler_refresh", sampler, &p.t);
@@ -1359,7 +1347,8 @@ int mzx_replay_sampler_refresh(const mzx_replay_sampler* sampler, const int32_t*
   if (n == 0) return MZX_OK;
   if (!d_slots) { set_error("mzx_replay_sampler_refresh: missing slot list"); return MZX_ERR_INVALID; }
   p.slot_list = d_slots; p.game_ids = nullptr; p.n = n;
-  return replay_refresh_launch(p, (stream_t)stream);
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayRefreshBody{p}, (stream_t)stream));
+  return MZX_OK;
 }
 
 int mzx_replay_sample(const mzx_replay_sampler* sampler, const mzx_replay_sample_io* io, void* stream) {
@@ -1387,31 +1376,10 @@ int mzx_replay_sample(const mzx_replay_sampler* sampler, const mzx_replay_sample
   p.out_game = io->d_game_id; p.out_weight = io->d_weight; p.seed = io->seed; p.call_counter = io->call_counter;
   p.total_samples = io->total_samples; p.n = io->num_samples; p.per = io->per ? 1 : 0; p.U = io->num_unroll_steps;
   p.A = io->num_actions; p.tiles = (sampler->slots + SAMPLER_TILE - 1) / SAMPLER_TILE;
-#ifdef MZX_HOSTCHECK
-  ReplayTileSumOp sums; sums.p = p;
-  MZX_TRY_LAUNCH(launch<64>(sums, (stream_t)stream));
-  ReplayTilePrefixOp prefix; prefix.p = p;
-  MZX_TRY_LAUNCH(launch<64>(prefix, (stream_t)stream));
-  ReplayDrawOp draw; draw.p = p;
-  MZX_TRY_LAUNCH(launch<64>(draw, (stream_t)stream));
-  if (p.per) {
-    ReplayWeightFinishOp finish; finish.p = p;
-    MZX_TRY_LAUNCH(launch<64>(finish, (stream_t)stream));
-  }
-#else
-  const unsigned tile_grid = (unsigned)((p.tiles + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
-  hipLaunchKernelGGL(replay_tile_sum_kernel, dim3(tile_grid), dim3(64 * SAMPLER_WAVES), 0, (stream_t)stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-  hipLaunchKernelGGL(replay_tile_prefix_kernel, dim3(1), dim3(128), 0, (stream_t)stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-  const unsigned grid = (unsigned)(((int64_t)p.n + SAMPLER_WAVES - 1) / SAMPLER_WAVES);
-  hipLaunchKernelGGL(replay_draw_kernel, dim3(grid), dim3(64 * SAMPLER_WAVES), 0, (stream_t)stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-  if (p.per) {
-    hipLaunchKernelGGL(replay_weight_finish_kernel, dim3(1), dim3(SAMPLER_FINISH_BLOCK), 0, (stream_t)stream, p);
-    MZX_TRY_LAUNCH((int)hipGetLastError());
-  }
-#endif
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayTileSumBody{p}, (stream_t)stream));
+  MZX_TRY_LAUNCH(launch_waves<2>(ReplayTilePrefixBody{p}, (stream_t)stream));
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayDrawBody{p}, (stream_t)stream));
+  if (p.per) MZX_TRY_LAUNCH(launch_block<SAMPLER_FINISH_BLOCK>(ReplayWeightFinishBody{p}, (stream_t)stream));
   return MZX_OK;
 }
 
@@ -1430,7 +1398,8 @@ int mzx_replay_update_priorities(const mzx_replay_sampler* sampler, const float*
   MZX_TRY_LAUNCH(launch<256>(op, (stream_t)stream));
   ReplayRefreshParams p;
   p.t = op.t; p.slot_list = nullptr; p.game_ids = d_game_id; p.n = n;
-  return replay_refresh_launch(p, (stream_t)stream);
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayRefreshBody{p}, (stream_t)stream));
+  return MZX_OK;
 }
 
 // ------------------------------------------------------------- the trainer's loss head (csrc/mzx_trainer.h)
@@ -1478,18 +1447,8 @@ int mzx_trainer_loss(const mzx_trainer_loss_io* io, void* stream) {
   p.scratch = (TrainerLossRow*)io->d_scratch; p.losses = io->d_losses;
   p.batch = io->batch; p.steps = io->steps; p.support_size = io->support_size; p.num_actions = io->num_actions;
   p.value_loss_weight = (float)io->value_loss_weight; p.per_alpha = (float)io->per_alpha;
-#ifdef MZX_HOSTCHECK
-  TrainerLossRowOp rows_op; rows_op.p = p;
-  MZX_TRY_LAUNCH(launch<64>(rows_op, (stream_t)stream));
-  TrainerFinishOp finish; finish.p = p;
-  MZX_TRY_LAUNCH(launch<64>(finish, (stream_t)stream));
-#else
-  const unsigned grid = (unsigned)((rows + TRAINER_WAVES - 1) / TRAINER_WAVES);
-  hipLaunchKernelGGL(trainer_loss_kernel, dim3(grid), dim3(64 * TRAINER_WAVES), 0, (stream_t)stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-  hipLaunchKernelGGL(trainer_finish_kernel, dim3(1), dim3(TRAINER_FINISH_BLOCK), 0, (stream_t)stream, p);
-  MZX_TRY_LAUNCH((int)hipGetLastError());
-#endif
+  MZX_TRY_LAUNCH(launch_waves<TRAINER_WAVES>(TrainerLossBody{p}, (stream_t)stream));
+  MZX_TRY_LAUNCH(launch_block<TRAINER_FINISH_BLOCK>(TrainerFinishBody{p}, (stream_t)stream));
   return MZX_OK;
 }
 
@@ -1554,6 +1513,7 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
   MZX_TRY_LAUNCH(fct_launch(p, 0, (stream_t)stream));
   if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
   MZX_TRY_LAUNCH(fct_launch(p, 1, (stream_t)stream));
+  MZX_TRY_LAUNCH(launch_waves<FCT_WAVES>(FctWgradBody{p}, (stream_t)stream));
   return MZX_OK;
 }
 

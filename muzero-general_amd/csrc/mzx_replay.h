@@ -21,6 +21,7 @@
 #pragma once
 #include "mzx_platform.h"
 #include "mzx_tree.h"
+#include "mzx_wave.h"
 
 namespace mzx {
 
@@ -224,8 +225,8 @@ struct ReplayReanalyseOp {
 // throughout (the reference divides by the maximum in float32: this opt-in path defines its own rounding); a sample drawn
 // while no game is live, and every sample when total_samples <= 0, gets the weight 0.
 //
-// Product build: wave-cooperative kernels (a wavefront per refreshed game / per tile / per sample).  tests/hostcheck build:
-// serial functors of the same definition.  The sums of one build are always taken in the same association, so a run
+// Wave bodies (mzx_wave.h): a wavefront per refreshed game / per tile / per sample in the product build, the same bodies
+// with one lane in the tests/hostcheck build.  The sums of one build are always taken in the same association, so a run
 // repeats bit for bit; the two builds associate differently and agree exactly wherever the sums are exact.
 constexpr int SAMPLER_TILE = 256;
 
@@ -385,94 +386,135 @@ struct ReplayClaimOp {
   }
 };
 
-#ifdef MZX_HOSTCHECK
+constexpr int SAMPLER_WAVES = 4;                                  // wavefronts (games, tiles, samples) per workgroup
+constexpr int SAMPLER_PER_LANE = SAMPLER_TILE / WAVE_LANES;       // weights of a tile a lane holds: indices 4l .. 4l + 3 on the device
 
-struct ReplayRefreshOp {
+// maximum and weight sum of a refreshed game: launch_waves<SAMPLER_WAVES>, a wavefront per game
+struct ReplayRefreshBody {
   ReplayRefreshParams p;
   MZX_HD size_t size() const { return (size_t)p.n; }
-  MZX_HD void operator()(size_t e) const {
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
     const int s = p.slot(e);
     if (s < 0) return;
+    const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
+    const float* __restrict__ pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
     float m = -(float)MZX_INF;
     double sum = 0.0;
-    const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
-    const float* pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
-    for (int i = 0; i < T; ++i) {
-      if (pr[i] > m) m = pr[i];
-      sum = sum + sampler_weight(pr[i]);
+    WAVE_FOR(i, T) {
+      const float v = pr[i];
+      if (v > m) m = v;
+      sum = sum + sampler_weight(v);
     }
-    p.t.slot_priority[s] = T ? m : 0.0f;
-    p.t.slot_sum[s] = sum;
+#pragma unroll
+    for (int o = WAVE_LANES / 2; o >= 1; o >>= 1) {
+      const float other = lane_xor(m, o);
+      if (other > m) m = other;
+    }
+    sum = wave_sum_f64(sum);
+    if (lane == 0) {
+      p.t.slot_priority[s] = T ? m : 0.0f;
+      p.t.slot_sum[s] = sum;
+    }
   }
 };
 
-struct ReplayTileSumOp {
+// the sums of both kinds of weight over a tile of 256 slots: launch_waves<SAMPLER_WAVES>, a wavefront per tile
+struct ReplayTileSumBody {
   ReplayDrawParams p;
   MZX_HD size_t size() const { return (size_t)p.tiles; }
-  MZX_HD void operator()(size_t k) const {
-    for (int kind = 0; kind < 2; ++kind) {
-      double sum = 0.0;
-      for (int j = 0; j < SAMPLER_TILE; ++j) sum = sum + p.t.weight((int)k * SAMPLER_TILE + j, kind);
-      p.tile_prefix[(size_t)kind * p.tiles + k] = sum;
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int k = (int)e;
+    double a = 0.0, b = 0.0;
+#pragma unroll
+    for (int j = 0; j < SAMPLER_PER_LANE; ++j) {
+      const int s = k * SAMPLER_TILE + SAMPLER_PER_LANE * lane + j;
+      a = a + p.t.weight(s, 0);
+      b = b + p.t.weight(s, 1);
+    }
+    a = wave_sum_f64(a);
+    b = wave_sum_f64(b);
+    if (lane == 0) {
+      p.tile_prefix[k] = a;
+      p.tile_prefix[(size_t)p.tiles + k] = b;
     }
   }
 };
 
-struct ReplayTilePrefixOp {
+// the tile sums -> their inclusive prefix, in place: launch_waves<2>, one workgroup, a wavefront per kind, WAVE_LANES tiles
+// per step with a carry
+struct ReplayTilePrefixBody {
   ReplayDrawParams p;
   MZX_HD size_t size() const { return 2; }
-  MZX_HD void operator()(size_t kind) const {
+  MZX_WAVE_FN void operator()(size_t kind, int lane) const {
     double* I = p.tile_prefix + kind * (size_t)p.tiles;
-    for (int k = 1; k < p.tiles; ++k) I[k] = I[k - 1] + I[k];
+    double carry = 0.0;
+    for (int k0 = 0; k0 < p.tiles; k0 += WAVE_LANES) {
+      const int k = k0 + lane;
+      const double v = wave_scan_f64(k < p.tiles ? I[k] : 0.0, lane);
+      if (k < p.tiles) I[k] = carry + v;
+      carry = carry + lane_value(v, WAVE_LANES - 1);
+    }
   }
 };
 
-struct ReplayDrawOp {
+// One level of a draw over the 256 weights of a tile, SAMPLER_PER_LANE per lane: the first index whose carry + inclusive
+// prefix exceeds t and whose weight is positive (-1: none), `last` the last index of positive weight (-1: none), `total`
+// the sum of the 256.  The same value in every lane.
+MZX_WAVE_FN int wave_pick(const double w[SAMPLER_PER_LANE], double carry, double t, int lane, int& last, double& total) {
+  constexpr int N = SAMPLER_PER_LANE;
+  double run[N];                     // the lane's own inclusive prefix
+  run[0] = w[0];
+#pragma unroll
+  for (int j = 1; j < N; ++j) run[j] = run[j - 1] + w[j];
+  const double incl = wave_scan_f64(run[N - 1], lane);
+  double below = lane_up(incl, 1);
+  if (lane == 0) below = 0.0;
+  total = lane_value(incl, WAVE_LANES - 1);
+  int first = -1, tail = -1;
+#pragma unroll
+  for (int j = N - 1; j >= 0; --j) if (w[j] > 0.0 && carry + (below + run[j]) > t) first = j;
+#pragma unroll
+  for (int j = 0; j < N; ++j) if (w[j] > 0.0) tail = j;
+  const int first_lane = wave_first_lane(first >= 0), tail_lane = wave_last_lane(tail >= 0);
+  const int first_j = lane_value(first, first_lane < 0 ? 0 : first_lane), tail_j = lane_value(tail, tail_lane < 0 ? 0 : tail_lane);
+  last = tail_lane < 0 ? -1 : N * tail_lane + tail_j;
+  return first_lane < 0 ? -1 : N * first_lane + first_j;
+}
+
+// One sample of a draw: launch_waves<SAMPLER_WAVES>, a wavefront per sample
+struct ReplayDrawBody {
   ReplayDrawParams p;
   MZX_HD size_t size() const { return (size_t)p.n; }
-
-  // first index of [0, count) with carry + prefix > t and a positive weight (-1: none); last: the last positive one
-  template <class W>
-  static int pick(const W& weight, int count, double carry, double t, int& last, double& total) {
-    double run = 0.0;
-    int first = -1;
-    last = -1;
-    for (int j = 0; j < count; ++j) {
-      const double w = weight(j);
-      run = run + w;
-      if (w > 0.0) {
-        last = j;
-        if (first < 0 && carry + run > t) first = j;
-      }
-    }
-    total = run;
-    return first;
-  }
-
-  MZX_HD void operator()(size_t e) const {
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    constexpr int N = SAMPLER_PER_LANE;
     const int i = (int)e;
-    double u_game, u_pos;
-    p.uniform_pair(i, u_game, u_pos);
+    double u_game = 0.0, u_pos = 0.0;
+    if (lane == 0) p.uniform_pair(i, u_game, u_pos);                  // lane 0's Philox block, broadcast
+    u_game = lane_value(u_game, 0);
+    u_pos = lane_value(u_pos, 0);
+
     const int kind = p.kind();
-    const double* I = p.tile_prefix + (size_t)kind * p.tiles;
+    const double* __restrict__ I = p.tile_prefix + (size_t)kind * p.tiles;
     const double S = I[p.tiles - 1];
     int slot = -1, last;
-    double total;
+    double total, w[N];
     if (S > 0.0) {
       const double t = u_game * S;
       const int k = p.pick_tile(I, t);
-      auto w = [&](int j) { return p.t.weight(k * SAMPLER_TILE + j, kind); };
-      int j = pick(w, SAMPLER_TILE, k ? I[k - 1] : 0.0, t, last, total);
+#pragma unroll
+      for (int j = 0; j < N; ++j) w[j] = p.t.weight(k * SAMPLER_TILE + N * lane + j, kind);
+      int j = wave_pick(w, k ? I[k - 1] : 0.0, t, lane, last, total);
       if (j < 0) j = last;
       if (j >= 0) slot = k * SAMPLER_TILE + j;
-      for (int k2 = p.tiles - 1; k2 >= 0 && slot < 0; --k2) {      // (a table whose prefix misled the search: its last live slot)
-        auto w2 = [&](int j2) { return p.t.weight(k2 * SAMPLER_TILE + j2, kind); };
-        pick(w2, SAMPLER_TILE, 0.0, 0.0, last, total);
+      for (int k2 = p.tiles - 1; k2 >= 0 && slot < 0; --k2) {          // (a table whose prefix misled the search: its last live slot)
+#pragma unroll
+        for (int j2 = 0; j2 < N; ++j2) w[j2] = p.t.weight(k2 * SAMPLER_TILE + N * lane + j2, kind);
+        wave_pick(w, 0.0, 0.0, lane, last, total);
         if (last >= 0) slot = k2 * SAMPLER_TILE + last;
       }
     }
     const int T = slot >= 0 ? p.t.slot_len[slot] : 0;
-    const float* pr = p.t.priorities + (slot >= 0 ? p.t.slot_base[slot] : 0);
+    const float* __restrict__ pr = p.t.priorities + (slot >= 0 ? p.t.slot_base[slot] : 0);
     int pos = -1;
     double p_i = 1.0, P = (double)T;
     const double sum = slot >= 0 ? p.t.slot_sum[slot] : 0.0;
@@ -480,9 +522,13 @@ struct ReplayDrawOp {
       const double t = u_pos * sum;
       double carry = 0.0;
       int seen = -1;
-      for (int c0 = 0; c0 < T && pos < 0; c0 += SAMPLER_TILE) {
-        auto w = [&](int j) { return c0 + j < T ? sampler_weight(pr[c0 + j]) : 0.0; };
-        const int j = pick(w, SAMPLER_TILE, carry, t, last, total);
+      for (int c0 = 0; c0 < T && pos < 0; c0 += SAMPLER_TILE) {        // (pos is the same in every lane)
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const int idx = c0 + N * lane + j;
+          w[j] = idx < T ? sampler_weight(pr[idx]) : 0.0;
+        }
+        const int j = wave_pick(w, carry, t, lane, last, total);
         if (last >= 0) seen = c0 + last;
         if (j >= 0) pos = c0 + j;
         carry = carry + total;
@@ -494,202 +540,29 @@ struct ReplayDrawOp {
       }
     }
     if (pos < 0) pos = T > 0 ? p.uniform_position(u_pos, T) : 0;
-    p.write_sample(i, slot, pos, slot >= 0 ? p.t.weight(slot, kind) : 0.0, S, p_i, P);
-    for (int u = 0; u <= p.U; ++u) p.out_tape[(size_t)i * (p.U + 1) + u] = u >= T + 1 - pos ? p.absorbing_action(i, u) : 0;
+    if (lane == 0) p.write_sample(i, slot, pos, slot >= 0 ? p.t.weight(slot, kind) : 0.0, S, p_i, P);
+    WAVE_FOR(u, p.U + 1) p.out_tape[(size_t)i * (p.U + 1) + u] = u >= T + 1 - pos ? p.absorbing_action(i, u) : 0;
   }
 };
 
-struct ReplayWeightFinishOp {
-  ReplayDrawParams p;
-  MZX_HD size_t size() const { return 1; }
-  MZX_HD void operator()(size_t) const {
-    double m = -MZX_INF;
-    for (int i = 0; i < p.n; ++i) if (p.raw[i] > m) m = p.raw[i];
-    for (int i = 0; i < p.n; ++i) p.out_weight[i] = m > 0.0 ? (float)(p.raw[i] / m) : 0.0f;
-  }
-};
-
-#else
-
-constexpr int SAMPLER_WAVES = 4;          // wavefronts (games, tiles, samples) per workgroup
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_refresh_kernel(const ReplayRefreshParams p) {
-  const int lane = threadIdx.x & 63;
-  const size_t e = (size_t)blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
-  if (e >= (size_t)p.n) return;                                   // (whole waves leave: no barrier below)
-  const int s = p.slot(e);
-  if (s < 0) return;
-  const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
-  const float* __restrict__ pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
-  float m = -(float)MZX_INF;
-  double sum = 0.0;
-  for (int i = lane; i < T; i += 64) {
-    const float v = pr[i];
-    if (v > m) m = v;
-    sum = sum + sampler_weight(v);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float other = __shfl_xor(m, o, 64);
-    if (other > m) m = other;
-  }
-  sum = wave_sum_f64(sum);
-  if (lane == 0) {
-    p.t.slot_priority[s] = T ? m : 0.0f;
-    p.t.slot_sum[s] = sum;
-  }
-}
-
-// the sums of both kinds of weight over a tile of 256 slots: four slots per lane, a butterfly over the lanes
-__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_tile_sum_kernel(const ReplayDrawParams p) {
-  const int lane = threadIdx.x & 63;
-  const int k = blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
-  if (k >= p.tiles) return;
-  double a = 0.0, b = 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int s = k * SAMPLER_TILE + 4 * lane + j;
-    a = a + p.t.weight(s, 0);
-    b = b + p.t.weight(s, 1);
-  }
-  a = wave_sum_f64(a);
-  b = wave_sum_f64(b);
-  if (lane == 0) {
-    p.tile_prefix[k] = a;
-    p.tile_prefix[(size_t)p.tiles + k] = b;
-  }
-}
-
-// inclusive scan over the 64 lanes (lane l ends with v_0 + ... + v_l in a fixed association)
-__device__ __forceinline__ double wave_scan_f64(double v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double below = __shfl_up(v, o, 64);
-    if (lane >= o) v = below + v;
-  }
-  return v;
-}
-
-// the tile sums -> their inclusive prefix, in place: one workgroup, a wavefront per kind, 64 tiles per step with a carry
-__global__ void __launch_bounds__(128) replay_tile_prefix_kernel(const ReplayDrawParams p) {
-  const int lane = threadIdx.x & 63;
-  double* I = p.tile_prefix + (size_t)(threadIdx.x >> 6) * p.tiles;
-  double carry = 0.0;
-  for (int k0 = 0; k0 < p.tiles; k0 += 64) {
-    const int k = k0 + lane;
-    const double v = wave_scan_f64(k < p.tiles ? I[k] : 0.0, lane);
-    if (k < p.tiles) I[k] = carry + v;
-    carry = carry + __shfl(v, 63, 64);
-  }
-}
-
-// One level of a draw over 256 weights, four per lane (lane l holds indices 4l .. 4l + 3): the first index whose
-// carry + inclusive prefix exceeds t and whose weight is positive (-1: none), `last` the last index of positive weight
-// (-1: none), `total` the sum of the 256.  The same value in every lane.
-__device__ __forceinline__ int wave_pick(const double w[4], double carry, double t, int lane, int& last, double& total) {
-  const double l0 = w[0], l1 = l0 + w[1], l2 = l1 + w[2], l3 = l2 + w[3];
-  const double incl = wave_scan_f64(l3, lane);
-  double below = __shfl_up(incl, 1, 64);
-  if (lane == 0) below = 0.0;
-  total = __shfl(incl, 63, 64);
-  int first = -1, tail = -1;
-  if (w[3] > 0.0 && carry + (below + l3) > t) first = 3;
-  if (w[2] > 0.0 && carry + (below + l2) > t) first = 2;
-  if (w[1] > 0.0 && carry + (below + l1) > t) first = 1;
-  if (w[0] > 0.0 && carry + (below + l0) > t) first = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) if (w[j] > 0.0) tail = j;
-  const uint64_t has_first = __ballot(first >= 0), has_tail = __ballot(tail >= 0);
-  const int tail_lane = has_tail ? 63 - __clzll((long long)has_tail) : 0;
-  const int first_lane = has_first ? __ffsll((long long)has_first) - 1 : 0;
-  const int tail_j = __shfl(tail, tail_lane, 64), first_j = __shfl(first, first_lane, 64);
-  last = has_tail ? 4 * tail_lane + tail_j : -1;
-  return has_first ? 4 * first_lane + first_j : -1;
-}
-
-__global__ void __launch_bounds__(64 * SAMPLER_WAVES) replay_draw_kernel(const ReplayDrawParams p) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * SAMPLER_WAVES + (threadIdx.x >> 6);
-  if (i >= p.n) return;                                             // (whole waves leave: no barrier below)
-  double u_game = 0.0, u_pos = 0.0;
-  if (lane == 0) p.uniform_pair(i, u_game, u_pos);                  // lane 0's Philox block, broadcast
-  u_game = __shfl(u_game, 0, 64);
-  u_pos = __shfl(u_pos, 0, 64);
-
-  const int kind = p.kind();
-  const double* __restrict__ I = p.tile_prefix + (size_t)kind * p.tiles;
-  const double S = I[p.tiles - 1];
-  int slot = -1, last;
-  double total, w[4];
-  if (S > 0.0) {
-    const double t = u_game * S;
-    const int k = p.pick_tile(I, t);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = p.t.weight(k * SAMPLER_TILE + 4 * lane + j, kind);
-    int j = wave_pick(w, k ? I[k - 1] : 0.0, t, lane, last, total);
-    if (j < 0) j = last;
-    if (j >= 0) slot = k * SAMPLER_TILE + j;
-    for (int k2 = p.tiles - 1; k2 >= 0 && slot < 0; --k2) {          // (a table whose prefix misled the search: its last live slot)
-#pragma unroll
-      for (int j2 = 0; j2 < 4; ++j2) w[j2] = p.t.weight(k2 * SAMPLER_TILE + 4 * lane + j2, kind);
-      wave_pick(w, 0.0, 0.0, lane, last, total);
-      if (last >= 0) slot = k2 * SAMPLER_TILE + last;
-    }
-  }
-  const int T = slot >= 0 ? p.t.slot_len[slot] : 0;
-  const float* __restrict__ pr = p.t.priorities + (slot >= 0 ? p.t.slot_base[slot] : 0);
-  int pos = -1;
-  double p_i = 1.0, P = (double)T;
-  const double sum = slot >= 0 ? p.t.slot_sum[slot] : 0.0;
-  if (p.per && sum > 0.0 && sum <= 1.7976931348623157e308) {
-    const double t = u_pos * sum;
-    double carry = 0.0;
-    int seen = -1;
-    for (int c0 = 0; c0 < T && pos < 0; c0 += SAMPLER_TILE) {        // (pos is the same in every lane)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int idx = c0 + 4 * lane + j;
-        w[j] = idx < T ? sampler_weight(pr[idx]) : 0.0;
-      }
-      const int j = wave_pick(w, carry, t, lane, last, total);
-      if (last >= 0) seen = c0 + last;
-      if (j >= 0) pos = c0 + j;
-      carry = carry + total;
-    }
-    if (pos < 0) pos = seen;
-    if (pos >= 0) {
-      p_i = sampler_weight(pr[pos]);
-      P = sum;
-    }
-  }
-  if (pos < 0) pos = T > 0 ? p.uniform_position(u_pos, T) : 0;
-  if (lane == 0) p.write_sample(i, slot, pos, slot >= 0 ? p.t.weight(slot, kind) : 0.0, S, p_i, P);
-  for (int u = lane; u <= p.U; u += 64) p.out_tape[(size_t)i * (p.U + 1) + u] = u >= T + 1 - pos ? p.absorbing_action(i, u) : 0;
-}
-
-// weight = float32(raw / max raw): one workgroup
+// weight = float32(raw / max raw): launch_block<SAMPLER_FINISH_BLOCK>
 constexpr int SAMPLER_FINISH_BLOCK = 256;
-__global__ void __launch_bounds__(SAMPLER_FINISH_BLOCK) replay_weight_finish_kernel(const ReplayDrawParams p) {
-  __shared__ double part[SAMPLER_FINISH_BLOCK];
-  const int t = threadIdx.x;
-  double m = -MZX_INF;
-  for (int i = t; i < p.n; i += SAMPLER_FINISH_BLOCK) if (p.raw[i] > m) m = p.raw[i];
-  part[t] = m;
-  __syncthreads();
-  for (int o = SAMPLER_FINISH_BLOCK / 2; o >= 1; o >>= 1) {
-    if (t < o && part[t + o] > part[t]) part[t] = part[t + o];
-    __syncthreads();
+struct ReplayWeightFinishBody {
+  ReplayDrawParams p;
+  MZX_WAVE_FN void operator()(int t) const {
+    constexpr int THREADS = block_threads(SAMPLER_FINISH_BLOCK);
+    MZX_BLOCK_SHARED double part[THREADS];
+    double m = -MZX_INF;
+    for (int i = t; i < p.n; i += THREADS) if (p.raw[i] > m) m = p.raw[i];
+    part[t] = m;
+    block_sync();
+    for (int o = THREADS / 2; o >= 1; o >>= 1) {
+      if (t < o && part[t + o] > part[t]) part[t] = part[t + o];
+      block_sync();
+    }
+    m = part[0];
+    for (int i = t; i < p.n; i += THREADS) p.out_weight[i] = m > 0.0 ? (float)(p.raw[i] / m) : 0.0f;
   }
-  m = part[0];
-  for (int i = t; i < p.n; i += SAMPLER_FINISH_BLOCK) p.out_weight[i] = m > 0.0 ? (float)(p.raw[i] / m) : 0.0f;
-}
-
-#endif  // MZX_HOSTCHECK
+};
 
 }  // namespace mzx

@@ -28,7 +28,7 @@
 //   4. fc_train_backward_kernel  the same mapping, steps from the last to the first.  Writes d loss / d pre-activation of
 //                                every layer to scratch.  arg-min / arg-max / scale of a state are recomputed from the
 //                                stored s_t by the function the forward pass used (same bits), not stored.
-//   5. fc_train_wgrad_kernel     d loss / d W[j][k] = sum over rows (step, sample) of dz[row][j] * x[row][k]: one wavefront
+//   5. wave_kernel<4, FctWgradBody>  d loss / d W[j][k] = sum over rows (step, sample) of dz[row][j] * x[row][k]: one wavefront
 //                                per parameter, lane l sums rows l, l + 64, ... in increasing order, then a xor butterfly
 //                                (32, 16, .. 1).  A fixed order, no atomics: the same bits on every run.
 // This differs from "per-workgroup partial gradients in LDS + a reduction of partials" in one respect: the partial sums
@@ -45,8 +45,8 @@
 //   value / reward / policy logits (only those the caller did not pass) | h [rows][E] |
 //   per layer: out [rows][width] (the heads' last layers are the logits) | per layer: dz [rows][width] (the heads' last
 //   layers are the loss head's gradients).
-// tests/hostcheck build: the same per-sample functions run serially, one element per sample (per parameter for the
-// weight gradients, rows in increasing order), the weights read from the flat buffer.
+// tests/hostcheck build: the same per-sample functions with one lane (mzx_wave.h), one element per sample, the weights read
+// from the flat buffer; the weight gradients are the same wave body, rows in increasing order.
 #pragma once
 #include <vector>
 
@@ -156,28 +156,24 @@ inline bool fct_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   return true;
 }
 
+// The per-sample functions are wave bodies (mzx_wave.h); what differs between the builds is where the weights are read:
+// the padded LDS image of the workgroup, with a barrier after each layer, or the flat buffer.
 #ifdef MZX_HOSTCHECK
-#define FCT_FN inline
-#define FCT_STRIDE 1
 #define FCT_SYNC() ((void)0)
 #define FCT_W(L) ((L).flat_w)
 #define FCT_B(L) ((L).flat_b)
 #define FCT_LDW(L) ((L).in)
 #else
-#define FCT_FN __device__ __forceinline__
-#define FCT_STRIDE 64
 #define FCT_SYNC() __syncthreads()
 #define FCT_W(L) ((L).lds_w)
 #define FCT_B(L) ((L).lds_b)
 #define FCT_LDW(L) ((L).ldw)
 #endif
-// "every lane its share of n items": lanes j, j + 64, ... on the device, all of them in the serial build
-#define FCT_LANES(j, n) for (int j = lane; j < (n); j += FCT_STRIDE)
 
 // min, max (first index on ties) and the scale of a state: what representation() / dynamics() normalise with.  Every
 // lane walks the E values itself (LDS broadcasts): no cross-lane step, the same bits in both passes.
 struct FctNorm { float lo, scale; int imin, imax; };
-FCT_FN FctNorm fct_norm(const float* s, int E) {
+MZX_WAVE_FN FctNorm fct_norm(const float* s, int E) {
   FctNorm n;
   float lo = s[0], hi = s[0];
   n.imin = 0; n.imax = 0;
@@ -195,7 +191,7 @@ FCT_FN FctNorm fct_norm(const float* s, int E) {
 // One MLP forward: input `x` (LDS / local), outputs of layer l to scratch (hidden layers, states) or `last_out` (rows of
 // `row`).  `action` >= 0: the one-hot block of the dynamics network's first layer.  Returns where the last layer's
 // outputs are (x0 or x1).
-FCT_FN const float* fct_mlp_forward(const FctParams& p, int m, const float* W, const float* x, float* x0, float* x1, size_t row,
+MZX_WAVE_FN const float* fct_mlp_forward(const FctParams& p, int m, const float* W, const float* x, float* x0, float* x1, size_t row,
                                     int action, float* last_out, bool valid, int lane) {
   const FctMlp& M = p.plan.mlp[m];
   for (int l = 0; l < M.n; ++l) {
@@ -205,7 +201,7 @@ FCT_FN const float* fct_mlp_forward(const FctParams& p, int m, const float* W, c
     const int dense = (action >= 0 && l == 0) ? p.plan.E : L.in;
     const int ldw = FCT_LDW(L);
     float* out = (last && last_out) ? last_out : p.scratch + L.act;
-    FCT_LANES(j, L.out) {
+    WAVE_FOR(j, L.out) {
       const float* wr = W + FCT_W(L) + (size_t)j * ldw;
       float acc = W[FCT_B(L) + j];
       for (int k = 0; k < dense; ++k) acc = fmaf(wr[k], x[k], acc);
@@ -221,20 +217,20 @@ FCT_FN const float* fct_mlp_forward(const FctParams& p, int m, const float* W, c
 }
 
 // Every step of one sample.  buf: 2 * maxw + 3 * E floats of this wave.
-FCT_FN void fct_forward_sample(const FctParams& p, const float* W, float* buf, int b, bool valid, int lane) {
+MZX_WAVE_FN void fct_forward_sample(const FctParams& p, const float* W, float* buf, int b, bool valid, int lane) {
   const FctPlan& P = p.plan;
   const int E = P.E, F = P.F;
   float* x0 = buf;
   float* x1 = buf + P.maxw;
   float* hn = buf + 2 * P.maxw;
-  FCT_LANES(k, P.in_size) x0[k] = p.obs[(size_t)b * P.in_size + k];
+  WAVE_FOR(k, P.in_size) x0[k] = p.obs[(size_t)b * P.in_size + k];
   FCT_SYNC();
   for (int t = 0; t < p.steps; ++t) {
     const size_t row = (size_t)t * p.B + b;
     const float* s;
     if (t == 0) {
       s = fct_mlp_forward(p, FCT_REP, W, x0, x0, x1, row, -1, nullptr, valid, lane);
-      FCT_LANES(j, F) if (valid) p.rlog[row * F + j] = (j == F / 2) ? 0.0f : -(float)MZX_INF;
+      WAVE_FOR(j, F) if (valid) p.rlog[row * F + j] = (j == F / 2) ? 0.0f : -(float)MZX_INF;
     } else {
       int a = p.action[(size_t)b * p.steps + t];
       a = a < 0 ? 0 : (a >= P.A ? P.A - 1 : a);
@@ -242,7 +238,7 @@ FCT_FN void fct_forward_sample(const FctParams& p, const float* W, float* buf, i
     }
     const FctNorm n = fct_norm(s, E);
     FCT_SYNC();          // (every lane has read h_{t-1} and s_t before h_t replaces it)
-    FCT_LANES(k, E) {
+    WAVE_FOR(k, E) {
       const float h = mzx_div(s[k] - n.lo, n.scale);
       hn[k] = h;
       if (valid) p.scratch[P.off_h + row * E + k] = h;
@@ -256,14 +252,14 @@ FCT_FN void fct_forward_sample(const FctParams& p, const float* W, float* buf, i
 
 // One MLP backward.  `g` (LDS / local, writable): d loss / d output of the last layer.  Writes d loss / d pre-activation
 // of every layer that has a scratch block; returns d loss / d input (the first `dense` entries) when `want_dx`.
-FCT_FN const float* fct_mlp_backward(const FctParams& p, int m, const float* W, float* g, float* x0, float* x1, size_t row,
+MZX_WAVE_FN const float* fct_mlp_backward(const FctParams& p, int m, const float* W, float* g, float* x0, float* x1, size_t row,
                                      int dense0, bool want_dx, bool valid, int lane) {
   const FctMlp& M = p.plan.mlp[m];
   for (int l = M.n - 1; l >= 0; --l) {
     const FctLayer& L = M.l[l];
     const bool last = l == M.n - 1;
     if (L.dz >= 0) {
-      FCT_LANES(j, L.out) {
+      WAVE_FOR(j, L.out) {
         float d = g[j];
         if (!last) {          // ELU'(z) from a = ELU(z): 1 for a > 0, exp(z) = a + 1 otherwise
           const float a = p.scratch[L.act + row * L.out + j];
@@ -278,7 +274,7 @@ FCT_FN const float* fct_mlp_backward(const FctParams& p, int m, const float* W, 
     float* dx = (g == x0) ? x1 : x0;
     const int nin = l == 0 ? dense0 : L.in;
     const int ldw = FCT_LDW(L);
-    FCT_LANES(k, nin) {
+    WAVE_FOR(k, nin) {
       const float* wc = W + FCT_W(L) + k;
       float acc = 0.f;
       for (int j = 0; j < L.out; ++j) acc = fmaf(wc[(size_t)j * ldw], g[j], acc);
@@ -290,7 +286,7 @@ FCT_FN const float* fct_mlp_backward(const FctParams& p, int m, const float* W, 
   return g;
 }
 
-FCT_FN void fct_backward_sample(const FctParams& p, const float* W, float* buf, int b, bool valid, int lane) {
+MZX_WAVE_FN void fct_backward_sample(const FctParams& p, const float* W, float* buf, int b, bool valid, int lane) {
   const FctPlan& P = p.plan;
   const int E = P.E, F = P.F, A = P.A;
   float* x0 = buf;
@@ -298,22 +294,22 @@ FCT_FN void fct_backward_sample(const FctParams& p, const float* W, float* buf, 
   float* gh = buf + 2 * P.maxw;      // d loss / d h_t, what has arrived so far
   float* gs = gh + E;                // d loss / d s_t
   float* st = gs + E;                // s_t
-  FCT_LANES(k, E) gh[k] = 0.0f;
+  WAVE_FOR(k, E) gh[k] = 0.0f;
   FCT_SYNC();
   for (int t = p.steps - 1; t >= 0; --t) {
     const size_t row = (size_t)t * p.B + b;
     const float* state_rows = p.scratch + (t == 0 ? P.mlp[FCT_REP].l[P.mlp[FCT_REP].n - 1].act : P.mlp[FCT_DYN].l[P.mlp[FCT_DYN].n - 1].act);
-    FCT_LANES(k, E) st[k] = state_rows[row * E + k];
+    WAVE_FOR(k, E) st[k] = state_rows[row * E + k];
     // the two heads that read h_t
-    FCT_LANES(j, A) x0[j] = p.gp[row * A + j];
+    WAVE_FOR(j, A) x0[j] = p.gp[row * A + j];
     FCT_SYNC();
     const float* dp = fct_mlp_backward(p, FCT_POL, W, x0, x0, x1, row, E, true, valid, lane);
-    FCT_LANES(k, E) gh[k] += dp[k];
+    WAVE_FOR(k, E) gh[k] += dp[k];
     FCT_SYNC();
-    FCT_LANES(j, F) x0[j] = p.gv[row * F + j];
+    WAVE_FOR(j, F) x0[j] = p.gv[row * F + j];
     FCT_SYNC();
     const float* dv = fct_mlp_backward(p, FCT_VAL, W, x0, x0, x1, row, E, true, valid, lane);
-    FCT_LANES(k, E) gh[k] = t > 0 ? (gh[k] + dv[k]) * 0.5f : gh[k] + dv[k];
+    WAVE_FOR(k, E) gh[k] = t > 0 ? (gh[k] + dv[k]) * 0.5f : gh[k] + dv[k];
     FCT_SYNC();
     // h = (s - min) / scale, scale = max - min (+ 1e-5): q = g / scale goes to s, -sum q to min, -sum q h to scale
     const FctNorm n = fct_norm(st, E);
@@ -324,7 +320,7 @@ FCT_FN void fct_backward_sample(const FctParams& p, const float* W, float* buf, 
       sum_qh += q * mzx_div(st[k] - n.lo, n.scale);
     }
     const float dscale = -sum_qh;
-    FCT_LANES(k, E) {
+    WAVE_FOR(k, E) {
       float d = mzx_div(gh[k], n.scale);
       if (k == n.imin) d += -sum_q - dscale;
       if (k == n.imax) d += dscale;
@@ -332,13 +328,13 @@ FCT_FN void fct_backward_sample(const FctParams& p, const float* W, float* buf, 
     }
     FCT_SYNC();
     if (t > 0) {      // the reward head reads s_t
-      FCT_LANES(j, F) x0[j] = p.gr[row * F + j];
+      WAVE_FOR(j, F) x0[j] = p.gr[row * F + j];
       FCT_SYNC();
       const float* dr = fct_mlp_backward(p, FCT_REW, W, x0, x0, x1, row, E, true, valid, lane);
-      FCT_LANES(k, E) gs[k] += dr[k];
+      WAVE_FOR(k, E) gs[k] += dr[k];
       FCT_SYNC();
       const float* dh = fct_mlp_backward(p, FCT_DYN, W, gs, x0, x1, row, E, true, valid, lane);
-      FCT_LANES(k, E) gh[k] = dh[k];
+      WAVE_FOR(k, E) gh[k] = dh[k];
       FCT_SYNC();
     } else {
       fct_mlp_backward(p, FCT_REP, W, gs, x0, x1, row, 0, false, valid, lane);
@@ -403,6 +399,21 @@ MZX_HD inline float fct_element_term(const FctParams& p, const FctElement& el, i
   return d;
 }
 
+// d loss / d parameter e: launch_waves<FCT_WAVES>, a wavefront per parameter, rows in increasing order per lane
+struct FctWgradBody {
+  FctParams p;
+  MZX_HD size_t size() const { return (size_t)p.plan.num_params; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    FctElement el;
+    float acc = 0.f;
+    if (fct_element(p, (int)e, el))
+      for (int64_t r = el.r0 + lane; r < el.r1; r += WAVE_LANES) acc += fct_element_term(p, el, r);
+    acc = wave_sum(acc);
+    if (lane == 0) p.grad_flat[e] = acc;
+  }
+};
+
+// The forward (phase 0) / backward (phase 1) pass; the weight gradients follow the backward pass as a launch of their own.
 #ifdef MZX_HOSTCHECK
 
 struct FctForwardOp {
@@ -421,24 +432,11 @@ struct FctBackwardOp {
     fct_backward_sample(p, p.flat, buf.data(), (int)b, true, 0);
   }
 };
-struct FctWgradOp {
-  FctParams p;
-  size_t size() const { return (size_t)p.plan.num_params; }
-  void operator()(size_t e) const {
-    FctElement el;
-    float acc = 0.f;
-    if (fct_element(p, (int)e, el))
-      for (int64_t r = el.r0; r < el.r1; ++r) acc += fct_element_term(p, el, r);
-    p.grad_flat[e] = acc;
-  }
-};
 
 inline int fct_launch(const FctParams& p, int phase, stream_t stream) {
   if (phase == 0) { FctForwardOp op; op.p = p; return launch<64>(op, stream); }
   FctBackwardOp bw; bw.p = p;
-  if (const int rc = launch<64>(bw, stream)) return rc;
-  FctWgradOp wg; wg.p = p;
-  return launch<64>(wg, stream);
+  return launch<64>(bw, stream);
 }
 
 #else
@@ -475,18 +473,6 @@ __global__ void __launch_bounds__(64 * FCT_WAVES) fc_train_backward_kernel(const
   fct_backward_sample(p, lds, lds + p.plan.lds_weight_floats + wave * p.plan.wave_floats, b < p.B ? b : p.B - 1, b < p.B, lane);
 }
 
-__global__ void __launch_bounds__(64 * FCT_WAVES) fc_train_wgrad_kernel(const FctParams p) {
-  const int lane = threadIdx.x & 63;
-  const int e = blockIdx.x * FCT_WAVES + (threadIdx.x >> 6);
-  if (e >= p.plan.num_params) return;          // (whole waves leave: no barrier below)
-  FctElement el;
-  float acc = 0.f;
-  if (fct_element(p, e, el))
-    for (int64_t r = el.r0 + lane; r < el.r1; r += 64) acc += fct_element_term(p, el, r);
-  acc = wave_sum(acc);
-  if (lane == 0) p.grad_flat[e] = acc;
-}
-
 inline int fct_launch(const FctParams& p, int phase, stream_t stream) {
   static std::atomic<uint64_t> fw_done{0}, bw_done{0};
   const int lds_bytes = 4 * (p.plan.lds_weight_floats + FCT_WAVES * p.plan.wave_floats);
@@ -498,9 +484,6 @@ inline int fct_launch(const FctParams& p, int phase, stream_t stream) {
   }
   if (const int rc = allow_large_lds((const void*)fc_train_backward_kernel, FCT_LDS_BUDGET, bw_done)) return rc;
   hipLaunchKernelGGL(fc_train_backward_kernel, dim3(grid), dim3(64 * FCT_WAVES), lds_bytes, stream, p);
-  if (const int rc = (int)hipGetLastError()) return rc;
-  const unsigned wgrid = (unsigned)((p.plan.num_params + FCT_WAVES - 1) / FCT_WAVES);
-  hipLaunchKernelGGL(fc_train_wgrad_kernel, dim3(wgrid), dim3(64 * FCT_WAVES), 0, stream, p);
   return (int)hipGetLastError();
 }
 

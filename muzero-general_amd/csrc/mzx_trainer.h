@@ -20,11 +20,12 @@
 // three passes (max, sum, gradient): a row is at most a few KB and belongs to one wave.  The value row is decoded a
 // second time in the CANONICAL 16-lane order of mzx_tree.h (element i to lane i % 16, butterfly16_sum) so that the
 // prediction behind the priority has the bits of mzx_support_to_scalar for the same logits.
-// tests/hostcheck build: the same arithmetic as a serial functor, one element per (sample, step), the lane loop a plain
-// loop (sums in increasing bin order -- the two builds are each held to the reference, not to each other).
+// tests/hostcheck build: the same bodies with one lane (mzx_wave.h), so the sums are taken in increasing bin order -- the two
+// builds are each held to the reference, not to each other.
 #pragma once
 #include "mzx_platform.h"
 #include "mzx_tree.h"
+#include "mzx_wave.h"
 
 namespace mzx {
 
@@ -108,106 +109,24 @@ MZX_HD inline float trainer_grad_factor(const TrainerLossParams& p, int b, int i
   return c;
 }
 
-#ifdef MZX_HOSTCHECK
-
-// Serial restatement: one element per (sample, step).
-struct TrainerLossRowOp {
-  TrainerLossParams p;
-  MZX_HD size_t size() const { return (size_t)p.batch * p.steps; }
-
-  // log-sum-exp statistics of a row: max, sum of exp(x - max)
-  static void row_stats(const float* x, int n, float& m, float& den) {
-    m = x[0];
-    for (int j = 1; j < n; ++j) m = fmaxf(m, x[j]);
-    den = 0.f;
-    for (int j = 0; j < n; ++j) den += mzx_expf(x[j] - m);
-  }
-
-  float support_row(const float* x, float* grad, float target, float c, bool ignored) const {
-    const int W = 2 * p.support_size + 1;
-    if (ignored) {
-      if (grad) for (int j = 0; j < W; ++j) grad[j] = 0.0f;
-      return 0.0f;
-    }
-    float m, den;
-    row_stats(x, W, m, den);
-    const float lse = m + logf(den);
-    const TargetPair t = scalar_to_support_pair(target, p.support_size);
-    const float l1 = t.i1 == t.i0 ? 0.0f : t.w1 * (x[t.i1] - lse);
-    const float loss = -(t.w0 * (x[t.i0] - lse) + l1);
-    if (grad) {
-      const float tsum = t.i1 == t.i0 ? t.w0 : t.w0 + t.w1;
-      for (int j = 0; j < W; ++j) {
-        float tj = j == t.i0 ? t.w0 : 0.0f;
-        if (j == t.i1 && t.i1 != t.i0) tj = t.w1;
-        grad[j] = c * (mzx_div(mzx_expf(x[j] - m), den) * tsum - tj);
-      }
-    }
-    return loss;
-  }
-
-  void operator()(size_t e) const {
-    const int b = (int)(e / (size_t)p.steps), i = (int)(e % (size_t)p.steps);
-    const int W = 2 * p.support_size + 1, A = p.num_actions;
-    const size_t row = (size_t)i * p.batch + b;
-    const bool grads = p.grad_value != nullptr;
-    const float* xv = p.value_logits + row * W;
-    const float tv = p.target_value[e];
-    const float vl = support_row(xv, grads ? p.grad_value + row * W : nullptr, tv,
-                                 trainer_grad_factor(p, b, i, p.value_loss_weight, true), false);
-    const float rl = support_row(p.reward_logits + row * W, grads ? p.grad_reward + row * W : nullptr, p.target_reward[e],
-                                 trainer_grad_factor(p, b, i, 1.0f, false), i == 0);
-    const float* xp = p.policy_logits + row * A;
-    const float* tp = p.target_policy + e * (size_t)A;
-    float m, den;
-    row_stats(xp, A, m, den);
-    const float lse = m + logf(den);
-    float dot = 0.f, tsum = 0.f;
-    for (int j = 0; j < A; ++j) {
-      dot += tp[j] * (xp[j] - lse);
-      tsum += tp[j];
-    }
-    if (grads) {
-      const float c = trainer_grad_factor(p, b, i, 1.0f, false);
-      float* g = p.grad_policy + row * A;
-      for (int j = 0; j < A; ++j) g[j] = c * (mzx_div(mzx_expf(xp[j] - m), den) * tsum - tp[j]);
-    }
-    p.scratch[e] = TrainerLossRow{vl, rl, -dot, 0.0f};
-    p.priorities[e] = trainer_priority(support_to_scalar(xv, p.support_size), tv, p.per_alpha);
-  }
-};
-
-#else
-
 constexpr int TRAINER_WAVES = 4;          // wavefronts (rows of the batch) per workgroup of the loss kernel
 constexpr int TRAINER_FINISH_BLOCK = 128;
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
 // max and sum of exp(x - max) of a row of n logits, in every lane
-__device__ __forceinline__ void wave_row_stats(const float* __restrict__ x, int n, int lane, float& m, float& den) {
+MZX_WAVE_FN void wave_row_stats(const float* __restrict__ x, int n, int lane, float& m, float& den) {
   float mx = -MZX_INF;
-  for (int j = lane; j < n; j += 64) mx = fmaxf(mx, x[j]);
+  WAVE_FOR(j, n) mx = fmaxf(mx, x[j]);
   m = wave_max(mx);
   float acc = 0.f;
-  for (int j = lane; j < n; j += 64) acc += mzx_expf(x[j] - m);
+  WAVE_FOR(j, n) acc += mzx_expf(x[j] - m);
   den = wave_sum(acc);
 }
 
 // One support head (value or reward) of one (sample, step): returns the loss in every lane, writes the gradient row.
-__device__ __forceinline__ float wave_support_row(const float* __restrict__ x, float* __restrict__ grad, int W, int support_size,
-                                                  float target, float c, bool ignored, int lane, float& row_max) {
+MZX_WAVE_FN float wave_support_row(const float* __restrict__ x, float* __restrict__ grad, int W, int support_size, float target,
+                                   float c, bool ignored, int lane, float& row_max) {
   if (ignored) {
-    if (grad) for (int j = lane; j < W; j += 64) grad[j] = 0.0f;
+    if (grad) WAVE_FOR(j, W) grad[j] = 0.0f;
     return 0.0f;
   }
   float m, den;
@@ -219,7 +138,7 @@ __device__ __forceinline__ float wave_support_row(const float* __restrict__ x, f
   const float loss = -(t.w0 * (x[t.i0] - lse) + l1);
   if (grad) {
     const float tsum = t.i1 == t.i0 ? t.w0 : t.w0 + t.w1;
-    for (int j = lane; j < W; j += 64) {
+    WAVE_FOR(j, W) {
       float tj = j == t.i0 ? t.w0 : 0.0f;
       if (j == t.i1 && t.i1 != t.i0) tj = t.w1;
       grad[j] = c * (mzx_div(mzx_expf(x[j] - m), den) * tsum - tj);
@@ -231,132 +150,110 @@ __device__ __forceinline__ float wave_support_row(const float* __restrict__ x, f
 // support_to_scalar (mzx_tree.h) of a row with 16 lanes at work: lane l holds the partial of canonical lane l % 16
 // (elements l % 16, l % 16 + 16, ... in increasing order), the 16 partials are combined by butterfly16_sum -- the
 // operations of the serial function in its order, hence its bits.  `m` is the row max (exact in any order).
-__device__ __forceinline__ float wave_support_to_scalar(const float* __restrict__ x, int support_size, float m, int lane) {
+MZX_WAVE_FN float wave_support_to_scalar(const float* __restrict__ x, int support_size, float m, int lane) {
+#ifdef MZX_HOSTCHECK
+  return support_to_scalar(x, support_size);
+#else
   const int F = 2 * support_size + 1;
   const int j = lane & 15;
   float acc = 0.f;
   for (int i = j; i < F; i += 16) acc += mzx_expf(x[i] - m);
   float part[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) part[k] = __shfl(acc, k, 64);
+  for (int k = 0; k < 16; ++k) part[k] = lane_value(acc, k);
   const float den = butterfly16_sum(part);
   acc = 0.f;
   for (int i = j; i < F; i += 16) acc += (float)(i - support_size) * mzx_div(mzx_expf(x[i] - m), den);
 #pragma unroll
-  for (int k = 0; k < 16; ++k) part[k] = __shfl(acc, k, 64);
+  for (int k = 0; k < 16; ++k) part[k] = lane_value(acc, k);
   return support_inverse_transform(butterfly16_sum(part));
+#endif
 }
 
-__global__ void __launch_bounds__(64 * TRAINER_WAVES) trainer_loss_kernel(const TrainerLossParams p) {
-  const int lane = threadIdx.x & 63;
-  const size_t e = (size_t)blockIdx.x * TRAINER_WAVES + (threadIdx.x >> 6);      // (sample, step), sample-major
-  if (e >= (size_t)p.batch * p.steps) return;                                      // (whole waves leave: no barrier below)
-  const int b = (int)(e / (size_t)p.steps), i = (int)(e % (size_t)p.steps);
-  const int W = 2 * p.support_size + 1, A = p.num_actions;
-  const size_t row = (size_t)i * p.batch + b;                                       // step-major logits
-  const bool grads = p.grad_value != nullptr;
+// The three heads of one (sample, step), e sample-major: launch_waves<TRAINER_WAVES>.
+struct TrainerLossBody {
+  TrainerLossParams p;
+  MZX_HD size_t size() const { return (size_t)p.batch * p.steps; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int b = (int)(e / (size_t)p.steps), i = (int)(e % (size_t)p.steps);
+    const int W = 2 * p.support_size + 1, A = p.num_actions;
+    const size_t row = (size_t)i * p.batch + b;                                       // step-major logits
+    const bool grads = p.grad_value != nullptr;
 
-  const float* xv = p.value_logits + row * W;
-  const float tv = p.target_value[e];
-  float vmax = 0.f, unused = 0.f;
-  const float vl = wave_support_row(xv, grads ? p.grad_value + row * W : nullptr, W, p.support_size, tv,
-                                    trainer_grad_factor(p, b, i, p.value_loss_weight, true), false, lane, vmax);
-  const float rl = wave_support_row(p.reward_logits + row * W, grads ? p.grad_reward + row * W : nullptr, W, p.support_size,
-                                    p.target_reward[e], trainer_grad_factor(p, b, i, 1.0f, false), i == 0, lane, unused);
+    const float* xv = p.value_logits + row * W;
+    const float tv = p.target_value[e];
+    float vmax = 0.f, unused = 0.f;
+    const float vl = wave_support_row(xv, grads ? p.grad_value + row * W : nullptr, W, p.support_size, tv,
+                                      trainer_grad_factor(p, b, i, p.value_loss_weight, true), false, lane, vmax);
+    const float rl = wave_support_row(p.reward_logits + row * W, grads ? p.grad_reward + row * W : nullptr, W, p.support_size,
+                                      p.target_reward[e], trainer_grad_factor(p, b, i, 1.0f, false), i == 0, lane, unused);
 
-  const float* xp = p.policy_logits + row * A;
-  const float* tp = p.target_policy + e * (size_t)A;
-  float m, den;
-  wave_row_stats(xp, A, lane, m, den);
-  const float lse = m + logf(den);
-  float dot = 0.f, tsum = 0.f;
-  for (int j = lane; j < A; j += 64) {
-    const float t = tp[j];
-    dot += t * (xp[j] - lse);
-    tsum += t;
-  }
-  dot = wave_sum(dot);
-  tsum = wave_sum(tsum);
-  if (grads) {
-    const float c = trainer_grad_factor(p, b, i, 1.0f, false);
-    float* g = p.grad_policy + row * A;
-    for (int j = lane; j < A; j += 64) g[j] = c * (mzx_div(mzx_expf(xp[j] - m), den) * tsum - tp[j]);
-  }
+    const float* xp = p.policy_logits + row * A;
+    const float* tp = p.target_policy + e * (size_t)A;
+    float m, den;
+    wave_row_stats(xp, A, lane, m, den);
+    const float lse = m + logf(den);
+    float dot = 0.f, tsum = 0.f;
+    WAVE_FOR(j, A) {
+      const float t = tp[j];
+      dot += t * (xp[j] - lse);
+      tsum += t;
+    }
+    dot = wave_sum(dot);
+    tsum = wave_sum(tsum);
+    if (grads) {
+      const float c = trainer_grad_factor(p, b, i, 1.0f, false);
+      float* g = p.grad_policy + row * A;
+      WAVE_FOR(j, A) g[j] = c * (mzx_div(mzx_expf(xp[j] - m), den) * tsum - tp[j]);
+    }
 
-  const float prediction = wave_support_to_scalar(xv, p.support_size, vmax, lane);
-  if (lane == 0) {
-    p.scratch[e] = TrainerLossRow{vl, rl, -dot, 0.0f};
-    p.priorities[e] = trainer_priority(prediction, tv, p.per_alpha);
+    const float prediction = wave_support_to_scalar(xv, p.support_size, vmax, lane);
+    if (lane == 0) {
+      p.scratch[e] = TrainerLossRow{vl, rl, -dot, 0.0f};
+      p.priorities[e] = trainer_priority(prediction, tv, p.per_alpha);
+    }
   }
-}
+};
 
 // The batch means: thread t sums samples t, t + 128, ... (per sample the steps in increasing order, as the reference's
-// `value_loss += current_value_loss`), then a fixed tree over the 128 partials in LDS.  One workgroup.
-__global__ void __launch_bounds__(TRAINER_FINISH_BLOCK) trainer_finish_kernel(const TrainerLossParams p) {
-  __shared__ float4 part[TRAINER_FINISH_BLOCK];
-  const int t = threadIdx.x;
-  float total = 0.f, value = 0.f, reward = 0.f, policy = 0.f;
-  for (int b = t; b < p.batch; b += TRAINER_FINISH_BLOCK) {
-    float vl = 0.f, rl = 0.f, pl = 0.f;
-    for (int i = 0; i < p.steps; ++i) {
-      const TrainerLossRow s = p.scratch[(size_t)b * p.steps + i];
-      vl += s.value;
-      rl += s.reward;
-      pl += s.policy;
-    }
-    float loss = vl * p.value_loss_weight + rl + pl;
-    if (p.weight) loss = loss * p.weight[b];
-    total += loss;
-    value += vl;
-    reward += rl;
-    policy += pl;
-  }
-  part[t] = make_float4(total, value, reward, policy);
-  __syncthreads();
-  for (int o = TRAINER_FINISH_BLOCK / 2; o >= 1; o >>= 1) {
-    if (t < o) {
-      const float4 a = part[t], c = part[t + o];
-      part[t] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
-    }
-    __syncthreads();
-  }
-  if (t < 4) {
-    const float4 s = part[0];
-    const float v = t == 0 ? s.x : (t == 1 ? s.y : (t == 2 ? s.z : s.w));
-    p.losses[t] = v / (float)p.batch;
-  }
-}
-
-#endif  // MZX_HOSTCHECK
-
-#ifdef MZX_HOSTCHECK
-// The batch means of the serial build: samples in increasing order.
-struct TrainerFinishOp {
+// `value_loss += current_value_loss`), then a fixed tree over the 128 partials in LDS.  launch_block<TRAINER_FINISH_BLOCK>.
+struct alignas(16) TrainerSums { float total, value, reward, policy; };
+struct TrainerFinishBody {
   TrainerLossParams p;
-  MZX_HD size_t size() const { return 1; }
-  MZX_HD void operator()(size_t) const {
-    float total = 0.f, value = 0.f, reward = 0.f, policy = 0.f;
-    for (int b = 0; b < p.batch; ++b) {
+  MZX_WAVE_FN void operator()(int t) const {
+    constexpr int THREADS = block_threads(TRAINER_FINISH_BLOCK);
+    MZX_BLOCK_SHARED TrainerSums part[THREADS];
+    TrainerSums s{0.f, 0.f, 0.f, 0.f};
+    for (int b = t; b < p.batch; b += THREADS) {
       float vl = 0.f, rl = 0.f, pl = 0.f;
       for (int i = 0; i < p.steps; ++i) {
-        const TrainerLossRow s = p.scratch[(size_t)b * p.steps + i];
-        vl += s.value;
-        rl += s.reward;
-        pl += s.policy;
+        const TrainerLossRow r = p.scratch[(size_t)b * p.steps + i];
+        vl += r.value;
+        rl += r.reward;
+        pl += r.policy;
       }
       float loss = vl * p.value_loss_weight + rl + pl;
       if (p.weight) loss = loss * p.weight[b];
-      total += loss;
-      value += vl;
-      reward += rl;
-      policy += pl;
+      s.total += loss;
+      s.value += vl;
+      s.reward += rl;
+      s.policy += pl;
     }
-    p.losses[0] = total / (float)p.batch;
-    p.losses[1] = value / (float)p.batch;
-    p.losses[2] = reward / (float)p.batch;
-    p.losses[3] = policy / (float)p.batch;
+    part[t] = s;
+    block_sync();
+    for (int o = THREADS / 2; o >= 1; o >>= 1) {
+      if (t < o) {
+        const TrainerSums a = part[t], c = part[t + o];
+        part[t] = TrainerSums{a.total + c.total, a.value + c.value, a.reward + c.reward, a.policy + c.policy};
+      }
+      block_sync();
+    }
+    for (int k = t; k < 4; k += THREADS) {
+      s = part[0];
+      const float v = k == 0 ? s.total : (k == 1 ? s.value : (k == 2 ? s.reward : s.policy));
+      p.losses[k] = v / (float)p.batch;
+    }
   }
 };
-#endif
 
 }  // namespace mzx

@@ -3,7 +3,10 @@ ISA facts of the shipped library per kernel: registers, scratch, spills (code-ob
 instruction mix of its body (llvm-objdump -d): MFMAs, LDS reads / writes, global accesses, binary64 instructions, barriers.
 No GPU needed.
 
-    python muzero-general_amd/tools/isa_summary.py [path to libmzx.so] > profiles/rNN_isa_summary.txt
+    python muzero-general_amd/tools/isa_summary.py [path to libmzx.so] [--keep name,name,...] > profiles/rNN_isa_summary.txt
+
+--keep: the substrings of the mangled kernel names to list instead of the search kernels; the last line counts every kernel
+of the code objects, listed or not.
 """
 import collections
 import os
@@ -66,13 +69,21 @@ def mixes(path):
 
 
 def main():
-    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(HERE), "mzx", "libmzx.so")
+    args = sys.argv[1:]
+    keep = KEEP
+    if "--keep" in args:
+        at = args.index("--keep")
+        keep = tuple(args[at + 1].split(","))
+        del args[at:at + 2]
+    lib = args[0] if args else os.path.join(os.path.dirname(HERE), "mzx", "libmzx.so")
     seen = collections.OrderedDict()
+    total = 0
     for n, path in enumerate(code_objects(lib)):
         mix = mixes(path)
         for k in metadata(path):
             name = k["name"]
-            if not any(s in name for s in KEEP):
+            total += 1
+            if not any(s in name for s in keep):
                 continue
             seen.setdefault(name, (k, mix.get(name, collections.Counter()), []))[2].append(n)
     names = subprocess.run(["c++filt"], input="\n".join(seen), capture_output=True, text=True).stdout.splitlines()
@@ -80,14 +91,15 @@ def main():
           "kernels defined in headers that two units include are compiled into both).  vgpr = unified VGPR + AGPR budget of a lane (512 max;\n"
           "256 -> two waves per SIMD), scratch = bytes of private memory per lane, spill = spilled VGPRs; instruction counts are static\n"
           "(whole kernel body, loops counted once)." % (os.path.basename(lib), os.path.getsize(lib)))
-    print("%-88s %4s %4s %4s %7s %5s | %6s %5s %5s %5s %5s %5s %4s %4s  objects" % ("kernel", "vgpr", "agpr", "sgpr", "scratch", "spill", "instr",
+    print("%-88s %4s %4s %4s %7s %5s %6s | %6s %5s %5s %5s %5s %5s %4s %4s  objects" % ("kernel", "vgpr", "agpr", "sgpr", "scratch", "spill", "lds", "instr",
                                                                                      "mfma", "ds_rd", "ds_wr", "vmem", "f64", "dpp", "bar"))
     for (name, (k, c, objs)), pretty in zip(seen.items(), names):
         pretty = re.sub(r"\(anonymous namespace\)::", "", pretty).replace("void mzx::", "").split("(mzx::")[0]
-        print("%-88s %4s %4s %4s %7s %5s | %6d %5d %5d %5d %5d %5d %4d %4d  %s" % (
+        print("%-88s %4s %4s %4s %7s %5s %6s | %6d %5d %5d %5d %5d %5d %4d %4d  %s" % (
             pretty[:88], k.get("vgpr_count"), k.get("agpr_count"), k.get("sgpr_count"), k.get("private_segment_fixed_size"),
-            k.get("vgpr_spill_count", "0"), c["instr"], c["mfma"], c["ds_rd"], c["ds_wr"], c["vmem"], c["f64"], c["dpp"], c["bar"],
+            k.get("vgpr_spill_count", "0"), k.get("group_segment_fixed_size"), c["instr"], c["mfma"], c["ds_rd"], c["ds_wr"], c["vmem"], c["f64"], c["dpp"], c["bar"],
             ",".join(map(str, objs))))
+    print("%d kernels in the code objects, %d listed" % (total, len(seen)))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """
 Training a fully connected network natively on the device (fc_train_forward_kernel, the loss head, fc_train_backward_kernel,
-fc_train_wgrad_kernel behind mzx_train_fc_step; mzx.trainer with a HipNetwork) against tests/golden/fc_train.npz, with the
+wave_kernel<4, FctWgradBody> behind mzx_train_fc_step; mzx.trainer with a HipNetwork) against tests/golden/fc_train.npz, with the
 gates of tests/test_fc_train.py (fc_train_cases.check_case), and the whole step -- device sampler, native gradients, Adam,
 priority feedback -- followed by a search on the trained buffer.
 """
