@@ -579,6 +579,40 @@ int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples,
 int mzx_replay_batch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Reanalyse with fresh searches (DeviceGameStore.reanalyse_search; csrc/mzx_replay.h): a chunk of the sample list
+ * mzx_replay_positions writes is searched under the current weights and its visit distributions and root values become
+ * the pool's targets, in place.  Between mzx_replay_positions / mzx_replay_batch (observation only) and mzx_search_run,
+ * and between mzx_search_run and mzx_replay_values, the two entries below; one launch each, a wavefront per sample.
+ * Sample n is row = d_sample_base[n] + d_sample_pos[n] of the pool.
+ * mzx_replay_search_inputs: the mzx_search_io inputs of num_samples roots (A = pool->action_space_size).
+ *   d_to_play [n] i32 = pool->d_to_play[row].
+ *   d_legal [n][A] i32: d_legal_mask is an optional column u32 [pool->rows][ceil(A / 32)], bit a % 32 of word a / 32 set
+ *     when action a is legal at that row (bits past A are ignored).  With it: the set bits in INCREASING action order,
+ *     padded with -1.  NULL: the identity 0 .. A-1.  A mask row without a bit yields the identity too and sets bit 0 of
+ *     d_input_flags [n] i32 (mzx_search_run needs a non-empty list; mzx_replay_search_write passes such a sample over).
+ *     Bit 1: the row lies outside 0 .. pool->rows-1; nothing is read from the pool for it.  0 otherwise.
+ *   d_tape [n][tape_words] u32: tie-break words from Philox4x32-10, key (seed lo, seed hi ^ 0x52454153), counter
+ *     (first_index + n, sweep_counter lo, sweep_counter hi, block); block b supplies words 4b .. 4b + 3.  first_index is
+ *     the index of sample 0 in the sweep's flat sequence; first_index + num_samples <= 2^32.
+ *   There is no exploration noise (the sweep passes d_noise = NULL): the targets are a function of (seed, sweep_counter).
+ * mzx_replay_search_write: the outputs of that search -- d_visit_counts [n][A] i32, d_root_value [n] f64, d_info [n][4]
+ *   i32 -- as targets: d_child_visits[row][a] = (double)visits[a] / (double)sum_a visits[a] (the binary64 quotient of
+ *   GameHistory.store_search_statistics, self_play.py:496-511; 0 for an action that is no child; the sum is an integer)
+ *   and d_root_values[row] = d_root_value[n].  A sample whose d_info[n][1] is non-zero (tie tape or node overflow), whose
+ *   d_input_flags[n] is non-zero or whose visits sum to less than 1 is SKIPPED: both rows keep their contents and
+ *   d_skipped[0] (i32, zeroed by the caller before the sweep) grows by one.  d_child_visits / d_root_values are the
+ *   pool's columns, passed writable (the pool holds them const); mzx_replay_values afterwards refreshes the n-step targets.
+ * ------------------------------------------------------------------------- */
+int mzx_replay_search_inputs(const mzx_replay_pool* pool, const uint32_t* d_legal_mask, const int64_t* d_sample_base,
+                             const int32_t* d_sample_pos, int32_t num_samples, int32_t tape_words, uint64_t seed,
+                             uint64_t sweep_counter, int64_t first_index, int32_t* d_to_play, int32_t* d_legal, uint32_t* d_tape,
+                             int32_t* d_input_flags, void* stream);
+int mzx_replay_search_write(const int32_t* d_visit_counts, const double* d_root_value, const int32_t* d_info,
+                            const int32_t* d_input_flags, int32_t num_samples, int32_t action_space_size,
+                            const int64_t* d_sample_base, const int32_t* d_sample_pos, double* d_child_visits,
+                            double* d_root_values, int32_t* d_skipped, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Prioritised sampling and priority feedback for the store above (csrc/mzx_replay.h): the PER priorities live in the pool
  * too, batches are DRAWN on the device and the trainer's new priorities are scattered back there, so get_batch, the loss
  * head and update_priorities are launches on one stream.  Stateless like the entries above: the caller owns every array

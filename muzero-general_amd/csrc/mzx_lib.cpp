@@ -1268,6 +1268,56 @@ int mzx_replay_reanalyse_write(const float* d_value_logits, int32_t num_samples,
   return MZX_OK;
 }
 
+int mzx_replay_search_inputs(const mzx_replay_pool* pool, const uint32_t* d_legal_mask, const int64_t* d_sample_base,
+                             const int32_t* d_sample_pos, int32_t num_samples, int32_t tape_words, uint64_t seed,
+                             uint64_t sweep_counter, int64_t first_index, int32_t* d_to_play, int32_t* d_legal, uint32_t* d_tape,
+                             int32_t* d_input_flags, void* stream) {
+  if (!pool) { set_error("mzx_replay_search_inputs: null pool"); return MZX_ERR_INVALID; }
+  if (num_samples < 0 || tape_words < 1 || pool->action_space_size < 1 || pool->rows < 1) {
+    set_error("mzx_replay_search_inputs: num_samples %d must not be negative, tape_words %d, action_space_size %d and rows %lld positive",
+              num_samples, tape_words, pool->action_space_size, (long long)pool->rows);
+    return MZX_ERR_INVALID;
+  }
+  if (first_index < 0 || first_index + (int64_t)num_samples > ((int64_t)1 << 32)) {
+    set_error("mzx_replay_search_inputs: positions [%lld, %lld) leave the 32-bit index of the tape's counter", (long long)first_index,
+              (long long)(first_index + num_samples));
+    return MZX_ERR_INVALID;
+  }
+  if (!pool->d_to_play || !d_sample_base || !d_sample_pos || !d_to_play || !d_legal || !d_tape || !d_input_flags) {
+    set_error("mzx_replay_search_inputs: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  if (num_samples == 0) return MZX_OK;
+  ReplaySearchInputsBody b;
+  b.pool_to_play = pool->d_to_play; b.legal_mask = d_legal_mask; b.sample_base = d_sample_base; b.sample_pos = d_sample_pos;
+  b.to_play = d_to_play; b.legal = d_legal; b.tape = d_tape; b.flags = d_input_flags; b.seed = seed; b.sweep_counter = sweep_counter;
+  b.first_index = first_index; b.rows = pool->rows; b.n = num_samples; b.A = pool->action_space_size; b.tape_words = tape_words;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(b, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_replay_search_write(const int32_t* d_visit_counts, const double* d_root_value, const int32_t* d_info,
+                            const int32_t* d_input_flags, int32_t num_samples, int32_t action_space_size,
+                            const int64_t* d_sample_base, const int32_t* d_sample_pos, double* d_child_visits,
+                            double* d_root_values, int32_t* d_skipped, void* stream) {
+  if (num_samples < 0 || action_space_size < 1) {
+    set_error("mzx_replay_search_write: num_samples %d must not be negative, action_space_size %d positive", num_samples, action_space_size);
+    return MZX_ERR_INVALID;
+  }
+  if (!d_visit_counts || !d_root_value || !d_info || !d_input_flags || !d_sample_base || !d_sample_pos || !d_child_visits ||
+      !d_root_values || !d_skipped) {
+    set_error("mzx_replay_search_write: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  if (num_samples == 0) return MZX_OK;
+  ReplaySearchWriteBody b;
+  b.visits = d_visit_counts; b.root_value = d_root_value; b.info = d_info; b.flags = d_input_flags; b.sample_base = d_sample_base;
+  b.sample_pos = d_sample_pos; b.child_visits = d_child_visits; b.root_values = d_root_values; b.skipped = d_skipped;
+  b.n = num_samples; b.A = action_space_size;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(b, (stream_t)stream));
+  return MZX_OK;
+}
+
 extern "C++" {
 template <int VEC>
 static int replay_obs_launch(const mzx_replay_pool* pool, const mzx_replay_batch_io* io, stream_t stream) {

@@ -565,4 +565,108 @@ struct ReplayWeightFinishBody {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Reanalyse with fresh searches (DeviceGameStore.reanalyse_search): a chunk of the sweep's sample list (ReplayPositionsOp)
+// becomes the inputs of one mzx_search_run, and the chunk's search outputs become the policy and root-value targets of the
+// pool, in place.  Two wave bodies, launch_waves<SAMPLER_WAVES>, a wavefront per sample.
+//
+// The optional legal-mask column is u32 [rows][ceil(A / 32)], bit a % 32 of word a / 32 set when action a is legal at that
+// row; bits past A are ignored.  The roots see their legal actions in INCREASING action order.
+// Tie-break tape: Philox4x32-10 under the key (seed lo, seed hi ^ "REAS") -- apart from the sampler's stream --, counter
+// (position's index in the sweep, sweep counter lo, hi, block); block b supplies words 4b .. 4b + 3 of the sample's row.
+constexpr uint32_t REANALYSE_SEARCH_KEY = 0x52454153u;
+constexpr int32_t SEARCH_INPUT_EMPTY_MASK = 1;     // d_input_flags: the mask row had no bit set (the identity list is searched)
+constexpr int32_t SEARCH_INPUT_BAD_ROW = 2;        // the sample's row lies outside the pool (nothing of the pool is read)
+
+MZX_HD inline int mask_popcount(uint32_t w) { return __builtin_popcount(w); }
+// word w of a mask row with the bits of actions >= A cleared
+MZX_HD inline uint32_t mask_word(const uint32_t* m, int w, int A) {
+  const int left = A - 32 * w;
+  return left >= 32 ? m[w] : m[w] & ((1u << left) - 1u);
+}
+
+struct ReplaySearchInputsBody {
+  const int32_t* pool_to_play;  // the pool column
+  const uint32_t* legal_mask;   // [rows][mask_words] nullable: every action legal
+  const int64_t* sample_base;   // [n]
+  const int32_t* sample_pos;    // [n]
+  int32_t* to_play;             // [n]
+  int32_t* legal;               // [n][A]
+  uint32_t* tape;               // [n][tape_words]
+  int32_t* flags;               // [n]
+  uint64_t seed, sweep_counter;
+  int64_t first_index, rows;
+  int32_t n, A, tape_words;
+
+  MZX_HD size_t size() const { return (size_t)n; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int64_t row = sample_base[e] + sample_pos[e];
+    const bool inside = row >= 0 && row < rows;
+    const int words = (A + 31) / 32;
+    const uint32_t* __restrict__ m = legal_mask && inside ? legal_mask + row * words : nullptr;
+    int count = 0;                                     // (every lane counts the few words of the row itself)
+    if (m) for (int w = 0; w < words; ++w) count += mask_popcount(mask_word(m, w, A));
+    int32_t* __restrict__ out = legal + e * (size_t)A;
+    if (count == 0) {
+      WAVE_FOR(a, A) out[a] = a;
+    } else {
+      WAVE_FOR(a, A) {
+        const int w = a >> 5;
+        const uint32_t word = mask_word(m, w, A);
+        if ((word >> (a & 31)) & 1u) {                 // its slot: the number of legal actions below it
+          int rank = mask_popcount(word & ((1u << (a & 31)) - 1u));
+          for (int v = 0; v < w; ++v) rank += mask_popcount(m[v]);
+          out[rank] = a;
+        }
+        if (a >= count) out[a] = -1;
+      }
+    }
+    if (lane == 0) {
+      to_play[e] = inside ? pool_to_play[row] : 0;
+      flags[e] = !inside ? SEARCH_INPUT_BAD_ROW : (m && count == 0 ? SEARCH_INPUT_EMPTY_MASK : 0);
+    }
+    const uint64_t index = (uint64_t)first_index + e;
+    uint32_t* __restrict__ t = tape + e * (size_t)tape_words;
+    WAVE_FOR(b, (tape_words + 3) / 4) {
+      uint32_t w[4];
+      philox4x32_10((uint32_t)index, (uint32_t)sweep_counter, (uint32_t)(sweep_counter >> 32), (uint32_t)b, (uint32_t)seed,
+                    (uint32_t)(seed >> 32) ^ REANALYSE_SEARCH_KEY, w);
+      for (int j = 0; j < 4 && 4 * b + j < tape_words; ++j) t[4 * b + j] = w[j];
+    }
+  }
+};
+
+// visits / sum(visits) in binary64 (GameHistory.store_search_statistics, self_play.py:496-511: 0 for an action that is no
+// child) and the root value into the pool rows of the samples.  A sample whose search was flagged (info[1]: tie tape or
+// node overflow), whose input flag is set or that has no visit keeps both of its rows and counts in skipped[0].
+struct ReplaySearchWriteBody {
+  const int32_t* visits;        // [n][A]
+  const double* root_value;     // [n]
+  const int32_t* info;          // [n][4]
+  const int32_t* flags;         // [n]
+  const int64_t* sample_base;   // [n]
+  const int32_t* sample_pos;    // [n]
+  double* child_visits;         // the pool columns
+  double* root_values;
+  int32_t* skipped;             // [1]
+  int32_t n, A;
+
+  MZX_HD size_t size() const { return (size_t)n; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int32_t* __restrict__ v = visits + e * (size_t)A;
+    int32_t sum = 0;
+    WAVE_FOR(a, A) sum += v[a];
+    sum = wave_sum_i32(sum);
+    if (info[4 * e + 1] != 0 || flags[e] != 0 || sum < 1) {       // (the same in every lane)
+      if (lane == 0) wave_atomic_add(skipped, 1);
+      return;
+    }
+    const int64_t row = sample_base[e] + sample_pos[e];
+    double* __restrict__ cv = child_visits + row * A;
+    const double total = (double)sum;
+    WAVE_FOR(a, A) cv[a] = (double)v[a] / total;
+    if (lane == 0) root_values[row] = root_value[e];
+  }
+};
+
 }  // namespace mzx

@@ -24,6 +24,7 @@ inline int wave_first_lane(bool flag) { return flag ? 0 : -1; }
 inline int wave_last_lane(bool flag) { return flag ? 0 : -1; }
 constexpr int block_threads(int) { return 1; }
 inline void block_sync() {}
+inline void wave_atomic_add(int32_t* p, int32_t v) { *p += v; }
 #else
 constexpr int WAVE_LANES = 64;
 #define MZX_WAVE_FN __device__ __forceinline__
@@ -42,6 +43,8 @@ __device__ __forceinline__ int wave_last_lane(bool flag) {
 }
 constexpr int block_threads(int block) { return block; }
 __device__ __forceinline__ void block_sync() { __syncthreads(); }
+// one lane's addition to a counter other wavefronts add to as well (an ordinary vector atomic; the plain sum when serial)
+__device__ __forceinline__ void wave_atomic_add(int32_t* p, int32_t v) { atomicAdd(p, v); }
 #endif
 
 // "every lane its share of n items": lanes j, j + 64, ... on the device, all of them in the serial build
@@ -59,6 +62,11 @@ MZX_WAVE_FN float wave_sum(float v) {
   return v;
 }
 MZX_WAVE_FN double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = WAVE_LANES / 2; o >= 1; o >>= 1) v = v + lane_xor(v, o);
+  return v;
+}
+MZX_WAVE_FN int32_t wave_sum_i32(int32_t v) {
 #pragma unroll
   for (int o = WAVE_LANES / 2; o >= 1; o >>= 1) v = v + lane_xor(v, o);
   return v;

@@ -243,6 +243,9 @@ PROTOTYPES = {
     "mzx_replay_positions": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_reanalyse_write": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_batch": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplayBatchIO), c_vp]),
+    "mzx_replay_search_inputs": (ctypes.c_int, [ctypes.POINTER(ReplayPool), c_vp, c_vp, c_vp, c_i32, c_i32, ctypes.c_uint64,
+                                                ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_replay_search_write": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_sampler_refresh": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_i32, c_vp]),
     "mzx_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), ctypes.POINTER(ReplaySampleIO), c_vp]),
     "mzx_replay_update_priorities": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),

@@ -177,6 +177,11 @@ class ShardGameHistory(GameHistory):
             value = rows[i]
             self.__dict__[name] = value
             return value
+        if name == "legal_actions":       # one list per position from the record's legal mask (absent: every action legal)
+            view = self.__dict__.get("_view")       # (a restored history has no view: it carries the lists or has none)
+            if view is not None and view[0].legal_mask is not None:
+                source, i, n = view
+                return [numpy.nonzero(source.legal_mask[i, t])[0].tolist() for t in range(n)]
         raise AttributeError(name)
 
     def materialize(self):
@@ -184,6 +189,9 @@ class ShardGameHistory(GameHistory):
             value = getattr(self, name)
             if name in ShardGameHistory._PER:
                 self.__dict__[name] = value
+        legal = getattr(self, "legal_actions", None)      # the record's legal mask goes along as this game's lists
+        if legal is not None:
+            self.__dict__["legal_actions"] = legal
         return self
 
     def __getstate__(self):

@@ -19,6 +19,8 @@ device_store=store).get_batch()`` assembles the trainer's tensors on the device 
 numpy's, in the reference's order, and only fill index arrays.  ``trainer_tensors`` is the binding line of a trainer.
 ``DeviceGameStore.reanalyse`` / ``Reanalyse.reanalyse_store`` re-evaluate every resident game in a sweep: a handful of
 launches per chunk of positions, the decoded values written straight into the pool (opt-in: ``config.reanalyse_sweep``).
+``DeviceGameStore.reanalyse_search`` (``config.reanalyse_search``) SEARCHES every resident position again instead and
+refreshes the policy targets together with the root values, in place; ``ReplayBuffer.sync_targets`` writes them back.
 A store built with ``max_games`` also holds the PER priorities and a game table: ``ReplayBuffer(..., device_sampler=True)``
 then DRAWS the batch on the device (``mzx_replay_sample``, a counter-based generator -- not numpy's draws, hence opt-in)
 and scatters the trainer's priorities back there (``mzx_replay_update_priorities``).
@@ -270,9 +272,17 @@ class DeviceGameStore:
     host and flushed with one small upload before the next launch that reads the table; ``update`` leaves priorities
     alone.  ``sample`` / ``update_priorities`` / ``priorities_of`` are the sampler's surface.  Without ``max_games`` none
     of this is allocated.
+
+    ``legal_masks=True`` adds the legal-mask column of ``reanalyse_search``: u32 [rows][ceil(A / 32)], bit ``a`` of a row
+    set when action ``a`` is legal at that position.  ``add_many`` fills it from ``game_history.legal_actions`` (T lists,
+    what ``SelfPlay`` records with ``config.reanalyse_search``); a history WITHOUT the attribute gets all-ones rows, i.e.
+    every action is treated as legal -- the store cannot tell such a history from one of a game whose positions really
+    offer every action, so feed a game with fewer legal actions than ``A`` only histories that carry the attribute.  The
+    sweep's roots see the legal actions in increasing action order.  Without the flag nothing is allocated and every
+    action is legal at every root.
     """
 
-    def __init__(self, config, backend, max_positions, max_games=None):
+    def __init__(self, config, backend, max_positions, max_games=None, legal_masks=False):
         self.config, self.backend = config, backend
         self.shape = tuple(int(v) for v in config.observation_shape)
         if len(self.shape) != 3 or min(self.shape) < 1:
@@ -288,6 +298,10 @@ class DeviceGameStore:
         self.rewards, self.root_values, self.values = (z((self.rows,), torch.float64) for _ in range(3))
         self.child_visits = z((self.rows, self.A), torch.float64)
         self.sample_shape = (self.shape[0] * (self.k + 1) + self.k,) + self.shape[1:]
+        # the optional legal-mask column of reanalyse_search: u32 words held as int32 (the same bits)
+        self.mask_words = -(-self.A // 32)
+        self.legal_mask = z((self.rows, self.mask_words), torch.int32) if legal_masks else None
+        self.search_sweep_counter = 0      # reanalyse_search calls so far: the counter of the sweep's tie-break stream
         pool = self.pool = _lib.ReplayPool()
         pool.d_frames, pool.d_actions, pool.d_rewards = self.frames.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr()
         pool.d_to_play, pool.d_root_values = self.to_play.data_ptr(), self.root_values.data_ptr()
@@ -385,6 +399,24 @@ class DeviceGameStore:
                 numpy.array([int(p) for p in gh.to_play_history], dtype=numpy.int32),
                 numpy.array([float(v) for v in roots] + [0.0], dtype=numpy.float64), visits)
 
+    def _mask_rows(self, gh, T):
+        """The T + 1 rows of the legal-mask column of a game: bit a of a row set when action a is legal at that position
+        (``game_history.legal_actions``, T lists); all-ones -- the full action space -- for a history without the attribute
+        and for the padding row T."""
+        rows = numpy.full((T + 1, self.mask_words), 0xFFFFFFFF, numpy.uint32)
+        legal = getattr(gh, "legal_actions", None)
+        if legal is None:
+            return rows.view(numpy.int32)
+        if len(legal) != T:
+            raise ValueError("legal_actions must hold one list per searched position")
+        rows[:T] = 0
+        for t, actions in enumerate(legal):
+            acts = numpy.asarray(actions, dtype=numpy.int64).reshape(-1)
+            if acts.size and (acts.min() < 0 or acts.max() >= self.A):
+                raise ValueError("legal_actions outside the action space")
+            numpy.bitwise_or.at(rows[t], acts >> 5, (numpy.uint32(1) << (acts & 31).astype(numpy.uint32)))
+        return rows.view(numpy.int32)
+
     def _run_values(self, entries):
         be, lib = self.backend, self.backend.lib
         base = self._up(numpy.array([b for b, _ in entries], dtype=numpy.int64))
@@ -409,6 +441,8 @@ class DeviceGameStore:
                 raise ValueError(f"game {game_id} is already resident")
         columns = [self._columns(gh) for _, gh in items]
         lengths = [len(gh.root_values) for _, gh in items]
+        if self.legal_mask is not None:
+            masks = [self._mask_rows(gh, T) for (_, gh), T in zip(items, lengths)]
         if self.sampler is not None:
             priorities = [self._priority_rows(gh, T) for (_, gh), T in zip(items, lengths)]
             taken = dict(self._slot_owner)
@@ -434,6 +468,8 @@ class DeviceGameStore:
                 column[b0:b1].copy_(self._up(numpy.concatenate([columns[i][c] for i in range(lo, hi)])))
             if self.sampler is not None and self.config.PER:
                 self.priorities[b0:b1].copy_(self._up(numpy.concatenate([priorities[i] for i in range(lo, hi)])))
+            if self.legal_mask is not None:
+                self.legal_mask[b0:b1].copy_(self._up(numpy.concatenate([masks[i] for i in range(lo, hi)])))
             if (b1 - b0) * int(numpy.prod(self.shape)) < (1 << 22):      # small frames: one upload for the run
                 frames = numpy.array([numpy.asarray(o) for i in range(lo, hi) for o in items[i][1].observation_history])
                 self.frames[b0:b1].copy_(observations._frames_to_device(self.backend, frames.reshape((b1 - b0,) + self.shape)))
@@ -674,6 +710,96 @@ class DeviceGameStore:
         host = out.cpu().numpy()
         return {g: host[f:f + T] for g, f, T in zip(ids, first.tolist(), lengths.tolist())}
 
+    def reanalyse_search(self, engine, game_ids=None, chunk_positions=None, seed=None):
+        """
+        MuZero Reanalyse with fresh SEARCHES: every position of the resident games -- all of them in allocation order, or
+        ``game_ids`` -- is searched again under the current weights of ``engine`` (a ``BatchedMCTS`` over a ``HipNetwork``
+        on this store's backend; its ``num_simulations`` and ``max_trees`` are the caller's choice), and the normalised
+        visit counts and root values replace the pool's ``child_visits`` and ``root_values`` rows in place.  The positions
+        form one flat sequence taken in chunks of ``min(chunk_positions or engine.max_trees, engine.max_trees,
+        reanalyse_chunk_limit())``.  Per chunk, on the backend's stream and with nothing built, uploaded or synchronised
+        on the host: ``mzx_replay_positions``, ``mzx_replay_batch`` (observation pointer only),
+        ``mzx_replay_search_inputs``, ``mzx_search_run``, ``mzx_replay_search_write``.  Then ONE ``mzx_replay_values``
+        launch for the games swept and ONE download, of the skipped counter.  Returns ``{"positions", "skipped", "chunks"}``.
+
+        The roots get no exploration noise and draw their tie-breaks from a counter-based stream keyed by ``seed``
+        (default ``config.seed``) and the store's ``search_sweep_counter``, which advances by one per sweep run: the targets of a
+        sweep are a pure function of the pool, the weights and those two numbers.  A position whose search exhausted its
+        tie-break tape or its nodes, or whose legal mask is empty, keeps its old targets and counts as skipped.
+
+        Legal actions: a store built with ``legal_masks=True`` searches every root over the actions its mask row holds, in
+        INCREASING action order (the order the ``legal_actions()`` of the reference's tic-tac-toe, connect4 and gomoku
+        return); without the column every action is legal at every root.  Priorities are not touched.  An unknown game
+        raises KeyError, an engine of another action space or observation size ValueError.
+        """
+        from .search import TAPE_WORDS
+
+        be, lib = self.backend, self.backend.lib
+        if engine.backend is not be:
+            raise ValueError("reanalyse_search: the engine must live on the store's backend")
+        if engine.A != self.A or int(engine.model.input_size) != int(numpy.prod(self.sample_shape)):
+            raise ValueError(f"reanalyse_search: the engine searches {engine.A} actions over {int(engine.model.input_size)} "
+                             f"observation floats, the store holds {self.A} and {int(numpy.prod(self.sample_shape))}")
+        ids = list(dict.fromkeys(self.games if game_ids is None else game_ids))
+        entries = [self.games[g] for g in ids]
+        chunk = engine.max_trees if chunk_positions is None else int(chunk_positions)
+        if chunk < 1:
+            raise ValueError("chunk_positions must be positive")
+        seed = int(self.config.seed if seed is None else seed) & (2 ** 64 - 1)
+        lengths = numpy.array([T for _, T in entries], dtype=numpy.int64)
+        total = int(lengths.sum())
+        if total == 0:
+            return {"positions": 0, "skipped": 0, "chunks": 0}
+        if total >= 2 ** 32:
+            raise ValueError("reanalyse_search: a sweep takes fewer than 2**32 positions")
+        chunk = min(chunk, engine.max_trees, self.reanalyse_chunk_limit(), total)
+        sweep = self.search_sweep_counter          # (a refused or empty call above consumes no counter value)
+        self.search_sweep_counter = sweep + 1
+        first = numpy.concatenate([[0], numpy.cumsum(lengths)[:-1]]).astype(numpy.int64)
+        G = len(ids)
+        d_base = self._up(numpy.array([b for b, _ in entries], dtype=numpy.int64))
+        d_len, d_first = self._up(lengths.astype(numpy.int32)), self._up(first)
+        s_base, s_len, s_pos = be.empty((chunk,), torch.int64), be.empty((chunk,), torch.int32), be.empty((chunk,), torch.int32)
+        obs = be.empty((chunk,) + self.sample_shape, torch.float32)
+        to_play, flags = be.empty((chunk,), torch.int32), be.empty((chunk,), torch.int32)
+        legal, tape = be.empty((chunk, self.A), torch.int32), be.empty((chunk, TAPE_WORDS), torch.int32)
+        visits, info = be.empty((chunk, self.A), torch.int32), be.empty((chunk, 4), torch.int32)
+        root_value, predicted = be.empty((chunk,), torch.float64), be.empty((chunk,), torch.float64)
+        skipped = be.zeros((1,), torch.int32)
+        batch_io = _lib.ReplayBatchIO()
+        batch_io.d_base, batch_io.d_len, batch_io.d_pos = s_base.data_ptr(), s_len.data_ptr(), s_pos.data_ptr()
+        batch_io.d_observation, batch_io.stacked_observations = obs.data_ptr(), self.k
+        search_io = _lib.SearchIO(be.ptr(obs), be.ptr(legal), be.ptr(to_play), None, be.ptr(tape), be.ptr(visits),
+                                  be.ptr(root_value), be.ptr(predicted), be.ptr(info))
+        chunks = 0
+        for lo in range(0, total, chunk):
+            n = min(chunk, total - lo)
+            lib.check(lib.mzx_replay_positions(be.ptr(d_base), be.ptr(d_len), be.ptr(d_first), G, total, lo, n, be.ptr(s_base),
+                                               be.ptr(s_len), be.ptr(s_pos), be.stream()))
+            batch_io.num_samples = n
+            lib.check(lib.mzx_replay_batch(ctypes.byref(self.pool), ctypes.byref(batch_io), be.stream()))
+            lib.check(lib.mzx_replay_search_inputs(ctypes.byref(self.pool), be.ptr(self.legal_mask), be.ptr(s_base), be.ptr(s_pos),
+                                                   n, TAPE_WORDS, seed, sweep, lo, be.ptr(to_play), be.ptr(legal), be.ptr(tape),
+                                                   be.ptr(flags), be.stream()))
+            arena = engine.arena(n)
+            lib.check(lib.mzx_search_run(engine.handle(n, TAPE_WORDS), ctypes.byref(search_io), be.ptr(arena), arena.numel(),
+                                         be.stream()))
+            lib.check(lib.mzx_replay_search_write(be.ptr(visits), be.ptr(root_value), be.ptr(info), be.ptr(flags), n, self.A,
+                                                  be.ptr(s_base), be.ptr(s_pos), be.ptr(self.child_visits),
+                                                  be.ptr(self.root_values), be.ptr(skipped), be.stream()))
+            chunks += 1
+        engine.arena_used_externally()
+        self._run_values([e for e in entries if e[1] > 0])
+        return {"positions": total, "skipped": int(skipped.cpu().numpy()[0]), "chunks": chunks}
+
+    def download_targets(self, game_ids=None):
+        """{game_id: (child_visits [T, A] f64, root_values [T] f64)} of the resident games (or ``game_ids``) as the pool
+        holds them: one download per column."""
+        ids = list(dict.fromkeys(self.games if game_ids is None else game_ids))
+        entries = [self.games[g] for g in ids]
+        visits, roots = self.child_visits.cpu().numpy(), self.root_values.cpu().numpy()
+        return {g: (visits[b:b + T].copy(), roots[b:b + T].copy()) for g, (b, T) in zip(ids, entries)}
+
 
 def trainer_tensors(batch, device):
     """
@@ -860,6 +986,26 @@ class ReplayBuffer:
                 if T:
                     game_history.priorities = priorities[base:base + T].copy()
                     game_history.game_priority = top[game_id % store.max_games]
+
+    def sync_targets(self):
+        """The device targets written back into the resident ``GameHistory`` objects after ``reanalyse_search`` (for
+        checkpoints and a host-side ``get_batch``): ``child_visits`` as a list of lists, ``root_values`` as a list of floats,
+        ``reanalysed_predicted_root_values = None`` -- the pool's root values ARE the searched ones.  One download per
+        column; a no-op without a device store.  A game whose host history has another length than the store's copy raises
+        ValueError before anything is written: a checkpoint must not mix synchronised and stale games."""
+        store = self._store
+        if store is None:
+            return
+        targets = store.download_targets([g for g in self._stock.buffer if g in store])
+        odd = [g for g, (_, roots) in targets.items() if len(self._stock.buffer[g].root_values) != len(roots)]
+        if odd:
+            raise ValueError(f"sync_targets: games {odd[:8]} changed length since they entered the device store")
+        for game_id, (visits, roots) in targets.items():
+            game_history = self._stock.buffer[game_id]
+            game_history.child_visits = visits.tolist()
+            game_history.root_values = roots.tolist()
+            game_history.reanalysed_predicted_root_values = None
+            self._arrays.pop(game_id, None)
 
     def sample_game(self, force_uniform=False):
         return self._stock.sample_game(force_uniform)
@@ -1048,6 +1194,7 @@ class Reanalyse:
         self.model.set_weights(initial_checkpoint["weights"])
         self.model.eval()
         self.num_reanalysed_games = initial_checkpoint["num_reanalysed_games"]
+        self._search_engine = None      # reanalyse_store(search=True): built on first use
 
     def reanalyse_game(self, game_history, game_id=None):
         """
@@ -1069,7 +1216,7 @@ class Reanalyse:
         values = models.support_to_scalar(value_logits, self.config.support_size, _backend=backend)
         return torch.squeeze(values).detach().cpu().numpy()
 
-    def reanalyse_store(self, replay_buffer, game_ids=None):
+    def reanalyse_store(self, replay_buffer, game_ids=None, search=None):
         """
         The sweep as a worker step (``DeviceGameStore.reanalyse`` under the current weights): every game of the buffer's
         device store that the stock buffer still holds -- or those of ``game_ids`` -- gets its float32 array [T] as
@@ -1077,12 +1224,30 @@ class Reanalyse:
         it counts in ``num_reanalysed_games``; the pool's root values and n-step values are already refreshed in place.  A
         game the stock buffer has evicted is passed over.  Needs an in-process ``ReplayBuffer`` with a device store (device
         pointers do not cross processes).  Returns the number of games refreshed.
+
+        ``search`` (default ``config.reanalyse_search``, False when the config has no such field): the games are SEARCHED
+        again instead (``DeviceGameStore.reanalyse_search``) -- policy targets and root values refreshed in the pool; the
+        host histories go stale until ``replay_buffer.sync_targets()``.  The worker builds its ``BatchedMCTS`` once:
+        ``config.reanalyse_search_trees`` roots per chunk (default 1024), ``config.reanalyse_search_simulations``
+        simulations (default ``config.num_simulations``).
         """
         store = replay_buffer.device_store if isinstance(replay_buffer, ReplayBuffer) else None
         if store is None:
             raise ValueError("reanalyse_store needs an in-process mzx.replay.ReplayBuffer with a device_store")
         buffer = replay_buffer.buffer
         ids = [g for g in (store.games if game_ids is None else game_ids) if g in buffer or g not in store]
+        if getattr(self.config, "reanalyse_search", False) if search is None else search:
+            if self._search_engine is None:
+                from .search import BatchedMCTS
+                self._search_engine = BatchedMCTS(
+                    self.config, self.model, int(getattr(self.config, "reanalyse_search_trees", 1024)),
+                    num_simulations=int(getattr(self.config, "reanalyse_search_simulations", self.config.num_simulations)))
+            ids = list(dict.fromkeys(ids))
+            store.reanalyse_search(self._search_engine, ids)
+            for game_id in ids:
+                replay_buffer._arrays.pop(game_id, None)      # the cached host targets are stale
+            self.num_reanalysed_games += len(ids)
+            return len(ids)
         done = 0
         for game_id, values in store.reanalyse(self.model, ids).items():
             game_history = buffer.get(game_id)

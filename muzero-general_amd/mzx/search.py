@@ -284,6 +284,11 @@ class BatchedMCTS:
         """The trees of the last search of handle(B) are in the arena, complete: a continue_search may start from them."""
         self._carry = dict(B=B, root_actions=[list(a) for a in root_actions], visits=numpy.array(visits, copy=True))
 
+    def arena_used_externally(self):
+        """A caller ran ``mzx_search_run`` on ``handle`` / ``arena`` itself (``DeviceGameStore.reanalyse_search``): the trees
+        of this engine's last ``run`` are gone, so a ``continue_search`` must not start from them."""
+        self._carry = None
+
     def _require_capacity(self):
         if not self.max_carried_nodes:
             raise ValueError("continued searches need BatchedMCTS(..., max_carried_nodes=...) > 0")

@@ -426,6 +426,7 @@ class SelfPlay:
         if batch is None or batch.shape != (G,) + shape:
             batch = self._obs_batch = numpy.empty((G,) + shape, numpy.float32)
         histories = []
+        record_legal = bool(getattr(cfg, "reanalyse_search", False))      # GameHistory.legal_actions, as in _play
         for s, game in enumerate(games):
             gh = GameHistory()
             observation = game.reset()
@@ -433,6 +434,8 @@ class SelfPlay:
             gh.observation_history.append(observation)
             gh.reward_history.append(0)
             gh.to_play_history.append(game.to_play())
+            if record_legal:
+                gh.legal_actions = []
             self._check_observation(observation)
             batch[s] = observation
             histories.append(gh)
@@ -469,6 +472,8 @@ class SelfPlay:
             still = []
             for j, s in enumerate(active):
                 game, gh, action = games[s], histories[s], actions[j]
+                if record_legal:
+                    gh.legal_actions.append([int(a) for a in legal[j]])
                 observation, reward, done = game.step(action)
                 if plain:
                     gh.child_visits.append(rows[j])
@@ -498,6 +503,9 @@ class SelfPlay:
         A = len(cfg.action_space)
         histories = {}
         observations = {}
+        # config.reanalyse_search: the legal actions of every position go into the history (GameHistory.legal_actions, one
+        # list per position) -- what DeviceGameStore(legal_masks=True) turns into the mask rows of its search sweep
+        record_legal = bool(getattr(cfg, "reanalyse_search", False))
         for s in slots:
             gh = GameHistory()
             observation = self.games[s].reset()
@@ -505,6 +513,8 @@ class SelfPlay:
             gh.observation_history.append(observation)
             gh.reward_history.append(0)
             gh.to_play_history.append(self.games[s].to_play())
+            if record_legal:
+                gh.legal_actions = []
             histories[s] = gh
             observations[s] = observation
             if render:
@@ -537,9 +547,10 @@ class SelfPlay:
             result = None
             if searching:
                 t0 = time.perf_counter()
+                legal_lists = [self.games[s].legal_actions() for s in searching]
                 result = self.engine.run(
                     stacked if store is None else store.stacked(searching),
-                    [self.games[s].legal_actions() for s in searching],
+                    legal_lists,
                     [self.games[s].to_play() for s in searching], True,
                     (self.bank, searching) if self.bank is not None else [self.rngs[s] for s in searching],
                 )
@@ -577,6 +588,8 @@ class SelfPlay:
                         print(f"Root value for player {game.to_play()}: {root.value():.2f}")
                 else:
                     action, root = self.select_opponent_action(opponent, stacked_by_slot[s], game)
+                if record_legal:
+                    gh.legal_actions.append([int(a) for a in (legal_lists[position[s]] if s in position else game.legal_actions())])
                 observation, reward, done = game.step(action)
                 if render:
                     print(f"Played action: {game.action_to_string(action)}")
