@@ -685,6 +685,59 @@ int mzx_replay_update_priorities(const mzx_replay_sampler* sampler, const float*
                                  const int32_t* d_pos, int32_t n, int32_t steps, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Bulk ingest of finished games into the store above (DeviceGameStore.add_records; csrc/mzx_replay.h): num_games games
+ * staged on the device as a shard hands them out -- game-major, ragged, the layout of mzx_actor_take -- become pool rows,
+ * sampler priorities and table slots in ONE call, whatever their number and lengths.  Stateless; every pointer is a device
+ * pointer.  The pool's columns, the sampler's slot columns (d_slot_game / d_slot_base / d_slot_len) and the mask column
+ * are WRITTEN: the structs hold most of them const for their readers, the entry casts that away.
+ * Game g has T = d_len[g] searched positions and goes to pool rows d_base[g] .. d_base[g] + T.  Its staged rows start at
+ * d_src1[g] in the arrays of T + 1 entries per game and at d_src0[g] in those of T entries: the exclusive prefixes of
+ * len + 1 and of len, computed by the CALLER (O(games) host work, as d_first of mzx_replay_positions); total_rows =
+ * sum(len + 1).  Staged arrays:
+ *   d_observations [total_rows][channels * height * width] f32, d_actions [total_rows] i64, d_rewards [total_rows] f64,
+ *   d_to_play [total_rows] i64; d_visits [sum T][A] i32 (visit counts), d_root_values [sum T] f64 (raw search values),
+ *   d_legal_mask [sum T][A] u8 (NULL: every action legal), d_priorities [sum T] f32 (NULL: computed here).
+ * Pool row base + i, i <= T: the frame copied; actions / to_play narrowed to i32; the reward copied.  For i < T, with
+ *   total = the sum of the row's visit counts: root_values = total > 0 ? value : 0.0 and child_visits[a] = legal(a) &&
+ *   total > 0 ? (double)visits[a] / (double)total : 0.0 (one binary64 division: Python's int / int).  The padding row i ==
+ *   T holds 0.0 and zeros.  d_pool_legal_mask (u32 [mask_rows][ceil(A / 32)], nullable; mask_rows must equal pool->rows):
+ *   bit a set iff action a is legal; all-ones words on the padding row and, without d_legal_mask, on every row.
+ * sampler (nullable): d_priorities[base + T] = 0; rows i < T get 0 with per == 0, the staged priority with per and
+ *   d_priorities, else (float)(|root - value| ** per_alpha) -- the function of mzx_replay_priorities, bit for bit.  Slot
+ *   d_game_id[g] % slots takes (game_id, base, T) and its d_slot_priority / d_slot_sum are refreshed.
+ * pool->d_values of every ingested game as mzx_replay_values writes it (td_steps, d_discount_pow as there).
+ * Launches, on the caller's stream, independent of num_games: the rows (a wavefront per pool row), the n-step values,
+ *   and with a sampler the slots.  num_games == 0 succeeds and launches nothing.  MZX_ERR_INVALID, before anything is
+ *   launched: a NULL required pointer, num_games < 0 or total_rows < num_games, action_space_size or the frame shape of
+ *   the io other than the pool's, sampler->rows or mask_rows other than pool->rows.
+ * What the device arrays HOLD is the caller's contract, as in the rest of this section: 0 <= base, base + T < rows, no two
+ *   games on one row or in one slot (the Python store checks residency, slots and room before it stages anything).  A
+ *   game whose rows would leave the pool is passed over.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_replay_ingest_io {
+  const int32_t* d_len;            /* [num_games] T */
+  const int64_t* d_base;           /* [num_games] destination pool row */
+  const int64_t* d_game_id;        /* [num_games] */
+  const int64_t* d_src1;           /* [num_games] exclusive prefix of len + 1 */
+  const int64_t* d_src0;           /* [num_games] exclusive prefix of len */
+  const float* d_observations;
+  const int64_t* d_actions;
+  const double* d_rewards;
+  const int64_t* d_to_play;
+  const int32_t* d_visits;
+  const double* d_root_values;
+  const uint8_t* d_legal_mask;     /* nullable */
+  const float* d_priorities;       /* nullable */
+  const double* d_discount_pow;    /* [td_steps + 1] */
+  double per_alpha;
+  int64_t total_rows;              /* sum(len + 1) */
+  int32_t num_games, td_steps, per, action_space_size;
+  int32_t channels, height, width, reserved;
+} mzx_replay_ingest_io;
+int mzx_replay_ingest(const mzx_replay_pool* pool, const mzx_replay_sampler* sampler, uint32_t* d_pool_legal_mask,
+                      int64_t mask_rows, const mzx_replay_ingest_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The loss head of the trainer (mzx.trainer; csrc/mzx_trainer.h): what Trainer.update_weights computes between the
  * network's logits and loss.backward() (trainer.py:161-258).  Stateless; every pointer is a device pointer, fp32.
  * mzx_scalar_to_support = models.scalar_to_support (models.py:669-689) of `rows` scalars -> d_out [rows][2 * support_size

@@ -1452,6 +1452,81 @@ int mzx_replay_update_priorities(const mzx_replay_sampler* sampler, const float*
   return MZX_OK;
 }
 
+int mzx_replay_ingest(const mzx_replay_pool* pool, const mzx_replay_sampler* sampler, uint32_t* d_pool_legal_mask,
+                      int64_t mask_rows, const mzx_replay_ingest_io* io, void* stream) {
+  if (!pool || !io) { set_error("mzx_replay_ingest: null argument"); return MZX_ERR_INVALID; }
+  if (io->num_games < 0 || io->td_steps < 0 || io->total_rows < io->num_games) {
+    set_error("mzx_replay_ingest: num_games %d and td_steps %d must not be negative, total_rows %lld at least num_games",
+              io->num_games, io->td_steps, (long long)io->total_rows);
+    return MZX_ERR_INVALID;
+  }
+  if (pool->rows < 1 || pool->action_space_size < 1 || pool->channels < 1 || pool->height < 1 || pool->width < 1) {
+    set_error("mzx_replay_ingest: the pool's rows, action space and observation shape must be positive");
+    return MZX_ERR_INVALID;
+  }
+  if (io->action_space_size != pool->action_space_size || io->channels != pool->channels || io->height != pool->height ||
+      io->width != pool->width) {
+    set_error("mzx_replay_ingest: staged games of %d actions and %d x %d x %d frames, the pool holds %d and %d x %d x %d",
+              io->action_space_size, io->channels, io->height, io->width, pool->action_space_size, pool->channels, pool->height,
+              pool->width);
+    return MZX_ERR_INVALID;
+  }
+  const int64_t frame_floats = (int64_t)pool->channels * pool->height * pool->width;
+  if (frame_floats >= ((int64_t)1 << 31)) { set_error("mzx_replay_ingest: frame too large"); return MZX_ERR_INVALID; }
+  if (d_pool_legal_mask && mask_rows != pool->rows) {
+    set_error("mzx_replay_ingest: the mask column has %lld rows, the pool %lld", (long long)mask_rows, (long long)pool->rows);
+    return MZX_ERR_INVALID;
+  }
+  ReplayIngestSlotBody slots;
+  if (sampler) {
+    const int rc = replay_sampler_table("mzx_replay_ingest", sampler, &slots.t);
+    if (rc) return rc;
+    if (sampler->rows != pool->rows) {
+      set_error("mzx_replay_ingest: the sampler has %lld rows, the pool %lld", (long long)sampler->rows, (long long)pool->rows);
+      return MZX_ERR_INVALID;
+    }
+  }
+  if (io->num_games == 0) return MZX_OK;
+  if (!pool->d_frames || !pool->d_actions || !pool->d_rewards || !pool->d_to_play || !pool->d_root_values ||
+      !pool->d_child_visits || !pool->d_values) {
+    set_error("mzx_replay_ingest: missing pool column");
+    return MZX_ERR_INVALID;
+  }
+  if (!io->d_len || !io->d_base || !io->d_game_id || !io->d_src1 || !io->d_src0 || !io->d_observations || !io->d_actions ||
+      !io->d_rewards || !io->d_to_play || !io->d_visits || !io->d_root_values || !io->d_discount_pow) {
+    set_error("mzx_replay_ingest: missing staged array");
+    return MZX_ERR_INVALID;
+  }
+  const bool per = sampler && io->per;
+  ReplayIngestParams p;
+  p.len = io->d_len; p.base = io->d_base; p.game_id = io->d_game_id; p.src1 = io->d_src1; p.src0 = io->d_src0;
+  p.observations = io->d_observations; p.actions = io->d_actions; p.rewards = io->d_rewards; p.to_play = io->d_to_play;
+  p.visits = io->d_visits; p.root_values = io->d_root_values; p.legal = io->d_legal_mask;
+  p.staged_priorities = per ? io->d_priorities : nullptr;
+  // the pool's columns, writable here (the struct holds them const for the entries that read them)
+  p.pool_frames = const_cast<float*>(pool->d_frames); p.pool_actions = const_cast<int32_t*>(pool->d_actions);
+  p.pool_rewards = const_cast<double*>(pool->d_rewards); p.pool_to_play = const_cast<int32_t*>(pool->d_to_play);
+  p.pool_root_values = const_cast<double*>(pool->d_root_values); p.pool_child_visits = const_cast<double*>(pool->d_child_visits);
+  p.pool_mask = d_pool_legal_mask; p.pool_priorities = sampler ? sampler->d_priorities : nullptr;
+  p.rows = pool->rows; p.total_rows = io->total_rows; p.G = io->num_games; p.A = pool->action_space_size;
+  p.frame_floats = (int32_t)frame_floats; p.per = per ? 1 : 0;
+  p.vec = frame_floats % 4 == 0 && ((uintptr_t)io->d_observations % 16) == 0 && ((uintptr_t)pool->d_frames % 16) == 0;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayIngestRowBody{p}, (stream_t)stream));
+  ReplayValuesOp op;
+  op.root_values = pool->d_root_values; op.rewards = pool->d_rewards; op.to_play = pool->d_to_play;
+  op.discount_pow = io->d_discount_pow; op.values = pool->d_values; op.base = io->d_base; op.len = io->d_len;
+  op.num_games = io->num_games; op.td_steps = io->td_steps; op.rows = pool->rows;
+  if (per && !io->d_priorities) { op.priorities = sampler->d_priorities; op.per_alpha = io->per_alpha; }
+  MZX_TRY_LAUNCH(launch<64>(op, (stream_t)stream));
+  if (sampler) {
+    slots.slot_game = const_cast<int64_t*>(sampler->d_slot_game); slots.slot_base = const_cast<int64_t*>(sampler->d_slot_base);
+    slots.slot_len = const_cast<int32_t*>(sampler->d_slot_len);
+    slots.game_id = io->d_game_id; slots.base = io->d_base; slots.len = io->d_len; slots.n = io->num_games;
+    MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(slots, (stream_t)stream));
+  }
+  return MZX_OK;
+}
+
 // ------------------------------------------------------------- the trainer's loss head (csrc/mzx_trainer.h)
 
 int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream) {

@@ -45,6 +45,14 @@ MZX_HD inline double n_step_value(const double* rv, const double* rw, const int3
   return value;
 }
 
+// |root - target| ** PER_alpha in binary64 (replay_buffer.py:44): sqrt for 0.5 (every shipped configuration), the identity
+// for 1, pow otherwise.  The one statement of it: mzx_replay_priorities and the bulk ingest both go through here.
+MZX_HD inline double priority_of_gap(double gap, double per_alpha) {
+  if (per_alpha == 0.5) return sqrt(gap);
+  if (per_alpha == 1.0) return gap;
+  return pow(gap, per_alpha);
+}
+
 struct ReplayPriorityOp {
   const double* root_values;    // [G][T]     root.value() of every searched position (0 for an unvisited root)
   const double* rewards;        // [G][T + 1] reward_history (leading 0)
@@ -63,12 +71,7 @@ struct ReplayPriorityOp {
     const double value = n_step_value(rv, rewards + (size_t)g * (T + 1), to_play + (size_t)g * (T + 1), discount_pow, T,
                                       index, td_steps);
     if (targets) targets[e] = value;
-    const double gap = fabs(rv[index] - value);
-    double p;
-    if (per_alpha == 0.5) p = sqrt(gap);
-    else if (per_alpha == 1.0) p = gap;
-    else p = pow(gap, per_alpha);
-    priorities[e] = (float)p;
+    priorities[e] = (float)priority_of_gap(fabs(rv[index] - value), per_alpha);
   }
 };
 
@@ -94,7 +97,9 @@ struct ReplayGameMaxOp {       // game_priority = numpy.max(priorities)
 
 // n-step values of ragged games: compute_target_value for every position of the games (base[g], len[g]) into `values`.
 // One wavefront-sized group of 64 elements per game (lane l takes positions l, l + 64, ...), so one launch covers every
-// game of an ingest whatever their lengths.
+// game of an ingest whatever their lengths.  The bulk ingest (mzx_replay_ingest) runs the same operator with `priorities`
+// set: the initial PER priority of every position, (float)priority_of_gap(|root - value|), goes to the sampler's column next
+// to the value; and with `rows` set a game whose rows would leave the pool is passed over.
 struct ReplayValuesOp {
   const double* root_values;
   const double* rewards;
@@ -103,6 +108,9 @@ struct ReplayValuesOp {
   double* values;
   const int64_t* base;          // [num_games]
   const int32_t* len;           // [num_games] T
+  float* priorities = nullptr;  // the sampler's column, or null
+  double per_alpha = 0.0;
+  int64_t rows = 0;             // > 0: the pool's row count, checked per game
   int32_t num_games, td_steps;
 
   MZX_HD size_t size() const { return (size_t)num_games * 64; }
@@ -110,8 +118,12 @@ struct ReplayValuesOp {
     const size_t g = e >> 6;
     const int64_t b = base[g];
     const int T = len[g];
-    for (int index = (int)(e & 63); index < T; index += 64)
-      values[b + index] = n_step_value(root_values + b, rewards + b, to_play + b, discount_pow, T, index, td_steps);
+    if (rows > 0 && (b < 0 || T < 0 || b + T >= rows)) return;
+    for (int index = (int)(e & 63); index < T; index += 64) {
+      const double value = n_step_value(root_values + b, rewards + b, to_play + b, discount_pow, T, index, td_steps);
+      values[b + index] = value;
+      if (priorities) priorities[b + index] = (float)priority_of_gap(fabs(root_values[b + index] - value), per_alpha);
+    }
   }
 };
 
@@ -389,6 +401,28 @@ struct ReplayClaimOp {
 constexpr int SAMPLER_WAVES = 4;                                  // wavefronts (games, tiles, samples) per workgroup
 constexpr int SAMPLER_PER_LANE = SAMPLER_TILE / WAVE_LANES;       // weights of a tile a lane holds: indices 4l .. 4l + 3 on the device
 
+// maximum and weight sum of the T priorities from row `base` on into slot s (T == 0: 0 / 0): a wavefront's work
+MZX_WAVE_FN void refresh_slot(const ReplaySamplerTable& t, int s, int64_t base, int T, int lane) {
+  const float* __restrict__ pr = t.priorities + (T ? base : 0);
+  float m = -(float)MZX_INF;
+  double sum = 0.0;
+  WAVE_FOR(i, T) {
+    const float v = pr[i];
+    if (v > m) m = v;
+    sum = sum + sampler_weight(v);
+  }
+#pragma unroll
+  for (int o = WAVE_LANES / 2; o >= 1; o >>= 1) {
+    const float other = lane_xor(m, o);
+    if (other > m) m = other;
+  }
+  sum = wave_sum_f64(sum);
+  if (lane == 0) {
+    t.slot_priority[s] = T ? m : 0.0f;
+    t.slot_sum[s] = sum;
+  }
+}
+
 // maximum and weight sum of a refreshed game: launch_waves<SAMPLER_WAVES>, a wavefront per game
 struct ReplayRefreshBody {
   ReplayRefreshParams p;
@@ -396,25 +430,7 @@ struct ReplayRefreshBody {
   MZX_WAVE_FN void operator()(size_t e, int lane) const {
     const int s = p.slot(e);
     if (s < 0) return;
-    const int T = p.t.resident(s) ? p.t.slot_len[s] : 0;
-    const float* __restrict__ pr = p.t.priorities + (T ? p.t.slot_base[s] : 0);
-    float m = -(float)MZX_INF;
-    double sum = 0.0;
-    WAVE_FOR(i, T) {
-      const float v = pr[i];
-      if (v > m) m = v;
-      sum = sum + sampler_weight(v);
-    }
-#pragma unroll
-    for (int o = WAVE_LANES / 2; o >= 1; o >>= 1) {
-      const float other = lane_xor(m, o);
-      if (other > m) m = other;
-    }
-    sum = wave_sum_f64(sum);
-    if (lane == 0) {
-      p.t.slot_priority[s] = T ? m : 0.0f;
-      p.t.slot_sum[s] = sum;
-    }
+    refresh_slot(p.t, s, p.t.slot_base[s], p.t.resident(s) ? p.t.slot_len[s] : 0, lane);
   }
 };
 
@@ -666,6 +682,140 @@ struct ReplaySearchWriteBody {
     const double total = (double)sum;
     WAVE_FOR(a, A) cv[a] = (double)v[a] / total;
     if (lane == 0) root_values[row] = root_value[e];
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Bulk ingest (mzx_replay_ingest, include/mzx.h): the finished games of a hand-off, staged game-major and ragged as the
+// shard's records hold them, become pool rows.  Three launches whatever the number of games: ReplayIngestRowBody (a
+// wavefront per pool row), ReplayValuesOp with the priority column, ReplayIngestSlotBody (a wavefront per game).
+// Staged row r of the arrays with T + 1 entries per game belongs to the LAST game g with src1[g] <= r (src1 is strictly
+// increasing: every game has its padding row), index i = r - src1[g]; its row of the arrays with T entries is src0[g] + i.
+
+// a 16-byte group of a frame, and a load of staged data that is read once (non-temporal on the device)
+#ifdef MZX_HOSTCHECK
+struct f32x4 { float v[4]; };
+template <class T> inline T load_once(const T* p) { return *p; }
+#else
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <class T> __device__ __forceinline__ T load_once(const T* p) { return __builtin_nontemporal_load(p); }
+#endif
+
+struct ReplayIngestParams {
+  const int32_t* len;           // [G]
+  const int64_t* base;          // [G]
+  const int64_t* game_id;       // [G]
+  const int64_t* src1;          // [G]
+  const int64_t* src0;          // [G]
+  const float* observations;    // staged, see include/mzx.h
+  const int64_t* actions;
+  const double* rewards;
+  const int64_t* to_play;
+  const int32_t* visits;
+  const double* root_values;
+  const uint8_t* legal;         // nullable
+  const float* staged_priorities;   // nullable
+  float* pool_frames;           // the pool's columns
+  int32_t* pool_actions;
+  double* pool_rewards;
+  int32_t* pool_to_play;
+  double* pool_root_values;
+  double* pool_child_visits;
+  uint32_t* pool_mask;          // nullable
+  float* pool_priorities;       // nullable: no sampler
+  int64_t rows, total_rows;
+  int32_t G, A, frame_floats, vec, per;
+};
+
+struct ReplayIngestRowBody {
+  ReplayIngestParams p;
+  MZX_HD size_t size() const { return (size_t)p.total_rows; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int64_t r = (int64_t)e;
+    int lo = 0, hi = p.G - 1;            // src1[lo] <= r always (src1[0] == 0); the same search in every lane
+    while (lo < hi) {
+      const int mid = lo + (hi - lo + 1) / 2;
+      if (p.src1[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    const int g = lo;
+    const int T = p.len[g];
+    const int64_t i = r - p.src1[g], b = p.base[g];
+    if (i < 0 || i > T || b < 0 || b + T >= p.rows) return;      // (an entry that leaves the pool is never followed)
+    const int64_t row = b + i;
+    const bool inside = i < T;
+    const int A = p.A;
+
+    // the frame: 16 bytes per lane and step where the row size and both addresses allow it, a dword otherwise
+    if (p.vec) {
+      const f32x4* __restrict__ src = (const f32x4*)(p.observations + r * p.frame_floats);
+      f32x4* __restrict__ dst = (f32x4*)(p.pool_frames + row * p.frame_floats);
+      WAVE_FOR(j, p.frame_floats / 4) dst[j] = load_once(src + j);
+    } else {
+      const float* __restrict__ src = p.observations + r * p.frame_floats;
+      float* __restrict__ dst = p.pool_frames + row * p.frame_floats;
+      WAVE_FOR(j, p.frame_floats) dst[j] = load_once(src + j);
+    }
+
+    // child visits: visits / their sum, 0 for an illegal action, an unvisited root and the padding row
+    const int64_t r0 = p.src0[g] + i;
+    const int32_t* __restrict__ v = p.visits + r0 * A;
+    const uint8_t* __restrict__ ok = p.legal && inside ? p.legal + r0 * A : nullptr;
+    int32_t sum = 0;
+    if (inside) WAVE_FOR(a, A) sum += load_once(v + a);
+    sum = wave_sum_i32(sum);
+    const double total = (double)sum;
+    double* __restrict__ cv = p.pool_child_visits + row * A;
+    WAVE_FOR(a, A) cv[a] = inside && sum > 0 && (!ok || ok[a]) ? (double)v[a] / total : 0.0;
+
+    // the legal-mask column: a lane per word
+    if (p.pool_mask) {
+      const int words = (A + 31) / 32;
+      uint32_t* __restrict__ m = p.pool_mask + row * words;
+      WAVE_FOR(w, words) {
+        uint32_t word = 0xFFFFFFFFu;
+        if (ok) {
+          word = 0;
+          for (int a = 32 * w; a < A && a < 32 * w + 32; ++a) word |= ok[a] ? 1u << (a & 31) : 0u;
+        }
+        m[w] = word;
+      }
+    }
+
+    if (lane == 0) {
+      p.pool_actions[row] = (int32_t)load_once(p.actions + r);
+      p.pool_rewards[row] = load_once(p.rewards + r);
+      p.pool_to_play[row] = (int32_t)load_once(p.to_play + r);
+      p.pool_root_values[row] = inside && sum > 0 ? load_once(p.root_values + r0) : 0.0;
+      if (p.pool_priorities) {
+        if (!inside || !p.per) p.pool_priorities[row] = 0.0f;
+        else if (p.staged_priorities) p.pool_priorities[row] = load_once(p.staged_priorities + r0);
+      }                                   // (per without staged priorities: the values launch writes them)
+    }
+  }
+};
+
+// the table slots of the ingested games and their maximum / sum: launch_waves<SAMPLER_WAVES>, a wavefront per game
+struct ReplayIngestSlotBody {
+  ReplaySamplerTable t;
+  int64_t* slot_game;           // the table's columns, writable
+  int64_t* slot_base;
+  int32_t* slot_len;
+  const int64_t* game_id;       // [n]
+  const int64_t* base;
+  const int32_t* len;
+  int32_t n;
+  MZX_HD size_t size() const { return (size_t)n; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int64_t id = game_id[e], b = base[e];
+    const int T = len[e];
+    if (id < 0 || b < 0 || T < 0 || b + T >= t.rows) return;      // (as the other two launches: such a game is passed over)
+    const int s = (int)(id % t.slots);
+    if (lane == 0) {
+      slot_game[s] = id;
+      slot_base[s] = b;
+      slot_len[s] = T;
+    }
+    refresh_slot(t, s, b, T, lane);
   }
 };
 

@@ -145,6 +145,17 @@ class ReplaySampleIO(ctypes.Structure):
     ]
 
 
+class ReplayIngestIO(ctypes.Structure):
+    """``mzx_replay_ingest_io``: the staged games of one mzx_replay_ingest call (DeviceGameStore.add_records)."""
+    _fields_ = [
+        ("d_len", c_vp), ("d_base", c_vp), ("d_game_id", c_vp), ("d_src1", c_vp), ("d_src0", c_vp), ("d_observations", c_vp),
+        ("d_actions", c_vp), ("d_rewards", c_vp), ("d_to_play", c_vp), ("d_visits", c_vp), ("d_root_values", c_vp),
+        ("d_legal_mask", c_vp), ("d_priorities", c_vp), ("d_discount_pow", c_vp), ("per_alpha", c_f64), ("total_rows", c_i64),
+        ("num_games", c_i32), ("td_steps", c_i32), ("per", c_i32), ("action_space_size", c_i32), ("channels", c_i32),
+        ("height", c_i32), ("width", c_i32), ("reserved", c_i32),
+    ]
+
+
 class TrainerLossIO(ctypes.Structure):
     """``mzx_trainer_loss_io``: the inputs and outputs of one mzx_trainer_loss call (mzx.trainer)."""
     _fields_ = [
@@ -249,6 +260,8 @@ PROTOTYPES = {
     "mzx_replay_sampler_refresh": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_i32, c_vp]),
     "mzx_replay_sample": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), ctypes.POINTER(ReplaySampleIO), c_vp]),
     "mzx_replay_update_priorities": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "mzx_replay_ingest": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplaySampler), c_vp, c_i64,
+                                         ctypes.POINTER(ReplayIngestIO), c_vp]),
     "mzx_scalar_to_support": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_trainer_loss_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "mzx_trainer_loss": (ctypes.c_int, [ctypes.POINTER(TrainerLossIO), c_vp]),

@@ -32,13 +32,17 @@ import numpy
 import torch
 
 from . import _lib, models, observations
-from .history import gc_paused
+from .history import ShardGameHistory, gc_paused
 
 # DeviceGameStore.reanalyse: the stacked observations of one chunk of positions stay within this many bytes (the network's
 # activations scale with the same count), and within the 64-lane groups one mzx_replay_batch gather accepts
 # (csrc/mzx_lib.cpp replay_obs_launch)
 REANALYSE_CHUNK_BYTES = 512 << 20
 REPLAY_GATHER_GROUPS = 1 << 26
+# DeviceGameStore.add_records: staged bytes per upload + mzx_replay_ingest pair.  add_many sends a run of up to 1 << 22 frame
+# floats (16 MiB) as one upload; the bulk path stages every column of a game, so its block is four of those: a whole
+# cartpole or connect4 hand-off of thousands of games is one pair, image games split every few hundred frames
+INGEST_CHUNK_BYTES = 4 * 4 * (1 << 22)
 
 
 def n_step_values(game_history, config):
@@ -313,6 +317,9 @@ class DeviceGameStore:
         self.games = {}       # game_id -> (base, T), oldest allocation first
         self._with_positions = 0      # resident games of T > 0 (what the sampler can draw from)
         self._head = 0        # next free row
+        # add_records: the pinned staging block, its device twin and the event recorded behind the last ingest that read it
+        self._stage = self._stage_dev = self._stage_event = None
+        self.ingest_calls = 0         # mzx_replay_ingest calls so far (add_records: one per staged chunk)
         self.max_games = None if max_games is None else int(max_games)
         self.sampler = None
         if self.max_games is not None:
@@ -484,6 +491,243 @@ class DeviceGameStore:
             slots = self._up(numpy.array([g % self.max_games for g, _ in items], dtype=numpy.int32))
             be, lib = self.backend, self.backend.lib
             lib.check(lib.mzx_replay_sampler_refresh(ctypes.byref(self.sampler), be.ptr(slots), len(items), be.stream()))
+
+    # ---- bulk ingest of shard records
+    def _fresh_view(self, gh, known=None):
+        """The ``(record, row, T)`` of a history that is still a fresh view of a shard record -- nothing of it materialised
+        or assigned, no reanalysed values: ``fill_initial_priorities_many``'s test -- else None.  ``known``: the ids of the
+        records the hand-off came with."""
+        d = gh.__dict__
+        view = d.get("_view")
+        if view is None or d.get("reanalysed_predicted_root_values") is not None or "legal_actions" in d:
+            return None
+        if known is not None and id(view[0]) not in known:
+            return None
+        for name in ShardGameHistory._LAZY:
+            if name in d:
+                return None
+        if view[0].priorities is None and d.get("priorities") is not None:      # (priorities of its own: add_many uploads them)
+            return None
+        return view
+
+    def add_records(self, items, records=None, chunk_bytes=None):
+        """
+        ``add_many`` for the games of a shard hand-off -- ``items`` [(game_id, game_history), ...] in hand-off order,
+        ``records`` the ``ShardGames.records`` grouping the views came from -- with nothing built per game: the pool ends
+        up bit for bit as ``add_many(items)`` leaves it (tests/replay_ingest_cases.py).
+
+        Games that are still FRESH VIEWS of a record (``_fresh_view``) take the bulk path: residency, slots and room are
+        checked for the whole hand-off, rows are allocated in the order of ``items`` (the bases ``add_many`` would give),
+        the host bookkeeping is filled in, pending slot drops are flushed, and then every record's arrays go into the
+        store's pinned staging block AS THEY LIE -- ``record.obs[:k]`` and its siblings, or one fancy-index gather per
+        record when only some of its games are handed over; observations become float32 and rewards binary64 on the way --
+        followed by ONE upload and ONE ``mzx_replay_ingest`` (three launches: rows, n-step values, slots).  The staging
+        block (section by section, each 16-byte aligned: len i32, base / game_id / src1 / src0 i64 per game; observations
+        f32, actions i64, rewards f64, to_play i64 per history row; visits i32 [A], root values f64, and optionally the
+        legal mask u8 [A] and the priorities f32 per searched position) is owned by the store, grown on demand and guarded
+        by an event recorded behind the ingest, which is waited for before the block is overwritten.  A hand-off that
+        stages more than ``chunk_bytes`` (default ``INGEST_CHUNK_BYTES``) is split at game boundaries into several such
+        pairs.  The bound is approximate: a game is counted with the bytes of its rows, not with the padding that aligns
+        the sections, and a single game beyond it travels alone.  There is one block, not two: a chunk is copied into it
+        only after the previous chunk's ingest has finished.
+
+        Priorities (a store with ``max_games``, ``config.PER``): a record that carries ``priorities`` has them staged; for one
+        without, the kernel computes them (``mzx_replay_priorities``' function) and the host views stay without: the
+        device columns are authoritative, ``ReplayBuffer.sync_priorities()`` brings them back.
+
+        Every other game -- a plain ``GameHistory``, a view with a materialised or assigned field -- goes through
+        ``add_many``.  A mixed hand-off is ingested in runs: maximal runs of fresh views and of other games, each run in
+        turn in ``items`` order, so order and bases are those of ``add_many(items)``.  ``StoreFull`` (no room, or a slot
+        held by a resident game) is raised before anything is stored and leaves the store unchanged.
+        """
+        items = list(items)
+        if not items:
+            return
+        known = {id(record) for record, _, _ in records} if records else None
+        views = [self._fresh_view(gh, known) for _, gh in items]
+        if not any(v is not None for v in views):
+            return self.add_many(items)
+        for game_id, _ in items:
+            if game_id in self.games:
+                raise ValueError(f"game {game_id} is already resident")
+        lengths = [len(gh.root_values) if v is None else v[2] for (_, gh), v in zip(items, views)]
+        if self.sampler is not None:
+            taken = dict(self._slot_owner)
+            for game_id, _ in items:
+                if taken.setdefault(game_id % self.max_games, game_id) != game_id:
+                    raise StoreFull(f"slot {game_id % self.max_games} of game {game_id} is held by resident game "
+                                    f"{taken[game_id % self.max_games]} ({self.max_games} slots)")
+        head = self._head
+        self._place(lengths)          # room for the whole hand-off, or StoreFull with the store unchanged
+        self._head = head             # (the runs below allocate the same rows again, in the same order)
+        limit = INGEST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+        lo = 0
+        while lo < len(items):
+            hi = lo + 1
+            while hi < len(items) and (views[hi] is None) == (views[lo] is None):
+                hi += 1
+            if views[lo] is None:
+                self.add_many(items[lo:hi])
+            else:
+                self._ingest_views(items[lo:hi], views[lo:hi], limit)
+            lo = hi
+
+    def _ingest_views(self, items, views, limit):
+        """A run of fresh views: allocation and host bookkeeping as add_many, then the staged chunks."""
+        self._reserve([(game_id, v[2]) for (game_id, _), v in zip(items, views)])
+        self._stage_views(items, views, limit)
+
+    def _reserve(self, entries):
+        """The host half of ``add_many`` for games ``[(game_id, T), ...]`` whose rows ``_stage_views`` fills later: the same
+        checks in the same order (ValueError for a resident id, StoreFull -- with the store unchanged -- for a slot held
+        by a resident game or no room), the same allocation, the same entries in ``games`` and ``_slot_owner``.  The table
+        slots are written by the ingest, not through ``_slot_dirty``."""
+        for game_id, _ in entries:
+            if game_id in self.games:
+                raise ValueError(f"game {game_id} is already resident")
+        if self.sampler is not None:
+            taken = {}
+            for game_id, _ in entries:
+                slot = game_id % self.max_games
+                holder = self._slot_owner.get(slot, taken.setdefault(slot, game_id))
+                if holder != game_id:
+                    raise StoreFull(f"slot {slot} of game {game_id} is held by resident game {holder} ({self.max_games} slots)")
+        bases = self._place([T for _, T in entries])
+        for (game_id, T), base in zip(entries, bases):
+            self.games[game_id] = (base, T)
+            self._with_positions += T > 0
+            if self.sampler is not None:
+                self._slot_owner[game_id % self.max_games] = game_id
+
+    def _stage_views(self, items, views, limit=None):
+        """The device half for reserved games that are fresh views: the staged chunks, each one upload and one ingest."""
+        if not items:
+            return
+        limit = INGEST_CHUNK_BYTES if limit is None else limit
+        groups = {}
+        sampled, slots = self.sampler is not None, self.max_games
+        for (game_id, _), (record, row, T) in zip(items, views):
+            base = self.games[game_id][0]
+            group = groups.get((id(record), T))
+            if group is None:
+                group = groups[(id(record), T)] = (record, T, [], [], [])
+            group[2].append(row)
+            group[3].append(base)
+            group[4].append(game_id)
+        if sampled:
+            for game_id, _ in items:       # (the kernel writes these slots: a pending entry must not overwrite them later)
+                self._slot_dirty.pop(game_id % slots, None)
+            self._flush_slots()
+        F, A = int(numpy.prod(self.shape)), self.A
+        per = sampled and bool(self.config.PER)
+        chunk, used, carried = [], 0, None
+        for record, T, rows, base, ids in groups.values():
+            rows, base, ids = numpy.array(rows, dtype=numpy.int64), numpy.array(base, dtype=numpy.int64), numpy.array(ids, dtype=numpy.int64)
+            game_bytes = (T + 1) * (4 * F + 24) + T * (5 * A + 12) + 36
+            has = None if not (per and T) else record.priorities is not None
+            if chunk and has is not None and carried is not None and has != carried:      # staged and computed priorities apart
+                self._ingest_chunk(chunk)
+                chunk, used, carried = [], 0, None
+            carried = has if has is not None else carried
+            k, lo = len(rows), 0
+            while lo < k:
+                room = (limit - used) // game_bytes
+                if room < 1:
+                    if chunk:
+                        self._ingest_chunk(chunk)
+                        chunk, used = [], 0
+                        continue
+                    room = 1          # (a game beyond the limit travels alone)
+                hi = min(k, lo + room)
+                chunk.append((record, T, rows[lo:hi], base[lo:hi], ids[lo:hi]))
+                used += (hi - lo) * game_bytes
+                lo = hi
+        if chunk:
+            self._ingest_chunk(chunk)
+
+    def _staging(self, nbytes):
+        """The pinned staging block as a numpy byte array of at least ``nbytes``, free to be overwritten."""
+        on_gpu = self.backend.device.type == "cuda"
+        if self._stage is None or self._stage.numel() < nbytes:
+            capacity = max(nbytes, 2 * (0 if self._stage is None else self._stage.numel()))
+            self._stage = torch.empty(capacity, dtype=torch.uint8, pin_memory=on_gpu)
+            self._stage_dev = torch.empty(capacity, dtype=torch.uint8, device=self.backend.device)
+        elif self._stage_event is not None:
+            self._stage_event.synchronize()
+        return self._stage.numpy()
+
+    def _ingest_chunk(self, pieces):
+        """One upload and one ``mzx_replay_ingest``: ``pieces`` [(record, T, rows of the record, bases, game ids)]."""
+        be, lib = self.backend, self.backend.lib
+        F, A = int(numpy.prod(self.shape)), self.A
+        lens = numpy.concatenate([numpy.full(len(p[2]), p[1], numpy.int64) for p in pieces])
+        G = int(lens.size)
+        R0 = int(lens.sum())
+        R1 = R0 + G
+        per = self.sampler is not None and bool(self.config.PER)
+        searched = [p for p in pieces if p[1] > 0]
+        with_mask = any(p[0].legal_mask is not None for p in searched)
+        with_priorities = per and bool(searched) and all(p[0].priorities is not None for p in searched)
+        sections = [("len", numpy.int32, G), ("base", numpy.int64, G), ("game_id", numpy.int64, G), ("src1", numpy.int64, G),
+                    ("src0", numpy.int64, G), ("obs", numpy.float32, R1 * F), ("acts", numpy.int64, R1), ("rews", numpy.float64, R1),
+                    ("tps", numpy.int64, R1), ("vis", numpy.int32, R0 * A), ("vals", numpy.float64, R0)]
+        if with_mask:
+            sections.append(("mask", numpy.uint8, R0 * A))
+        if with_priorities:
+            sections.append(("pri", numpy.float32, R0))
+        offsets, total = {}, 0
+        for name, dtype, count in sections:
+            offsets[name] = total
+            total = -(-(total + count * numpy.dtype(dtype).itemsize) // 16) * 16
+        total = max(total, 16)
+        host = self._staging(total)
+        col = {name: host[offsets[name]:offsets[name] + count * numpy.dtype(dtype).itemsize].view(dtype)
+               for name, dtype, count in sections}
+        col["len"][:] = lens
+        col["base"][:] = numpy.concatenate([p[3] for p in pieces])
+        col["game_id"][:] = numpy.concatenate([p[4] for p in pieces])
+        col["src1"][:] = numpy.cumsum(lens + 1) - (lens + 1)
+        col["src0"][:] = numpy.cumsum(lens) - lens
+        o1 = o0 = 0
+        put = lambda dst, src: numpy.copyto(dst, numpy.asarray(src).reshape(dst.shape), casting="unsafe")
+        for record, T, rows, _, _ in pieces:
+            k = len(rows)
+            first = int(rows[0])
+            sel = slice(first, first + k) if int(rows[-1]) - first == k - 1 and (k < 3 or bool((numpy.diff(rows) == 1).all())) else rows
+            n1, n0 = k * (T + 1), k * T
+            put(col["obs"][o1 * F:(o1 + n1) * F].reshape(k, T + 1, F), record.obs[sel, :T + 1])
+            put(col["acts"][o1:o1 + n1].reshape(k, T + 1), record.acts[sel, :T + 1])
+            put(col["rews"][o1:o1 + n1].reshape(k, T + 1), record.rews[sel, :T + 1])
+            put(col["tps"][o1:o1 + n1].reshape(k, T + 1), record.tps[sel, :T + 1])
+            if T:
+                put(col["vis"][o0 * A:(o0 + n0) * A].reshape(k, T, A), record.vis[sel, :T])
+                put(col["vals"][o0:o0 + n0].reshape(k, T), record.vals[sel, :T])
+                if with_mask:
+                    if record.legal_mask is None:
+                        col["mask"][o0 * A:(o0 + n0) * A] = 1
+                    else:
+                        put(col["mask"][o0 * A:(o0 + n0) * A].reshape(k, T, A), record.legal_mask[sel, :T])
+                if with_priorities:
+                    put(col["pri"][o0:o0 + n0].reshape(k, T), record.priorities[sel, :T])
+            o1, o0 = o1 + n1, o0 + n0
+        dev = self._stage_dev
+        dev[:total].copy_(self._stage[:total], non_blocking=True)
+        at = lambda name: dev.data_ptr() + offsets[name] if name in offsets else None
+        io = _lib.ReplayIngestIO()
+        io.d_len, io.d_base, io.d_game_id, io.d_src1, io.d_src0 = at("len"), at("base"), at("game_id"), at("src1"), at("src0")
+        io.d_observations, io.d_actions, io.d_rewards, io.d_to_play = at("obs"), at("acts"), at("rews"), at("tps")
+        io.d_visits, io.d_root_values, io.d_legal_mask, io.d_priorities = at("vis"), at("vals"), at("mask"), at("pri")
+        io.d_discount_pow, io.per_alpha = self._discount_pow.data_ptr(), float(getattr(self.config, "PER_alpha", 1.0))
+        io.total_rows, io.num_games, io.td_steps, io.per, io.action_space_size = R1, G, int(self.config.td_steps), int(per), A
+        io.channels, io.height, io.width = self.shape
+        lib.check(lib.mzx_replay_ingest(ctypes.byref(self.pool), None if self.sampler is None else ctypes.byref(self.sampler),
+                                        be.ptr(self.legal_mask), self.rows if self.legal_mask is not None else 0,
+                                        ctypes.byref(io), be.stream()))
+        self.ingest_calls += 1
+        if be.device.type == "cuda":
+            if self._stage_event is None:
+                self._stage_event = torch.cuda.Event()
+            self._stage_event.record(torch.cuda.current_stream(be.device))
 
     # ---- the sampler's state
     def _priority_rows(self, gh, T):
@@ -939,14 +1183,32 @@ class ReplayBuffer:
             except StoreFull:
                 if len(stock.buffer) <= 1:
                     raise
-            # the capacity bound in positions: the stock buffer's eviction (replay_buffer.py:59-61), applied once more
-            del_id = stock.num_played_games - len(stock.buffer)
-            stock.total_samples -= len(stock.buffer[del_id].root_values)
-            del stock.buffer[del_id]
-            self._arrays.pop(del_id, None)
-            if del_id in store:
-                store.drop(del_id)
+            del_id = self._evict_oldest()
             new_games = [(g, h) for g, h in new_games if g != del_id]
+
+    def _evict_oldest(self):
+        """The capacity bound in positions: the stock buffer's eviction (replay_buffer.py:59-61), applied once more."""
+        store, stock = self._store, self._stock
+        del_id = stock.num_played_games - len(stock.buffer)
+        stock.total_samples -= len(stock.buffer[del_id].root_values)
+        del stock.buffer[del_id]
+        self._arrays.pop(del_id, None)
+        if del_id in store:
+            store.drop(del_id)
+        return del_id
+
+    def _store_reserve(self, game_id, T):
+        """``_store_sync`` of one game that the stock buffer has just saved, on the host alone: the game gets its rows and
+        its slot (``DeviceGameStore._reserve``), the oldest games making room exactly as they do for ``add_many`` -- the
+        rows are filled later, by one ingest for the whole hand-off."""
+        store, stock = self._store, self._stock
+        while game_id in stock.buffer:
+            try:
+                return store._reserve([(game_id, T)])
+            except StoreFull:
+                if len(stock.buffer) <= 1:
+                    raise
+            self._evict_oldest()
 
     def __getattr__(self, name):
         if name in ("_stock", "_arrays", "_store", "_sampler", "_sample_calls"):
@@ -1031,6 +1293,73 @@ class ReplayBuffer:
             for game_id in [g for g in self._arrays if g < oldest]:
                 del self._arrays[game_id]
         return out
+
+    def save_games(self, histories, shared_storage=None):
+        """
+        ``save_game`` for every game of a hand-off.  Without a device store, or for ``histories`` without ``records`` (a
+        plain list), exactly that loop.  With a device store and a shard's ``ShardGames``: the initial priorities through
+        ``fill_initial_priorities_many`` (records that came with theirs return at once); the size check of ``save_game`` for
+        EVERY game before anything is stored; then per game the stock ``save_game`` for the stock buffer's own bookkeeping
+        -- ``buffer``, the counters, eviction by ``replay_buffer_size``; called without ``shared_storage``, the two counters
+        are published once at the end -- and the HOST half of the store's synchronisation (``_store_reserve``): the game
+        gets the rows and the slot ``add_many`` would give it at that point, the oldest games leaving store and stock
+        buffer when it does not fit, statement for statement what the loop does.  Nothing touches the device until the
+        end: ONE ``DeviceGameStore`` ingest (``_stage_views``: one upload, one ``mzx_replay_ingest`` per chunk) fills the
+        rows of the games that are still resident; a game of the hand-off that was evicted again within it is never
+        uploaded.  Stock buffer, counters, residency, bases and pool contents are those of the loop, whatever is evicted
+        (tests/replay_ingest_cases.py: ``check_save_games``).  A game that is no fresh view of the hand-off's records (a
+        plain ``GameHistory``, a materialised view) goes through ``save_game`` in its turn, the games before it ingested
+        first.  After an exception the games saved so far are in both, as after the loop.
+        """
+        store, stock = self._store, self._stock
+        records = getattr(histories, "records", None)
+        if store is None or not records:
+            for game_history in histories:
+                self.save_game(game_history, shared_storage)
+            return
+        config = stock.config
+        known = {id(record) for record, _, _ in records}
+        views = []             # (taken first: the steps below read fields of a view, which materialises them)
+        for game_history in histories:
+            view = store._fresh_view(game_history, known)
+            T = len(game_history.root_values) if view is None else view[2]
+            if T + 1 > store.rows:
+                raise StoreFull(f"a game of {T} positions exceeds the device store's {store.rows} rows")
+            views.append(view)
+        fill_initial_priorities_many(histories, config, backend=store.backend)
+        for game_id in [g for g in store.games if g not in stock.buffer]:
+            store.drop(game_id)
+        pending = []           # reserved fresh views whose rows are not filled yet: (game_id, game_history), view
+
+        def flush():
+            live = [(item, view) for item, view in pending if item[0] in store.games]
+            del pending[:]
+            store._stage_views([item for item, _ in live], [view for _, view in live])
+
+        try:
+            for game_history, view in zip(histories, views):
+                if view is None:                  # any other game: the per-game path, behind the games before it
+                    flush()
+                    self.save_game(game_history, None)
+                    continue
+                oldest = next(iter(stock.buffer), None)
+                stock.save_game(game_history, None)
+                if oldest is not None and oldest not in stock.buffer and oldest in store:      # evicted by replay_buffer_size
+                    store.drop(oldest)
+                game_id = stock.num_played_games - 1
+                self._store_reserve(game_id, view[2])
+                pending.append(((game_id, game_history), view))
+        finally:
+            flush()
+        if self._arrays and stock.buffer:
+            oldest = next(iter(stock.buffer))
+            for game_id in [g for g in self._arrays if g < oldest]:
+                del self._arrays[game_id]
+        if shared_storage:
+            set_info = shared_storage.set_info
+            set_info = getattr(set_info, "remote", set_info)
+            set_info("num_played_games", stock.num_played_games)
+            set_info("num_played_steps", stock.num_played_steps)
 
     def update_game_history(self, game_id, game_history):
         self._arrays.pop(game_id, None)          # reanalysed root values change the n-step targets

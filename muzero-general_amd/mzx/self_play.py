@@ -268,6 +268,11 @@ class SelfPlay:
             shared_storage.refresh(self.model, block=True)     # the trainer's weights before the first game
         save_game = replay_buffer.save_game
         save_is_remote = hasattr(save_game, "remote")
+        # a local buffer that takes a whole hand-off at once (mzx.replay.ReplayBuffer.save_games: with a device store the
+        # games reach the pool through one bulk ingest instead of a dozen runtime calls per game)
+        save_games = getattr(replay_buffer, "save_games", None)
+        if save_games is not None and hasattr(save_games, "remote"):
+            save_games = None
 
         def hand_off(histories):
             # initial PER priorities, on the device (replay_buffer.py:39-51 would loop in Python) -- the games a shard
@@ -276,6 +281,8 @@ class SelfPlay:
             if save_is_remote:
                 for game_history in histories:
                     _remote(save_game, game_history, shared_storage)
+            elif save_games is not None:
+                save_games(histories, shared_storage)
             else:
                 for game_history in histories:
                     save_game(game_history, shared_storage)
