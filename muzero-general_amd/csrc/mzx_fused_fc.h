@@ -93,9 +93,14 @@ constexpr int DPP_HALF_MIRROR = 0x141; // row_half_mirror: i <-> 7-i inside each
 constexpr int DPP_MIRROR = 0x140;      // row_mirror: i <-> 15-i
 constexpr int DPP_BCAST0 = 0x150;      // row_newbcast:0 (gfx90a+): every lane reads lane k of its row
 
+// One DPP move inside the 16-lane row.  Whole-row form: `old` is a constant and bound_ctrl is set, so the move reads its
+// source in place and folds into the instruction that consumes it (v_add_f32_dpp, v_cndmask_b32_dpp, ...) -- with `old`
+// tied to the source, every move cost a register copy and two wait states first.  A lane whose SOURCE lane is switched
+// off by exec reads 0: every caller runs with whole rows active (rows leave a kernel, freeze or branch as a whole), where
+// all the controls used here (quad_perm, half-mirror, mirror, row_newbcast) read a live lane of the same row.
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false);
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
@@ -121,20 +126,44 @@ __device__ __forceinline__ float row_sum(float v) {
   v = v + dpp_f<DPP_MIRROR>(v);
   return v;
 }
-__device__ __forceinline__ float row_max(float v) {
-  v = fmaxf(v, dpp_f<DPP_XOR1>(v));
-  v = fmaxf(v, dpp_f<DPP_XOR2>(v));
-  v = fmaxf(v, dpp_f<DPP_HALF_MIRROR>(v));
-  v = fmaxf(v, dpp_f<DPP_MIRROR>(v));
-  return v;
-}
-__device__ __forceinline__ float row_min(float v) {
-  v = fminf(v, dpp_f<DPP_XOR1>(v));
-  v = fminf(v, dpp_f<DPP_XOR2>(v));
-  v = fminf(v, dpp_f<DPP_HALF_MIRROR>(v));
-  v = fminf(v, dpp_f<DPP_MIRROR>(v));
-  return v;
-}
+// fp32 max / min butterflies: ONE v_max_f32_dpp / v_min_f32_dpp per step, the instruction that produced the result
+// of fmaxf(v, partner) before (behind a move and two self-maxima that only quiet signalling NaNs: none arrive here).
+// The input comes from plain VALU code, and a step reads what the step before wrote: two wait states each (VALU
+// write -> DPP read, which hipcc does not track through an asm statement); the _2 forms run two independent
+// butterflies side by side, so one wait state per step covers both.
+#define MZX_RD(OP, V, CTRL) OP " " V ", " V ", " V " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define MZX_RD_XOR1 "quad_perm:[1,0,3,2]"
+#define MZX_RD_XOR2 "quad_perm:[2,3,0,1]"
+#define MZX_RD_HALF "row_half_mirror"
+#define MZX_RD_FULL "row_mirror"
+#define MZX_ROW_REDUCE(NAME, OP)                                                                                   \
+  template <int W>                                                                                                 \
+  __device__ __forceinline__ float NAME(float v) {                                                                 \
+    static_assert(W == 2 || W == 4 || W == 8 || W == 16, "butterfly width");                                       \
+    if constexpr (W == 2) asm("s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR1) : [v] "+v"(v));                          \
+    else if constexpr (W == 4)                                                                                     \
+      asm("s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR1) "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR2) : [v] "+v"(v)); \
+    else if constexpr (W == 8)                                                                                     \
+      asm("s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR1) "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR2)               \
+          "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_HALF) : [v] "+v"(v));                                             \
+    else                                                                                                           \
+      asm("s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR1) "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_XOR2)               \
+          "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_HALF) "s_nop 1\n\t" MZX_RD(OP, "%[v]", MZX_RD_FULL) : [v] "+v"(v)); \
+    return v;                                                                                                      \
+  }
+MZX_ROW_REDUCE(row_max_w, "v_max_f32_dpp")
+MZX_ROW_REDUCE(row_min_w, "v_min_f32_dpp")
+#undef MZX_ROW_REDUCE
+__device__ __forceinline__ float row_max(float v) { return row_max_w<16>(v); }
+__device__ __forceinline__ float row_min(float v) { return row_min_w<16>(v); }
+// a <- OPA butterfly of a, b <- OPB butterfly of b, over the whole row
+#define MZX_RD_STEP2(OPA, OPB, CTRL) MZX_RD(OPA, "%[a]", CTRL) MZX_RD(OPB, "%[b]", CTRL)
+#define MZX_ROW_REDUCE2(OPA, OPB, A, B)                                                                            \
+  asm("s_nop 1\n\t" MZX_RD_STEP2(OPA, OPB, MZX_RD_XOR1) "s_nop 0\n\t" MZX_RD_STEP2(OPA, OPB, MZX_RD_XOR2)          \
+      "s_nop 0\n\t" MZX_RD_STEP2(OPA, OPB, MZX_RD_HALF) "s_nop 0\n\t" MZX_RD_STEP2(OPA, OPB, MZX_RD_FULL)          \
+      : [a] "+v"(A), [b] "+v"(B))
+__device__ __forceinline__ void row_max_2(float& a, float& b) { MZX_ROW_REDUCE2("v_max_f32_dpp", "v_max_f32_dpp", a, b); }
+__device__ __forceinline__ void row_min_max(float& lo, float& hi) { MZX_ROW_REDUCE2("v_min_f32_dpp", "v_max_f32_dpp", lo, hi); }
 // binary64 max / min over the first W lanes of the row (W = 2, 4 or 16; the other lanes hold
 // the neutral element); exact, so the order of the butterfly does not matter
 template <int W>
@@ -686,8 +715,8 @@ __device__ __forceinline__ void dot16x5_bcast(float xr, float xp, float xv, cons
 __device__ __forceinline__ void row_decode2x2(float a0, float a1, float b0, float b1, int F, int support, int sub,
                                               float& out_a, float& out_b) {
   const bool v0 = sub < F, v1 = sub + 16 < F;
-  const float ma = row_max(fmaxf(v0 ? a0 : -MZX_INF, v1 ? a1 : -MZX_INF));
-  const float mb = row_max(fmaxf(v0 ? b0 : -MZX_INF, v1 ? b1 : -MZX_INF));
+  float ma = fmaxf(v0 ? a0 : -MZX_INF, v1 ? a1 : -MZX_INF), mb = fmaxf(v0 ? b0 : -MZX_INF, v1 ? b1 : -MZX_INF);
+  row_max_2(ma, mb);
   const float ea0 = v0 ? mzx_expf(a0 - ma) : 0.f, ea1 = v1 ? mzx_expf(a1 - ma) : 0.f;
   const float eb0 = v0 ? mzx_expf(b0 - mb) : 0.f, eb1 = v1 ? mzx_expf(b1 - mb) : 0.f;
   float da = 0.f, db = 0.f;      // canonical lane partial: 0 + e[sub] + e[sub + 16]
@@ -768,7 +797,8 @@ struct SmallNet {
   // min-max scale of the state held one element per lane (lanes >= E hold junk)
   __device__ __forceinline__ float scale(float s, int sub) const {
     const bool in = sub < E;
-    const float lo = row_min(in ? s : MZX_INF), hi = row_max(in ? s : -MZX_INF);
+    float lo = in ? s : MZX_INF, hi = in ? s : -MZX_INF;
+    row_min_max(lo, hi);
     float sc = hi - lo;
     if (sc < 1e-5f) sc += 1e-5f;
     return mzx_div(s - lo, sc);

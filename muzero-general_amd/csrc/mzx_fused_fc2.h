@@ -86,21 +86,13 @@ __device__ __forceinline__ double prior_score(double pbcN, double sqN, int n, do
 
 // Butterflies over the first W lanes of a row (the other lanes hold the neutral element): the canonical
 // order xor 1, xor 2, half-mirror, mirror cut after log2(W) steps -- the skipped steps would add zeros / compare
-// with the neutral element, so the result has the same bits as the 16-lane form.
+// with the neutral element, so the result has the same bits as the 16-lane form.  (row_max_w / row_min_w: mzx_fused_fc.h.)
 template <int W>
 __device__ __forceinline__ float row_sum_w(float v) {
   v = v + dpp_f<DPP_XOR1>(v);
   if constexpr (W > 2) v = v + dpp_f<DPP_XOR2>(v);
   if constexpr (W > 4) v = v + dpp_f<DPP_HALF_MIRROR>(v);
   if constexpr (W > 8) v = v + dpp_f<DPP_MIRROR>(v);
-  return v;
-}
-template <int W>
-__device__ __forceinline__ float row_max_w(float v) {
-  v = fmaxf(v, dpp_f<DPP_XOR1>(v));
-  if constexpr (W > 2) v = fmaxf(v, dpp_f<DPP_XOR2>(v));
-  if constexpr (W > 4) v = fmaxf(v, dpp_f<DPP_HALF_MIRROR>(v));
-  if constexpr (W > 8) v = fmaxf(v, dpp_f<DPP_MIRROR>(v));
   return v;
 }
 constexpr int DPP_ROW_SHL1 = 0x101;   // lane i reads lane i + 1 of its row (lane 15: keeps `old`)
@@ -194,14 +186,17 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
     int sl, cw;
     if constexpr (AW == 2) {
       // two candidates: every lane sees both scores; no ballot
+      // (the child is selected by the comparison itself: through `sl` it cost a compare and its wait states more)
       const double a0 = bcast_d<0>(sc), a1 = bcast_d<1>(sc);
-      sl = (a1 > a0) ? 1 : 0;
+      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);
+      const bool up = a1 > a0;
+      sl = up ? 1 : 0;
+      cw = up ? c1 : c0;
       if (__builtin_expect(a0 == a1 && !done, 0)) {  // numpy.random.choice([0, 1]): first walk of a search, rare later
         ++st.ties;
         sl = tape_draw(tape, tape_words, st.tape_pos, st.flags, 2);
+        cw = sl ? c1 : c0;
       }
-      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);
-      cw = sl ? c1 : c0;
     } else {
       const double best = row_max_d<AW>(sc);
       const unsigned bits = row_bits(__ballot(sc == best), row_in_wave) & ((1u << AW) - 1u);
@@ -218,13 +213,15 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
       else cw = perm_i(c, sl, row_in_wave);
     }
     const bool act = !done;
+    cw = act ? cw : -1;              // a finished row has no child to go to: `cw >= 0` alone says "walk on"
     // entry of the level just decided; a finished row rewrites the entry beyond its leaf (never read)
     if (sub == 0) T.path[depth + 1] = make_int2(cw, sl);
     depth += act ? 1 : 0;
     slot = act ? sl : slot;
-    node = (act && cw >= 0) ? cw : node;
-    done = done || (cw < 0);
-    if (__all(done)) break;
+    const bool go = cw >= 0;
+    node = go ? cw : node;
+    done = !go;
+    if (__builtin_amdgcn_ballot_w64(go) == 0) break;   // __all(done), as a ballot of the comparison itself
   }
   Fc2Walk w;
   // players play turn by turn (self_play.py:331-334): the leaf's player follows from the depth
