@@ -212,6 +212,15 @@ __device__ __forceinline__ unsigned row_bits(unsigned long long ballot, int row_
   return (unsigned)(ballot >> (row_in_wave * FUSED_ROW)) & 0xFFFFu;
 }
 
+// support_inverse_transform of TWO row-uniform values in one pass: the sequence (an IEEE sqrt, an IEEE division, a
+// square, a sign) computes one scalar per tree in all 16 lanes, so the even lanes run it on `a` and the odd lanes on
+// `b`, and both results come back by a quad_perm move.  The shared function body per value, hence its bits.
+__device__ __forceinline__ void support_inverse_transform_2(float a, float b, int sub, float& out_a, float& out_b) {
+  const float t = support_inverse_transform((sub & 1) ? b : a);
+  out_a = dpp_f<0xA0>(t);    // quad_perm:[0,0,2,2]: the even lane of each pair
+  out_b = dpp_f<0xF5>(t);    // quad_perm:[1,1,3,3]: the odd lane
+}
+
 // support_to_scalar (models.py:645-666), canonical lane order: this lane holds
 // logits l0 (index sub) and l1 (index sub + 16); indices >= F are absent.
 __device__ __forceinline__ float row_decode2(float l0, float l1, int F, int support, int sub) {
@@ -726,8 +735,7 @@ __device__ __forceinline__ void row_decode2x2(float a0, float a1, float b0, floa
   float na = 0.f, nb = 0.f;
   if (v0) { na += (float)(sub - support) * mzx_div(ea0, dena); nb += (float)(sub - support) * mzx_div(eb0, denb); }
   if (v1) { na += (float)(sub + 16 - support) * mzx_div(ea1, dena); nb += (float)(sub + 16 - support) * mzx_div(eb1, denb); }
-  out_a = support_inverse_transform(row_sum(na));
-  out_b = support_inverse_transform(row_sum(nb));
+  support_inverse_transform_2(row_sum(na), row_sum(nb), sub, out_a, out_b);
 }
 
 template <int K, int I = 0>

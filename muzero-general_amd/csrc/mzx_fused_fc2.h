@@ -50,7 +50,10 @@ struct Fc2Args {
 
 #ifndef MZX_HOSTCHECK
 
-struct __attribute__((aligned(16))) Fc2Slot {   // one child slot of a node
+// One child slot of a node.  INVARIANT: every one of the AW slots of a node that exists is written when the node is made
+// (root expansion, fc2_expand, fc2_from_arena) -- slots beyond its actions with n = 0, prior = 0, ps = -inf.
+// fc2_load_lane reads all AW slots of a path node without asking how many actions there are.
+struct __attribute__((aligned(16))) Fc2Slot {
   double ps;       // cached prior score of the slot at the parent's current visit count
   double q;        // reward + discount * (+-value()) of the child (written by back-propagation)
   int32_t n;       // child's visit count
@@ -104,41 +107,47 @@ __device__ __forceinline__ double shl1_d(double v, double old) {
 }
 
 // One step of the value recurrence  value = (+-reward) + discount * value  (self_play.py:417 / :424-427) at path
-// lane J: the lane notes the value arriving at its node, every lane advances the row-uniform value.  Rows whose
-// leaf is above lane J (J > ld) keep theirs -- a select, no exec-mask branch.
+// lane J.  Lane `sub` advances its own copy of the value while the step is below its row's leaf and above its own
+// node (sub < J <= ld) and then stops: what it holds when the chain ends IS the value arriving at its node, and lane 0
+// holds the row's final value.  Until a lane stops, its copy went through the same operations on the same operands as
+// every other copy of the row, hence the same bits as one row-uniform value.  `lim` = max(ld - sub, 0): the condition
+// is one unsigned compare of the lane constant J - 1 - sub against it -- a select, no exec-mask branch.
 template <int J>
-__device__ __forceinline__ void chain_step2(double r_eff, double disc, int ld, int sub, double& val, double& my_in) {
+__device__ __forceinline__ void chain_step2(double r_eff, double disc, unsigned lim, int sub, double& val) {
+  const bool on = (unsigned)(J - 1 - sub) < lim;
+  __builtin_amdgcn_sched_barrier(0);
   const double rj = bcast_d<J>(r_eff);
   const double nv = rj + disc * val;
-  my_in = (sub == J) ? val : my_in;
-  val = (J <= ld) ? nv : val;
+  val = on ? nv : val;
 }
 // Steps 15 .. 1 in groups guarded by the deepest row of the wave (wmax, wave-uniform: plain scalar branches, no
 // exec masking); a step above a row's own leaf is a no-op by its select, so a group may run a step too many.
-__device__ __forceinline__ void value_chain(double r_eff, double disc, int ld, int sub, int wmax, double& val, double& my_in) {
+__device__ __forceinline__ void value_chain(double r_eff, double disc, int ld, int sub, int wmax, double& val) {
+  const int room = ld - sub;
+  const unsigned lim = (unsigned)(room > 0 ? room : 0);
   if (wmax >= 13) {
-    chain_step2<15>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<14>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<13>(r_eff, disc, ld, sub, val, my_in);
+    chain_step2<15>(r_eff, disc, lim, sub, val);
+    chain_step2<14>(r_eff, disc, lim, sub, val);
+    chain_step2<13>(r_eff, disc, lim, sub, val);
   }
   if (wmax >= 9) {
-    chain_step2<12>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<11>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<10>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<9>(r_eff, disc, ld, sub, val, my_in);
+    chain_step2<12>(r_eff, disc, lim, sub, val);
+    chain_step2<11>(r_eff, disc, lim, sub, val);
+    chain_step2<10>(r_eff, disc, lim, sub, val);
+    chain_step2<9>(r_eff, disc, lim, sub, val);
   }
   if (wmax >= 7) {
-    chain_step2<8>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<7>(r_eff, disc, ld, sub, val, my_in);
+    chain_step2<8>(r_eff, disc, lim, sub, val);
+    chain_step2<7>(r_eff, disc, lim, sub, val);
   }
   if (wmax >= 5) {
-    chain_step2<6>(r_eff, disc, ld, sub, val, my_in);
-    chain_step2<5>(r_eff, disc, ld, sub, val, my_in);
+    chain_step2<6>(r_eff, disc, lim, sub, val);
+    chain_step2<5>(r_eff, disc, lim, sub, val);
   }
-  if (wmax >= 4) chain_step2<4>(r_eff, disc, ld, sub, val, my_in);
-  if (wmax >= 3) chain_step2<3>(r_eff, disc, ld, sub, val, my_in);
-  if (wmax >= 2) chain_step2<2>(r_eff, disc, ld, sub, val, my_in);
-  if (wmax >= 1) chain_step2<1>(r_eff, disc, ld, sub, val, my_in);
+  if (wmax >= 4) chain_step2<4>(r_eff, disc, lim, sub, val);
+  if (wmax >= 3) chain_step2<3>(r_eff, disc, lim, sub, val);
+  if (wmax >= 2) chain_step2<2>(r_eff, disc, lim, sub, val);
+  if (wmax >= 1) chain_step2<1>(r_eff, disc, lim, sub, val);
 }
 
 
@@ -173,6 +182,48 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
   const bool norm_on = mx > mn;
   int node = 0, depth = 0, slot = 0;
   int levels = 0;                  // walk iterations = depth of the deepest leaf in this wave (scalar)
+  if constexpr (AW == 2) {
+    // Two candidates: every lane sees both scores, no ballot.  One loop counter, one backward conditional branch.
+    // While max <= min the reference takes q as it is: with minimum 0 and divisor 1 the division returns q bit for
+    // bit ((q - 0) * 1, a zero remainder, div_fixup(q, 1, q) = q), so the select is made once per walk, not per level.
+    const double mn_e = norm_on ? mn : 0.0, dd_e = norm_on ? dd : 1.0, yd_e = norm_on ? yd : 1.0;
+    unsigned long long more = __builtin_amdgcn_ballot_w64(true);   // lanes whose row has not reached its leaf
+    do {
+      const bool act = __builtin_amdgcn_inverse_ballot_w64(more);
+      ++levels;
+      asm volatile("" : "+s"(levels));      // one induction variable (the compiler kept three copies of it)
+      const Fc2Slot* rp = T.slots + (node * 2 + (sub & 1));
+      const double ps = rp->ps, q = rp->q;
+      const int n = rp->n, c = rp->child;
+      const bool seen = n > 0;
+      __builtin_amdgcn_sched_barrier(0);    // the compare first: the division fills its wait states before the select
+      const double v = div_by(q - mn_e, dd_e, yd_e);
+      const double wv = ps + v;
+      const double sc = seen ? wv : ps;
+      const double a0 = bcast_d<0>(sc), a1 = bcast_d<1>(sc);
+      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);
+      const bool up = a1 > a0;     // the child is selected by the comparison itself
+      int sl = up ? 1 : 0;
+      int cw = up ? c1 : c0;
+      const bool eq = a0 == a1;
+      if (__builtin_expect((__builtin_amdgcn_ballot_w64(eq) & more) != 0, 0)) {   // wave-uniform: a scalar branch, no exec round trip
+        if (eq && act) {           // numpy.random.choice([0, 1]): first walk of a search, rare later
+          ++st.ties;
+          sl = tape_draw(tape, tape_words, st.tape_pos, st.flags, 2);
+          cw = sl ? c1 : c0;
+        }
+      }
+      cw = act ? cw : -1;          // a finished row has no child to go to: `cw >= 0` alone says "walk on"
+      // entry of the level just decided; a finished row rewrites the entry beyond its leaf (never read)
+      T.path[depth + 1] = make_int2(cw, sl);      // row-uniform address and value: every lane of the row stores it
+      depth += act ? 1 : 0;
+      asm volatile("" : "+v"(depth));
+      slot = act ? sl : slot;
+      const bool go = cw >= 0;
+      node = go ? cw : node;
+      more = __builtin_amdgcn_ballot_w64(go);
+    } while (more != 0);
+  } else {
   bool done = false;
   for (;;) {
     ++levels;
@@ -184,20 +235,7 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
     const double wv = ps + v;
     const double sc = (n > 0) ? wv : ps;
     int sl, cw;
-    if constexpr (AW == 2) {
-      // two candidates: every lane sees both scores; no ballot
-      // (the child is selected by the comparison itself: through `sl` it cost a compare and its wait states more)
-      const double a0 = bcast_d<0>(sc), a1 = bcast_d<1>(sc);
-      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);
-      const bool up = a1 > a0;
-      sl = up ? 1 : 0;
-      cw = up ? c1 : c0;
-      if (__builtin_expect(a0 == a1 && !done, 0)) {  // numpy.random.choice([0, 1]): first walk of a search, rare later
-        ++st.ties;
-        sl = tape_draw(tape, tape_words, st.tape_pos, st.flags, 2);
-        cw = sl ? c1 : c0;
-      }
-    } else {
+    {
       const double best = row_max_d<AW>(sc);
       const unsigned bits = row_bits(__ballot(sc == best), row_in_wave) & ((1u << AW) - 1u);
       const int nbest = __popc(bits);
@@ -222,6 +260,7 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
     node = go ? cw : node;
     done = !go;
     if (__builtin_amdgcn_ballot_w64(go) == 0) break;   // __all(done), as a ballot of the comparison itself
+  }
   }
   Fc2Walk w;
   // players play turn by turn (self_play.py:331-334): the leaf's player follows from the depth
@@ -250,27 +289,30 @@ template <int AW>
 __device__ __forceinline__ Fc2Lane<AW> fc2_load_lane(const Fc2Tree& T, const Fc2Walk& w, int c, int sub) {
   Fc2Lane<AW> L;
   const int d = c * 16 + sub;
-  const bool active = d <= w.depth, is_leaf = d == w.depth;
-  L.nd = 0; L.pslot = 0; L.par = 0; L.vc = 0; L.tp = w.vtp; L.vs = 0.0; L.rr = 0.0;
-  if (active) {
-    const int2 pe = T.path[d];
-    L.nd = pe.x; L.pslot = pe.y;
-    if (d > 0) L.par = T.path[d - 1].x;
-  }
-  if (active && !is_leaf) {
-    const Fc2Node* np = T.nodes + L.nd;
-    L.vs = np->value_sum; L.rr = np->reward; L.vc = np->visit;
-    if (T.P == 2) L.tp = np->to_play;
-  }
+  // No guard on a READ: a lane at or beyond the leaf reads the leaf's path entry and, for the node record, the leaf's
+  // parent -- a real record, so every count below indexes its table in range.  Back-propagation guards every WRITE with
+  // `active` / `is_leaf`, and what a lane beyond the leaf hands down by row_shl only reaches the leaf lane, which the
+  // refresh skips; the leaf lane itself needs a fresh node's zeros (value_sum, visit) and the walk's player.
+  const bool inner = d < w.depth;
+  const int dq = inner ? d : w.depth;
+  const int2 pe = T.path[dq];
+  L.nd = pe.x; L.pslot = pe.y;
+  L.par = T.path[dq > 0 ? dq - 1 : 0].x;     // (depth >= 1: a walk takes at least the root's level)
+  const int nr = inner ? L.nd : L.par;
+  const Fc2Node* np = T.nodes + nr;
+  const double vs = np->value_sum;
+  const int vc = np->visit;
+  L.rr = np->reward;   // (beyond the leaf: the parent's reward -- the chain consumes lanes J <= ld and lane 0 of an active chunk only)
+  L.vs = inner ? vs : 0.0; L.vc = inner ? vc : 0;
+  L.tp = w.vtp;
+  if (T.P == 2) L.tp = inner ? np->to_play : w.vtp;
   L.inv_vc2 = T.inv_y[L.vc + 1];        // reciprocal of this node's visit count after the update
   L.inv_vc3 = T.inv_y[L.vc + 2];        // ... and of (that + 1): what its PARENT's prior score divides by
   L.pb = T.pbc[L.vc + 1]; L.sv = T.sqt[L.vc + 1];
   if constexpr (AW <= 4) {
+    // all AW slots of a real node are initialised (padding slots: n = 0, prior = 0)
 #pragma unroll
-    for (int s = 0; s < AW; ++s) {
-      L.sn[s] = 0; L.sprior[s] = 0.0;
-      if (active && !is_leaf && s < T.A) { L.sn[s] = T.slots[L.nd * AW + s].n; L.sprior[s] = T.slots[L.nd * AW + s].prior; }
-    }
+    for (int s = 0; s < AW; ++s) { L.sn[s] = T.slots[nr * AW + s].n; L.sprior[s] = T.slots[nr * AW + s].prior; }
 #pragma unroll
     for (int s = 0; s < AW; ++s) L.sinv[s] = T.inv_y[L.sn[s] + 1];
   }
@@ -311,11 +353,11 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
     const double rr = is_leaf ? reward : L.rr;
     const bool same = (L.tp == vtp);
     const double r_eff = (P == 1 || !same) ? rr : -rr;   // value = (+-reward) + discount * value
-    double my_in = val;
     const int wm = w.levels - c * 16;           // deepest leaf of the wave relative to this chunk (wave-uniform)
-    value_chain(r_eff, disc, ld, sub, wm > 15 ? 15 : (wm < 0 ? 0 : wm), val, my_in);
-    if (sub == 0) my_in = val;
-    if (c > 0 && ld >= 0) val = bcast_d<0>(r_eff) + disc * val;   // hand the value to the chunk above
+    value_chain(r_eff, disc, ld, sub, wm > 15 ? 15 : (wm < 0 ? 0 : wm), val);
+    const double my_in = val;                   // the value arriving at this lane's node (lane 0: the chunk's final value)
+    // hand the value to the chunk above: lane 0's, through lane 0's node -- row-uniform again
+    if (c > 0 && ld >= 0) val = bcast_d<0>(r_eff) + disc * bcast_d<0>(val);
     const int vc2 = L.vc + 1;
     const double vs2 = L.vs + ((P == 1 || same) ? my_in : -my_in);
     double qv = 0.0;
