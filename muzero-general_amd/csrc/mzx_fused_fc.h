@@ -820,12 +820,16 @@ struct SmallNet {
     dot2_bcast<HV>(v1, w_v2a, w_v2b, va, vb);
     o.value = row_decode2(va + b_v2a, vb + b_v2b, F, support, sub);
   }
+  // initial / recurrent: h_out[sub] = hn is stored by the WHOLE row (no exec mask): lanes >= E hold a defined value nobody uses, and it
+  // lands in h_out[E .. 16) -- the hidden state of the NEXT node, which is written when that node is expanded and read only
+  // after, or, for the last node, the dead tail the plans leave behind a tree's hidden states (fused_plan, fc2_plan).  The
+  // export and the continued-search import copy n_nodes * E floats.
   __device__ __forceinline__ void initial(const float* obs, float* h_out, float*, int sub, NetOut& o) const {
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < IN; ++k) acc = fmaf(obs[k], w_rep[k], acc);
     const float hn = scale(acc + b_rep, sub);
-    if (sub < E) h_out[sub] = hn;
+    h_out[sub] = hn;
     heads(hn, sub, o);
   }
   __device__ __forceinline__ void recurrent(const float* h_in, int action, float* h_out, float*, int sub,
@@ -841,7 +845,7 @@ struct SmallNet {
     if constexpr (E == 8 && HR == 16 && HP == 16 && HV == 16) {
       // the three towers behind the dynamics state side by side (see dot8x3_bcast): same values, bit for bit
       const float hn = scale(s, sub);
-      if (sub < E) h_out[sub] = hn;
+      h_out[sub] = hn;
       float r1, p1, v1;
       dot8x3_bcast(s, hn, w_r1, w_p1, w_v1, r1, p1, v1);          // the reward head reads the UNscaled state
       r1 = mzx_elu(r1 + b_r1); p1 = mzx_elu(p1 + b_p1); v1 = mzx_elu(v1 + b_v1);
@@ -855,7 +859,7 @@ struct SmallNet {
     float ra, rb;
     dot2_bcast<HR>(r1, w_r2a, w_r2b, ra, rb);
     const float hn = scale(s, sub);
-    if (sub < E) h_out[sub] = hn;
+    h_out[sub] = hn;
     o.reward = row_decode2(ra + b_r2a, rb + b_r2b, F, support, sub);
     heads(hn, sub, o);
   }
@@ -1060,7 +1064,7 @@ inline FusedPlan fused_plan(const mzx_search* s, bool allow_small = true) {
   a.lds_weights = (int32_t)o; o += P.small ? 0 : al16(int64_t(4) * net->num_params);
   a.lds_trees = (int32_t)o;
   a.off_hidden = (int32_t)al16(s->L.tree_bytes);
-  a.off_scratch = (int32_t)(a.off_hidden + al16(int64_t(4) * s->p.num_nodes * E));
+  a.off_scratch = (int32_t)(a.off_hidden + al16(int64_t(4) * (s->p.num_nodes * E + (P.small && E < FUSED_ROW ? FUSED_ROW - E : 0))));
   a.tree_stride = (int32_t)(a.off_scratch + int64_t(4) * FUSED_SCRATCH);
   int tpb = 16;
   while (tpb >= 4 && o + int64_t(tpb) * a.tree_stride > FUSED_LDS_BUDGET) tpb /= 2;

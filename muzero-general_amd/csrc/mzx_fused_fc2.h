@@ -120,7 +120,7 @@ __device__ __forceinline__ void chain_step2(double r_eff, double disc, unsigned 
   const double nv = rj + disc * val;
   val = on ? nv : val;
 }
-// Steps 15 .. 1 in groups guarded by the deepest row of the wave (wmax, wave-uniform: plain scalar branches, no
+// Steps 15 .. 7 in three groups guarded by the deepest row of the wave (wmax, wave-uniform: plain scalar branches, no
 // exec masking); a step above a row's own leaf is a no-op by its select, so a group may run a step too many.
 __device__ __forceinline__ void value_chain(double r_eff, double disc, int ld, int sub, int wmax, double& val) {
   const int room = ld - sub;
@@ -140,14 +140,14 @@ __device__ __forceinline__ void value_chain(double r_eff, double disc, int ld, i
     chain_step2<8>(r_eff, disc, lim, sub, val);
     chain_step2<7>(r_eff, disc, lim, sub, val);
   }
-  if (wmax >= 5) {
-    chain_step2<6>(r_eff, disc, lim, sub, val);
-    chain_step2<5>(r_eff, disc, lim, sub, val);
-  }
-  if (wmax >= 4) chain_step2<4>(r_eff, disc, lim, sub, val);
-  if (wmax >= 3) chain_step2<3>(r_eff, disc, lim, sub, val);
-  if (wmax >= 2) chain_step2<2>(r_eff, disc, lim, sub, val);
-  if (wmax >= 1) chain_step2<1>(r_eff, disc, lim, sub, val);
+  // steps 6 .. 1 without a guard: of the waves of a C2 search (4096 trees x 50 simulations) 71 % reach depth 5 and 50 %
+  // depth 6; a compare-and-branch pair per step cost more than the steps a shallow wave now runs for nothing
+  chain_step2<6>(r_eff, disc, lim, sub, val);
+  chain_step2<5>(r_eff, disc, lim, sub, val);
+  chain_step2<4>(r_eff, disc, lim, sub, val);
+  chain_step2<3>(r_eff, disc, lim, sub, val);
+  chain_step2<2>(r_eff, disc, lim, sub, val);
+  chain_step2<1>(r_eff, disc, lim, sub, val);
 }
 
 
@@ -253,7 +253,7 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
     const bool act = !done;
     cw = act ? cw : -1;              // a finished row has no child to go to: `cw >= 0` alone says "walk on"
     // entry of the level just decided; a finished row rewrites the entry beyond its leaf (never read)
-    if (sub == 0) T.path[depth + 1] = make_int2(cw, sl);
+    T.path[depth + 1] = make_int2(cw, sl);       // row-uniform address and value: every lane of the row stores it
     depth += act ? 1 : 0;
     slot = act ? sl : slot;
     const bool go = cw >= 0;
@@ -267,7 +267,7 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
   w.vtp = (T.P == 1) ? 0 : ((st.root_to_play + depth) & 1);
   int leaf = st.n_nodes;
   if (leaf >= T.NN) { st.flags |= TF_NODE_OVERFLOW; leaf = T.NN - 1; }
-  if (sub == 0) T.path[depth] = make_int2(leaf, slot);
+  T.path[depth] = make_int2(leaf, slot);         // by the whole row, like the entries of the levels above
   const int ra = T.roota[slot < AW ? slot : 0];
   w.parent = node; w.slot = slot; w.leaf = leaf; w.depth = depth; w.levels = levels;
   w.action = (node == 0) ? ra : slot;
@@ -277,7 +277,7 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
 // What back-propagation needs about the path node a lane owns (lane j of chunk c <-> depth 16 c + j).
 template <int AW>
 struct Fc2Lane {
-  int nd, pslot, par, vc, tp;
+  int nd, pslot, par, vc, tp, rpar;    // rpar: the `parent` field the lane's node record keeps (root: -1)
   double vs, rr, inv_vc2, inv_vc3, pb, sv;
   int sn[AW <= 4 ? AW : 1];
   double sprior[AW <= 4 ? AW : 1], sinv[AW <= 4 ? AW : 1];
@@ -290,9 +290,9 @@ __device__ __forceinline__ Fc2Lane<AW> fc2_load_lane(const Fc2Tree& T, const Fc2
   Fc2Lane<AW> L;
   const int d = c * 16 + sub;
   // No guard on a READ: a lane at or beyond the leaf reads the leaf's path entry and, for the node record, the leaf's
-  // parent -- a real record, so every count below indexes its table in range.  Back-propagation guards every WRITE with
-  // `active` / `is_leaf`, and what a lane beyond the leaf hands down by row_shl only reaches the leaf lane, which the
-  // refresh skips; the leaf lane itself needs a fresh node's zeros (value_sum, visit) and the walk's player.
+  // parent -- a real record, so every count below indexes its table in range.  Such a lane ends up with the LEAF's operands
+  // (path entry, value_sum = 0, visit = 0, the walk's player): back-propagation computes the leaf's record in it once more and
+  // stores it to the leaf's address again (fc2_backprop), so no write needs a guard either.
   const bool inner = d < w.depth;
   const int dq = inner ? d : w.depth;
   const int2 pe = T.path[dq];
@@ -301,11 +301,11 @@ __device__ __forceinline__ Fc2Lane<AW> fc2_load_lane(const Fc2Tree& T, const Fc2
   const int nr = inner ? L.nd : L.par;
   const Fc2Node* np = T.nodes + nr;
   const double vs = np->value_sum;
-  const int vc = np->visit;
-  L.rr = np->reward;   // (beyond the leaf: the parent's reward -- the chain consumes lanes J <= ld and lane 0 of an active chunk only)
-  L.vs = inner ? vs : 0.0; L.vc = inner ? vc : 0;
-  L.tp = w.vtp;
-  if (T.P == 2) L.tp = inner ? np->to_play : w.vtp;
+  const int4 hv = *(const int4*)&np->visit;   // {visit, to_play, parent, parent_slot}: the record's second half in one read
+  L.rr = np->reward;   // (at and beyond the leaf: the parent's reward -- back-propagation replaces it by the leaf's)
+  L.vs = inner ? vs : 0.0; L.vc = inner ? hv.x : 0;
+  L.tp = inner ? hv.y : w.vtp;           // written back with the record; one player: compared by nobody
+  L.rpar = inner ? hv.z : L.par;         // the root keeps its -1 (its path entry names node 0 as its own parent)
   L.inv_vc2 = T.inv_y[L.vc + 1];        // reciprocal of this node's visit count after the update
   L.inv_vc3 = T.inv_y[L.vc + 2];        // ... and of (that + 1): what its PARENT's prior score divides by
   L.pb = T.pbc[L.vc + 1]; L.sv = T.sqt[L.vc + 1];
@@ -319,16 +319,18 @@ __device__ __forceinline__ Fc2Lane<AW> fc2_load_lane(const Fc2Tree& T, const Fc2
   return L;
 }
 
-// Node.expand (self_play.py:451-465): child slot `sub` of the new leaf (lanes < AW; `in`: the slot exists).
+// Node.expand (self_play.py:451-465): child slot `sub` of the new leaf (lanes < AW; `in`: the slot exists).  Whole rows only.
 template <int AW>
 __device__ __forceinline__ void fc2_expand(const Fc2Tree& T, int leaf, int sub, bool in, double prior) {
-  if (sub < AW) {
-    Fc2Slot s;
-    s.prior = in ? prior : 0.0;
-    s.q = 0.0; s.n = 0; s.child = -1;
-    s.ps = in ? T.pb_leaf * s.prior : -MZX_INF;   // prior score once the leaf has its first visit (N = 1, n = 0)
-    T.slots[leaf * AW + sub] = s;
-  }
+  Fc2Slot s;
+  s.prior = in ? prior : 0.0;
+  s.q = 0.0; s.n = 0; s.child = -1;
+  s.ps = in ? T.pb_leaf * s.prior : -MZX_INF;   // prior score once the leaf has its first visit (N = 1, n = 0)
+  // no exec mask: the lanes beyond the record lanes store into the tree's dead slot row ("node -1", see fc2_plan)
+  static_assert(AW <= 4 || AW == FUSED_ROW, "a dead slot row exists for 2- and 4-lane records only");
+  int at = leaf * AW + sub;
+  if constexpr (AW < FUSED_ROW) at = (sub < AW) ? at : -AW;
+  T.slots[at] = s;
 }
 
 // MCTS.backpropagate (self_play.py:406-430) + refresh of the cached prior scores along the path.  `L` = the
@@ -336,6 +338,7 @@ __device__ __forceinline__ void fc2_expand(const Fc2Tree& T, int leaf, int sub, 
 template <int AW>
 __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const Fc2Walk& w, Fc2Lane<AW> L, int sub,
                                              double value, double reward) {
+  static_assert(AW <= 4 || AW == FUSED_ROW, "a dead slot row exists for 2- and 4-lane records only");
   const int depth = w.depth, vtp = w.vtp, P = T.P;
   const double disc = T.disc;
   st.n_nodes = w.leaf + 1;
@@ -349,60 +352,67 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
     if (c != cmax) { wave_sync(); L = fc2_load_lane<AW>(T, w, c, sub); }
     const int d = c * 16 + sub;
     const int ld = depth - c * 16;             // row-uniform: depth of the leaf relative to this chunk
-    const bool active = d <= depth, is_leaf = d == depth;
-    const double rr = is_leaf ? reward : L.rr;
+    const bool inner = d < depth;               // lanes at AND beyond the leaf carry the leaf's operands (fc2_load_lane)
+    const double rr = inner ? L.rr : reward;
     const bool same = (L.tp == vtp);
     const double r_eff = (P == 1 || !same) ? rr : -rr;   // value = (+-reward) + discount * value
     const int wm = w.levels - c * 16;           // deepest leaf of the wave relative to this chunk (wave-uniform)
     value_chain(r_eff, disc, ld, sub, wm > 15 ? 15 : (wm < 0 ? 0 : wm), val);
     const double my_in = val;                   // the value arriving at this lane's node (lane 0: the chunk's final value)
-    // hand the value to the chunk above: lane 0's, through lane 0's node -- row-uniform again
-    if (c > 0 && ld >= 0) val = bcast_d<0>(r_eff) + disc * bcast_d<0>(val);
+    // hand the value to the chunk above: lane 0's, through lane 0's node -- row-uniform again.  Behind a scalar branch:
+    // the first chunk of a search no deeper than 15 plies (c == 0) issues none of it.
+    if (c > 0) {
+      const double nv = bcast_d<0>(r_eff) + disc * bcast_d<0>(val);
+      val = (ld >= 0) ? nv : val;
+    }
     const int vc2 = L.vc + 1;
     const double vs2 = L.vs + ((P == 1 || same) ? my_in : -my_in);
-    double qv = 0.0;
-    if (active) {
-      const double mean = div_by(vs2, (double)vc2, L.inv_vc2);
-      qv = rr + disc * ((P == 1) ? mean : -mean);
-      if (is_leaf) {
-        Fc2Node r;
-        r.value_sum = vs2; r.reward = reward; r.visit = vc2; r.to_play = vtp; r.parent = L.par; r.parent_slot = L.pslot;
-        T.nodes[L.nd] = r;
-        T.slots[L.par * AW + L.pslot].child = L.nd;
-      } else {
-        T.nodes[L.nd].value_sum = vs2;
-        T.nodes[L.nd].visit = vc2;
-      }
-      if (d > 0) {
+    // No store below has a guard (2- and 4-lane records).  An inner lane stores its own node; the lanes at and beyond the
+    // leaf ALL hold the leaf's operands and store the leaf's record, link and slot statistics -- the same values to the
+    // same addresses, as the walk stores a path entry.  The root lane has no parent slot: its {q, n, child} land in
+    // slot -1, the last record of the dead slot row in front of the tree's slots (fc2_plan), which nothing reads.
+    const double mean = div_by(vs2, (double)vc2, L.inv_vc2);
+    const double qv = rr + disc * ((P == 1) ? mean : -mean);
+    {
+      Fc2Node r;
+      r.value_sum = vs2; r.reward = rr; r.visit = vc2; r.to_play = L.tp; r.parent = L.rpar; r.parent_slot = L.pslot;
+      T.nodes[L.nd] = r;
+      // 16-lane records have no dead row (512 bytes a tree: a plan at the LDS budget no longer fitted);
+      // there the root lane is masked off
+      if (AW <= 4 || d > 0) {
         Fc2Slot* ps = T.slots + (L.par * AW + L.pslot);
         ps->q = qv;
-        ps->n = vc2;
+        *(int2*)&ps->n = make_int2(vc2, L.nd);     // {n, child}: the link is rewritten (inner node) or made (leaf)
       }
-      // MinMaxStats.update (self_play.py:562-564): pure min / max over the path nodes, order-free
-      __hip_atomic_fetch_min(&T.mm[0], qv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_max(&T.mm[1], qv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      // MinMaxStats.update (self_play.py:562-564): pure min / max over the path nodes, order-free.  The one guard that
+      // stays: LDS atomics of several lanes on ONE address are served lane after lane, and the ten or so lanes beyond
+      // the leaf repeating the leaf's value cost 9 % of the launch (profiles/fc2_tree_writes_ab.txt).
+      if (d <= depth) {
+        __hip_atomic_fetch_min(&T.mm[0], qv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_max(&T.mm[1], qv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
     }
     // prior scores of this node's child slots at its new visit count N = vc2 (see header).  The slot on the
     // path just received the child's new visit count: taken from the lane above instead of LDS.
     if constexpr (AW <= 4) {
       const int ch_vc2 = shl1_i(vc2, carry_vc2), ch_slot = shl1_i(L.pslot, carry_pslot);
       const double ch_inv = shl1_d(L.inv_vc3, carry_inv);
-      if (active && !is_leaf) {
-        const int nslots = (L.nd == 0) ? st.root_n : T.A;
+      // unconditional: a lane without an inner node aims at the dead slot row; a slot beyond the node's actions holds
+      // -inf and receives -inf
+      const int nslots = (L.nd == 0) ? st.root_n : T.A;
+      Fc2Slot* sp = T.slots + (inner ? L.nd : -1) * AW;
 #pragma unroll
-        for (int s = 0; s < AW; ++s) {
-          if (s < nslots) {
-            const bool on_path = (s == ch_slot);
-            const int ns = on_path ? ch_vc2 : L.sn[s];
-            const double iv = on_path ? ch_inv : L.sinv[s];
-            T.slots[L.nd * AW + s].ps = prior_score(L.pb, L.sv, ns, iv, L.sprior[s]);
-          }
-        }
+      for (int s = 0; s < AW; ++s) {
+        const bool on_path = (s == ch_slot);
+        const int ns = on_path ? ch_vc2 : L.sn[s];
+        const double iv = on_path ? ch_inv : L.sinv[s];
+        const double psc = prior_score(L.pb, L.sv, ns, iv, L.sprior[s]);
+        sp[s].ps = (s < nslots) ? psc : -MZX_INF;
       }
       carry_vc2 = bcast_i<0>(vc2); carry_pslot = bcast_i<0>(L.pslot); carry_inv = bcast_d<0>(L.inv_vc3);
     } else {
       wave_sync();
-      if (active && !is_leaf) {
+      if (inner) {
         Fc2Slot* sp = T.slots + L.nd * AW;
         const int nslots = (L.nd == 0) ? st.root_n : T.A;
         for (int s = 0; s < nslots; ++s) {
@@ -658,12 +668,18 @@ inline Fc2Plan fc2_plan(const mzx_search* s, bool allow_small = true) {
   a.f.lds_weights = (int32_t)o; o += P.small ? 0 : al16(int64_t(4) * s->net->num_params);
   a.f.lds_trees = (int32_t)o;
   int64_t t = 0;
+  // 2- and 4-lane records: the dead slot row, "node -1", in front of the slots.  It takes the unguarded stores of lanes that
+  // own no slot (fc2_backprop, fc2_expand) and is never read: the walk, fc2_load_lane, the export and fc2_from_arena start at
+  // node 0.  16-lane records have none (512 bytes a tree: fc2_backprop keeps its guards there).
+  t += AW <= 4 ? int64_t(32) * AW : 0;
   a.off_slots = (int32_t)t;   t += int64_t(32) * N * AW;
   a.off_nodes = (int32_t)t;   t += int64_t(32) * N;
   a.off_path = (int32_t)t;    t += al16(int64_t(8) * (N + 1));
   a.off_roota = (int32_t)t;   t += al16(int64_t(4) * AW);
   a.off_mm = (int32_t)t;      t += 16;
-  a.off_hidden = (int32_t)t;  t += al16(int64_t(4) * N * E);
+  // SmallNet stores a hidden state by the whole row: the lanes >= E spill into the next node's state (written before it is
+  // read) or, for node N - 1, into a dead tail of FUSED_ROW - E floats
+  a.off_hidden = (int32_t)t;  t += al16(int64_t(4) * (N * E + (P.small && E < FUSED_ROW ? FUSED_ROW - E : 0)));
   a.off_scratch = (int32_t)t; t += int64_t(4) * (P.small ? 16 : FUSED_SCRATCH);
   // the four rows of a wave touch the same offsets of four consecutive slabs in one instruction:
   // keep the slab stride off the multiples of 256 bytes so that they land in different bank groups

@@ -173,7 +173,8 @@ __device__ __forceinline__ float row_decode_wide(const float* lg, int F, int sup
 // floats of LDS per tree / per workgroup for the record form of an LDS-resident tree (TREC kernels)
 __host__ __device__ inline int64_t rz_trec_tree_floats(int N, int AW) {
   auto al16 = [](int64_t x) { return (x + 15) & ~int64_t(15); };
-  return (int64_t(32) * N * AW + int64_t(32) * N + al16(int64_t(8) * (N + 1)) + al16(int64_t(4) * AW) + 16) / 4;
+  // 4-lane records: N + 1 slot rows, the first is the dead row in front of node 0 (fc2_plan, mzx_fused_fc2.h)
+  return (int64_t(32) * (N + (AW <= 4 ? 1 : 0)) * AW + int64_t(32) * N + al16(int64_t(8) * (N + 1)) + al16(int64_t(4) * AW) + 16) / 4;
 }
 inline int64_t rz_trec_extra_floats(int N) { return 2 * (int64_t)(N + 2); }   // refined-reciprocal table
 
@@ -201,8 +202,8 @@ __device__ __forceinline__ void fc2_to_arena(const Fc2Tree& FT, const Fc2Row& rs
 // Carves one tree's records out of `rec` (rz_trec_tree_floats(NN, RW) floats)
 template <int RW>
 __device__ __forceinline__ void fc2_carve(Fc2Tree& FT, char* rec, int NN) {
-  FT.slots = (Fc2Slot*)rec;
-  FT.nodes = (Fc2Node*)(rec + (size_t)32 * NN * RW);
+  FT.slots = (Fc2Slot*)rec + (RW <= 4 ? RW : 0);       // behind the dead slot row (4-lane records)
+  FT.nodes = (Fc2Node*)(rec + (size_t)32 * (NN + (RW <= 4 ? 1 : 0)) * RW);
   FT.path = (int2*)((char*)FT.nodes + (size_t)32 * NN);
   FT.roota = (int32_t*)((char*)FT.path + (((size_t)8 * (NN + 1) + 15) & ~(size_t)15));
   FT.mm = (double*)((char*)FT.roota + (((size_t)4 * RW + 15) & ~(size_t)15));
