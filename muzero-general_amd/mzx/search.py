@@ -123,7 +123,9 @@ class BatchedMCTS:
         except Exception:
             pass
 
-    def handle(self, num_trees, tape_words=TAPE_WORDS):
+    def handle(self, num_trees, tape_words=None):
+        if tape_words is None:      # (read at call time: a caller that set TAPE_WORDS gets the handle its searches ran on)
+            tape_words = TAPE_WORDS
         key = num_trees if tape_words == TAPE_WORDS else (num_trees, tape_words)
         if key not in self._handles:
             lib = self.backend.lib

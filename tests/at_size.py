@@ -49,8 +49,9 @@ GATES = {
     "connect4-9216": (0.60, 0.88, 0.12, 0.006, 5e-2),                                 # 48/64      61/64        0.045    1.7e-3    1.5e-2
     # games/gomoku.py: 400 simulations dig 100- to 400-ply single lines; the oracle's OWN fp32 and binary64 searches share no
     # tree and end at distributions 0.27 .. 0.40 apart (L1 0.10 .. 0.23) -- the device is as far from the fp32 oracle as exact
-    # arithmetic is.  The bounds are what a search on garbage would break (max dv -> 1, L1 -> 2), no more; the margin gate at
-    # every first divergence is the sharp check for these trees
+    # arithmetic is.  The bounds are what a search on garbage would break (max dv -> 1, L1 -> 2), no more; walks deeper than a
+    # wavefront has lanes are held bit for bit to the per-operator path by the `last` cases of tests/test_gpu_tree_edges.py
+    # (70 plies at 128 and 129 actions, row and wavefront selection), and that path to the oracle by tests/tree_edge_cases.py
     "gomoku-1024": (0.0, 0.0, 0.70, 0.40, 3.0),                                       # 0/16       2/16         0.415    0.158     1.05
     "gomoku-1024 (reference weights)": (0.0, 0.35, 0.65, 0.35, 1.0),                  # 0/16       10/16        0.39     0.157     0.37
     # rt_search_kernel at the other shard sizes (tests/test_gpu_tower_search.py)

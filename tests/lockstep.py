@@ -59,7 +59,7 @@ def rng_inputs(cfg, cases, A, tape_words=LOCKSTEP_TAPE_WORDS):
 
 
 class Lockstep:
-    def __init__(self, backend, cfg, B, S, hidden_net=None):
+    def __init__(self, backend, cfg, B, S, hidden_net=None, tape_words=LOCKSTEP_TAPE_WORDS):
         self.be, self.lib, self.cfg, self.B, self.S = backend, backend.lib, cfg, B, S
         self.A = len(cfg.action_space)
         n = S + 1
@@ -67,7 +67,7 @@ class Lockstep:
         self._sqrt = (ctypes.c_double * n)(*[math.sqrt(k) for k in range(n)])
         c = _lib.SearchConfig()
         c.num_trees, c.num_simulations, c.action_space_size = B, S, self.A
-        c.num_players, c.support_size, c.tape_words = len(cfg.players), cfg.support_size, LOCKSTEP_TAPE_WORDS
+        c.num_players, c.support_size, c.tape_words = len(cfg.players), cfg.support_size, tape_words
         c.discount, c.root_exploration_fraction = float(cfg.discount), float(cfg.root_exploration_fraction)
         c.h_pb_c_table = ctypes.cast(self._pbc, ctypes.POINTER(ctypes.c_double))
         c.h_sqrt_table = ctypes.cast(self._sqrt, ctypes.POINTER(ctypes.c_double))
@@ -84,10 +84,11 @@ class Lockstep:
     def run(self, legal, noise, tape, to_play, values, rewards, priors, check_select=None):
         """
         values/rewards: [B][S+1] float64, priors: [B][S+1][A] float64 (node order = expansion order).
+        tape: [B][tape_words of the handle]; noise None: a search without exploration noise.
         check_select(k, parent, action, leaf) is called per simulation with host arrays.
         """
         be, lib, B, S, A = self.be, self.lib, self.B, self.S, self.A
-        t_legal, t_noise = self.dev(legal, torch.int32), self.dev(noise, torch.float64)
+        t_legal, t_noise = self.dev(legal, torch.int32), None if noise is None else self.dev(noise, torch.float64)
         t_tape, t_tp = self.dev(tape.view(numpy.int32), torch.int32), self.dev(to_play, torch.int32)
         out = dict(visits=be.zeros((B, A), torch.int32), root_value=be.zeros((B,), torch.float64),
                    info=be.zeros((B, 4), torch.int32))

@@ -20,7 +20,7 @@ import lockstep
 import shipped_shapes
 import test_hostcheck_search as common
 from conftest import GOLDEN
-from mzx import _lib, configs, models, self_play, synthetic
+from mzx import _lib, configs, models, search, self_play, synthetic
 from oracle import mcts_oracle, net_oracle, parallel
 
 pytestmark = pytest.mark.gpu
@@ -799,20 +799,29 @@ def test_tie_tape_overflow_through_the_small_board_kernels(backend, name):
     obs = synthetic.observations(B, net.input_shape, seed=3)
     legal = [list(cfg.action_space)] * B
     outs = []
-    old = self_play.TAPE_WORDS
+    old = search.TAPE_WORDS      # (the engine reads the module constant of mzx.search; mzx.self_play only re-exports its value)
     try:
-        for words in (4, 4096):
-            self_play.TAPE_WORDS = words
-            engine = self_play.BatchedMCTS(cfg, net, B)
+        for words, mode in ((4, None), (4096, None), (4096, 0)):
+            search.TAPE_WORDS = words
+            engine = self_play.BatchedMCTS(cfg, net, B, mode=mode)
             res = engine.run(list(obs), legal, [0] * B, True, [numpy.random.RandomState(40 + i) for i in range(B)])
             outs.append(res)
     finally:
-        self_play.TAPE_WORDS = old
-    short, long_ = outs
+        search.TAPE_WORDS = old
+    short, long_, per_operator = outs
     assert (short.tape_used > 4).any()
     assert numpy.array_equal(short.visit_counts, long_.visit_counts)
     assert numpy.array_equal(short.root_values.view(numpy.int64), long_.root_values.view(numpy.int64))
     assert numpy.array_equal(short.tape_used, long_.tape_used) and (short.flags == 0).all()
+    # ... and the long-tape result is the per-operator path's (mode 0), bit for bit: ties among up to nine children, whose
+    # draws reject tape words, so the tape position is part of the comparison
+    assert (long_.tape_used < 4096).all(), long_.tape_used
+    assert numpy.array_equal(long_.visit_counts, per_operator.visit_counts)
+    assert numpy.array_equal(long_.root_values.view(numpy.int64), per_operator.root_values.view(numpy.int64))
+    assert numpy.array_equal(long_.root_predicted_values.view(numpy.int64), per_operator.root_predicted_values.view(numpy.int64))
+    assert numpy.array_equal(long_.max_tree_depth, per_operator.max_tree_depth)
+    assert numpy.array_equal(long_.tape_used, per_operator.tape_used), (long_.tape_used, per_operator.tape_used)
+    assert (long_.flags == 0).all() and (per_operator.flags == 0).all()
 
 
 @pytest.mark.parametrize("net_name", ["cartpole", "tictactoe"])

@@ -14,7 +14,7 @@ import torch
 import hostcheck
 import lockstep
 from conftest import GOLDEN
-from mzx import configs, models, self_play, synthetic
+from mzx import configs, models, search, self_play, synthetic
 
 NET_FOR_GAME = {"cartpole": "net_fc_cartpole.npz", "tictactoe": "net_resnet_tictactoe.npz",
                 "connect4": "net_resnet_connect4.npz", "lunarlander": "net_fc_lunarlander_pretrained.npz"}
@@ -132,8 +132,8 @@ def _zero_weight_search(backend, rngs_kind, tape_words):
     B = 3
     obs = synthetic.observations(B, cfg.observation_shape, seed=3)
     legal = [list(cfg.action_space)] * B
-    old = self_play.TAPE_WORDS
-    self_play.TAPE_WORDS = tape_words
+    old = search.TAPE_WORDS      # (the engine reads the module constant of mzx.search; mzx.self_play only re-exports its value)
+    search.TAPE_WORDS = tape_words
     try:
         engine = self_play.BatchedMCTS(cfg, net, B)
         if rngs_kind == "bank":
@@ -146,7 +146,7 @@ def _zero_weight_search(backend, rngs_kind, tape_words):
             res = engine.run(list(obs), legal, [0] * B, True, rngs)
             final = [r.get_state() for r in rngs]
     finally:
-        self_play.TAPE_WORDS = old
+        search.TAPE_WORDS = old
     return res, final
 
 
