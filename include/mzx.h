@@ -499,6 +499,57 @@ int mzx_selfplay_select(mzx_rng* r, const mzx_move* m, const int32_t* n_legal, c
                         int64_t* action);
 
 /* ------------------------------------------------------------------------- *
+ * Self-play draws on the device (opt-in, config.device_draws; csrc/mzx_draws.h holds the definition in full): root noise,
+ * tie-break tape and action choice as a pure function of (seed, stream, counter) -- NOT numpy's draws, no mzx_rng involved.
+ *   seed: what separates one actor's draws from another's -- mzx.self_play passes the actor's own seed (the one its games
+ *     and, on host draws, its bank streams are seeded from), not a value shared by every rank of a job.
+ *   Words: Philox4x32-10, key = (seed lo, seed hi ^ 0x53454C46), counter = (stream, counter lo, counter hi,
+ *     (purpose << 30) | index); purpose 0 noise, 1 tape, 2 action.  stream k = d_streams[k], or first_stream + k when
+ *     d_streams is NULL.  Uniforms: ((w0 << 21) | (w1 >> 11)) * 2^-53, then the same of w2, w3, of consecutive blocks.
+ *   Tape: word 4b + j of row k is word j of block index b (a longer tape begins with the shorter one).
+ *   Noise: child j < n draws g_j = standard_gamma(dirichlet_alpha) by numpy's legacy algorithm (csrc/mzx_rng.h) from the
+ *     uniforms of blocks index (j << 14) | 0, 1, ...; noise_j = g_j / (g_0 + ... + g_{n-1}) (left-to-right binary64 sum),
+ *     0.0 for j >= n; 1.0 / n when the sum is 0 or not finite.  n = entries >= 0 of the row of d_legal_actions, or d_n[k]
+ *     when d_legal_actions is NULL (continued searches).  d_noise NULL: no noise.
+ *   Action: u = first uniform of block (purpose 2, index 0), or d_uniforms[k] (tests).  Temperature 0: first maximum of the
+ *     visit counts in legal order; +inf: position min(n - 1, floor(u * n)); else w_j = pow_table[row(T)][count_j] (a count
+ *     outside the table weighs 0), inclusive left-to-right prefix P_j, t = u * P_{n-1}: the smallest j with P_j > t, else the
+ *     last j with w_j > 0.  d_action[k] = legal[j]; -1 for a row without a legal action or a temperature without a table row.
+ * Every pointer is a device pointer.  MZX_ERR_INVALID before any launch for: tape_words < 1, action_space_size > 4096,
+ * missing outputs, noise without a row count.  One launch each, a wavefront per game.
+ * mzx_selfplay_move_device: mzx_selfplay_search + mzx_selfplay_select with these draws -- legal rows validated on the
+ *   host and staged as there (m->streams and the bank are not used), then upload, draws into io.d_noise / io.d_tape
+ *   (m->dirichlet_alpha), mzx_search_run, the action choice on io.d_legal_actions / io.d_visit_counts (sel's two row
+ *   pointers are ignored; sel NULL: no action choice), download, synchronisation unless MZX_MOVE_NO_SYNC -- all on `stream`.  sel->d_temperature and
+ *   the power table must be on the device when the call is made (inside d_in: the call uploads h_in); sel->d_action inside
+ *   d_out arrives in h_out.  io.d_noise must be set exactly when m->add_exploration_noise is.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_draws {
+  uint64_t seed, counter;
+  const int32_t* d_streams;        /* [B] nullable */
+  int32_t first_stream, num_games, action_space_size, tape_words;
+  double dirichlet_alpha;
+  const int32_t* d_legal_actions;  /* [B][A] padded with -1, or NULL */
+  const int32_t* d_n;              /* [B] children per root, read when d_legal_actions is NULL */
+  double* d_noise;                 /* out [B][A], nullable */
+  uint32_t* d_tape;                /* out [B][tape_words] */
+} mzx_draws;
+typedef struct mzx_draws_select {
+  const int32_t* d_legal_actions;  /* [B][A] */
+  const int32_t* d_visit_counts;   /* [B][A] by action */
+  const double* d_temperature;     /* [B] */
+  const double* d_pow_table;       /* [num_temperatures][table_stride] */
+  const double* d_table_temperatures;
+  int32_t table_stride, num_temperatures;
+  const double* d_uniforms;        /* [B] nullable */
+  int64_t* d_action;               /* out [B] */
+} mzx_draws_select;
+int mzx_selfplay_draws(const mzx_draws* draws, void* stream);
+int mzx_selfplay_select_device(const mzx_draws* draws, const mzx_draws_select* sel, void* stream);
+int mzx_selfplay_move_device(mzx_search* s, const mzx_move* m, const mzx_draws* draws, const mzx_draws_select* sel,
+                             int32_t* n_legal, void* d_arena, int64_t arena_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Replay hand-off: the INITIAL prioritised-replay priorities of finished games on the device --
  * ReplayBuffer.save_game, replay_buffer.py:39-51, with compute_target_value (:230-262) -- for G games of T searched
  * positions each (a shard record: games that started and ended together).  Device arrays:
@@ -903,6 +954,20 @@ typedef struct mzx_rounds {
                                       retries, 5 the rest of the call */
 } mzx_rounds;
 int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds* io, void* stream);
+/* Device draws for a slot group (csrc/mzx_draws.h; before its first round or between calls): from now on the group's moves
+ * go through mzx_selfplay_move_device -- seed, counter = first_counter + the number of searches the group has begun since,
+ * streams = the group's slots (its `streams` must be consecutive) -- and no stream of the bank is read or advanced.
+ * d_temperature [B] f64 inside move.d_in and d_action [B] i64 inside move.d_out: the loop writes every move's temperatures
+ * (temperature_threshold gate) into the input block and reads the chosen actions from the output block; the move's
+ * io.d_noise / io.d_tape may lie outside the staged blocks (device scratch).  A game whose search raised the tape-overflow
+ * flag goes through the retry callback as before (the callback draws the longer tape with mzx_selfplay_draws under the same
+ * stream and counter, mzx_actor_draw_counter - 1); its action is then taken by the same function on the host.
+ * mzx_actor_draw_counter: the counter of the group's NEXT search (-1 for a null actor). */
+int mzx_actor_set_device_draws(mzx_actor* actor, uint64_t seed, uint64_t first_counter, double* d_temperature, int64_t* d_action);
+int64_t mzx_actor_draw_counter(const mzx_actor* actor);
+/* The counter of the group's next search (a checkpoint's restore); refused while a search is in flight or before
+ * mzx_actor_set_device_draws. */
+int mzx_actor_set_draw_counter(mzx_actor* actor, uint64_t counter);
 int mzx_actor_finished(mzx_actor* a, int64_t before_sequence, int64_t out[3]);
 int mzx_actor_take(mzx_actor* a, int64_t before_sequence, int32_t* slot, int32_t* length, int64_t* sequence, float* observations, int64_t* actions,
                    double* rewards, int64_t* to_play, int32_t* visit_counts, double* root_values, uint8_t* legal_mask,

@@ -69,6 +69,13 @@ struct mzx_actor {
   // (taken by mzx_actor_take, possibly from another thread while a rounds call is appending: the queue has its own lock)
   std::deque<Batch> finished;
   std::mutex finished_lock;
+  // device draws (mzx_actor_set_device_draws; mzx_draws.h): the group's search number is the counter, its slots the streams
+  bool device_draws = false;
+  uint64_t draw_seed = 0, draw_counter = 0;          // draw_counter: of the NEXT search
+  double* d_temperature = nullptr;                    // [B] inside move.d_in
+  int64_t* d_action = nullptr;                        // [B] inside move.d_out
+  void* d_pow = nullptr;                              // device copy of the call's power table + its temperatures
+  std::vector<double> pow_host;                       // what d_pow holds
 };
 
 namespace mzx {
@@ -116,7 +123,18 @@ inline void actor_refresh(mzx_actor* a) {
   });
 }
 
-inline int actor_begin(mzx_actor* a, void* stream, double* search_seconds, double* phase) {
+// the temperature of every slot's next move (self_play.py:151-157)
+inline void actor_move_temps(mzx_actor* a, int32_t temperature_threshold) {
+  for (int k = 0; k < a->B; ++k) {
+    const int64_t moves_before = a->round - a->start[k];
+    a->move_temps[k] = (temperature_threshold && moves_before + 1 >= temperature_threshold) ? 0.0 : a->temps[k];
+  }
+}
+
+struct RoundsArgs;
+inline int actor_begin_device(mzx_actor* a, const RoundsArgs& args, void* stream);
+
+inline int actor_begin(mzx_actor* a, const RoundsArgs& args, void* stream, double* search_seconds, double* phase) {
   const double t0 = actor_now();
   mzx_move& m = a->move;
   m.streams = a->streams.data();
@@ -125,7 +143,8 @@ inline int actor_begin(mzx_actor* a, void* stream, double* search_seconds, doubl
   m.observation = a->cur_obs.data();
   m.observation_floats = a->E;
   m.flags = MZX_MOVE_NO_SYNC;
-  int rc = mzx_selfplay_search(a->search, a->bank, &m, a->n_legal.data(), a->d_arena, a->arena_bytes, stream);
+  int rc = a->device_draws ? actor_begin_device(a, args, stream)
+                           : mzx_selfplay_search(a->search, a->bank, &m, a->n_legal.data(), a->d_arena, a->arena_bytes, stream);
   if (rc) return rc;
   rc = event_record(&a->event, (stream_t)stream);
   if (rc) { set_error("mzx_selfplay_rounds: event record failed: %s", runtime_error_string(rc)); return MZX_ERR_RUNTIME; }
@@ -204,6 +223,43 @@ struct RoundsArgs {
   actor_retry_fn retry; void* retry_ctx;
 };
 
+// the device-draws move of a group: temperatures into the input block, then upload, draws, search, action choice and
+// download behind one call (mzx_selfplay_move_device); no host stream is touched
+inline int actor_begin_device(mzx_actor* a, const RoundsArgs& args, void* stream) {
+  mzx_move& m = a->move;
+  actor_move_temps(a, args.temperature_threshold);
+  double* h_temps = (double*)((char*)m.h_in + ((const char*)a->d_temperature - (const char*)m.d_in));
+  memcpy(h_temps, a->move_temps.data(), sizeof(double) * (size_t)a->B);
+  mzx_draws d{};
+  d.seed = a->draw_seed; d.counter = a->draw_counter; d.first_stream = a->streams[0];
+  d.num_games = a->B; d.action_space_size = a->A; d.tape_words = m.tape_words; d.dirichlet_alpha = m.dirichlet_alpha;
+  mzx_draws_select sel{};
+  sel.d_temperature = a->d_temperature; sel.d_action = a->d_action;
+  if (args.num_temperatures > 0) {
+    sel.d_pow_table = (const double*)a->d_pow;
+    sel.d_table_temperatures = (const double*)a->d_pow + (size_t)args.num_temperatures * args.table_stride;
+    sel.table_stride = args.table_stride; sel.num_temperatures = args.num_temperatures;
+  }
+  const int rc = mzx_selfplay_move_device(a->search, &m, &d, &sel, a->n_legal.data(), a->d_arena, a->arena_bytes, stream);
+  if (rc == MZX_OK) ++a->draw_counter;
+  return rc;
+}
+
+// the call's power table on the device (uploaded when it differs from what the actor holds; blocking, before any search)
+inline int actor_upload_pow(mzx_actor* a, const RoundsArgs& args) {
+  if (!a->device_draws || args.num_temperatures < 1) return MZX_OK;
+  const size_t n = (size_t)args.num_temperatures * args.table_stride, total = n + (size_t)args.num_temperatures;
+  std::vector<double> want(total);
+  memcpy(want.data(), args.pow_table, sizeof(double) * n);
+  memcpy(want.data() + n, args.table_temperatures, sizeof(double) * (size_t)args.num_temperatures);
+  if (a->d_pow && want.size() == a->pow_host.size() && memcmp(want.data(), a->pow_host.data(), sizeof(double) * total) == 0) return MZX_OK;
+  if (a->d_pow) { device_free(a->d_pow); a->d_pow = nullptr; a->pow_host.clear(); }
+  if (device_alloc(&a->d_pow, sizeof(double) * total) != 0) { a->d_pow = nullptr; set_error("mzx_selfplay_rounds: power table allocation failed"); return MZX_ERR_RUNTIME; }
+  if (copy_h2d_blocking(a->d_pow, want.data(), sizeof(double) * total) != 0) { set_error("mzx_selfplay_rounds: power table upload failed"); return MZX_ERR_RUNTIME; }
+  a->pow_host.swap(want);
+  return MZX_OK;
+}
+
 inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_t* sequence, int64_t* games_done,
                          double* search_seconds) {
   const double t0 = actor_now();
@@ -237,12 +293,23 @@ inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_
   for (int k = 0; k < B; ++k)
     if (info[4 * k + 1] != 0) { set_error("search flagged tree %d (flags %d): node arena exhausted", k, info[4 * k + 1]); return MZX_ERR_RUNTIME; }
   const int64_t r = a->round;
-  for (int k = 0; k < B; ++k) {
-    a->words[k] = info[4 * k + 2];
-    const int64_t moves_before = r - a->start[k];
-    a->move_temps[k] = (args.temperature_threshold && moves_before + 1 >= args.temperature_threshold) ? 0.0 : a->temps[k];   // self_play.py:151-157
+  const bool dev = a->device_draws;
+  if (!dev) for (int k = 0; k < B; ++k) a->words[k] = info[4 * k + 2];      // (what the host streams consume; device draws consume nothing)
+  actor_move_temps(a, args.temperature_threshold);
+  if (dev) {
+    // the device chose the actions; the few games searched again take theirs by the same function on the host
+    memcpy(a->actions.data(), host_of(a->d_action), sizeof(int64_t) * (size_t)B);
+    if (!redo.empty()) {
+      SelfplaySelectParams sp{};
+      sp.seed = a->draw_seed; sp.counter = a->draw_counter - 1; sp.first_stream = a->streams[0];
+      sp.legal = a->legal.data(); sp.visits = visits; sp.temperature = a->move_temps.data(); sp.pow_table = args.pow_table;
+      sp.table_temperatures = args.table_temperatures; sp.action = a->actions.data(); sp.B = B; sp.A = A;
+      sp.table_stride = args.table_stride; sp.num_temperatures = args.num_temperatures;
+      for (int32_t k : redo) a->actions[k] = draw_select_action(sp, (size_t)k);
+    }
   }
   if (A > 4096) { set_error("mzx_selfplay_rounds: more than 4096 actions"); return MZX_ERR_INVALID; }
+  // (host draws: what select_range indexes; device draws: the same table rows and bounds the device's choice relied on)
   rc = select_check(a->legal.data(), a->n_legal.data(), visits, a->move_temps.data(), B, A, args.table_stride, args.table_temperatures,
                     args.num_temperatures);
   if (rc) return rc;
@@ -261,7 +328,7 @@ inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_
   // the move's row of the log -- position searched (observation, side to move), action, search statistics, legal set --,
   // Game.step, the reward, and the next position (observation, side to move, legal actions) for the next search
   rng_parallel(a->bank, B, m.num_threads, [=](int lo, int hi) {
-    select_range(sa, lo, hi);
+    if (!dev) select_range(sa, lo, hi);
     const size_t n = (size_t)(hi - lo);
     memcpy(&a->r_obs[(size_t)((c * B + lo) * E)], &a->cur_obs[(size_t)lo * E], sizeof(float) * n * (size_t)E);
     memcpy(&a->r_tp[(size_t)(c * B + lo)], &a->to_play[lo], sizeof(int32_t) * n);

@@ -8,6 +8,7 @@
 #include <new>
 #include <string>
 
+#include "mzx_draws.h"
 #include "mzx_obs.h"
 #include "mzx_replay.h"
 #include "mzx_rng.h"
@@ -1192,6 +1193,131 @@ int mzx_selfplay_select(mzx_rng* r, const mzx_move* m, const int32_t* n_legal, c
   return MZX_OK;
 }
 
+// ------------------------------------------------------------- self-play draws on the device (mzx_draws.h)
+
+static int draws_check(const char* who, const mzx_draws* d) {
+  if (!d) { set_error("%s: null mzx_draws", who); return MZX_ERR_INVALID; }
+  if (d->num_games < 1 || d->action_space_size < 1) { set_error("%s: num_games and action_space_size must be positive", who); return MZX_ERR_INVALID; }
+  if (d->action_space_size > DRAWS_MAX_ACTIONS) {
+    set_error("%s: %d actions, the device draws take at most %d", who, d->action_space_size, DRAWS_MAX_ACTIONS);
+    return MZX_ERR_INVALID;
+  }
+  return MZX_OK;
+}
+
+int mzx_selfplay_draws(const mzx_draws* d, void* stream) {
+  const int rc = draws_check("mzx_selfplay_draws", d);
+  if (rc) return rc;
+  if (d->tape_words < 1) { set_error("mzx_selfplay_draws: tape_words %d must be at least 1", d->tape_words); return MZX_ERR_INVALID; }
+  if (!d->d_tape) { set_error("mzx_selfplay_draws: d_tape missing"); return MZX_ERR_INVALID; }
+  if (d->d_noise && !d->d_legal_actions && !d->d_n) {
+    set_error("mzx_selfplay_draws: noise needs d_legal_actions or d_n");
+    return MZX_ERR_INVALID;
+  }
+  if (d->d_noise && !(d->dirichlet_alpha > 0.0 && d->dirichlet_alpha <= 1.7976931348623157e308)) {
+    set_error("mzx_selfplay_draws: dirichlet_alpha %g must be positive and finite", d->dirichlet_alpha);
+    return MZX_ERR_INVALID;
+  }
+  SelfplayDrawsParams p;
+  p.seed = d->seed; p.counter = d->counter; p.streams = d->d_streams; p.legal = d->d_legal_actions; p.n_rows = d->d_n;
+  p.noise = d->d_noise; p.tape = d->d_tape; p.alpha = d->dirichlet_alpha; p.first_stream = d->first_stream;
+  p.B = d->num_games; p.A = d->action_space_size; p.tape_words = d->tape_words;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(SelfplayDrawsBody{p}, (stream_t)stream));
+  return MZX_OK;
+}
+
+static int draws_select_params(const char* who, const mzx_draws* d, const mzx_draws_select* sel, SelfplaySelectParams* p,
+                               bool rows_of_move = false) {
+  const int rc = draws_check(who, d);
+  if (rc) return rc;
+  if (!sel) { set_error("%s: null mzx_draws_select", who); return MZX_ERR_INVALID; }
+  if ((!rows_of_move && (!sel->d_legal_actions || !sel->d_visit_counts)) || !sel->d_temperature || !sel->d_action) {
+    set_error("%s: d_legal_actions, d_visit_counts, d_temperature and d_action are required", who);
+    return MZX_ERR_INVALID;
+  }
+  if (sel->num_temperatures < 0 ||
+      (sel->num_temperatures > 0 && (!sel->d_pow_table || !sel->d_table_temperatures || sel->table_stride < 1))) {
+    set_error("%s: power table missing", who);
+    return MZX_ERR_INVALID;
+  }
+  p->seed = d->seed; p->counter = d->counter; p->streams = d->d_streams; p->legal = sel->d_legal_actions;
+  p->visits = sel->d_visit_counts; p->temperature = sel->d_temperature; p->pow_table = sel->d_pow_table;
+  p->table_temperatures = sel->d_table_temperatures; p->uniforms = sel->d_uniforms; p->action = sel->d_action;
+  p->first_stream = d->first_stream; p->B = d->num_games; p->A = d->action_space_size; p->table_stride = sel->table_stride;
+  p->num_temperatures = sel->num_temperatures;
+  return MZX_OK;
+}
+
+int mzx_selfplay_select_device(const mzx_draws* d, const mzx_draws_select* sel, void* stream) {
+  SelfplaySelectParams p;
+  const int rc = draws_select_params("mzx_selfplay_select_device", d, sel, &p);
+  if (rc) return rc;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(SelfplaySelectBody{p}, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_selfplay_move_device(mzx_search* s, const mzx_move* m, const mzx_draws* d, const mzx_draws_select* sel, int32_t* n_legal,
+                             void* d_arena, int64_t arena_bytes, void* stream) {
+  const char* who = "mzx_selfplay_move_device";
+  if (!m) { set_error("%s: null mzx_move", who); return MZX_ERR_INVALID; }
+  if (!s || !n_legal || !m->legal_actions || !m->to_play || !m->h_in || !m->d_in || !m->h_out || !m->d_out || m->in_bytes < 1 ||
+      m->out_bytes < 1) {
+    set_error("%s: missing buffer", who);
+    return MZX_ERR_INVALID;
+  }
+  SelfplaySelectParams sp;
+  int rc = sel ? draws_select_params(who, d, sel, &sp, true) : draws_check(who, d);      // (no sel: no action choice)
+  if (rc) return rc;
+  const int B = m->num_games, A = m->action_space_size, W = m->tape_words;
+  if (B != d->num_games || A != d->action_space_size || W != d->tape_words || W < 1) {
+    set_error("%s: the move and the draws disagree on num_games / action_space_size / tape_words (>= 1)", who);
+    return MZX_ERR_INVALID;
+  }
+  const mzx_search_io& io = m->io;
+  if (m->add_exploration_noise ? !io.d_noise : io.d_noise != nullptr) {
+    set_error("%s: io.d_noise must be set with add_exploration_noise and NULL without", who);
+    return MZX_ERR_INVALID;
+  }
+  if (!io.d_tape || !io.d_visit_counts) { set_error("%s: io.d_tape / io.d_visit_counts missing", who); return MZX_ERR_INVALID; }
+  int32_t* h_legal = (int32_t*)move_host(io.d_legal_actions, m->d_in, m->h_in, m->in_bytes);
+  int32_t* h_to_play = (int32_t*)move_host(io.d_to_play, m->d_in, m->h_in, m->in_bytes);
+  float* h_obs = (float*)move_host(io.d_observation, m->d_in, m->h_in, m->in_bytes);
+  if (!h_legal || !h_to_play || (m->observation && !h_obs) || (!m->observation && !io.d_observation)) {
+    set_error("%s: io fields must lie inside the staged input block", who);
+    return MZX_ERR_INVALID;
+  }
+  for (int k = 0; k < B; ++k) {      // self_play.py:296-301 on the padded lists, as mzx_selfplay_search
+    const int32_t* row = m->legal_actions + (size_t)k * A;
+    int n = 0;
+    while (n < A && row[n] >= 0) ++n;
+    if (n == 0) { set_error("Legal actions should not be an empty array. Got [] (game %d).", k); return MZX_ERR_INVALID; }
+    for (int j = 0; j < A; ++j)
+      if (j < n ? row[j] >= A : row[j] >= 0) {
+        set_error("Legal actions should be a subset of the action space (padded with -1 at the end); game %d.", k);
+        return MZX_ERR_INVALID;
+      }
+    n_legal[k] = n;
+  }
+  memcpy(h_legal, m->legal_actions, sizeof(int32_t) * (size_t)B * A);
+  memcpy(h_to_play, m->to_play, sizeof(int32_t) * (size_t)B);
+  if (m->observation) memcpy(h_obs, m->observation, sizeof(float) * (size_t)B * m->observation_floats);
+  if (m->h_in != m->d_in) MZX_TRY_LAUNCH(copy_h2d(m->d_in, m->h_in, (size_t)m->in_bytes, (stream_t)stream));
+  mzx_draws dd = *d;                 // the move's own arrays: legal rows, noise and tape of the search
+  dd.d_legal_actions = io.d_legal_actions; dd.d_n = nullptr; dd.d_noise = (double*)io.d_noise; dd.d_tape = (uint32_t*)io.d_tape;
+  dd.dirichlet_alpha = m->dirichlet_alpha;
+  rc = mzx_selfplay_draws(&dd, stream);
+  if (rc) return rc;
+  rc = mzx_search_run(s, &io, d_arena, arena_bytes, stream);
+  if (rc) return rc;
+  if (sel) {
+    sp.legal = io.d_legal_actions; sp.visits = io.d_visit_counts;
+    MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(SelfplaySelectBody{sp}, (stream_t)stream));
+  }
+  if (m->h_out != m->d_out) MZX_TRY_LAUNCH(copy_d2h(m->h_out, m->d_out, (size_t)m->out_bytes, (stream_t)stream));
+  if (!(m->flags & MZX_MOVE_NO_SYNC)) MZX_TRY_LAUNCH(stream_sync((stream_t)stream));
+  return MZX_OK;
+}
+
 // ------------------------------------------------------------- replay hand-off: initial PER priorities on the device
 
 int mzx_replay_priorities(const double* d_root_values, const double* d_rewards, const int32_t* d_to_play, int32_t num_games,
@@ -1743,7 +1869,39 @@ void mzx_actor_destroy(mzx_actor* a) {
   event_destroy(a->event);
   event_destroy(a->start_event);
   stream_destroy(a->own_stream);
+  if (a->d_pow) device_free(a->d_pow);
   delete a;
+}
+
+int mzx_actor_set_device_draws(mzx_actor* a, uint64_t seed, uint64_t first_counter, double* d_temperature, int64_t* d_action) {
+  if (!a) { set_error("mzx_actor_set_device_draws: null actor"); return MZX_ERR_INVALID; }
+  if (a->pending) { set_error("mzx_actor_set_device_draws: a search is in flight"); return MZX_ERR_INVALID; }
+  if (a->A > DRAWS_MAX_ACTIONS || a->move.tape_words < 1) {
+    set_error("mzx_actor_set_device_draws: at most %d actions and at least one tape word", DRAWS_MAX_ACTIONS);
+    return MZX_ERR_INVALID;
+  }
+  for (int k = 1; k < a->B; ++k)
+    if (a->streams[k] != a->streams[0] + k) { set_error("mzx_actor_set_device_draws: the group's streams must be consecutive slots"); return MZX_ERR_INVALID; }
+  const mzx_move& m = a->move;
+  const ptrdiff_t t_off = (const char*)d_temperature - (const char*)m.d_in, a_off = (const char*)d_action - (const char*)m.d_out;
+  if (!d_temperature || !d_action || t_off < 0 || t_off + (ptrdiff_t)(sizeof(double) * a->B) > m.in_bytes || a_off < 0 ||
+      a_off + (ptrdiff_t)(sizeof(int64_t) * a->B) > m.out_bytes) {
+    set_error("mzx_actor_set_device_draws: d_temperature must lie inside the staged input block, d_action inside the output block");
+    return MZX_ERR_INVALID;
+  }
+  if (!m.io.d_noise || !m.io.d_tape) { set_error("mzx_actor_set_device_draws: io.d_noise / io.d_tape missing"); return MZX_ERR_INVALID; }
+  a->device_draws = true; a->draw_seed = seed; a->draw_counter = first_counter;
+  a->d_temperature = d_temperature; a->d_action = d_action;
+  return MZX_OK;
+}
+
+int64_t mzx_actor_draw_counter(const mzx_actor* a) { return a ? (int64_t)a->draw_counter : -1; }
+
+int mzx_actor_set_draw_counter(mzx_actor* a, uint64_t counter) {
+  if (!a || !a->device_draws) { set_error("mzx_actor_set_draw_counter: not an actor on device draws"); return MZX_ERR_INVALID; }
+  if (a->pending) { set_error("mzx_actor_set_draw_counter: a search is in flight"); return MZX_ERR_INVALID; }
+  a->draw_counter = counter;
+  return MZX_OK;
 }
 
 int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds* io, void* stream) {
@@ -1779,10 +1937,11 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
     }
     streams[(size_t)k] = a->own_stream;
   }
+  for (int k = 0; k < num_groups && rc == MZX_OK; ++k) rc = actor_upload_pow(groups[k], args);
   // SelfPlay._rounds_batched, statement for statement
   while (rc == MZX_OK && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
     for (int k = 0; k < num_groups && rc == MZX_OK; ++k)
-      if (!groups[k]->pending) rc = actor_begin(groups[k], streams[(size_t)k], &search_seconds, io->phase_seconds);
+      if (!groups[k]->pending) rc = actor_begin(groups[k], args, streams[(size_t)k], &search_seconds, io->phase_seconds);
     for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
       rc = actor_consume(groups[k], k, args, &sequence, &finished, &search_seconds);
       if (rc) break;
@@ -1791,7 +1950,7 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
       for (int j = k + 1; j < num_groups; ++j) later += groups[j]->B;
       // certain to be consumed by this call: runs while the host plays the groups after it
       if (pipelined && k + 1 < num_groups && finished + later < io->min_games && (io->max_rounds < 0 || rounds + 1 < io->max_rounds))
-        rc = actor_begin(groups[k], streams[(size_t)k], &search_seconds, io->phase_seconds);
+        rc = actor_begin(groups[k], args, streams[(size_t)k], &search_seconds, io->phase_seconds);
     }
     ++rounds;
   }

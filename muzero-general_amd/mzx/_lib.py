@@ -64,6 +64,24 @@ class Move(ctypes.Structure):
     ]
 
 
+class Draws(ctypes.Structure):
+    """``mzx_draws``: (seed, counter, streams) and the arrays of one mzx_selfplay_draws call (csrc/mzx_draws.h)."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("d_streams", c_vp), ("first_stream", c_i32),
+        ("num_games", c_i32), ("action_space_size", c_i32), ("tape_words", c_i32), ("dirichlet_alpha", c_f64),
+        ("d_legal_actions", c_vp), ("d_n", c_vp), ("d_noise", c_vp), ("d_tape", c_vp),
+    ]
+
+
+class DrawsSelect(ctypes.Structure):
+    """``mzx_draws_select``: the rows, temperatures and power table of one mzx_selfplay_select_device call."""
+    _fields_ = [
+        ("d_legal_actions", c_vp), ("d_visit_counts", c_vp), ("d_temperature", c_vp), ("d_pow_table", c_vp),
+        ("d_table_temperatures", c_vp), ("table_stride", c_i32), ("num_temperatures", c_i32), ("d_uniforms", c_vp),
+        ("d_action", c_vp),
+    ]
+
+
 class ActorConfig(ctypes.Structure):
     """``mzx_actor_config``: one slot group of a shard of natively stepped games (mzx_selfplay_rounds)."""
     _fields_ = [
@@ -249,6 +267,10 @@ PROTOTYPES = {
     "mzx_rng_randint": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mzx_rng_choice_weighted": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "mzx_selfplay_search": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_i64, c_vp]),
+    "mzx_selfplay_draws": (ctypes.c_int, [ctypes.POINTER(Draws), c_vp]),
+    "mzx_selfplay_select_device": (ctypes.c_int, [ctypes.POINTER(Draws), ctypes.POINTER(DrawsSelect), c_vp]),
+    "mzx_selfplay_move_device": (ctypes.c_int, [c_vp, ctypes.POINTER(Move), ctypes.POINTER(Draws), ctypes.POINTER(DrawsSelect),
+                                                c_vp, c_vp, c_i64, c_vp]),
     "mzx_replay_priorities": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "mzx_replay_values": (ctypes.c_int, [ctypes.POINTER(ReplayPool), c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_replay_positions": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -279,6 +301,9 @@ PROTOTYPES = {
     "mzx_actor_create": (ctypes.c_int, [ctypes.POINTER(ActorConfig), ctypes.POINTER(c_vp)]),
     "mzx_actor_destroy": (None, [c_vp]),
     "mzx_selfplay_rounds": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(Rounds), c_vp]),
+    "mzx_actor_set_device_draws": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
+    "mzx_actor_draw_counter": (c_i64, [c_vp]),
+    "mzx_actor_set_draw_counter": (ctypes.c_int, [c_vp, ctypes.c_uint64]),
     "mzx_actor_finished": (ctypes.c_int, [c_vp, c_i64, ctypes.POINTER(c_i64 * 3)]),
     "mzx_actor_take": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32)]),
     "mzx_selfplay_select": (ctypes.c_int, [c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32,

@@ -19,9 +19,10 @@ import ctypes
 
 import numpy
 
-from . import _lib
+from . import _lib, draws
 from .history import ShardGameHistory, ShardGames, _ShardRecord, gc_paused
-from .search import TAPE_WORDS, BatchedMCTS
+from . import search as _search
+from .search import BatchedMCTS
 
 
 def usable(actor):
@@ -41,18 +42,22 @@ class _Group:
         assert tuple(game.shape) == tuple(cfg.observation_shape), \
             f"Observation should match the observation_shape defined in MuZeroConfig. Expected {tuple(cfg.observation_shape)} but got {tuple(game.shape)}."
         assert game.A == A, f"the game has {game.A} actions, the configuration {A}"
-        st = self.staging = engine._staging(n, TAPE_WORDS, obs_floats, True)
+        device_draws = bool(getattr(actor, "device_draws", False))
+        st = self.staging = engine._staging(n, _search.TAPE_WORDS, obs_floats, True, device_draws=device_draws)
         pin, pout = st["pin"], st["pout"]
         c_vp = ctypes.c_void_p
+        if device_draws:        # noise and tape are device scratch: nothing of them is uploaded (csrc/mzx_draws.h)
+            pin = dict(pin, noise=st["draw_noise"].data_ptr(), tape=st["draw_tape"].data_ptr())
         self.streams = numpy.arange(first, first + n, dtype=numpy.int32)
+        self.tape_words = _search.TAPE_WORDS      # (of this group's handle and staging; the retries grow from it)
         self.arena = engine.arena(n)
         conf = _lib.ActorConfig()
-        conf.game, conf.search, conf.bank = game.native_handle, engine.handle(n, TAPE_WORDS), actor.bank.handle
+        conf.game, conf.search, conf.bank = game.native_handle, engine.handle(n, _search.TAPE_WORDS), actor.bank.handle
         conf.streams, conf.first_slot, conf.max_moves = self.streams.ctypes.data, first, int(cfg.max_moves)
         conf.temperature = float(temperature)
         conf.d_arena, conf.arena_bytes = self.arena.data_ptr(), self.arena.numel()
         mv = conf.move
-        mv.num_games, mv.action_space_size, mv.tape_words, mv.num_threads = n, A, TAPE_WORDS, actor.bank.threads
+        mv.num_games, mv.action_space_size, mv.tape_words, mv.num_threads = n, A, _search.TAPE_WORDS, actor.bank.threads
         mv.dirichlet_alpha, mv.add_exploration_noise = float(cfg.root_dirichlet_alpha), 1
         mv.h_in, mv.d_in, mv.in_bytes = st["h_in"].data_ptr(), st["d_in"].data_ptr(), st["h_in"].numel()
         mv.h_out, mv.d_out, mv.out_bytes = st["h_out"].data_ptr(), st["d_out"].data_ptr(), st["h_out"].numel()
@@ -61,6 +66,9 @@ class _Group:
         self.handle = c_vp()
         lib.check(lib.mzx_actor_create(ctypes.byref(conf), ctypes.byref(self.handle)))
         self.lib = lib
+        if device_draws:        # the group's search number is its counter, its slots are the streams
+            lib.check(lib.mzx_actor_set_device_draws(self.handle, engine.draw_seed & (2 ** 64 - 1), int(actor.draw_counter),
+                                                     c_vp(pin["temperature"]), c_vp(pout["action"])))
 
     def close(self):
         handle, self.handle = self.handle, None
@@ -88,6 +96,7 @@ class NativeShard:
             game = actor.batched_game if single else type(actor.batched_game)(actor._game_seeds[first:last],
                                                                               _backend=actor.model.backend)
             engine = actor.engine if single else BatchedMCTS(cfg, actor.model, last - first)
+            engine.draw_seed = getattr(actor, "draw_seed", engine.draw_seed)
             self.groups.append(_Group(actor, game, first, last - first, engine, temperature))
         self.handles = (ctypes.c_void_p * len(self.groups))(*[g.handle for g in self.groups])
         self.temperatures = set()
@@ -100,6 +109,11 @@ class NativeShard:
         for g in self.groups:
             g.close()
 
+    def set_draw_counter(self, value):
+        """Device draws: every group's next search takes this counter (``SelfPlay.draw_counter``)."""
+        for g in self.groups:
+            g.lib.check(g.lib.mzx_actor_set_draw_counter(g.handle, int(value) & (2 ** 64 - 1)))
+
     # ---- the rare path: a search exhausted its tie-break tape (equal priors at every level of a walk) ------------------
     def _retry_flagged(self, ctx, group, count, games):
         """Searches the flagged games of slot group ``group`` again on a longer tape -- same roots, same noise, the stream
@@ -110,16 +124,26 @@ class NativeShard:
             redo = numpy.array([games[k] for k in range(count)], dtype=numpy.int64)
             vin, vout = g.staging["vin"], g.staging["vout"]
             legal, to_play = vin["legal"].reshape(n, A), vin["to_play"]
-            noise, obs = vin["noise"].reshape(n, A), vin["obs"].reshape(n, -1)
+            device_draws = "draw_noise" in g.staging
+            if device_draws:     # the noise the roots got, and the (stream, counter) the longer tapes are drawn under
+                noise = g.staging["draw_noise"].cpu().numpy()
+                counter = int(self.groups[group].lib.mzx_actor_draw_counter(g.handle)) - 1
+            else:
+                noise = vin["noise"].reshape(n, A)
+            obs = vin["obs"].reshape(n, -1)
             visits, info = vout["visits"].reshape(n, A), vout["info"].reshape(n, 4)
             n_legal = (legal >= 0).sum(1).astype(numpy.int32)
-            words = TAPE_WORDS
+            words = g.tape_words
             while redo.size:
                 words *= 8
                 if words > (1 << 22):
                     raise _lib.MzxError("tie-break tape: a search consumed more than 4M random words")
-                _, long_tape = actor.bank.root_draws(g.streams[redo], cfg.root_dirichlet_alpha, n_legal[redo], A, words,
-                                                     with_noise=False)
+                if device_draws:
+                    long_tape = draws.root_draws(actor.model.backend, g.engine.draw_seed, counter, len(redo), A, words,
+                                                 streams=g.streams[redo], noise=False)[1].cpu().numpy().view(numpy.uint32)
+                else:
+                    _, long_tape = actor.bank.root_draws(g.streams[redo], cfg.root_dirichlet_alpha, n_legal[redo], A, words,
+                                                         with_noise=False)
                 v2, r2, p2, i2 = g.engine._launch(len(redo), obs[redo].copy(), legal[redo].copy(), to_play[redo].copy(),
                                                   noise[redo].copy(), long_tape, words, None)
                 visits[redo], vout["root_value"][redo], vout["predicted"][redo], info[redo] = v2, r2, p2, i2

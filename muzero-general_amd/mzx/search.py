@@ -12,7 +12,7 @@ import math
 import numpy
 import torch
 
-from . import _lib
+from . import _lib, draws
 from .history import Node
 
 # raw MT19937 words per tree handed to a search for its tie draws: a search normally consumes ONE (the all-zero
@@ -83,8 +83,16 @@ class BatchedMCTS:
 
     fused_move = True     # A/B switch of the tests: False = the separate calls (root_draws, _launch, advance, numpy select)
 
-    def __init__(self, config, model, max_trees, num_simulations=None, mode=None, max_carried_nodes=0):
+    def __init__(self, config, model, max_trees, num_simulations=None, mode=None, max_carried_nodes=0, device_draws=None):
         _validate(config)
+        # device draws (csrc/mzx_draws.h): noise, tape and action choice as a function of (draw_seed, stream, counter); a
+        # call with rngs=None takes them, streams default to the tree numbers and the counter to draw_counter (then + 1)
+        self.device_draws = bool(getattr(config, "device_draws", False)) if device_draws is None else bool(device_draws)
+        # (draw_seed: config.seed for an engine on its own; SelfPlay sets its actor's seed, so that actors sharing a
+        # configuration draw apart -- csrc/mzx_draws.h)
+        self.draw_seed = int(getattr(config, "seed", 0))
+        self.draw_counter = 0
+        self.tape_retries = 0      # trees searched again on a longer tape so far (diagnostics, tests)
         self.config = config
         self.model = model
         self.backend = model.backend
@@ -212,7 +220,7 @@ class BatchedMCTS:
         keep = (t_obs, t_legal, t_tp, t_noise, t_tape)
         return io, out, keep
 
-    def run_from_roots(self, roots, to_play, add_exploration_noise, rngs):
+    def run_from_roots(self, roots, to_play, add_exploration_noise, rngs=None, streams=None, counter=None):
         """
         MCTS.run(..., override_root_with=root) (self_play.py:275-277) for B roots the caller expanded itself
         (``Node.expand`` after a ``recurrent_inference``, diagnose_model.py:57-74): the roots' hidden states,
@@ -238,7 +246,7 @@ class BatchedMCTS:
         )
         if override["hidden"].shape[1] != self.model.hidden_size:
             raise ValueError("override_root_with: hidden_state does not match the network's encoded state")
-        return self.run(None, legal, to_play, add_exploration_noise, rngs, _override=override)
+        return self.run(None, legal, to_play, add_exploration_noise, rngs, _override=override, streams=streams, counter=counter)
 
     def node_graph(self, num_trees, i, root_actions, _trees=None):
         """
@@ -295,9 +303,31 @@ class BatchedMCTS:
         if not self.max_carried_nodes:
             raise ValueError("continued searches need BatchedMCTS(..., max_carried_nodes=...) > 0")
 
-    def _root_draws(self, root_n, add_exploration_noise, rngs):
-        """Dirichlet noise over the root's children, then the tie-break tape, from each tree's stream (as ``run``)."""
+    def _draw_ids(self, B, rngs, streams, counter):
+        """(streams [B] int32, counter) of a call that draws on the device; None for a call on host streams."""
+        if rngs is not None:
+            if streams is not None or counter is not None:
+                raise ValueError("streams= / counter= belong to device draws (rngs=None)")
+            return None
+        if not self.device_draws:
+            raise ValueError("rngs=None needs device draws: config.device_draws or BatchedMCTS(..., device_draws=True)")
+        if self.A > draws.MAX_ACTIONS:
+            raise NotImplementedError(f"device draws take at most {draws.MAX_ACTIONS} actions")
+        streams = numpy.arange(B, dtype=numpy.int32) if streams is None else numpy.ascontiguousarray(streams, dtype=numpy.int32)
+        if streams.shape != (B,):
+            raise ValueError("streams: one entry per tree")
+        if counter is None:
+            counter, self.draw_counter = self.draw_counter, self.draw_counter + 1
+        return streams, int(counter)
+
+    def _root_draws(self, root_n, add_exploration_noise, rngs, ids=None):
+        """Dirichlet noise over the root's children, then the tie-break tape, from each tree's stream (as ``run``); with
+        ``ids`` one library call (``mzx_selfplay_draws``) whose arrays stay on the device."""
         B, A, alpha = len(root_n), self.A, self.config.root_dirichlet_alpha
+        if ids is not None:
+            noise, tape = draws.root_draws(self.backend, self.draw_seed, ids[1], B, A, TAPE_WORDS, alpha=alpha,
+                                           n=numpy.asarray(root_n, numpy.int32), streams=ids[0], noise=bool(add_exploration_noise))
+            return noise, tape, None
         assert len(rngs) == B
         noise = numpy.zeros((B, A), numpy.float64) if add_exploration_noise else None
         tape = numpy.zeros((B, TAPE_WORDS), numpy.uint32)
@@ -312,10 +342,10 @@ class BatchedMCTS:
     def _run_continued(self, B, root_actions, to_play, noise, tape, states, rngs):
         """mzx_search_run_continued on the carried trees of the arena; the result record of ``run``."""
         be, lib, A = self.backend, self.backend.lib, self.A
-        dev = lambda a, dt: torch.as_tensor(numpy.ascontiguousarray(a)).to(dt).to(be.device)
+        dev = lambda a, dt: a if isinstance(a, torch.Tensor) else torch.as_tensor(numpy.ascontiguousarray(a)).to(dt).to(be.device)
         t_tp = dev(numpy.asarray(to_play, numpy.int32), torch.int32)
         t_noise = None if noise is None else dev(noise, torch.float64)
-        t_tape = dev(tape.view(numpy.int32), torch.int32)
+        t_tape = dev(tape if isinstance(tape, torch.Tensor) else tape.view(numpy.int32), torch.int32)
         out = dict(visits=be.zeros((B, A), torch.int32), root_value=be.zeros((B,), torch.float64),
                    predicted=be.zeros((B,), torch.float64), info=be.zeros((B, 4), torch.int32))
         io = _lib.SearchIO(None, None, be.ptr(t_tp), be.ptr(t_noise), be.ptr(t_tape), be.ptr(out["visits"]),
@@ -324,7 +354,7 @@ class BatchedMCTS:
         lib.check(lib.mzx_search_run_continued(self.handle(B), ctypes.byref(io), be.ptr(arena), arena.numel(), be.stream()))
         res = {k: v.cpu().numpy() for k, v in out.items()}
         info = res["info"]
-        for i in range(B):      # rewind, then consume exactly what the device consumed
+        for i in range(B if states is not None else 0):      # rewind, then consume exactly what the device consumed
             rngs[i].set_state(states[i])
             if info[i, 2]:
                 rngs[i].randint(0, 2 ** 32, size=int(info[i, 2]), dtype=numpy.uint32)
@@ -337,7 +367,7 @@ class BatchedMCTS:
         self._note_searched(B, root_actions, res["visits"])
         return result
 
-    def continue_search(self, actions, to_play, add_exploration_noise, rngs):
+    def continue_search(self, actions, to_play, add_exploration_noise, rngs=None, streams=None, counter=None):
         """
         MCTS.run(model, None, _, to_play_i, add_exploration_noise, override_root_with=old_root_i.children[actions[i]])
         (self_play.py:260-361) for the B trees the last ``run`` / ``continue_search`` / ``run_from_trees`` of this engine
@@ -345,7 +375,9 @@ class BatchedMCTS:
         device (``mzx_search_advance``): visits, values, priors and hidden states stay, ``num_simulations`` more
         simulations follow (Dirichlet noise over the carried root's children, fresh MinMaxStats).  Returns a
         ``SearchResult`` (``root_predicted_values`` are None, as in the reference); ``export_trees`` / ``node_graph``
-        read the continued trees.  rngs: B numpy RandomState-like objects.
+        read the continued trees.  rngs: B numpy RandomState-like objects; None (device draws): noise and tape come
+        from one ``mzx_selfplay_draws`` call under (``draw_seed``, ``streams``, ``counter``) and never visit the host
+        (what stays per tree on the host is list bookkeeping: the action check and the root action lists of the result).
         """
         self._require_capacity()
         B = len(actions)
@@ -363,7 +395,7 @@ class BatchedMCTS:
                 raise ValueError(f"continue_search: action {a} of tree {i} is not an expanded child of its root")
             root_actions.append(list(range(A)))
         root_n = [len(r) for r in root_actions]
-        noise, tape, states = self._root_draws(root_n, add_exploration_noise, rngs)
+        noise, tape, states = self._root_draws(root_n, add_exploration_noise, rngs, self._draw_ids(B, rngs, streams, counter))
         be = self.backend
         if self._arena_alt is None or self._arena_alt.numel() != self._arena.numel():
             self._arena_alt = be.zeros((self._arena.numel(),), torch.uint8)
@@ -375,7 +407,7 @@ class BatchedMCTS:
         self._arena, self._arena_alt = self._arena_alt, self._arena
         return self._run_continued(B, root_actions, to_play, noise, tape, states, rngs)
 
-    def run_from_trees(self, roots, to_play, add_exploration_noise, rngs):
+    def run_from_trees(self, roots, to_play, add_exploration_noise, rngs=None, streams=None, counter=None):
         """
         MCTS.run(..., override_root_with=root) (self_play.py:260-361) for B expanded reference ``Node`` graphs that may
         already carry visits and expanded descendants: the graphs are flattened on the host (hidden states from
@@ -423,7 +455,8 @@ class BatchedMCTS:
         arena = self.arena(B)
         self._carry = None
         be.lib.check(be.lib.mzx_search_load(self.handle(B), ctypes.byref(h), be.ptr(arena), be.stream()))
-        noise, tape, states = self._root_draws([len(r) for r in root_actions], add_exploration_noise, rngs)
+        noise, tape, states = self._root_draws([len(r) for r in root_actions], add_exploration_noise, rngs,
+                                               self._draw_ids(B, rngs, streams, counter))
         res = self._run_continued(B, root_actions, to_play, noise, tape, states, rngs)
         trees = self.export_trees(B)
         for i, root in enumerate(roots):      # the reference searches the given objects in place
@@ -449,14 +482,16 @@ class BatchedMCTS:
                 raise ValueError("run_from_trees: canonical_index of the root must be the smallest")
         return nodes
 
-    def _staging(self, B, tape_words, obs_floats, with_noise):
+    def _staging(self, B, tape_words, obs_floats, with_noise, device_draws=False):
         """
         Persistent I/O of one (B, tape) geometry: ONE pinned host block + ONE device block for a move's inputs
         (observations | noise | legal | to_play | tape; 8-byte fields first) and one of each for its outputs
         (root value | predicted root value | visit counts | info) -- a move costs one upload, one launch, one
         download and one stream synchronisation instead of five uploads and four blocking downloads.
+        ``device_draws``: noise and tape are device scratch outside the uploaded block (``draw_noise`` / ``draw_tape``);
+        the inputs carry the temperatures, the outputs the chosen actions.
         """
-        key = ("staging", B, tape_words, obs_floats, bool(with_noise))
+        key = ("staging", B, tape_words, obs_floats, bool(with_noise)) + (("device_draws",) if device_draws else ())
         st = self._buffers.get(key)
         if st is not None:
             return st
@@ -471,10 +506,16 @@ class BatchedMCTS:
                 off += (nbytes + 15) & ~15
             return table, max(off, 16)
 
-        fin, n_in = carve([("noise", numpy.float64, B * A if with_noise else 0), ("obs", numpy.float32, B * obs_floats),
-                           ("legal", numpy.int32, B * A), ("to_play", numpy.int32, B), ("tape", numpy.uint32, B * tape_words)])
-        fout, n_out = carve([("root_value", numpy.float64, B), ("predicted", numpy.float64, B),
-                             ("visits", numpy.int32, B * A), ("info", numpy.int32, B * 4)])
+        if device_draws:
+            fin, n_in = carve([("temperature", numpy.float64, B), ("obs", numpy.float32, B * obs_floats),
+                               ("legal", numpy.int32, B * A), ("to_play", numpy.int32, B)])
+            fout, n_out = carve([("root_value", numpy.float64, B), ("predicted", numpy.float64, B), ("action", numpy.int64, B),
+                                 ("visits", numpy.int32, B * A), ("info", numpy.int32, B * 4)])
+        else:
+            fin, n_in = carve([("noise", numpy.float64, B * A if with_noise else 0), ("obs", numpy.float32, B * obs_floats),
+                               ("legal", numpy.int32, B * A), ("to_play", numpy.int32, B), ("tape", numpy.uint32, B * tape_words)])
+            fout, n_out = carve([("root_value", numpy.float64, B), ("predicted", numpy.float64, B),
+                                 ("visits", numpy.int32, B * A), ("info", numpy.int32, B * 4)])
         h_in = torch.empty(n_in, dtype=torch.uint8, pin_memory=on_gpu)
         h_out = torch.empty(n_out, dtype=torch.uint8, pin_memory=on_gpu)
         d_in = be.empty((n_in,), torch.uint8) if on_gpu else h_in
@@ -484,6 +525,10 @@ class BatchedMCTS:
         st = dict(h_in=h_in, h_out=h_out, d_in=d_in, d_out=d_out, vin=views(h_in, fin), vout=views(h_out, fout),
                   pin={k: d_in.data_ptr() + o for k, (o, _, _) in fin.items()},
                   pout={k: d_out.data_ptr() + o for k, (o, _, _) in fout.items()}, on_gpu=on_gpu)
+        if device_draws:
+            st["draw_noise"] = be.zeros((B, A), torch.float64) if with_noise else None
+            st["draw_tape"] = be.zeros((B, tape_words), torch.int32)
+            st["draw_streams"] = be.zeros((B,), torch.int32)
         self._buffers[key] = st
         return st
 
@@ -584,8 +629,89 @@ class BatchedMCTS:
         outputs.keep = keep
         return outputs
 
-    def run(self, observations, legal_actions, to_play, add_exploration_noise, rngs, _override=None, _defer_advance=False,
-            _asynchronous=False):
+    def _power_table(self, temps):
+        """Device copies of ``draws.power_table`` over every visit count a search of this engine can report."""
+        key = tuple(numpy.unique(temps[(temps != 0) & ~numpy.isinf(temps)]).tolist())
+        entry = self._buffers.get(("pow", key))
+        if entry is None:
+            table, distinct = draws.power_table(numpy.array(key, numpy.float64), self.num_nodes + 1)
+            dev = lambda a: None if a is None else torch.as_tensor(a).to(self.backend.device)
+            entry = self._buffers[("pow", key)] = (dev(table), dev(distinct) if len(key) else None, table, distinct)
+        return entry
+
+    def _move_search_device(self, B, obs, legal, to_play, ids, with_noise, temperature, asynchronous=False):
+        """
+        ``mzx_selfplay_move_device``: the legal rows validated and staged, ONE upload, the draws, the search, the action
+        choice (``temperature`` [B], or None: none), ONE download -- one library call, no host stream, no per-game loop.
+        Returns the function ``_move_search`` returns; its ``actions`` attribute hands out the chosen actions.
+        """
+        lib, A, be = self.backend.lib, self.A, self.backend
+        obs_dev = obs if isinstance(obs, torch.Tensor) else None
+        obs_floats = 0 if obs_dev is not None else int(obs.size // B)
+        st = self._staging(B, TAPE_WORDS, obs_floats, with_noise, device_draws=True)
+        pin, pout, c_vp = st["pin"], st["pout"], ctypes.c_void_p
+        mv = st.get("move")
+        if mv is None:
+            mv = st["move"] = _lib.Move()
+            mv.num_games, mv.action_space_size, mv.tape_words = B, A, TAPE_WORDS
+            mv.h_in, mv.d_in, mv.in_bytes = st["h_in"].data_ptr(), st["d_in"].data_ptr(), st["h_in"].numel()
+            mv.h_out, mv.d_out, mv.out_bytes = st["h_out"].data_ptr(), st["d_out"].data_ptr(), st["h_out"].numel()
+            mv.io = _lib.SearchIO(c_vp(pin["obs"]), c_vp(pin["legal"]), c_vp(pin["to_play"]), be.ptr(st["draw_noise"]),
+                                  be.ptr(st["draw_tape"]), c_vp(pout["visits"]), c_vp(pout["root_value"]),
+                                  c_vp(pout["predicted"]), c_vp(pout["info"]))
+        asynchronous = bool(asynchronous) and st["on_gpu"]
+        mv.flags = _lib.MOVE_NO_SYNC if asynchronous else 0
+        mv.streams, mv.legal_actions, mv.to_play = None, legal.ctypes.data, to_play.ctypes.data
+        mv.dirichlet_alpha, mv.add_exploration_noise = float(self.config.root_dirichlet_alpha), int(with_noise)
+        if obs_dev is not None:
+            mv.observation, mv.observation_floats = None, 0
+            mv.io.d_observation = obs_dev.data_ptr()
+        else:
+            mv.observation, mv.observation_floats = obs.ctypes.data, obs_floats
+        streams, counter = ids
+        d = _lib.Draws(seed=self.draw_seed & (2 ** 64 - 1), counter=counter & (2 ** 64 - 1), num_games=B, action_space_size=A,
+                       tape_words=TAPE_WORDS, dirichlet_alpha=float(self.config.root_dirichlet_alpha))
+        if numpy.array_equal(streams, streams[0] + numpy.arange(B, dtype=numpy.int32)):
+            d.first_stream = int(streams[0])
+        else:
+            st["draw_streams"].copy_(torch.as_tensor(streams))
+            d.d_streams = be.ptr(st["draw_streams"])
+        sel, keep = None, (obs, legal, to_play)
+        if temperature is not None:
+            st["vin"]["temperature"][:] = temperature
+            table, distinct, _, _ = self._power_table(temperature)
+            sel = _lib.DrawsSelect(d_temperature=c_vp(pin["temperature"]), d_pow_table=be.ptr(table),
+                                   d_table_temperatures=be.ptr(distinct), table_stride=0 if table is None else table.shape[1],
+                                   num_temperatures=0 if table is None else table.shape[0], d_action=c_vp(pout["action"]))
+        n_legal = numpy.empty(B, numpy.int32)
+        arena = self.arena(B)
+        rc = lib.mzx_selfplay_move_device(self.handle(B, TAPE_WORDS), ctypes.byref(mv), ctypes.byref(d),
+                                          None if sel is None else ctypes.byref(sel), n_legal.ctypes.data, be.ptr(arena),
+                                          arena.numel(), be.stream())
+        if rc != 0:
+            message = lib.mzx_last_error().decode()
+            if message.startswith("Legal actions"):       # self_play.py:296-301 raise AssertionError
+                raise AssertionError(message)
+            lib.check(rc)
+        done = None
+        if asynchronous:
+            done = st.get("event")
+            if done is None:
+                done = st["event"] = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(be.device))
+
+        def outputs():
+            if done is not None:
+                done.synchronize()
+            vout = st["vout"]
+            outputs.actions = vout["action"].copy() if sel is not None else None
+            return (vout["visits"].reshape(B, A).copy(), vout["root_value"].copy(), vout["predicted"].copy(),
+                    vout["info"].reshape(B, 4).copy(), n_legal, None)
+        outputs.keep, outputs.device_noise, outputs.actions = keep, st["draw_noise"], None
+        return outputs
+
+    def run(self, observations, legal_actions, to_play, add_exploration_noise, rngs=None, _override=None, _defer_advance=False,
+            _asynchronous=False, streams=None, counter=None, temperature=None):
         """
         observations: B stacked observations; legal_actions: B lists; to_play: B ints;
         rngs: B numpy RandomState-like objects (dirichlet / randint / get_state / set_state), or a pair
@@ -595,25 +721,34 @@ class BatchedMCTS:
         (``mzx_selfplay_select`` does it in the same pass as the action draw); ``result.pending_words`` holds them.
         ``_asynchronous`` (bank searches): returns a ``PendingSearch`` as soon as the search is queued on the device;
         its ``result()`` waits and completes the call -- the host steps another group of games in between.
+        ``rngs=None`` (device draws): noise, tape and -- with ``temperature`` (a number or [B]) -- the action choice are
+        drawn on the device under (``draw_seed``, ``streams``, ``counter``): ONE ``mzx_selfplay_move_device`` call;
+        ``result.actions`` holds the chosen actions.
         """
         cfg, A = self.config, self.A
         B = len(legal_actions)
         bank = None
+        ids = self._draw_ids(B, rngs, streams, counter)
+        if temperature is not None:
+            if ids is None:
+                raise ValueError("temperature= belongs to device draws (rngs=None)")
+            temperature = numpy.ascontiguousarray(numpy.broadcast_to(numpy.asarray(temperature, numpy.float64), (B,)))
         if isinstance(rngs, tuple):
             bank, bank_idx = rngs
             bank_idx = numpy.ascontiguousarray(bank_idx, dtype=numpy.int32)
             assert bank_idx.size == B
-        else:
+        elif ids is None:
             assert len(rngs) == B
         assert len(to_play) == B
         legal = numpy.full((B, A), -1, numpy.int32)
         n_legal = numpy.empty(B, numpy.int32)
         action_set = set(cfg.action_space)
         fused = self.fused_move and bank is not None and _override is None     # the move's host side behind one library call
+        device_fused = ids is not None and _override is None
         if isinstance(legal_actions, numpy.ndarray):   # batched protocol: [B][A] int32, lists padded with -1
             legal = numpy.ascontiguousarray(legal_actions, dtype=numpy.int32)
             assert legal.shape == (B, A), "legal_actions array must be [num_trees][len(action_space)]"
-            if not fused:                              # (mzx_selfplay_search validates the rows itself)
+            if not (fused or device_fused):            # (mzx_selfplay_search / _move_device validate the rows themselves)
                 n_legal = (legal >= 0).sum(1).astype(numpy.int32)
                 assert (n_legal > 0).all(), "Legal actions should not be an empty array."
                 assert (legal < A).all() and ((legal >= 0) == (numpy.arange(A)[None, :] < n_legal[:, None])).all(), \
@@ -637,8 +772,14 @@ class BatchedMCTS:
             assert len(set(acts)) == len(acts), "Legal actions must not repeat."
             legal[i, : len(acts)] = acts
             n_legal[i] = len(acts)
-        if fused:
+        states = None
+        if fused or device_fused:
             noise = tape = None
+        elif ids is not None:                          # given roots: the draws by one library call, then the ordinary launch
+            t_noise, t_tape = draws.root_draws(self.backend, self.draw_seed, ids[1], B, A, TAPE_WORDS, alpha=cfg.root_dirichlet_alpha,
+                                               legal=legal, streams=ids[0], noise=bool(add_exploration_noise))
+            noise = None if t_noise is None else t_noise.cpu().numpy()
+            tape = t_tape.cpu().numpy().view(numpy.uint32)
         elif bank is not None:
             noise, tape = bank.root_draws(bank_idx, cfg.root_dirichlet_alpha, n_legal, A, TAPE_WORDS,
                                           with_noise=bool(add_exploration_noise))
@@ -662,13 +803,15 @@ class BatchedMCTS:
         outputs = None
         if fused:
             outputs = self._move_search(B, obs, legal, to_play, bank, bank_idx, bool(add_exploration_noise), _asynchronous)
+        elif device_fused:
+            outputs = self._move_search_device(B, obs, legal, to_play, ids, bool(add_exploration_noise), temperature, _asynchronous)
         pending = PendingSearch(lambda: self._complete_run(
             outputs, B, obs, legal, legal_actions, shared, to_play, n_legal, noise, tape, bank, bank_idx if bank is not None else None,
-            rngs, states if bank is None else None, _override, _defer_advance))
+            rngs, states if bank is None else None, _override, _defer_advance, ids, temperature))
         return pending if _asynchronous else pending.result()
 
     def _complete_run(self, outputs, B, obs, legal, legal_actions, shared, to_play, n_legal, noise, tape, bank, bank_idx, rngs,
-                      states, _override, _defer_advance):
+                      states, _override, _defer_advance, ids=None, temperature=None):
         """The second half of ``run``: outputs of the (possibly still running) search, tape retries, the result record."""
         cfg, A = self.config, self.A
         if outputs is not None:
@@ -679,12 +822,20 @@ class BatchedMCTS:
         # again with a longer tape: same roots, same noise, the stream peeked further -- the reference never
         # fails here (numpy.random.choice at self_play.py:371 simply keeps drawing).
         words = TAPE_WORDS
+        redone = numpy.zeros(B, bool)
         while (info[:, 1] & 1).any():
             words *= 8
             if words > (1 << 22):
                 raise _lib.MzxError("tie-break tape: a search consumed more than 4M random words")
             redo = numpy.nonzero(info[:, 1] & 1)[0]
-            if bank is not None:
+            redone[redo] = True
+            self.tape_retries += len(redo)
+            if ids is not None:      # a longer tape under the same (stream, counter) begins with the shorter one
+                _, t_tape = draws.root_draws(self.backend, self.draw_seed, ids[1], len(redo), A, words, streams=ids[0][redo], noise=False)
+                long_tape = t_tape.cpu().numpy().view(numpy.uint32)
+                if noise is None and getattr(outputs, "device_noise", None) is not None:
+                    noise = outputs.device_noise.cpu().numpy()      # (read before _launch below draws anything)
+            elif bank is not None:
                 _, long_tape = bank.root_draws(bank_idx[redo], cfg.root_dirichlet_alpha, n_legal[redo], A, words,
                                                with_noise=False)
             else:
@@ -708,7 +859,19 @@ class BatchedMCTS:
         if (info[:, 1] != 0).any():
             raise _lib.MzxError(f"search flagged trees {numpy.nonzero(info[:, 1])[0][:8]} (flags {set(info[:, 1])}): "
                                 "node arena exhausted")
-        if bank is not None:
+        result.actions = None
+        if ids is not None:
+            result.legal_array, result.n_legal, result.streams = legal, n_legal, ids[0]
+            if temperature is not None:
+                result.actions = getattr(outputs, "actions", None)
+                again = numpy.arange(B) if result.actions is None else numpy.nonzero(redone)[0]
+                if again.size:       # the searches run again (and the given roots): the same select function over them
+                    if result.actions is None:
+                        result.actions = numpy.zeros(B, numpy.int64)
+                    _, _, table, distinct = self._power_table(temperature)
+                    result.actions[again] = draws.select(self.backend, self.draw_seed, ids[1], legal[again], visits[again],
+                                                         temperature[again], table, distinct, streams=ids[0][again]).cpu().numpy()
+        elif bank is not None:
             result.legal_array, result.n_legal, result.streams = legal, n_legal, bank_idx
             if _defer_advance and self.fused_move:     # (the numpy action draw of the A/B switch does not advance)
                 result.pending_words = numpy.ascontiguousarray(info[:, 2], dtype=numpy.int32)

@@ -68,7 +68,8 @@ class _BatchedGroup(dict):
         super().__init__(game=game, first=first, n=n, engine=engine, slots=list(range(first, first + n)),
                          streams=numpy.arange(first, first + n, dtype=numpy.int32), everyone=numpy.arange(n), obs=obs,
                          tp=numpy.asarray(game.to_play()).astype(numpy.int64), start=numpy.zeros(n, numpy.int64),
-                         temps=numpy.full(n, float(temperature)), round=0, store=None, pending=None, legal=None)
+                         temps=numpy.full(n, float(temperature)), round=0, store=None, pending=None, legal=None,
+                         counter=int(actor.draw_counter))      # (device draws: the counter of the group's next search)
         self.A, self.max_moves = len(cfg.action_space), int(cfg.max_moves)
         self.ring, self.cap = None, 0
         if cfg.stacked_observations > 0:   # frames stay in HBM; the stacked inputs are assembled there (csrc/mzx_obs.h)
@@ -106,16 +107,24 @@ class _BatchedGroup(dict):
                 self.ring[name] = self.ring[name].astype(numpy.result_type(value.dtype, have))
         return r % self.cap
 
+    def move_temps(self, temperature_threshold):
+        """The temperature of every slot's next move (self_play.py:151-157)."""
+        temps = self["temps"]
+        if temperature_threshold:
+            temps = numpy.where(self["round"] - self["start"] + 1 < temperature_threshold, temps, 0.0)
+        return temps
+
     def play(self, actor, result, temperature, temperature_threshold):
         """One move of every slot after its search: action draw, game step, log, finished games out, slots refilled."""
         cfg, g, n, A = actor.config, self["game"], self["n"], self.A
         r, start, store, everyone = self["round"], self["start"], self["store"], self["everyone"]
         legal = self["legal"]
         moves_before = r - start                      # len(action_history) - 1 of every slot's game
-        temps = self["temps"]
-        if temperature_threshold:                     # self_play.py:151-157
-            temps = numpy.where(moves_before + 1 < temperature_threshold, temps, 0.0)
-        actions = numpy.asarray(actor._select_actions_bank(result, self["streams"], temps), numpy.int64)
+        if actor.device_draws:                        # drawn on the device behind the search (csrc/mzx_draws.h)
+            actions = numpy.asarray(result.actions, numpy.int64)
+        else:
+            actions = numpy.asarray(actor._select_actions_bank(result, self["streams"], self.move_temps(temperature_threshold)),
+                                    numpy.int64)
         obs2, reward, done = g.step(actions, None)
         obs2, reward = numpy.asarray(obs2), numpy.asarray(reward)
         c = self._row(r, self["obs"], reward)
@@ -241,10 +250,48 @@ class SelfPlay:
         self.model.set_weights(initial_checkpoint["weights"])
         self.model.eval()
         self.engine = BatchedMCTS(self.config, self.model, self.num_games)
+        # config.device_draws: noise, tie words and action choice drawn on the device as a function of (config.seed, slot,
+        # counter) -- csrc/mzx_draws.h; not numpy's draws (opt-in), no host stream is read.  Batched shards only.
+        # The key is THIS actor's seed -- the number that seeds its games and, on host draws, its streams -- not config.seed:
+        # the ranks of a job share a configuration (rank r is seeded config.seed + r * num_games) and must not draw alike.
+        self.device_draws = bool(getattr(self.config, "device_draws", False))
+        self.draw_seed = int(seed)
+        self.engine.draw_seed = self.draw_seed
+        self._draw_counter = 0
         if self.num_games > 1 or self.batched_game is not None:
             self.bank = _rng.StreamBank(self.model.backend.lib, [(seed + i) & 0xFFFFFFFF for i in range(self.num_games)])
         self.stats = {"searches": 0, "simulations": 0, "search_seconds": 0.0}
         self._live = None       # state of the games in progress under play_rounds
+
+    @property
+    def draw_counter(self):
+        """Device draws: the counter of the next search (of every slot group: they advance together).  Saved with a
+        checkpoint and set on a fresh actor in the same game state, it continues the same games.  A search queued ahead and
+        not yet consumed is dropped first (as the setter and ``close_game`` do), so the value read is the one to restore."""
+        self._drain_searches()
+        live = self._live
+        if self.device_draws and live is not None:
+            if live.get("native") is not None:
+                return max(int(g.lib.mzx_actor_draw_counter(g.handle)) for g in live["groups"])
+            return max(int(g["counter"]) for g in live["groups"])
+        return self._draw_counter
+
+    @draw_counter.setter
+    def draw_counter(self, value):
+        self._drain_searches()
+        self._draw_counter = int(value)
+        live = self._live
+        if self.device_draws and live is not None:
+            if live.get("native") is not None:
+                live["native"].set_draw_counter(self._draw_counter)
+            else:
+                for g in live["groups"]:
+                    g["counter"] = self._draw_counter
+
+    def _no_device_draws(self, what):
+        if self.device_draws:
+            raise NotImplementedError(f"config.device_draws covers the batched game protocol (play_games / play_rounds of a "
+                                      f"batched game); {what} draws from numpy streams and would mix the two generators")
 
     # ------------------------------------------------------------------ loops
     def continuous_self_play(self, shared_storage, replay_buffer, test_mode=False):
@@ -380,6 +427,7 @@ class SelfPlay:
 
     def play_game(self, temperature, temperature_threshold, render, opponent, muzero_player):
         """self_play.py:110-183: one game (game slot 0, process-global numpy stream)."""
+        self._no_device_draws("play_game")
         return self._play([0], temperature, temperature_threshold, render, opponent, muzero_player)[0]
 
     def play_games(self, temperature, temperature_threshold, render, opponent, muzero_player):
@@ -389,6 +437,7 @@ class SelfPlay:
             if opponent != "self" or render:
                 raise NotImplementedError("the batched game protocol covers self-play without rendering")
             return self._play_batched(temperature, temperature_threshold)
+        self._no_device_draws("the per-object game path (opponents, human play, rendering, unbatched shards)")
         if self.bank is not None and opponent == "self" and not render:
             return self._play_shard(temperature, temperature_threshold)
         return self._play(list(range(self.num_games)), temperature, temperature_threshold, render, opponent,
@@ -398,6 +447,8 @@ class SelfPlay:
         """Ends the games in progress under ``play_rounds``: queued searches drained, the slot groups' own game objects
         (and native actors) released."""
         self._drain_searches()
+        if self.device_draws and self._live is not None:
+            self._draw_counter = self.draw_counter        # (the next shard's searches go on counting)
         live, self._live = self._live, None
         for group in (live or {}).get("groups", ()):      # (slot groups of the batched protocol own their game objects)
             if group.get("game") is not None and group["game"] is not self.batched_game:
@@ -665,12 +716,16 @@ class SelfPlay:
                 legal = legal[idx] if isinstance(legal, numpy.ndarray) else [legal[i] for i in idx]
             to_play = tp_hist[-1] if everyone else tp_hist[-1][idx]
             t0 = time.perf_counter()
-            result = self.engine.run(stacked, legal, to_play, True, (self.bank, idx))
+            t = temperature if not temperature_threshold or move + 1 < temperature_threshold else 0
+            if self.device_draws:       # one fused move: streams are the shard slots, one counter per move
+                result = self.engine.run(stacked, legal, to_play, True, None, streams=idx, counter=self._draw_counter, temperature=t)
+                self._draw_counter += 1
+            else:
+                result = self.engine.run(stacked, legal, to_play, True, (self.bank, idx))
             self.stats["search_seconds"] += time.perf_counter() - t0
             self.stats["searches"] += len(idx)
             self.stats["simulations"] += len(idx) * self.engine.num_simulations
-            t = temperature if not temperature_threshold or move + 1 < temperature_threshold else 0
-            chosen = self._select_actions_bank(result, idx, t)
+            chosen = result.actions if self.device_draws else self._select_actions_bank(result, idx, t)
             if everyone:
                 actions = numpy.asarray(chosen, numpy.int64)
                 visits, values = result.visit_counts, result.root_values
@@ -752,6 +807,7 @@ class SelfPlay:
         self.finished_slots = []      # slot of every returned game, in the same order (slot s = the actor seeded seed + s)
         if self.batched_game is not None:
             return self._rounds_batched(temperature, temperature_threshold, min_games, max_rounds)
+        self._no_device_draws("the per-object shard")
         return self._rounds_shard(temperature, temperature_threshold, min_games, max_rounds)
 
     def _slot_groups(self, G):
@@ -951,6 +1007,7 @@ class SelfPlay:
             for first, last in spans:
                 game = self.batched_game if len(spans) == 1 else type(self.batched_game)(self._game_seeds[first:last])
                 engine = self.engine if len(spans) == 1 else BatchedMCTS(cfg, self.model, last - first)
+                engine.draw_seed = self.draw_seed
                 groups.append(_BatchedGroup(self, game, first, last - first, engine, temperature))
             live = self._live = dict(groups=groups)
         groups = live["groups"]
@@ -962,8 +1019,14 @@ class SelfPlay:
             legal = group["game"].legal_actions()
             stacked = group["store"].stacked(None) if group["store"] is not None else group["obs"]
             group["legal"] = legal
-            group["pending"] = group["engine"].run(stacked, legal, group["tp"], True, (self.bank, group["streams"]),
-                                                   _defer_advance=True, _asynchronous=True)
+            if self.device_draws:     # the group's search number is its counter, its slots are the streams
+                group["pending"] = group["engine"].run(stacked, legal, group["tp"], True, None, streams=group["streams"],
+                                                       counter=group["counter"], _asynchronous=True,
+                                                       temperature=group.move_temps(temperature_threshold))
+                group["counter"] += 1
+            else:
+                group["pending"] = group["engine"].run(stacked, legal, group["tp"], True, (self.bank, group["streams"]),
+                                                       _defer_advance=True, _asynchronous=True)
             self.stats["search_seconds"] += time.perf_counter() - t0
 
         def consume(group):
@@ -1058,6 +1121,8 @@ class SelfPlay:
             if pending is None or not hasattr(pending, "result"):
                 continue
             group["pending"] = None
+            if self.device_draws and "counter" in group:
+                group["counter"] -= 1        # (the dropped search's draws are a function of this counter: taken again)
             try:
                 pending.result()
             except Exception as e:       # (the search is being discarded anyway; the failure is not)
