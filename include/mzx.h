@@ -903,6 +903,28 @@ int mzx_game_to_play(const mzx_game* g, int32_t* out);
 int mzx_game_step(mzx_game* g, const int64_t* actions, const uint8_t* active /* nullable: games with 0 stay untouched */,
                   double* reward, uint8_t* done);
 
+/* The device-resident twin of a game object (csrc/mzx_games_device.h): the shard's boards, players, keys, step counters
+ * and seeds in device memory, played by kernels (one wavefront per game) that call the very rule functions the host
+ * object's loops call -- reward, done, observation bits, legal row and side to move equal the host object's for the same
+ * actions.  Every array argument is DEVICE memory and every call but create / destroy / download only enqueues on `stream`.
+ * create uploads the host object's current state (blocking); download makes the host object that state again and
+ * synchronises the stream; the host object must be the kind and size the twin was created from.
+ * step: one move of every game; d_actions [num_games] i64; d_active nullable [num_games] u8: a board game with 0 is left
+ * untouched (reward 0, not done) -- the synthetic game steps every game, as mzx_game_step does; d_reward [num_games] f64 and
+ * d_done [num_games] u8 nullable.  A game that ends is NOT reset here.  An action outside the action space leaves its game
+ * untouched (reward 0, not done): the host cannot refuse what it does not see.
+ * position: d_obs [num_games][C*H*W] f32, d_legal [num_games][actions] i32 (increasing, padded with -1), d_to_play
+ * [num_games] i32, each nullable.  reset: d_games [count] i32 device indices (NULL: every game; entries outside the shard
+ * are skipped). */
+typedef struct mzx_game_device mzx_game_device;
+int mzx_game_device_create(const mzx_game* host, mzx_game_device** out);
+void mzx_game_device_destroy(mzx_game_device* d);
+int mzx_game_device_step(mzx_game_device* d, const int64_t* d_actions, const uint8_t* d_active, double* d_reward, uint8_t* d_done,
+                         void* stream);
+int mzx_game_device_position(const mzx_game_device* d, float* d_obs, int32_t* d_legal, int32_t* d_to_play, void* stream);
+int mzx_game_device_reset(mzx_game_device* d, const int32_t* d_games, int32_t count, void* stream);
+int mzx_game_device_download(const mzx_game_device* d, mzx_game* host, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * The self-play ROUND LOOP of a shard of natively stepped games in one call (self_play.py:110-183 for every slot of the
  * shard + the actor loop :31-52; csrc/mzx_actor.h).  An `mzx_actor` is one SLOT GROUP: its game object, search handle,
@@ -968,6 +990,28 @@ int64_t mzx_actor_draw_counter(const mzx_actor* actor);
 /* The counter of the group's next search (a checkpoint's restore); refused while a search is in flight or before
  * mzx_actor_set_device_draws. */
 int mzx_actor_set_draw_counter(mzx_actor* actor, uint64_t counter);
+/* RESIDENT rounds (csrc/mzx_resident.h; after mzx_actor_set_device_draws, before the group's first round): the group's
+ * games (an mzx_game_device made from its game object), its move log and its per-slot bookkeeping live on the device, and
+ * mzx_selfplay_rounds queues whole rounds back to back on the group's stream -- draws, search, action choice + vote,
+ * commit (log row, step, max_moves cut, finished games recorded and restarted, the next search's inputs and temperatures
+ * written straight into the move's input block) -- with no upload, download or wait in between.  The host comes back once
+ * per chunk of `chunk_rounds` rounds (fewer at the end of a max_rounds call): one small download (control block and
+ * finished list), a gather launch that packs the finished games, one download of those; sequence numbers are assigned on
+ * the host in (round, group, slot) order across groups.  Same games, field for field, as the host loop on device draws.
+ * Every group of a call must be resident, or none (MZX_ERR_INVALID).  max_rounds is exact.  With min_games the call plays
+ * whole chunks and stops at the first chunk end with enough finished games: it may play up to chunk_rounds - 1 rounds more
+ * than the host loop would.  io->rounds / searches / games report what was committed; nothing is in flight when the call
+ * returns, and the group's host game object holds the device state again (mzx_game_device_download).  A search that
+ * exhausts its tie-break tape HALTS the group: nothing commits in that round or behind it, the host searches the round
+ * again under the same counter, calls `retry` for the flagged trees (the staging blocks hold the round's inputs and
+ * outputs), takes their actions on the host, uploads the patched outputs, commits the round and queues the rest of the
+ * chunk again; counters of rounds that did not commit are not consumed.  The device log (max_moves + chunk_rounds + 1 rows
+ * per slot and the chunk's finished list) is refused above `max_log_bytes` with a message that states its size.
+ * phase_seconds of a resident call: 0 queueing, 1 waiting, 2 unused (0), 3 harvest, 4 repairs, 5 the rest.
+ * mzx_actor_resident_stats: out[0] rounds committed, 1 chunks, 2 repair rounds, 3 host synchronisations (stream waits),
+ * 4 bytes downloaded, 5 bytes of device log, 6 games harvested, 7 reserved. */
+int mzx_actor_set_resident(mzx_actor* actor, int32_t chunk_rounds, int64_t max_log_bytes);
+int mzx_actor_resident_stats(const mzx_actor* actor, int64_t out[8]);
 int mzx_actor_finished(mzx_actor* a, int64_t before_sequence, int64_t out[3]);
 int mzx_actor_take(mzx_actor* a, int64_t before_sequence, int32_t* slot, int32_t* length, int64_t* sequence, float* observations, int64_t* actions,
                    double* rewards, int64_t* to_play, int32_t* visit_counts, double* root_values, uint8_t* legal_mask,

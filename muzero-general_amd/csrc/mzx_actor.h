@@ -18,6 +18,11 @@
 // consumed, so nothing is in flight between calls -- weights may change there).  Same draws in the same order, same
 // games field for field as the Python loop: tests/test_native_rounds.py.
 //
+// Resident rounds (mzx_actor_set_resident; mzx_resident.h, mzx_games_device.h): on device draws nothing of a move needs the
+// host, and a group may keep its games, this log and its per-slot bookkeeping on the device -- whole rounds are queued back
+// to back and the host returns once per chunk of rounds for the finished games.  The loop above is then the comparator
+// (tests/resident_rounds_cases.py) and the repair path's model (tape retries).
+//
 // Not here (the Python loop keeps them): stacked observations (the device frame store), Python plugin games, opponents.
 #pragma once
 #include <chrono>
@@ -27,6 +32,8 @@
 #include <vector>
 
 #include "mzx_games.h"
+
+struct mzx_actor_resident;
 
 struct mzx_actor {
   mzx_game* game = nullptr;
@@ -76,6 +83,8 @@ struct mzx_actor {
   int64_t* d_action = nullptr;                        // [B] inside move.d_out
   void* d_pow = nullptr;                              // device copy of the call's power table + its temperatures
   std::vector<double> pow_host;                       // what d_pow holds
+  // resident rounds (mzx_actor_set_resident; mzx_resident.h): games, log and bookkeeping on the device
+  mzx_actor_resident* resident = nullptr;
 };
 
 namespace mzx {

@@ -1,5 +1,6 @@
-// mzx_games.h -- games that step NATIVELY for a whole shard (host code, no GPU): the environments a self-play shard plays
-// without returning to the interpreter per move (mzx_selfplay_rounds, mzx_actor.h).
+// mzx_games.h -- games that step NATIVELY for a whole shard (the classes: host code, no GPU; the rules they call: both
+// builds): the environments a self-play shard plays without returning to the interpreter per move (mzx_selfplay_rounds,
+// mzx_actor.h).
 //
 // What they restate.  The reference steps one `Game` object per actor in Python (self_play.py:129-181:
 // legal_actions / step / to_play per move, games/abstract_game.py:9-105).  mzx.games ships three of its board games in
@@ -13,12 +14,98 @@
 // Observations are emitted as float32 (what torch.tensor(obs).float() makes of them, self_play.py:280-285; board planes
 // hold -1 / 0 / 1: exact); `obs_dtype` names the dtype the reference game returns so that the host mirror hands out
 // GameHistory.observation_history in it.  Game for game identical to the Python classes: tests/test_native_games.py.
+//
+// One source for both builds.  The per-game RULES -- the counter hash, a board cell as an observation element, the cell a
+// move lands on, "this line is won", "this action is free", what an ended game pays -- are MZX_HD functions over a plain
+// view of a shard's state (GameView: raw arrays, the same struct whether they are this file's vectors or device memory).
+// The classes below call them in their per-game loops; the device twin (mzx_games_device.h) calls the same functions
+// from one wavefront per game.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include <string>
 #include <vector>
+
+#include "mzx_platform.h"
+
+namespace mzx {
+
+struct GameView {
+  int32_t kind = 0;                 // 0 synthetic, 1 k in a row
+  int32_t num_games = 0, num_actions = 0, num_players = 1, obs_elems = 0;
+  // synthetic: [B] each
+  uint32_t* seeds = nullptr;
+  uint32_t* key = nullptr;
+  uint32_t* t = nullptr;
+  int32_t* turn = nullptr;          // whose move it is, 0 .. num_players - 1
+  // k in a row
+  int32_t rows = 0, cols = 0, k = 0, gravity = 0, end_pays = 0, reward_scale = 1, num_lines = 0;
+  int8_t* board = nullptr;          // [B][rows * cols]: 0 empty, 1 / -1
+  int8_t* player = nullptr;         // [B]: 1 / -1
+  const int32_t* lines = nullptr;   // [num_lines][k] flat cell indices
+};
+
+MZX_HD inline uint32_t game_hash_u32(uint32_t x) {     // mzx/synthetic.py _hash_u32 (wrapping 32-bit arithmetic)
+  x = (x ^ 61u) ^ (x >> 16);
+  x *= 9u;
+  x ^= x >> 4;
+  x *= 0x27D4EB2Du;
+  x ^= x >> 15;
+  return x;
+}
+
+// ---- synthetic (mzx/synthetic.py make_synthetic_batched_game)
+// (seeds * 7919 + 17 in uint64, truncated to uint32: the same value modulo 2**32)
+MZX_HD inline uint32_t synth_first_key(uint32_t seed64_low) { return game_hash_u32(seed64_low * 7919u + 17u); }
+MZX_HD inline float synth_obs_elem(uint32_t key, int64_t j) {
+  const uint32_t lane = (uint32_t)((uint64_t)j * 2654435761ull);
+  const uint32_t h = game_hash_u32(lane + key);
+  return (float)((double)h / 4294967296.0);
+}
+MZX_HD inline uint32_t synth_next_key(uint32_t key, int64_t action, uint32_t t_after) {
+  uint32_t k = key * 31u;
+  k += (uint32_t)action * 131u;
+  k += t_after;
+  return game_hash_u32(k);
+}
+MZX_HD inline int32_t synth_next_turn(int32_t turn, int32_t num_players) { return num_players > 1 ? (turn + 1) % num_players : turn; }
+MZX_HD inline double synth_reward(uint32_t key) { return (double)(key & 1u); }
+
+// ---- k in a row (mzx/games.py _KInARowBatched); b: the game's board
+// element j of plane 0 / 1 / 2: my stones, the other side's, the side to move
+MZX_HD inline float kin_obs_elem(int8_t cell, int8_t player, int plane) {
+  return plane == 0 ? (cell == 1 ? 1.f : 0.f) : plane == 1 ? (cell == -1 ? 1.f : 0.f) : (float)player;
+}
+MZX_HD inline bool kin_action_free(const GameView& v, const int8_t* b, int a) {
+  return v.gravity ? b[(v.rows - 1) * v.cols + a] == 0 : b[a] == 0;
+}
+// the cell a move lands on: the lowest empty cell of the column (-1: the reference's loop places nothing in a full one),
+// or the cell itself
+MZX_HD inline int kin_landing_cell(const GameView& v, const int8_t* b, int a) {
+  if (!v.gravity) return a;
+  for (int r = 0; r < v.rows; ++r)
+    if (b[r * v.cols + a] == 0) return r * v.cols + a;
+  return -1;
+}
+// the board with `me` on `placed` (-1: as stored) -- a wavefront judges the position before its one lane stores the stone
+MZX_HD inline int8_t kin_cell(const int8_t* b, int c, int placed, int8_t me) { return c == placed ? me : b[c]; }
+MZX_HD inline bool kin_line_won(const GameView& v, const int8_t* b, int l, int placed, int8_t me) {
+  bool all = true;
+  for (int i = 0; i < v.k && all; ++i) all = kin_cell(b, v.lines[(size_t)l * v.k + i], placed, me) == me;
+  return all;
+}
+// element j of "can anybody still move": top cells of the columns under gravity, every cell otherwise
+MZX_HD inline int kin_move_cells(const GameView& v) { return v.gravity ? v.cols : v.rows * v.cols; }
+MZX_HD inline bool kin_move_cell_taken(const GameView& v, const int8_t* b, int j, int placed, int8_t me) {
+  return kin_cell(b, v.gravity ? (v.rows - 1) * v.cols + j : j, placed, me) != 0;
+}
+MZX_HD inline double kin_reward(const GameView& v, bool won, bool over) {
+  return (v.end_pays ? over : won) ? (double)v.reward_scale : 0.0;
+}
+MZX_HD inline int32_t kin_to_play(int8_t player) { return player == 1 ? 0 : 1; }
+
+}  // namespace mzx
 
 struct mzx_game {
   int32_t num_games = 0, num_actions = 0, num_players = 1;
@@ -36,43 +123,36 @@ struct mzx_game {
   // active (nullable): games with active[g] == 0 are left untouched (reward 0, not done) -- the lock-step loop of
   // SelfPlay.play_games keeps stepping a shard whose shorter games have ended
   virtual void step(int lo, int hi, const int64_t* actions, const uint8_t* active, double* reward, uint8_t* done) = 0;
+  // the object's state as raw arrays (what the rules read and the device twin uploads / downloads)
+  virtual mzx::GameView view() const = 0;
 };
 
 namespace mzx {
-
-inline uint32_t game_hash_u32(uint32_t x) {     // mzx/synthetic.py _hash_u32 (wrapping 32-bit arithmetic)
-  x = (x ^ 61u) ^ (x >> 16);
-  x *= 9u;
-  x ^= x >> 4;
-  x *= 0x27D4EB2Du;
-  x ^= x >> 15;
-  return x;
-}
 
 // mzx/synthetic.py make_synthetic_batched_game
 struct SyntheticGame : mzx_game {
   std::vector<uint32_t> seeds, key, t;
   std::vector<int32_t> player;
 
-  uint32_t first_key(uint32_t seed64_low) const { return game_hash_u32(seed64_low * 7919u + 17u); }
-
+  GameView view() const override {
+    GameView v;
+    v.kind = 0; v.num_games = num_games; v.num_actions = num_actions; v.num_players = num_players; v.obs_elems = (int32_t)obs_elems();
+    v.seeds = const_cast<uint32_t*>(seeds.data()); v.key = const_cast<uint32_t*>(key.data()); v.t = const_cast<uint32_t*>(t.data());
+    v.turn = const_cast<int32_t*>(player.data());
+    return v;
+  }
   void reset(const int32_t* idx, int32_t count) override {
     for (int32_t k = 0; k < count; ++k) {
       const int g = idx ? idx[k] : k;
       t[g] = 0; player[g] = 0;
-      // (seeds * 7919 + 17 in uint64, truncated to uint32: the same value modulo 2**32)
-      key[g] = first_key(seeds[g]);
+      key[g] = synth_first_key(seeds[g]);
     }
   }
   void observe(int lo, int hi, float* out) const override {
     const int64_t E = obs_elems();
     for (int g = lo; g < hi; ++g) {
       float* o = out + (int64_t)g * E;
-      for (int64_t j = 0; j < E; ++j) {
-        const uint32_t lane = (uint32_t)((uint64_t)j * 2654435761ull);
-        const uint32_t h = game_hash_u32(lane + key[g]);
-        o[j] = (float)((double)h / 4294967296.0);
-      }
+      for (int64_t j = 0; j < E; ++j) o[j] = synth_obs_elem(key[g], j);
     }
   }
   void legal_actions(int lo, int hi, int32_t* out) const override {
@@ -86,12 +166,9 @@ struct SyntheticGame : mzx_game {
             uint8_t* done) override {
     for (int g = lo; g < hi; ++g) {
       t[g] += 1u;
-      uint32_t k = key[g] * 31u;
-      k += (uint32_t)actions[g] * 131u;
-      k += t[g];
-      key[g] = game_hash_u32(k);
-      if (num_players > 1) player[g] = (player[g] + 1) % num_players;
-      reward[g] = (double)(key[g] & 1u);
+      key[g] = synth_next_key(key[g], actions[g], t[g]);
+      player[g] = synth_next_turn(player[g], num_players);
+      reward[g] = synth_reward(key[g]);
       done[g] = 0;
     }
   }
@@ -106,6 +183,14 @@ struct KInARowGame : mzx_game {
   std::vector<int8_t> player;       // [B]: 1 / -1
   std::vector<int32_t> lines;       // [L][k] flat cell indices
 
+  GameView view() const override {
+    GameView v;
+    v.kind = 1; v.num_games = num_games; v.num_actions = num_actions; v.num_players = num_players; v.obs_elems = (int32_t)obs_elems();
+    v.rows = rows; v.cols = cols; v.k = k; v.gravity = gravity ? 1 : 0; v.end_pays = end_pays ? 1 : 0; v.reward_scale = reward_scale;
+    v.num_lines = (int32_t)(lines.size() / (size_t)k);
+    v.board = const_cast<int8_t*>(board.data()); v.player = const_cast<int8_t*>(player.data()); v.lines = lines.data();
+    return v;
+  }
   void build_lines() {
     static const int dirs[4][2] = {{0, 1}, {1, 0}, {1, 1}, {1, -1}};
     for (int r = 0; r < rows; ++r)
@@ -129,55 +214,43 @@ struct KInARowGame : mzx_game {
     for (int g = lo; g < hi; ++g) {
       float* o = out + (int64_t)g * 3 * cells;
       const int8_t* b = &board[(size_t)g * cells];
-      for (int j = 0; j < cells; ++j) {
-        o[j] = b[j] == 1 ? 1.f : 0.f;
-        o[cells + j] = b[j] == -1 ? 1.f : 0.f;
-        o[2 * cells + j] = (float)player[g];
-      }
+      for (int j = 0; j < cells; ++j)
+        for (int plane = 0; plane < 3; ++plane) o[plane * cells + j] = kin_obs_elem(b[j], player[g], plane);
     }
   }
   void legal_actions(int lo, int hi, int32_t* out) const override {
     const int cells = rows * cols, A = num_actions;
+    const GameView v = view();
     for (int g = lo; g < hi; ++g) {
       const int8_t* b = &board[(size_t)g * cells];
       int32_t* o = out + (int64_t)g * A;
       int n = 0;
-      for (int a = 0; a < A; ++a) {
-        const bool free_ = gravity ? b[(rows - 1) * cols + a] == 0 : b[a] == 0;
-        if (free_) o[n++] = a;
-      }
+      for (int a = 0; a < A; ++a)
+        if (kin_action_free(v, b, a)) o[n++] = a;
       for (; n < A; ++n) o[n] = -1;
     }
   }
   void to_play(int lo, int hi, int32_t* out) const override {
-    for (int g = lo; g < hi; ++g) out[g] = player[g] == 1 ? 0 : 1;
+    for (int g = lo; g < hi; ++g) out[g] = kin_to_play(player[g]);
   }
   void step(int lo, int hi, const int64_t* actions, const uint8_t* active, double* reward, uint8_t* done) override {
     const int cells = rows * cols;
-    const int L = (int)(lines.size() / (size_t)k);
+    const GameView v = view();
+    const int L = v.num_lines, M = kin_move_cells(v);
     for (int g = lo; g < hi; ++g) {
       if (active && !active[g]) { reward[g] = 0.0; done[g] = 0; continue; }
       int8_t* b = &board[(size_t)g * cells];
       const int a = (int)actions[g];
       const int8_t me = player[g];
-      if (gravity) {             // the lowest empty cell of the column; the reference's loop places nothing in a full one
-        for (int r = 0; r < rows; ++r)
-          if (b[r * cols + a] == 0) { b[r * cols + a] = me; break; }
-      } else {
-        b[a] = me;
-      }
+      const int cell = kin_landing_cell(v, b, a);
+      if (cell >= 0) b[cell] = me;
       bool won = false;
-      for (int l = 0; l < L && !won; ++l) {
-        bool all = true;
-        for (int i = 0; i < k && all; ++i) all = b[lines[(size_t)l * k + i]] == me;
-        won = all;
-      }
+      for (int l = 0; l < L && !won; ++l) won = kin_line_won(v, b, l, -1, me);
       bool no_move = true;
-      if (gravity) { for (int c = 0; c < cols && no_move; ++c) no_move = b[(rows - 1) * cols + c] != 0; }
-      else { for (int j = 0; j < cells && no_move; ++j) no_move = b[j] != 0; }
+      for (int j = 0; j < M && no_move; ++j) no_move = kin_move_cell_taken(v, b, j, -1, me);
       const bool over = won || no_move;
       done[g] = over ? 1 : 0;
-      reward[g] = ((end_pays ? over : won) ? (double)reward_scale : 0.0);
+      reward[g] = kin_reward(v, won, over);
       player[g] = (int8_t)-me;
     }
   }

@@ -1772,6 +1772,8 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
 
 // ------------------------------------------------------------- natively stepped games + the round loop of a shard
 #include "mzx_actor.h"
+#include "mzx_games_device.h"
+#include "mzx_resident.h"
 
 extern "C" {
 
@@ -1832,6 +1834,90 @@ int mzx_game_step(mzx_game* g, const int64_t* actions, const uint8_t* active, do
   return MZX_OK;
 }
 
+static void resident_free(mzx_actor* a);      // (resident rounds, below)
+
+// ---- the device-resident twin of a game object (mzx_games_device.h)
+
+int mzx_game_device_create(const mzx_game* host, mzx_game_device** out) {
+  if (!host || !out) { set_error("mzx_game_device_create: null argument"); return MZX_ERR_INVALID; }
+  const GameView h = host->view();
+  const GameDeviceLayout L = game_device_layout(h);
+  mzx_game_device* d = new (std::nothrow) mzx_game_device();
+  if (!d) { set_error("out of host memory"); return MZX_ERR_RUNTIME; }
+  d->v = h;
+  d->block_bytes = L.total;
+  if (device_alloc(&d->block, L.total) != 0) {
+    delete d;
+    set_error("mzx_game_device_create: device allocation of %lld bytes failed", (long long)L.total);
+    return MZX_ERR_RUNTIME;
+  }
+  game_device_point(&d->v, (char*)d->block, L);
+  int rc = 0;
+  if (h.kind == 0) {
+    rc = copy_h2d_blocking(d->v.seeds, h.seeds, 4 * (size_t)h.num_games);
+  } else {
+    rc = copy_h2d_blocking((void*)d->v.lines, h.lines, 4 * (size_t)h.num_lines * h.k);
+  }
+  std::vector<void*> src;
+  game_state_arrays(h, [&](void* p, size_t) { src.push_back(p); });
+  size_t q = 0;
+  game_state_arrays(d->v, [&](void* p, size_t bytes) { if (rc == 0) rc = copy_h2d_blocking(p, src[q], bytes); ++q; });
+  if (rc != 0) {
+    device_free(d->block);
+    delete d;
+    set_error("mzx_game_device_create: upload failed: %s", runtime_error_string(rc));
+    return MZX_ERR_RUNTIME;
+  }
+  *out = d;
+  return MZX_OK;
+}
+
+void mzx_game_device_destroy(mzx_game_device* d) {
+  if (!d) return;
+  if (d->block) device_free(d->block);
+  delete d;
+}
+
+int mzx_game_device_step(mzx_game_device* d, const int64_t* d_actions, const uint8_t* d_active, double* d_reward, uint8_t* d_done,
+                         void* stream) {
+  if (!d || !d_actions) { set_error("mzx_game_device_step: null game or actions"); return MZX_ERR_INVALID; }
+  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(GameStepBody{d->v, d_actions, d_active, d_reward, d_done}, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_game_device_position(const mzx_game_device* d, float* d_obs, int32_t* d_legal, int32_t* d_to_play, void* stream) {
+  if (!d) { set_error("mzx_game_device_position: null game"); return MZX_ERR_INVALID; }
+  if (!d_obs && !d_legal && !d_to_play) return MZX_OK;
+  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(GamePositionBody{d->v, d_obs, d_legal, d_to_play}, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_game_device_reset(mzx_game_device* d, const int32_t* d_games, int32_t count, void* stream) {
+  if (!d || count < 0) { set_error("mzx_game_device_reset: argument"); return MZX_ERR_INVALID; }
+  if (!d_games) count = d->v.num_games;
+  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(GameResetBody{d->v, d_games, count}, (stream_t)stream));
+  return MZX_OK;
+}
+
+int mzx_game_device_download(const mzx_game_device* d, mzx_game* host, void* stream) {
+  if (!d || !host) { set_error("mzx_game_device_download: null argument"); return MZX_ERR_INVALID; }
+  const GameView h = host->view();
+  if (h.kind != d->v.kind || h.num_games != d->v.num_games || h.num_actions != d->v.num_actions || h.num_players != d->v.num_players ||
+      h.obs_elems != d->v.obs_elems || h.rows != d->v.rows || h.cols != d->v.cols || h.k != d->v.k) {
+    set_error("mzx_game_device_download: the host object is not the kind and size of game the device state was created from");
+    return MZX_ERR_INVALID;
+  }
+  std::vector<void*> dst;
+  game_state_arrays(h, [&](void* p, size_t) { dst.push_back(p); });
+  int rc = 0;
+  size_t q = 0;
+  game_state_arrays(d->v, [&](void* p, size_t bytes) { if (rc == 0) rc = copy_d2h(dst[q], p, bytes, (stream_t)stream); ++q; });
+  const int waited = stream_sync((stream_t)stream);      // (also behind a failed copy: nothing stays in flight into the host object)
+  if (rc == 0) rc = waited;
+  if (rc != 0) { set_error("mzx_game_device_download: %s", runtime_error_string(rc)); return MZX_ERR_RUNTIME; }
+  return MZX_OK;
+}
+
 int mzx_actor_create(const mzx_actor_config* c, mzx_actor** out) {
   if (!c || !out || !c->game || !c->search || !c->bank || !c->streams || !c->d_arena) { set_error("mzx_actor_create: missing argument"); return MZX_ERR_INVALID; }
   const mzx_game* g = c->game;
@@ -1870,6 +1956,7 @@ void mzx_actor_destroy(mzx_actor* a) {
   event_destroy(a->start_event);
   stream_destroy(a->own_stream);
   if (a->d_pow) device_free(a->d_pow);
+  resident_free(a);
   delete a;
 }
 
@@ -1904,10 +1991,399 @@ int mzx_actor_set_draw_counter(mzx_actor* a, uint64_t counter) {
   return MZX_OK;
 }
 
+// ------------------------------------------------------------- resident rounds (mzx_resident.h)
+
+static void resident_free(mzx_actor* a) {
+  mzx_actor_resident* R = a->resident;
+  if (!R) return;
+  mzx_game_device_destroy(R->game);
+  if (R->block) device_free(R->block);
+  if (R->d_pack) device_free(R->d_pack);
+  delete R;
+  a->resident = nullptr;
+}
+
+int mzx_actor_set_resident(mzx_actor* a, int32_t chunk_rounds, int64_t max_log_bytes) {
+  const char* who = "mzx_actor_set_resident";
+  if (!a) { set_error("%s: null actor", who); return MZX_ERR_INVALID; }
+  if (!a->device_draws) { set_error("%s: the group must be on device draws first (mzx_actor_set_device_draws)", who); return MZX_ERR_INVALID; }
+  if (chunk_rounds < 1) { set_error("%s: chunk_rounds %d must be at least 1", who, chunk_rounds); return MZX_ERR_INVALID; }
+  if (a->pending || a->round != 0) { set_error("%s: the group has played rounds already", who); return MZX_ERR_INVALID; }
+  const mzx_move& m = a->move;
+  auto inside = [&](const void* p, size_t bytes, const void* base, int64_t total) {
+    const ptrdiff_t off = (const char*)p - (const char*)base;
+    return p && off >= 0 && off + (ptrdiff_t)bytes <= total;
+  };
+  const size_t B = (size_t)a->B, A = (size_t)a->A, E = (size_t)a->E;
+  if (!inside(m.io.d_observation, 4 * B * E, m.d_in, m.in_bytes) || !inside(m.io.d_legal_actions, 4 * B * A, m.d_in, m.in_bytes) ||
+      !inside(m.io.d_to_play, 4 * B, m.d_in, m.in_bytes) || !inside(m.io.d_visit_counts, 4 * B * A, m.d_out, m.out_bytes) ||
+      !inside(m.io.d_root_value, 8 * B, m.d_out, m.out_bytes) || !inside(m.io.d_info, 16 * B, m.d_out, m.out_bytes)) {
+    set_error("%s: the move's observation, legal rows and to_play must lie inside the input block, its outputs inside the output block", who);
+    return MZX_ERR_INVALID;
+  }
+  resident_free(a);
+  const int64_t cap = (int64_t)a->max_moves + chunk_rounds + 1;
+  const bool masks = !a->game->always_all_legal;
+  if (masks && a->game->view().kind != 1) { set_error("%s: a game with varying legal sets that is no board game", who); return MZX_ERR_INVALID; }
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+  const size_t rows = (size_t)cap * B, cells = (size_t)chunk_rounds * B;
+  const size_t o_start = take(8 * B), o_temps = take(8 * B), o_obs = take(4 * rows * E), o_tp = take(4 * rows), o_act = take(8 * rows),
+               o_vis = take(4 * rows * A), o_val = take(8 * rows), o_rew = take(8 * rows), o_mask = take(masks ? rows * A : 0),
+               o_ctrl = take(4 * (RESIDENT_CTRL_WORDS + cells)), o_ftp = take(4 * cells), o_fobs = take(4 * cells * E);
+  if ((int64_t)at > max_log_bytes) {
+    set_error("%s: the device log of this group takes %lld bytes (%lld rows of %d slots), more than max_log_bytes = %lld", who,
+              (long long)at, (long long)cap, a->B, (long long)max_log_bytes);
+    return MZX_ERR_INVALID;
+  }
+  mzx_actor_resident* R = new (std::nothrow) mzx_actor_resident();
+  if (!R) { set_error("out of host memory"); return MZX_ERR_RUNTIME; }
+  a->resident = R;
+  int rc = mzx_game_device_create(a->game, &R->game);
+  if (rc) { resident_free(a); return rc; }
+  if (device_alloc(&R->block, at) != 0) {
+    R->block = nullptr;
+    resident_free(a);
+    set_error("%s: device allocation of %lld bytes failed", who, (long long)at);
+    return MZX_ERR_RUNTIME;
+  }
+  R->block_bytes = (int64_t)at;
+  R->stats[5] = (int64_t)at;
+  char* base = (char*)R->block;
+  ResidentDevice& d = R->d;
+  d.game = R->game->v;
+  d.B = a->B; d.A = a->A; d.E = (int32_t)a->E; d.max_moves = a->max_moves; d.chunk = chunk_rounds; d.masks = masks ? 1 : 0; d.cap = cap;
+  d.start = (int64_t*)(base + o_start); d.temps = (double*)(base + o_temps); d.l_obs = (float*)(base + o_obs);
+  d.l_tp = (int32_t*)(base + o_tp); d.l_act = (int64_t*)(base + o_act); d.l_vis = (int32_t*)(base + o_vis);
+  d.l_val = (double*)(base + o_val); d.l_rew = (double*)(base + o_rew); d.l_mask = masks ? (uint8_t*)(base + o_mask) : nullptr;
+  d.ctrl = (int32_t*)(base + o_ctrl); d.fin_len = d.ctrl + RESIDENT_CTRL_WORDS; d.fin_tp = (int32_t*)(base + o_ftp);
+  d.fin_obs = (float*)(base + o_fobs);
+  d.in_obs = (float*)m.io.d_observation; d.in_legal = (int32_t*)m.io.d_legal_actions; d.in_to_play = (int32_t*)m.io.d_to_play;
+  d.in_temperature = a->d_temperature;
+  d.visits = m.io.d_visit_counts; d.root_value = m.io.d_root_value; d.action = a->d_action; d.info = m.io.d_info;
+  R->h_ctrl.assign(RESIDENT_CTRL_WORDS + cells, 0);
+  return MZX_OK;
+}
+
+int mzx_actor_resident_stats(const mzx_actor* a, int64_t out[8]) {
+  if (!a || !out) { set_error("mzx_actor_resident_stats: null"); return MZX_ERR_INVALID; }
+  if (!a->resident) { set_error("mzx_actor_resident_stats: not a resident group"); return MZX_ERR_INVALID; }
+  for (int k = 0; k < 8; ++k) out[k] = a->resident->stats[k];
+  return MZX_OK;
+}
+
+namespace {
+
+const int32_t RESIDENT_CTRL_CLEAR[RESIDENT_CTRL_WORDS] = {0, -1, 0, 0};
+
+struct ResidentPiece {            // the games one harvest of one group brought, not yet numbered
+  int group;
+  mzx_actor::Batch b;
+  std::vector<int64_t> round;     // round of the CALL each game ended in
+};
+
+int resident_fail(const char* what, int rc) {
+  set_error("mzx_selfplay_rounds (resident): %s: %s", what, runtime_error_string(rc));
+  return MZX_ERR_RUNTIME;
+}
+
+// draws -> search -> action choice of the group's next position under `counter`
+int resident_queue_search(mzx_actor* a, const RoundsArgs& args, uint64_t counter, void* stream) {
+  const mzx_move& m = a->move;
+  mzx_draws dd{};
+  dd.seed = a->draw_seed; dd.counter = counter; dd.first_stream = a->streams[0];
+  dd.num_games = a->B; dd.action_space_size = a->A; dd.tape_words = m.tape_words; dd.dirichlet_alpha = m.dirichlet_alpha;
+  dd.d_legal_actions = m.io.d_legal_actions; dd.d_noise = (double*)m.io.d_noise; dd.d_tape = (uint32_t*)m.io.d_tape;
+  int rc = mzx_selfplay_draws(&dd, stream);
+  if (rc) return rc;
+  rc = mzx_search_run(a->search, &m.io, a->d_arena, a->arena_bytes, stream);
+  if (rc) return rc;
+  mzx_draws_select sel{};
+  sel.d_legal_actions = m.io.d_legal_actions; sel.d_visit_counts = m.io.d_visit_counts;
+  sel.d_temperature = a->d_temperature; sel.d_action = a->d_action;
+  if (args.num_temperatures > 0) {
+    sel.d_pow_table = (const double*)a->d_pow;
+    sel.d_table_temperatures = (const double*)a->d_pow + (size_t)args.num_temperatures * args.table_stride;
+    sel.table_stride = args.table_stride; sel.num_temperatures = args.num_temperatures;
+  }
+  return mzx_selfplay_select_device(&dd, &sel, stream);
+}
+
+int resident_queue_commit(mzx_actor* a, const RoundsArgs& args, int64_t r, int q, int prime, void* stream) {
+  ResidentCommitBody body{a->resident->d, r, q, prime, args.temperature_threshold, args.temperature};
+  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(body, (stream_t)stream));
+  return MZX_OK;
+}
+
+// rounds [q0, q1) of the chunk for one group, the first one round a->round under a->draw_counter (the rest of a chunk behind a
+// repaired round); nothing is waited for
+int resident_queue_rounds(mzx_actor* a, const RoundsArgs& args, int q0, int q1, void* stream) {
+  mzx_actor_resident* R = a->resident;
+  for (int q = q0; q < q1; ++q) {
+    int rc = resident_queue_search(a, args, a->draw_counter + (uint64_t)(q - q0), stream);
+    if (rc) return rc;
+    MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(ResidentVoteBody{R->d, q}, (stream_t)stream));
+    rc = resident_queue_commit(a, args, a->round + (q - q0), q, 0, stream);
+    if (rc) return rc;
+  }
+  return MZX_OK;
+}
+
+// the downloads of a chunk's end: control block + finished lengths, and the game state into the host game object (so that
+// legal_actions() etc. are true between calls); queued behind the chunk's rounds, waited for by resident_wait
+int resident_queue_downloads(mzx_actor* a, int rounds_of_chunk, void* stream) {
+  mzx_actor_resident* R = a->resident;
+  const size_t bytes = sizeof(int32_t) * (RESIDENT_CTRL_WORDS + (size_t)rounds_of_chunk * a->B);
+  int rc = copy_d2h(R->h_ctrl.data(), R->d.ctrl, bytes, (stream_t)stream);
+  if (rc) return resident_fail("control block download", rc);
+  R->stats[4] += (int64_t)bytes;
+  const GameView h = a->game->view();
+  std::vector<void*> dst;
+  game_state_arrays(h, [&](void* p, size_t) { dst.push_back(p); });
+  size_t i = 0;
+  game_state_arrays(R->game->v, [&](void* p, size_t n) { if (rc == 0) { rc = copy_d2h(dst[i], p, n, (stream_t)stream); R->stats[4] += (int64_t)n; } ++i; });
+  if (rc) return resident_fail("game state download", rc);
+  return MZX_OK;
+}
+
+int resident_wait(mzx_actor* a, void* stream) {
+  const int rc = stream_sync((stream_t)stream);
+  a->resident->stats[3] += 1;
+  if (rc) return resident_fail("waiting for the group's stream", rc);
+  return MZX_OK;
+}
+
+// the games that ended in rounds [q0, q1) of the chunk (round q = round r_first + (q - q0) of the group, call_round0 + q of the
+// call): gathered on the device, downloaded, queued as one piece
+int resident_harvest(mzx_actor* a, int group, int q0, int q1, int64_t r_first, int64_t call_round0, void* stream,
+                     std::vector<ResidentPiece>& pieces) {
+  mzx_actor_resident* R = a->resident;
+  const int64_t B = a->B, A = a->A, E = a->E;
+  const int32_t* fin = R->h_ctrl.data() + RESIDENT_CTRL_WORDS;
+  std::vector<int64_t> table;
+  ResidentPiece piece;
+  piece.group = group;
+  mzx_actor::Batch& b = piece.b;
+  int64_t o1 = 0, o0 = 0;
+  for (int q = q0; q < q1; ++q)
+    for (int64_t s = 0; s < B; ++s) {
+      const int64_t n = fin[(size_t)q * B + s];
+      if (n == 0) continue;
+      const int64_t last = r_first + (q - q0);
+      if (n < 1 || n > a->max_moves || n > last + 1) {
+        set_error("mzx_selfplay_rounds (resident): slot %lld reports a game of %lld moves in round %lld", (long long)s, (long long)n, (long long)last);
+        return MZX_ERR_RUNTIME;
+      }
+      const int64_t row[5] = {last - n + 1, s, n, o1, o0};
+      table.insert(table.end(), row, row + 5);
+      b.slot.push_back(a->first_slot + (int32_t)s); b.n.push_back((int32_t)n); b.seq.push_back(0);
+      piece.round.push_back(call_round0 + q);
+      o1 += n + 1; o0 += n;
+    }
+  const int64_t k = (int64_t)b.slot.size();
+  if (k == 0) return MZX_OK;
+  const bool masks = R->d.masks != 0;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+  const size_t o_table = take(8 * table.size()), o_obs = take(4 * (size_t)(o1 * E)), o_act = take(8 * (size_t)o1), o_tp = take(8 * (size_t)o1),
+               o_rew = take(8 * (size_t)o1), o_vis = take(4 * (size_t)(o0 * A)), o_val = take(8 * (size_t)o0), o_mask = take(masks ? (size_t)(o0 * A) : 0);
+  if ((int64_t)at > R->pack_bytes) {
+    if (R->d_pack) device_free(R->d_pack);
+    R->d_pack = nullptr; R->pack_bytes = 0;
+    const size_t want = std::max(at, (size_t)1 << 16) * 2;
+    if (device_alloc(&R->d_pack, want) != 0) { R->d_pack = nullptr; set_error("mzx_selfplay_rounds (resident): gather buffer of %lld bytes", (long long)want); return MZX_ERR_RUNTIME; }
+    R->pack_bytes = (int64_t)want;
+  }
+  char* base = (char*)R->d_pack;
+  int rc = copy_h2d(base + o_table, table.data(), 8 * table.size(), (stream_t)stream);
+  if (rc) return resident_fail("gather table upload", rc);
+  ResidentGatherBody body{R->d, (const int64_t*)(base + o_table), (int32_t)k, q0, r_first, (float*)(base + o_obs), (int64_t*)(base + o_act),
+                          (int64_t*)(base + o_tp), (double*)(base + o_rew), (int32_t*)(base + o_vis), (double*)(base + o_val),
+                          masks ? (uint8_t*)(base + o_mask) : nullptr};
+  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(body, (stream_t)stream));
+  b.obs.resize((size_t)(o1 * E)); b.act.resize((size_t)o1); b.tp.resize((size_t)o1); b.rew.resize((size_t)o1);
+  b.vis.resize((size_t)(o0 * A)); b.val.resize((size_t)o0);
+  if (masks) b.mask.resize((size_t)(o0 * A));
+  struct { void* dst; const void* src; size_t bytes; } copies[7] = {
+      {b.obs.data(), base + o_obs, 4 * b.obs.size()}, {b.act.data(), base + o_act, 8 * b.act.size()}, {b.tp.data(), base + o_tp, 8 * b.tp.size()},
+      {b.rew.data(), base + o_rew, 8 * b.rew.size()}, {b.vis.data(), base + o_vis, 4 * b.vis.size()}, {b.val.data(), base + o_val, 8 * b.val.size()},
+      {b.mask.data(), base + o_mask, b.mask.size()}};
+  for (const auto& c : copies) {
+    if (c.bytes == 0) continue;
+    rc = copy_d2h(c.dst, c.src, c.bytes, (stream_t)stream);
+    if (rc) return resident_fail("finished games download", rc);
+    R->stats[4] += (int64_t)c.bytes;
+  }
+  rc = resident_wait(a, stream);
+  if (rc) return rc;
+  if (masks) {
+    bool any_illegal = false;
+    for (uint8_t x : b.mask) if (!x) { any_illegal = true; break; }
+    if (!any_illegal) { b.mask.clear(); b.mask.shrink_to_fit(); }
+  }
+  R->stats[6] += k;
+  pieces.push_back(std::move(piece));
+  return MZX_OK;
+}
+
+// the rare path: round a->round halted (a tree exhausted its tie-break tape).  The round is searched again under the same
+// counter and waited for, the flagged trees go through the retry callback and take their actions on the host (as
+// actor_consume does), the patched output block goes back and the round is committed.
+int resident_repair(mzx_actor* a, int group, const RoundsArgs& args, int q, void* stream) {
+  mzx_actor_resident* R = a->resident;
+  const mzx_move& m = a->move;
+  const int B = a->B, A = a->A;
+  const uint64_t counter = a->draw_counter;
+  int rc = resident_queue_search(a, args, counter, stream);
+  if (rc) return rc;
+  if (m.h_in != m.d_in) { rc = copy_d2h(m.h_in, m.d_in, (size_t)m.in_bytes, (stream_t)stream); R->stats[4] += m.in_bytes; }
+  if (rc == 0 && m.h_out != m.d_out) { rc = copy_d2h(m.h_out, m.d_out, (size_t)m.out_bytes, (stream_t)stream); R->stats[4] += m.out_bytes; }
+  if (rc) return resident_fail("download of the halted round", rc);
+  rc = resident_wait(a, stream);
+  if (rc) return rc;
+  a->draw_counter = counter + 1;        // (the retry callback reads mzx_actor_draw_counter - 1)
+  char* h_out = (char*)m.h_out;
+  const char* h_in = (const char*)m.h_in;
+  auto out_of = [&](const void* d) { return h_out + ((const char*)d - (const char*)m.d_out); };
+  auto in_of = [&](const void* d) { return h_in + ((const char*)d - (const char*)m.d_in); };
+  const int32_t* info = (const int32_t*)out_of(m.io.d_info);
+  std::vector<int32_t> redo;
+  for (int k = 0; k < B; ++k) if (info[4 * k + 1] & 1) redo.push_back(k);
+  if (!redo.empty()) {
+    if (!args.retry) { set_error("mzx_selfplay_rounds: a search exhausted its tie-break tape and no retry callback was given"); return MZX_ERR_RUNTIME; }
+    rc = args.retry(args.retry_ctx, group, (int32_t)redo.size(), redo.data());
+    if (rc) { set_error("mzx_selfplay_rounds: the tape-retry callback failed (%d)", rc); return MZX_ERR_RUNTIME; }
+  }
+  for (int k = 0; k < B; ++k)
+    if (info[4 * k + 1] != 0) { set_error("search flagged tree %d (flags %d): node arena exhausted", k, info[4 * k + 1]); return MZX_ERR_RUNTIME; }
+  if (!redo.empty()) {
+    SelfplaySelectParams sp{};
+    sp.seed = a->draw_seed; sp.counter = counter; sp.first_stream = a->streams[0];
+    sp.legal = (const int32_t*)in_of(m.io.d_legal_actions); sp.visits = (const int32_t*)out_of(m.io.d_visit_counts);
+    sp.temperature = (const double*)in_of(a->d_temperature); sp.pow_table = args.pow_table; sp.table_temperatures = args.table_temperatures;
+    sp.action = (int64_t*)out_of(a->d_action); sp.B = B; sp.A = A; sp.table_stride = args.table_stride; sp.num_temperatures = args.num_temperatures;
+    for (int32_t k : redo) sp.action[k] = draw_select_action(sp, (size_t)k);
+  }
+  if (m.h_out != m.d_out) {
+    rc = copy_h2d(m.d_out, m.h_out, (size_t)m.out_bytes, (stream_t)stream);
+    if (rc) return resident_fail("upload of the repaired round", rc);
+  }
+  rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)stream);
+  if (rc) return resident_fail("control block reset", rc);
+  rc = resident_queue_commit(a, args, a->round, q, 0, stream);
+  if (rc) return rc;
+  a->round += 1;
+  R->stats[0] += 1; R->stats[2] += 1;
+  return MZX_OK;
+}
+
+int resident_rounds(mzx_actor* const* groups, int num_groups, mzx_rounds* io, const RoundsArgs& args, const std::vector<void*>& streams,
+                    int64_t* out_finished, int64_t* out_rounds, int64_t* out_searches, int64_t* sequence) {
+  int rc = MZX_OK;
+  double* phase = io->phase_seconds;
+  int chunk = groups[0]->resident->d.chunk;
+  for (int k = 0; k < num_groups; ++k) chunk = std::min(chunk, (int)groups[k]->resident->d.chunk);
+  for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {      // the first search's inputs, written by the device from the games' state
+    mzx_actor* a = groups[k];
+    mzx_actor_resident* R = a->resident;
+    if (R->primed) continue;
+    const double t0 = actor_now();
+    void* st = streams[(size_t)k];
+    if ((rc = copy_h2d(R->d.start, a->start.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
+        (rc = copy_h2d(R->d.temps, a->temps.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
+        (rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)st)) != 0) {
+      rc = resident_fail("first upload", rc);
+      break;
+    }
+    rc = resident_queue_commit(a, args, a->round, 0, 1, st);
+    R->primed = rc == MZX_OK;
+    phase[0] += actor_now() - t0;
+  }
+  int64_t finished = 0, rounds = 0, searches = 0;
+  while (rc == MZX_OK && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
+    const int n = io->max_rounds < 0 ? chunk : (int)std::min<int64_t>(chunk, io->max_rounds - rounds);
+    std::vector<ResidentPiece> pieces;
+    double t0 = actor_now();
+    // the chunk's rounds, interleaved round by round so that every group's stream starts at once
+    for (int q = 0; q < n && rc == MZX_OK; ++q)
+      for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
+        mzx_actor* a = groups[k];
+        rc = resident_queue_search(a, args, a->draw_counter + (uint64_t)q, streams[(size_t)k]);
+        if (rc) break;
+        { const int e = launch_waves<GAME_WAVES>(ResidentVoteBody{a->resident->d, q}, (stream_t)streams[(size_t)k]); if (e) rc = resident_fail("vote launch", e); }
+        if (rc == MZX_OK) rc = resident_queue_commit(a, args, a->round + q, q, 0, streams[(size_t)k]);
+      }
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) rc = resident_queue_downloads(groups[k], n, streams[(size_t)k]);
+    phase[0] += actor_now() - t0;
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
+      mzx_actor* a = groups[k];
+      mzx_actor_resident* R = a->resident;
+      void* st = streams[(size_t)k];
+      // rounds of the chunk: [0, accounted) are committed and counted in a->round / a->draw_counter (a repaired round is,
+      // the moment resident_repair commits it), [0, harvested) have handed out their finished games
+      int accounted = 0, harvested = 0;
+      R->stats[1] += 1;
+      while (rc == MZX_OK) {
+        t0 = actor_now();
+        rc = resident_wait(a, st);
+        phase[1] += actor_now() - t0;
+        if (rc) break;
+        const bool halted = R->h_ctrl[0] != 0;
+        const int upto = halted ? R->h_ctrl[1] : n;       // the device committed rounds [accounted, upto) in this pass
+        if (upto < accounted || upto > n || (halted && upto >= n)) {
+          set_error("mzx_selfplay_rounds (resident): halt round %d outside the chunk's queued rounds [%d, %d)", upto, accounted, n);
+          rc = MZX_ERR_RUNTIME;
+          break;
+        }
+        t0 = actor_now();
+        rc = resident_harvest(a, k, harvested, upto, a->round - (accounted - harvested), rounds, st, pieces);
+        a->round += upto - accounted; a->draw_counter += (uint64_t)(upto - accounted); R->stats[0] += upto - accounted;
+        accounted = harvested = upto;
+        phase[3] += actor_now() - t0;
+        if (rc || !halted) break;
+        t0 = actor_now();
+        rc = resident_repair(a, k, args, upto, st);       // (commits round `upto`: harvested with the next pass)
+        accounted = upto + 1;
+        if (rc == MZX_OK) rc = resident_queue_rounds(a, args, accounted, n, st);
+        if (rc == MZX_OK) rc = resident_queue_downloads(a, n, st);
+        phase[4] += actor_now() - t0;
+      }
+    }
+    if (rc) break;
+    // sequence numbers in (round, group, slot) order across groups: the order the host loop finishes games in
+    struct Key { int64_t round; int group; int32_t slot; size_t piece, j; };
+    std::vector<Key> keys;
+    for (size_t p = 0; p < pieces.size(); ++p)
+      for (size_t j = 0; j < pieces[p].b.slot.size(); ++j) keys.push_back({pieces[p].round[j], pieces[p].group, pieces[p].b.slot[j], p, j});
+    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
+      return x.round != y.round ? x.round < y.round : x.group != y.group ? x.group < y.group : x.slot < y.slot;
+    });
+    for (const Key& key : keys) pieces[key.piece].b.seq[key.j] = (*sequence)++;
+    for (ResidentPiece& p : pieces) {
+      mzx_actor* a = groups[p.group];
+      std::lock_guard<std::mutex> lk(a->finished_lock);
+      a->finished.push_back(std::move(p.b));
+    }
+    finished += (int64_t)keys.size();
+    rounds += n;
+    for (int k = 0; k < num_groups; ++k) searches += (int64_t)n * groups[k]->B;
+  }
+  *out_finished = finished; *out_rounds = rounds; *out_searches = searches;
+  return rc;
+}
+
+}  // namespace
+
 int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds* io, void* stream) {
   if (!groups || num_groups < 1 || !io) { set_error("mzx_selfplay_rounds: missing argument"); return MZX_ERR_INVALID; }
   for (int k = 0; k < num_groups; ++k)
     if (!groups[k]) { set_error("mzx_selfplay_rounds: null group"); return MZX_ERR_INVALID; }
+  int resident_groups = 0;
+  for (int k = 0; k < num_groups; ++k) resident_groups += groups[k]->resident ? 1 : 0;
+  if (resident_groups != 0 && resident_groups != num_groups) {
+    set_error("mzx_selfplay_rounds: %d of the call's %d groups are resident (mzx_actor_set_resident): all or none", resident_groups, num_groups);
+    return MZX_ERR_INVALID;
+  }
   const double t_call = actor_now();
   for (double& x : io->phase_seconds) x = 0.0;
   RoundsArgs args;
@@ -1938,8 +2414,13 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
     streams[(size_t)k] = a->own_stream;
   }
   for (int k = 0; k < num_groups && rc == MZX_OK; ++k) rc = actor_upload_pow(groups[k], args);
+  if (rc == MZX_OK && resident_groups) {
+    for (int k = 0; k < num_groups; ++k)
+      if (groups[k]->pending) { set_error("mzx_selfplay_rounds: a search is in flight for resident group %d", k); rc = MZX_ERR_INVALID; }
+    if (rc == MZX_OK) rc = resident_rounds(groups, num_groups, io, args, streams, &finished, &rounds, &searches, &sequence);
+  }
   // SelfPlay._rounds_batched, statement for statement
-  while (rc == MZX_OK && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
+  while (rc == MZX_OK && !resident_groups && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
     for (int k = 0; k < num_groups && rc == MZX_OK; ++k)
       if (!groups[k]->pending) rc = actor_begin(groups[k], args, streams[(size_t)k], &search_seconds, io->phase_seconds);
     for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
@@ -1960,6 +2441,7 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
   }
   io->phase_seconds[5] = (actor_now() - t_call) - (io->phase_seconds[0] + io->phase_seconds[1] + io->phase_seconds[2] +
                                                    io->phase_seconds[3] + io->phase_seconds[4]);
+  if (resident_groups) search_seconds = io->phase_seconds[0] + io->phase_seconds[1];
   io->rounds = rounds; io->games = finished; io->searches = searches; io->search_seconds = search_seconds; io->sequence = sequence;
   return rc;
 }

@@ -22,9 +22,13 @@ template <class T> inline T lane_up(T v, int) { return v; }
 template <class T> inline T lane_value(T v, int) { return v; }
 inline int wave_first_lane(bool flag) { return flag ? 0 : -1; }
 inline int wave_last_lane(bool flag) { return flag ? 0 : -1; }
+inline uint64_t wave_ballot(bool flag) { return flag ? 1u : 0u; }
+inline int wave_rank_below(uint64_t, int) { return 0; }
 constexpr int block_threads(int) { return 1; }
 inline void block_sync() {}
 inline void wave_atomic_add(int32_t* p, int32_t v) { *p += v; }
+inline void wave_atomic_or(int32_t* p, int32_t v) { *p |= v; }
+inline void wave_fence() {}
 #else
 constexpr int WAVE_LANES = 64;
 #define MZX_WAVE_FN __device__ __forceinline__
@@ -41,10 +45,17 @@ __device__ __forceinline__ int wave_last_lane(bool flag) {
   const uint64_t set = __ballot(flag);
   return set ? 63 - __clzll((long long)set) : -1;
 }
+// bit l = lane l's flag, the same value in every lane; how many set bits lie below `lane` (a stable compaction's slot)
+__device__ __forceinline__ uint64_t wave_ballot(bool flag) { return __ballot(flag); }
+__device__ __forceinline__ int wave_rank_below(uint64_t set, int lane) { return __popcll(set & ((uint64_t(1) << lane) - 1u)); }
 constexpr int block_threads(int block) { return block; }
 __device__ __forceinline__ void block_sync() { __syncthreads(); }
 // one lane's addition to a counter other wavefronts add to as well (an ordinary vector atomic; the plain sum when serial)
 __device__ __forceinline__ void wave_atomic_add(int32_t* p, int32_t v) { atomicAdd(p, v); }
+__device__ __forceinline__ void wave_atomic_or(int32_t* p, int32_t v) { atomicOr(p, v); }
+// what one lane stored to global memory before it is what every lane of the wavefront loads after it (the lanes run in
+// step; the fence keeps the compiler and the memory pipeline from passing a load ahead of the store)
+__device__ __forceinline__ void wave_fence() { __threadfence_block(); }
 #endif
 
 // "every lane its share of n items": lanes j, j + 64, ... on the device, all of them in the serial build

@@ -298,12 +298,20 @@ PROTOTYPES = {
     "mzx_game_legal_actions": (ctypes.c_int, [c_vp, c_vp]),
     "mzx_game_to_play": (ctypes.c_int, [c_vp, c_vp]),
     "mzx_game_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_game_device_create": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "mzx_game_device_destroy": (None, [c_vp]),
+    "mzx_game_device_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_game_device_position": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_game_device_reset": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp]),
+    "mzx_game_device_download": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mzx_actor_create": (ctypes.c_int, [ctypes.POINTER(ActorConfig), ctypes.POINTER(c_vp)]),
     "mzx_actor_destroy": (None, [c_vp]),
     "mzx_selfplay_rounds": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(Rounds), c_vp]),
     "mzx_actor_set_device_draws": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
     "mzx_actor_draw_counter": (c_i64, [c_vp]),
     "mzx_actor_set_draw_counter": (ctypes.c_int, [c_vp, ctypes.c_uint64]),
+    "mzx_actor_set_resident": (ctypes.c_int, [c_vp, c_i32, c_i64]),
+    "mzx_actor_resident_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64 * 8)]),
     "mzx_actor_finished": (ctypes.c_int, [c_vp, c_i64, ctypes.POINTER(c_i64 * 3)]),
     "mzx_actor_take": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32)]),
     "mzx_selfplay_select": (ctypes.c_int, [c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32,

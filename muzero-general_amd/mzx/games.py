@@ -263,7 +263,7 @@ class NativeBatchedGame:
         from . import _lib
 
         backend = _backend or getattr(type(self), "backend", None) or _lib.default_backend()
-        self.lib = backend.lib
+        self.backend, self.lib = backend, backend.lib
         seeds = numpy.asarray([0 if s is None else int(s) & 0xFFFFFFFF for s in seeds], numpy.uint32)
         self.num_games = int(seeds.size)
         shape = numpy.asarray(self.observation_shape, numpy.int32)
@@ -319,6 +319,86 @@ class NativeBatchedGame:
         out = numpy.empty(self.num_games, numpy.int32)
         self.lib.check(self.lib.mzx_game_to_play(self.native_handle, out.ctypes.data))
         return out.astype(numpy.int64)
+
+    def device_state(self):
+        """The game's device-resident twin (``mzx_game_device_*``), holding this object's CURRENT state."""
+        return DeviceGameState(self)
+
+
+class DeviceGameState:
+    """
+    A shard of natively stepped games kept on the device (include/mzx.h ``mzx_game_device``, csrc/mzx_games_device.h):
+    created from a ``NativeBatchedGame``'s current state, stepped, observed and restarted by kernels, one wavefront per
+    game, that run the rule functions the host object runs.  Every array is a torch tensor on the backend's device and
+    every call but ``download`` only enqueues on the current stream.  Thin: for ``tests/test_device_games.py`` and for
+    loops that keep a shard's games on the device.
+    """
+
+    def __init__(self, game):
+        import ctypes
+
+        self.game, self.backend, self.lib = game, game.backend, game.lib
+        self.num_games, self.A, self.shape = game.num_games, game.A, game.shape
+        self.handle = ctypes.c_void_p()
+        self.lib.check(self.lib.mzx_game_device_create(game.native_handle, ctypes.byref(self.handle)))
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            try:
+                self.lib.mzx_game_device_destroy(handle)
+            except Exception:
+                pass
+
+    def _tensor(self, values, dtype):
+        import torch
+
+        t = values if isinstance(values, torch.Tensor) else torch.as_tensor(numpy.ascontiguousarray(values))
+        t = t.to(device=self.backend.device, dtype=dtype).contiguous()
+        if t.numel() != self.num_games:
+            raise ValueError(f"expected one entry per game ({self.num_games}), got {t.numel()}")
+        return t
+
+    def step(self, actions, active=None):
+        """One move of every game -> (reward float64 [B], done uint8 [B]) on the device; ended games are not reset."""
+        import torch
+
+        a = self._tensor(actions, torch.int64)
+        act = None if active is None else self._tensor(active, torch.uint8)
+        reward = self.backend.empty((self.num_games,), torch.float64)
+        done = self.backend.empty((self.num_games,), torch.uint8)
+        ptr = self.backend.ptr
+        self.lib.check(self.lib.mzx_game_device_step(self.handle, ptr(a), ptr(act), ptr(reward), ptr(done), self.backend.stream()))
+        return reward, done
+
+    def position(self):
+        """-> (observation float32 [B, C, H, W], legal rows int32 [B, A] padded with -1, to_play int32 [B]) on the device."""
+        import torch
+
+        obs = self.backend.empty((self.num_games,) + tuple(self.shape), torch.float32)
+        legal = self.backend.empty((self.num_games, self.A), torch.int32)
+        to_play = self.backend.empty((self.num_games,), torch.int32)
+        ptr = self.backend.ptr
+        self.lib.check(self.lib.mzx_game_device_position(self.handle, ptr(obs), ptr(legal), ptr(to_play), self.backend.stream()))
+        return obs, legal, to_play
+
+    def reset(self, games=None):
+        """Games ``games`` (indices; ``None``: every game) back at their first positions."""
+        import torch
+
+        if games is None:
+            self.lib.check(self.lib.mzx_game_device_reset(self.handle, None, 0, self.backend.stream()))
+            return
+        g = games if isinstance(games, torch.Tensor) else torch.as_tensor(numpy.ascontiguousarray(games, numpy.int32))
+        g = g.to(device=self.backend.device, dtype=torch.int32).contiguous()
+        self.lib.check(self.lib.mzx_game_device_reset(self.handle, self.backend.ptr(g), int(g.numel()), self.backend.stream()))
+
+    def download(self):
+        """The host game object := the device state (waits for the stream)."""
+        self.lib.check(self.lib.mzx_game_device_download(self.handle, self.game.native_handle, self.backend.stream()))
 
 
 class TicTacToeNative(NativeBatchedGame):

@@ -25,6 +25,31 @@ from . import search as _search
 from .search import BatchedMCTS
 
 
+def resident_wanted(config):
+    """``config.device_games``: the shard's games, move log and bookkeeping stay on the device (csrc/mzx_resident.h)."""
+    return bool(getattr(config, "device_games", False))
+
+
+def check_resident(actor):
+    """With ``config.device_games`` set, every case the resident loop does not cover is an error: no silent fall-back."""
+    cfg, game = actor.config, actor.batched_game
+    why = None
+    if not bool(getattr(actor, "device_draws", False)):
+        why = "config.device_draws is off (the resident rounds draw on the device)"
+    elif game is None:
+        why = "the per-object game paths are not covered (a batched, natively stepped game is needed)"
+    elif not getattr(game, "native_handle", None):
+        why = "the game has no native_handle (Python plugin games step in the interpreter)"
+    elif cfg.stacked_observations != 0:
+        why = "stacked observations are not covered"
+    elif not getattr(cfg, "native_rounds", True):
+        why = "config.native_rounds = False keeps the Python round loop"
+    elif not usable(actor):
+        why = "the shard cannot play its rounds natively"
+    if why is not None:
+        raise NotImplementedError(f"config.device_games: {why}")
+
+
 def usable(actor):
     """Whether ``actor``'s shard can play its rounds natively."""
     game = actor.batched_game
@@ -69,6 +94,15 @@ class _Group:
         if device_draws:        # the group's search number is its counter, its slots are the streams
             lib.check(lib.mzx_actor_set_device_draws(self.handle, engine.draw_seed & (2 ** 64 - 1), int(actor.draw_counter),
                                                      c_vp(pin["temperature"]), c_vp(pout["action"])))
+        self.resident = resident_wanted(cfg)
+        if self.resident:       # games, move log and bookkeeping on the device; the host returns once per chunk of rounds
+            lib.check(lib.mzx_actor_set_resident(self.handle, int(getattr(cfg, "device_games_chunk", 16)),
+                                                 int(getattr(cfg, "device_games_max_bytes", 2 << 30))))
+
+    def resident_stats(self):
+        out = (ctypes.c_int64 * 8)()
+        self.lib.check(self.lib.mzx_actor_resident_stats(self.handle, ctypes.byref(out)))
+        return list(out)
 
     def close(self):
         handle, self.handle = self.handle, None
@@ -99,6 +133,7 @@ class NativeShard:
             engine.draw_seed = getattr(actor, "draw_seed", engine.draw_seed)
             self.groups.append(_Group(actor, game, first, last - first, engine, temperature))
         self.handles = (ctypes.c_void_p * len(self.groups))(*[g.handle for g in self.groups])
+        self.resident = all(g.resident for g in self.groups)
         self.temperatures = set()
         self.sequence = 0
         self.error = None
@@ -166,7 +201,11 @@ class NativeShard:
     def rounds(self, temperature, temperature_threshold, min_games, max_rounds):
         """The library call alone (it holds no interpreter lock: ``continuous_self_play`` runs it on a worker thread while
         the main thread hands the previous call's games over).  Returns the sequence number behind the last game this call
-        finished: ``collect(before)`` hands out exactly the games finished so far."""
+        finished: ``collect(before)`` hands out exactly the games finished so far.
+
+        Resident rounds (``config.device_games``): ``max_rounds`` is exact.  With ``min_games`` the call plays whole chunks
+        and stops at the first chunk end with enough finished games.  It may play up to ``chunk_rounds - 1`` rounds more
+        than the host loop would."""
         actor = self._actor
         lib, engine = actor.model.backend.lib, actor.engine
         t = float(temperature)
@@ -192,6 +231,8 @@ class NativeShard:
         io.retry, io.retry_ctx = self._retry, None
         self.error = None
         rc = lib.mzx_selfplay_rounds(self.handles, len(self.groups), ctypes.byref(io), actor.model.backend.stream())
+        if self.resident:       # the eight counters of include/mzx.h mzx_actor_resident_stats, summed over the groups
+            actor.stats["resident"] = [sum(x) for x in zip(*[g.resident_stats() for g in self.groups])]
         if self.error is not None:
             raise self.error
         lib.check(rc)

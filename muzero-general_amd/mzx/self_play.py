@@ -800,6 +800,8 @@ class SelfPlay:
         Batched games need the optional ``reset_games(idx)`` hook; without it, and for a single-game actor, this falls
         back to ``play_games``.
         """
+        if native_rounds.resident_wanted(self.config):
+            native_rounds.check_resident(self)      # (NotImplementedError for what the resident loop does not cover)
         if self.bank is None or (self.batched_game is not None and not hasattr(self.batched_game, "reset_games")):
             self.finished_slots = list(range(self.num_games))
             return self.play_games(temperature, temperature_threshold, False, "self", 0)

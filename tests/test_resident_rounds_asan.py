@@ -1,0 +1,23 @@
+"""
+The host side of resident rounds under the address and undefined-behaviour sanitizers: tests/resident_asan_main.cpp, a
+stand-alone program with its own main that includes the library source as the serial build (-DMZX_HOSTCHECK), plays two
+resident shards across many chunk ends and log wraps and takes the finished games.  Harvest, offsets, log wrap and gather
+indexing are where an out-of-range index would turn into a GPU fault: they are walked here first.  Nothing is loaded into
+the interpreter: the program is compiled with g++ -fsanitize=address,undefined (which links both runtimes) and run as a
+child process.  CPU only.
+"""
+import os
+import subprocess
+
+from conftest import ROOT
+
+
+def test_resident_rounds_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "resident_asan")
+    src = os.path.join(ROOT, "tests", "resident_asan_main.cpp")
+    subprocess.run(["g++", "-O0", "-g1", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-DMZX_HOSTCHECK", "-x", "c++", src, "-o", exe],
+                   check=True)
+    done = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert done.returncode == 0, done.stdout[-4000:]
+    assert done.stdout.strip().endswith("ok") and "runtime error" not in done.stdout, done.stdout[-4000:]
