@@ -23,6 +23,10 @@
 // to back and the host returns once per chunk of rounds for the finished games.  The loop above is then the comparator
 // (tests/resident_rounds_cases.py) and the repair path's model (tape retries).
 //
+// Here: the group object, actor_begin / actor_consume / actor_rounds (the host loop), and what both loops share: actor_draws,
+// actor_queue_device_move (draws -> search -> action choice) and actor_retry_flagged (the tape repair).  The staging of a
+// move is mzx_selfplay.h's, the resident driver mzx_resident.h's; mzx_selfplay_rounds (mzx_lib.cpp) checks and dispatches.
+//
 // Not here (the Python loop keeps them): stacked observations (the device frame store), Python plugin games, opponents.
 #pragma once
 #include <chrono>
@@ -32,6 +36,7 @@
 #include <vector>
 
 #include "mzx_games.h"
+#include "mzx_selfplay.h"
 
 struct mzx_actor_resident;
 
@@ -140,8 +145,59 @@ inline void actor_move_temps(mzx_actor* a, int32_t temperature_threshold) {
   }
 }
 
-struct RoundsArgs;
-inline int actor_begin_device(mzx_actor* a, const RoundsArgs& args, void* stream);
+typedef int (*actor_retry_fn)(void* ctx, int32_t group, int32_t count, const int32_t* games);
+
+struct RoundsArgs {
+  double* phase;               // [6] accumulators (mzx_rounds::phase_seconds)
+  double temperature;
+  int32_t temperature_threshold;
+  const double* pow_table; int32_t table_stride; const double* table_temperatures; int32_t num_temperatures;
+  actor_retry_fn retry; void* retry_ctx;
+};
+
+// The group's draws of search number `counter` (mzx_draws.h): its slots are the streams; the action choice reads the
+// temperatures inside the input block and the call's power table on the device, its temperatures behind the rows
+// (actor_upload_pow).  The legal rows, noise, tape and visit counts are the move's own (actor_queue_device_move).
+inline void actor_draws(const mzx_actor* a, const RoundsArgs& args, uint64_t counter, mzx_draws* d, mzx_draws_select* sel) {
+  *d = mzx_draws{};
+  d->seed = a->draw_seed; d->counter = counter; d->first_stream = a->streams[0];
+  d->num_games = a->B; d->action_space_size = a->A; d->tape_words = a->move.tape_words; d->dirichlet_alpha = a->move.dirichlet_alpha;
+  *sel = mzx_draws_select{};
+  sel->d_temperature = a->d_temperature; sel->d_action = a->d_action;
+  if (args.num_temperatures > 0) {
+    sel->d_pow_table = (const double*)a->d_pow;
+    sel->d_table_temperatures = (const double*)a->d_pow + (size_t)args.num_temperatures * args.table_stride;
+    sel->table_stride = args.table_stride; sel->num_temperatures = args.num_temperatures;
+  }
+}
+
+// Draws into the move's noise and tape, the search, the action choice on its legal rows and visit counts (sel NULL: none):
+// queued on `stream`, nothing uploaded, downloaded or waited for.
+inline int actor_queue_device_move(mzx_search* s, const mzx_move* m, const mzx_draws* d, const mzx_draws_select* sel, void* d_arena,
+                                   int64_t arena_bytes, void* stream) {
+  const mzx_search_io& io = m->io;
+  mzx_draws dd = *d;
+  dd.d_legal_actions = io.d_legal_actions; dd.d_n = nullptr; dd.d_noise = (double*)io.d_noise; dd.d_tape = (uint32_t*)io.d_tape;
+  dd.dirichlet_alpha = m->dirichlet_alpha;
+  int rc = mzx_selfplay_draws(&dd, stream);
+  if (rc == MZX_OK) rc = mzx_search_run(s, &io, d_arena, arena_bytes, stream);
+  if (rc || !sel) return rc;
+  mzx_draws_select ss = *sel;
+  ss.d_legal_actions = io.d_legal_actions; ss.d_visit_counts = io.d_visit_counts;
+  return mzx_selfplay_select_device(&dd, &ss, stream);
+}
+
+// the device-draws move of a group: temperatures into the input block, then upload, draws, search, action choice and
+// download behind one call (mzx_selfplay_move_device); no host stream is touched
+inline int actor_begin_device(mzx_actor* a, const RoundsArgs& args, void* stream) {
+  actor_move_temps(a, args.temperature_threshold);
+  memcpy(move_in_host(&a->move, a->d_temperature), a->move_temps.data(), sizeof(double) * (size_t)a->B);
+  mzx_draws d; mzx_draws_select sel;
+  actor_draws(a, args, a->draw_counter, &d, &sel);
+  const int rc = mzx_selfplay_move_device(a->search, &a->move, &d, &sel, a->n_legal.data(), a->d_arena, a->arena_bytes, stream);
+  if (rc == MZX_OK) ++a->draw_counter;
+  return rc;
+}
 
 inline int actor_begin(mzx_actor* a, const RoundsArgs& args, void* stream, double* search_seconds, double* phase) {
   const double t0 = actor_now();
@@ -222,38 +278,6 @@ inline void actor_harvest(mzx_actor* a, const std::vector<int32_t>& idx, int64_t
   a->finished.push_back(std::move(b));
 }
 
-typedef int (*actor_retry_fn)(void* ctx, int32_t group, int32_t count, const int32_t* games);
-
-struct RoundsArgs {
-  double* phase;               // [6] accumulators (mzx_rounds::phase_seconds)
-  double temperature;
-  int32_t temperature_threshold;
-  const double* pow_table; int32_t table_stride; const double* table_temperatures; int32_t num_temperatures;
-  actor_retry_fn retry; void* retry_ctx;
-};
-
-// the device-draws move of a group: temperatures into the input block, then upload, draws, search, action choice and
-// download behind one call (mzx_selfplay_move_device); no host stream is touched
-inline int actor_begin_device(mzx_actor* a, const RoundsArgs& args, void* stream) {
-  mzx_move& m = a->move;
-  actor_move_temps(a, args.temperature_threshold);
-  double* h_temps = (double*)((char*)m.h_in + ((const char*)a->d_temperature - (const char*)m.d_in));
-  memcpy(h_temps, a->move_temps.data(), sizeof(double) * (size_t)a->B);
-  mzx_draws d{};
-  d.seed = a->draw_seed; d.counter = a->draw_counter; d.first_stream = a->streams[0];
-  d.num_games = a->B; d.action_space_size = a->A; d.tape_words = m.tape_words; d.dirichlet_alpha = m.dirichlet_alpha;
-  mzx_draws_select sel{};
-  sel.d_temperature = a->d_temperature; sel.d_action = a->d_action;
-  if (args.num_temperatures > 0) {
-    sel.d_pow_table = (const double*)a->d_pow;
-    sel.d_table_temperatures = (const double*)a->d_pow + (size_t)args.num_temperatures * args.table_stride;
-    sel.table_stride = args.table_stride; sel.num_temperatures = args.num_temperatures;
-  }
-  const int rc = mzx_selfplay_move_device(a->search, &m, &d, &sel, a->n_legal.data(), a->d_arena, a->arena_bytes, stream);
-  if (rc == MZX_OK) ++a->draw_counter;
-  return rc;
-}
-
 // the call's power table on the device (uploaded when it differs from what the actor holds; blocking, before any search)
 inline int actor_upload_pow(mzx_actor* a, const RoundsArgs& args) {
   if (!a->device_draws || args.num_temperatures < 1) return MZX_OK;
@@ -266,6 +290,36 @@ inline int actor_upload_pow(mzx_actor* a, const RoundsArgs& args) {
   if (device_alloc(&a->d_pow, sizeof(double) * total) != 0) { a->d_pow = nullptr; set_error("mzx_selfplay_rounds: power table allocation failed"); return MZX_ERR_RUNTIME; }
   if (copy_h2d_blocking(a->d_pow, want.data(), sizeof(double) * total) != 0) { set_error("mzx_selfplay_rounds: power table upload failed"); return MZX_ERR_RUNTIME; }
   a->pow_host.swap(want);
+  return MZX_OK;
+}
+
+struct ActorRows {             // host rows [B] of a searched move: what an action re-drawn on the host reads and writes
+  const int32_t* legal; const int32_t* visits; const double* temperature; int64_t* action;
+};
+
+// The tape repair of a searched move, `info` [B][4] being the host copy of what the search reported.  A tree that exhausted
+// its tie-break tape is searched again on a longer one (rare: equal priors at every level): the retry callback owns that
+// path (another staging geometry) and writes the results into the group's host output block.  Any flag left afterwards is
+// an error.  On device draws the device chose the actions; the games searched again (`redo`) take theirs by the same
+// function on the host, under the search's `counter`.
+inline int actor_retry_flagged(const mzx_actor* a, int group, const RoundsArgs& args, const int32_t* info, uint64_t counter,
+                               const ActorRows& rows, std::vector<int32_t>* redo) {
+  const int B = a->B;
+  for (int k = 0; k < B; ++k) if (info[4 * k + 1] & 1) redo->push_back(k);
+  if (!redo->empty()) {
+    if (!args.retry) { set_error("mzx_selfplay_rounds: a search exhausted its tie-break tape and no retry callback was given"); return MZX_ERR_RUNTIME; }
+    const int rc = args.retry(args.retry_ctx, group, (int32_t)redo->size(), redo->data());
+    if (rc) { set_error("mzx_selfplay_rounds: the tape-retry callback failed (%d)", rc); return MZX_ERR_RUNTIME; }
+  }
+  for (int k = 0; k < B; ++k)
+    if (info[4 * k + 1] != 0) { set_error("search flagged tree %d (flags %d): node arena exhausted", k, info[4 * k + 1]); return MZX_ERR_RUNTIME; }
+  if (!a->device_draws || redo->empty()) return MZX_OK;
+  SelfplaySelectParams sp{};
+  sp.seed = a->draw_seed; sp.counter = counter; sp.first_stream = a->streams[0];
+  sp.legal = rows.legal; sp.visits = rows.visits; sp.temperature = rows.temperature; sp.pow_table = args.pow_table;
+  sp.table_temperatures = args.table_temperatures; sp.action = rows.action; sp.B = B; sp.A = a->A;
+  sp.table_stride = args.table_stride; sp.num_temperatures = args.num_temperatures;
+  for (int32_t k : *redo) rows.action[k] = draw_select_action(sp, (size_t)k);
   return MZX_OK;
 }
 
@@ -282,41 +336,18 @@ inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_
   const int B = a->B, A = a->A;
   const int64_t E = a->E;
   const mzx_move& m = a->move;
-  const char* h_out = (const char*)m.h_out;
-  auto host_of = [&](const void* d) { return h_out + ((const char*)d - (const char*)m.d_out); };
-  int32_t* info = (int32_t*)host_of(m.io.d_info);
-  const int32_t* visits = (const int32_t*)host_of(m.io.d_visit_counts);
-  const double* root_value = (const double*)host_of(m.io.d_root_value);
-  // a tree that exhausted its tie-break tape is searched again on a longer one (rare: equal priors at every level); the
-  // host mirror owns that path (another staging geometry) and writes the results into this group's output block
-  std::vector<int32_t> redo;
-  for (int k = 0; k < B; ++k) if (info[4 * k + 1] & 1) redo.push_back(k);
-  if (!redo.empty()) {
-    if (!args.retry) { set_error("mzx_selfplay_rounds: a search exhausted its tie-break tape and no retry callback was given"); return MZX_ERR_RUNTIME; }
-    rc = args.retry(args.retry_ctx, group, (int32_t)redo.size(), redo.data());
-    if (rc) { set_error("mzx_selfplay_rounds: the tape-retry callback failed (%d)", rc); return MZX_ERR_RUNTIME; }
-    const double t2 = actor_now();
-    args.phase[4] += t2 - t1;
-    t1 = t2;
-  }
-  for (int k = 0; k < B; ++k)
-    if (info[4 * k + 1] != 0) { set_error("search flagged tree %d (flags %d): node arena exhausted", k, info[4 * k + 1]); return MZX_ERR_RUNTIME; }
-  const int64_t r = a->round;
+  const int32_t* info = move_out_host(&m, m.io.d_info);
+  const int32_t* visits = move_out_host(&m, m.io.d_visit_counts);
+  const double* root_value = move_out_host(&m, m.io.d_root_value);
   const bool dev = a->device_draws;
-  if (!dev) for (int k = 0; k < B; ++k) a->words[k] = info[4 * k + 2];      // (what the host streams consume; device draws consume nothing)
   actor_move_temps(a, args.temperature_threshold);
-  if (dev) {
-    // the device chose the actions; the few games searched again take theirs by the same function on the host
-    memcpy(a->actions.data(), host_of(a->d_action), sizeof(int64_t) * (size_t)B);
-    if (!redo.empty()) {
-      SelfplaySelectParams sp{};
-      sp.seed = a->draw_seed; sp.counter = a->draw_counter - 1; sp.first_stream = a->streams[0];
-      sp.legal = a->legal.data(); sp.visits = visits; sp.temperature = a->move_temps.data(); sp.pow_table = args.pow_table;
-      sp.table_temperatures = args.table_temperatures; sp.action = a->actions.data(); sp.B = B; sp.A = A;
-      sp.table_stride = args.table_stride; sp.num_temperatures = args.num_temperatures;
-      for (int32_t k : redo) a->actions[k] = draw_select_action(sp, (size_t)k);
-    }
-  }
+  if (dev) memcpy(a->actions.data(), move_out_host(&m, a->d_action), sizeof(int64_t) * (size_t)B);      // the device chose the actions
+  std::vector<int32_t> redo;
+  rc = actor_retry_flagged(a, group, args, info, a->draw_counter - 1, ActorRows{a->legal.data(), visits, a->move_temps.data(), a->actions.data()}, &redo);
+  if (rc) return rc;
+  if (!redo.empty()) { const double t2 = actor_now(); args.phase[4] += t2 - t1; t1 = t2; }
+  const int64_t r = a->round;
+  if (!dev) for (int k = 0; k < B; ++k) a->words[k] = info[4 * k + 2];      // (what the host streams consume; device draws consume nothing)
   if (A > 4096) { set_error("mzx_selfplay_rounds: more than 4096 actions"); return MZX_ERR_INVALID; }
   // (host draws: what select_range indexes; device draws: the same table rows and bounds the device's choice relied on)
   rc = select_check(a->legal.data(), a->n_legal.data(), visits, a->move_temps.data(), B, A, args.table_stride, args.table_temperatures,
@@ -358,11 +389,7 @@ inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_
     for (int k = lo; k < hi; ++k)
       if ((r - a->start[k]) + 2 > max_moves) a->done[k] = 1;        // len(action_history) <= max_moves, self_play.py:129
   });
-  {
-    const double t2 = actor_now();
-    args.phase[2] += t2 - t1;
-    t1 = t2;
-  }
+  { const double t2 = actor_now(); args.phase[2] += t2 - t1; t1 = t2; }
   std::vector<int32_t> over;
   for (int k = 0; k < B; ++k)
     if (a->done[k]) over.push_back(k);
@@ -389,6 +416,29 @@ inline int actor_consume(mzx_actor* a, int group, const RoundsArgs& args, int64_
   args.phase[3] += actor_now() - t1;
   a->round = r + 1;
   return MZX_OK;
+}
+
+// The host loop of a rounds call: SelfPlay._rounds_batched, statement for statement.
+inline int actor_rounds(mzx_actor* const* groups, int num_groups, const mzx_rounds* io, const RoundsArgs& args,
+                        const std::vector<void*>& streams, int64_t* finished, int64_t* rounds, int64_t* searches, int64_t* sequence,
+                        double* search_seconds) {
+  int rc = MZX_OK;
+  while (rc == MZX_OK && *finished < io->min_games && (io->max_rounds < 0 || *rounds < io->max_rounds)) {
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k)
+      if (!groups[k]->pending) rc = actor_begin(groups[k], args, streams[(size_t)k], search_seconds, args.phase);
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
+      rc = actor_consume(groups[k], k, args, sequence, finished, search_seconds);
+      if (rc) break;
+      *searches += groups[k]->B;
+      int64_t later = 0;
+      for (int j = k + 1; j < num_groups; ++j) later += groups[j]->B;
+      // certain to be consumed by this call: runs while the host plays the groups after it
+      if (k + 1 < num_groups && *finished + later < io->min_games && (io->max_rounds < 0 || *rounds + 1 < io->max_rounds))
+        rc = actor_begin(groups[k], args, streams[(size_t)k], search_seconds, args.phase);
+    }
+    ++*rounds;
+  }
+  return rc;
 }
 
 }  // namespace mzx

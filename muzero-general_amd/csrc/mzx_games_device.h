@@ -196,4 +196,13 @@ inline void game_state_arrays(const GameView& v, F&& each) {
   else { each((void*)v.board, B * (size_t)v.rows * v.cols); each((void*)v.player, B); }
 }
 
+// fn(dst array, src array, bytes) for every state array of two views of the same kind and size (host and device twin)
+template <class F>
+inline void game_state_copy(const GameView& dst, const GameView& src, F&& fn) {
+  void* to[3];
+  int n = 0, i = 0;
+  game_state_arrays(dst, [&](void* p, size_t) { to[n++] = p; });
+  game_state_arrays(src, [&](void* p, size_t bytes) { fn(to[i++], p, bytes); });
+}
+
 }  // namespace mzx

@@ -8,11 +8,15 @@
 #include <new>
 #include <string>
 
+#include "mzx_actor.h"
 #include "mzx_draws.h"
+#include "mzx_games_device.h"
 #include "mzx_obs.h"
 #include "mzx_replay.h"
+#include "mzx_resident.h"
 #include "mzx_rng.h"
 #include "mzx_search.h"
+#include "mzx_selfplay.h"
 #include "mzx_trainer.h"
 #include "mzx_train_fc.h"
 #include "mzx_tree_carry.h"
@@ -882,14 +886,6 @@ int mzx_support_to_scalar(const float* d_logits, int32_t rows, int32_t support_s
 
 // ------------------------------------------------------------- random streams
 
-static int rng_check(const mzx_rng* r, const int32_t* idx, int32_t count) {
-  if (!r || (count > 0 && !idx) || count < 0) { set_error("rng: null / negative argument"); return MZX_ERR_INVALID; }
-  const int32_t n = (int32_t)r->streams.size();
-  for (int32_t k = 0; k < count; ++k)
-    if (idx[k] < 0 || idx[k] >= n) { set_error("rng: stream index %d out of range (%d streams)", idx[k], n); return MZX_ERR_INVALID; }
-  return MZX_OK;
-}
-
 int mzx_rng_create(int32_t num_streams, mzx_rng** out) {
   if (num_streams < 1 || !out) { set_error("mzx_rng_create: invalid argument"); return MZX_ERR_INVALID; }
   mzx_rng* r = new (std::nothrow) mzx_rng();
@@ -934,21 +930,9 @@ int mzx_rng_root_draws(mzx_rng* r, const int32_t* idx, int32_t count, double alp
       if (n_legal[k] < 1 || n_legal[k] > action_space_size) { set_error("n_legal[%d] = %d out of range", k, n_legal[k]); return MZX_ERR_INVALID; }
   rng_parallel(r, count, n_threads, [=](int lo, int hi) {
     for (int k = lo; k < hi; ++k) {
-      if (k + 1 < hi) {   // the next game's generator state (2.5 KB each: a shard's bank does not stay in cache)
-        const Mt19937& nx = r->streams[idx[k + 1]];
-        __builtin_prefetch(&nx.pos);
-        __builtin_prefetch(&nx.key[nx.pos < 624 ? nx.pos : 0]);
-      }
+      rng_prefetch_next(r, idx, k, hi);
       Mt19937& m = r->streams[idx[k]];
-      if (noise) {  // RandomState.dirichlet([alpha] * n): gammas, then multiplication by 1 / sum
-        double* out = noise + (size_t)k * action_space_size;
-        const int n = n_legal[k];
-        double acc = 0.0;
-        for (int j = 0; j < n; ++j) { out[j] = m.standard_gamma(alpha); acc = acc + out[j]; }
-        const double invacc = 1 / acc;
-        for (int j = 0; j < n; ++j) out[j] = out[j] * invacc;
-        for (int j = n; j < action_space_size; ++j) out[j] = 0.0;
-      }
+      if (noise) dirichlet_row(m, alpha, n_legal[k], action_space_size, noise + (size_t)k * action_space_size);
       if (tape_words > 0) m.peek(tape_words, tape + (size_t)k * tape_words);   // generator state untouched
     }
   });
@@ -1009,165 +993,37 @@ int mzx_rng_choice_weighted(mzx_rng* r, const int32_t* idx, int32_t count, const
   return MZX_OK;
 }
 
-}  // extern "C"
-
-namespace mzx {
-
-// SelfPlay.select_action (self_play.py:222-245) for the games [lo, hi) of a move: the streams first consume the tie-break
-// words the search used (mzx_rng_advance), then every game's action is drawn.  Shared by mzx_selfplay_select and the round
-// loop of mzx_actor.h (where it runs inside the per-move region together with the game step).
-struct SelectArgs {
-  mzx_rng* r; const int32_t* idx; const int32_t* legal_all; const int32_t* n_legal; const int32_t* words; const int32_t* visit_counts;
-  const double* temperature; const double* pow_table; int32_t table_stride; const double* table_temperatures; int32_t num_temperatures;
-  int64_t* action; int32_t A;
-};
-
-inline void select_range(const SelectArgs& s, int lo, int hi) {
-  mzx_rng* r = s.r;
-  const int32_t* idx = s.idx;
-  const int A = s.A;
-  double cdf[4096];
-  for (int k = lo; k < hi; ++k) {
-    if (k + 1 < hi) {
-      const Mt19937& nx = r->streams[idx[k + 1]];
-      __builtin_prefetch(&nx.pos);
-      __builtin_prefetch(&nx.key[nx.pos < 624 ? nx.pos : 0]);
-    }
-    Mt19937& g = r->streams[idx[k]];
-    if (s.words) for (int32_t j = 0; j < s.words[k]; ++j) g.next32();        // what the search consumed (mzx_rng_advance)
-    const int32_t* legal = s.legal_all + (size_t)k * A;
-    const int32_t* vis = s.visit_counts + (size_t)k * A;
-    const int n = s.n_legal[k];
-    const double t = s.temperature[k];
-    int pos = 0;
-    if (t == 0.0) {                            // actions[numpy.argmax(visit_counts)]: the first maximum
-      int32_t best = vis[legal[0]];
-      for (int j = 1; j < n; ++j) if (vis[legal[j]] > best) { best = vis[legal[j]]; pos = j; }
-    } else if (t == MZX_INF) {                 // numpy.random.choice(actions)
-      pos = (int)g.bounded((uint32_t)n);
-    } else {                                   // numpy.random.choice(actions, p=dist / sum(dist)): mzx_rng_choice_weighted
-      int row = 0;
-      for (int q = 0; q < s.num_temperatures; ++q) if (s.table_temperatures[q] == t) row = q;
-      const double* tab = s.pow_table + (size_t)row * s.table_stride;
-      double total = 0.0;
-      for (int j = 0; j < n; ++j) total = total + tab[vis[legal[j]]];
-      double acc = 0.0;
-      for (int j = 0; j < n; ++j) { acc = acc + tab[vis[legal[j]]] / total; cdf[j] = acc; }
-      const double last = cdf[n - 1];
-      const double u = g.next_double();
-      for (int j = 0; j < n; ++j) pos += (cdf[j] / last <= u) ? 1 : 0;
-    }
-    s.action[k] = legal[pos < n ? pos : n - 1];
-  }
-}
-
-// the argument checks of mzx_selfplay_select (temperatures have a power table row, visit counts lie inside it)
-inline int select_check(const int32_t* legal_all, const int32_t* n_legal, const int32_t* visit_counts, const double* temperature,
-                        int B, int A, int32_t table_stride, const double* table_temperatures, int32_t num_temperatures) {
-  for (int k = 0; k < B; ++k) {
-    if (n_legal[k] < 1 || n_legal[k] > A) { set_error("n_legal[%d] = %d out of range", k, n_legal[k]); return MZX_ERR_INVALID; }
-    const double t = temperature[k];
-    if (t == 0.0 || t == MZX_INF) continue;
-    int row = -1;
-    for (int q = 0; q < num_temperatures; ++q) if (table_temperatures[q] == t) row = q;
-    if (row < 0) { set_error("mzx_selfplay_select: no power table for temperature %g", t); return MZX_ERR_INVALID; }
-    const int32_t* legal = legal_all + (size_t)k * A;
-    const int32_t* vis = visit_counts + (size_t)k * A;
-    for (int j = 0; j < n_legal[k]; ++j)
-      if (vis[legal[j]] < 0 || vis[legal[j]] >= table_stride) { set_error("visit count %d outside the power table", vis[legal[j]]); return MZX_ERR_INVALID; }
-  }
-  return MZX_OK;
-}
-
-}  // namespace mzx
-
-extern "C" {
-
-// ------------------------------------------------------------- a self-play move of a shard behind two calls
-
-static int move_check(const mzx_rng* r, const mzx_move* m) {
-  if (!m) { set_error("mzx_move: null"); return MZX_ERR_INVALID; }
-  if (m->num_games < 1 || m->action_space_size < 1 || m->tape_words < 0) { set_error("mzx_move: sizes"); return MZX_ERR_INVALID; }
-  if (!m->legal_actions) { set_error("mzx_move: legal_actions missing"); return MZX_ERR_INVALID; }
-  return rng_check(r, m->streams, m->num_games);
-}
-
-// host address of the field whose device address is `d` (NULL when the field lies outside the staged block)
-static void* move_host(const void* d, const void* d_block, void* h_block, int64_t bytes) {
-  if (!d) return nullptr;
-  const ptrdiff_t off = (const char*)d - (const char*)d_block;
-  if (off < 0 || off >= bytes) return nullptr;
-  return (char*)h_block + off;
-}
+// ------------------------------------------------------------- a self-play move of a shard behind two calls (mzx_selfplay.h)
 
 int mzx_selfplay_search(mzx_search* s, mzx_rng* r, const mzx_move* m, int32_t* n_legal, void* d_arena,
                         int64_t arena_bytes, void* stream) {
+  const char* who = "mzx_selfplay_search";
   int rc = move_check(r, m);
   if (rc) return rc;
-  if (!s || !n_legal || !m->to_play || !m->h_in || !m->d_in || !m->h_out || !m->d_out || m->in_bytes < 1 || m->out_bytes < 1) {
-    set_error("mzx_selfplay_search: missing buffer");
-    return MZX_ERR_INVALID;
-  }
+  if (!s) { set_error("%s: missing buffer", who); return MZX_ERR_INVALID; }
+  rc = move_stage(m, n_legal, who, true);
+  if (rc) return rc;
   const int B = m->num_games, A = m->action_space_size, W = m->tape_words;
-  const mzx_search_io& io = m->io;
-  double* h_noise = (double*)move_host(io.d_noise, m->d_in, m->h_in, m->in_bytes);
-  int32_t* h_legal = (int32_t*)move_host(io.d_legal_actions, m->d_in, m->h_in, m->in_bytes);
-  int32_t* h_to_play = (int32_t*)move_host(io.d_to_play, m->d_in, m->h_in, m->in_bytes);
-  uint32_t* h_tape = (uint32_t*)move_host(io.d_tape, m->d_in, m->h_in, m->in_bytes);
-  float* h_obs = (float*)move_host(io.d_observation, m->d_in, m->h_in, m->in_bytes);
-  if (!h_legal || !h_to_play || (W > 0 && !h_tape) || (m->observation && !h_obs) || (!m->observation && !io.d_observation) ||
-      (m->add_exploration_noise ? !h_noise : io.d_noise != nullptr)) {
-    set_error("mzx_selfplay_search: io fields must lie inside the staged input block");
-    return MZX_ERR_INVALID;
-  }
-  // self_play.py:296-301 on the padded lists
-  for (int k = 0; k < B; ++k) {
-    const int32_t* row = m->legal_actions + (size_t)k * A;
-    int n = 0;
-    while (n < A && row[n] >= 0) ++n;
-    if (n == 0) { set_error("Legal actions should not be an empty array. Got [] (game %d).", k); return MZX_ERR_INVALID; }
-    for (int j = 0; j < A; ++j)
-      if (j < n ? row[j] >= A : row[j] >= 0) {
-        set_error("Legal actions should be a subset of the action space (padded with -1 at the end); game %d.", k);
-        return MZX_ERR_INVALID;
-      }
-    n_legal[k] = n;
-  }
+  double* h_noise = move_in_host(m, m->io.d_noise);
+  uint32_t* h_tape = move_in_host(m, m->io.d_tape);
   const double alpha = m->dirichlet_alpha;
   const int32_t* idx = m->streams;
   rng_parallel(r, B, m->num_threads, [=](int lo, int hi) {
     for (int k = lo; k < hi; ++k) {
-      if (k + 1 < hi) {   // the next game's generator state (2.5 KB each, a shard's bank does not stay in cache)
-        const Mt19937& nx = r->streams[idx[k + 1]];
-        __builtin_prefetch(&nx.pos);
-        __builtin_prefetch(&nx.key[nx.pos < 624 ? nx.pos : 0]);
-      }
+      rng_prefetch_next(r, idx, k, hi);
       Mt19937& g = r->streams[idx[k]];
-      if (h_noise) {  // RandomState.dirichlet([alpha] * n): the statements of mzx_rng_root_draws
-        double* out = h_noise + (size_t)k * A;
-        const int n = n_legal[k];
-        double acc = 0.0;
-        for (int j = 0; j < n; ++j) { out[j] = g.standard_gamma(alpha); acc = acc + out[j]; }
-        const double invacc = 1 / acc;
-        for (int j = 0; j < n; ++j) out[j] = out[j] * invacc;
-        for (int j = n; j < A; ++j) out[j] = 0.0;
-      }
-      if (W > 0) g.peek(W, h_tape + (size_t)k * W);
+      if (h_noise) dirichlet_row(g, alpha, n_legal[k], A, h_noise + (size_t)k * A);
+      if (W > 0) g.peek(W, h_tape + (size_t)k * W);       // generator state untouched
     }
   });
-  memcpy(h_legal, m->legal_actions, sizeof(int32_t) * (size_t)B * A);
-  memcpy(h_to_play, m->to_play, sizeof(int32_t) * (size_t)B);
-  if (m->observation) memcpy(h_obs, m->observation, sizeof(float) * (size_t)B * m->observation_floats);
-  const bool staged = m->h_in != m->d_in;
-  if (staged) MZX_TRY_LAUNCH(copy_h2d(m->d_in, m->h_in, (size_t)m->in_bytes, (stream_t)stream));
+  rc = move_upload(m, stream);
+  if (rc) return rc;
   // (instrumented builds only, -DMZX_EXPERIMENT: the host envelope of a move timed without the search)
   if (!exp_int("MZX_MOVE_NO_SEARCH", 0)) {
-    rc = mzx_search_run(s, &io, d_arena, arena_bytes, stream);
+    rc = mzx_search_run(s, &m->io, d_arena, arena_bytes, stream);
     if (rc) return rc;
   }
-  if (m->h_out != m->d_out) MZX_TRY_LAUNCH(copy_d2h(m->h_out, m->d_out, (size_t)m->out_bytes, (stream_t)stream));
-  if (!(m->flags & MZX_MOVE_NO_SYNC)) MZX_TRY_LAUNCH(stream_sync((stream_t)stream));
-  return MZX_OK;
+  return move_finish(m, stream);
 }
 
 int mzx_selfplay_select(mzx_rng* r, const mzx_move* m, const int32_t* n_legal, const int32_t* words,
@@ -1195,16 +1051,6 @@ int mzx_selfplay_select(mzx_rng* r, const mzx_move* m, const int32_t* n_legal, c
 
 // ------------------------------------------------------------- self-play draws on the device (mzx_draws.h)
 
-static int draws_check(const char* who, const mzx_draws* d) {
-  if (!d) { set_error("%s: null mzx_draws", who); return MZX_ERR_INVALID; }
-  if (d->num_games < 1 || d->action_space_size < 1) { set_error("%s: num_games and action_space_size must be positive", who); return MZX_ERR_INVALID; }
-  if (d->action_space_size > DRAWS_MAX_ACTIONS) {
-    set_error("%s: %d actions, the device draws take at most %d", who, d->action_space_size, DRAWS_MAX_ACTIONS);
-    return MZX_ERR_INVALID;
-  }
-  return MZX_OK;
-}
-
 int mzx_selfplay_draws(const mzx_draws* d, void* stream) {
   const int rc = draws_check("mzx_selfplay_draws", d);
   if (rc) return rc;
@@ -1226,28 +1072,6 @@ int mzx_selfplay_draws(const mzx_draws* d, void* stream) {
   return MZX_OK;
 }
 
-static int draws_select_params(const char* who, const mzx_draws* d, const mzx_draws_select* sel, SelfplaySelectParams* p,
-                               bool rows_of_move = false) {
-  const int rc = draws_check(who, d);
-  if (rc) return rc;
-  if (!sel) { set_error("%s: null mzx_draws_select", who); return MZX_ERR_INVALID; }
-  if ((!rows_of_move && (!sel->d_legal_actions || !sel->d_visit_counts)) || !sel->d_temperature || !sel->d_action) {
-    set_error("%s: d_legal_actions, d_visit_counts, d_temperature and d_action are required", who);
-    return MZX_ERR_INVALID;
-  }
-  if (sel->num_temperatures < 0 ||
-      (sel->num_temperatures > 0 && (!sel->d_pow_table || !sel->d_table_temperatures || sel->table_stride < 1))) {
-    set_error("%s: power table missing", who);
-    return MZX_ERR_INVALID;
-  }
-  p->seed = d->seed; p->counter = d->counter; p->streams = d->d_streams; p->legal = sel->d_legal_actions;
-  p->visits = sel->d_visit_counts; p->temperature = sel->d_temperature; p->pow_table = sel->d_pow_table;
-  p->table_temperatures = sel->d_table_temperatures; p->uniforms = sel->d_uniforms; p->action = sel->d_action;
-  p->first_stream = d->first_stream; p->B = d->num_games; p->A = d->action_space_size; p->table_stride = sel->table_stride;
-  p->num_temperatures = sel->num_temperatures;
-  return MZX_OK;
-}
-
 int mzx_selfplay_select_device(const mzx_draws* d, const mzx_draws_select* sel, void* stream) {
   SelfplaySelectParams p;
   const int rc = draws_select_params("mzx_selfplay_select_device", d, sel, &p);
@@ -1260,16 +1084,11 @@ int mzx_selfplay_move_device(mzx_search* s, const mzx_move* m, const mzx_draws* 
                              void* d_arena, int64_t arena_bytes, void* stream) {
   const char* who = "mzx_selfplay_move_device";
   if (!m) { set_error("%s: null mzx_move", who); return MZX_ERR_INVALID; }
-  if (!s || !n_legal || !m->legal_actions || !m->to_play || !m->h_in || !m->d_in || !m->h_out || !m->d_out || m->in_bytes < 1 ||
-      m->out_bytes < 1) {
-    set_error("%s: missing buffer", who);
-    return MZX_ERR_INVALID;
-  }
+  if (!s) { set_error("%s: missing buffer", who); return MZX_ERR_INVALID; }
   SelfplaySelectParams sp;
   int rc = sel ? draws_select_params(who, d, sel, &sp, true) : draws_check(who, d);      // (no sel: no action choice)
   if (rc) return rc;
-  const int B = m->num_games, A = m->action_space_size, W = m->tape_words;
-  if (B != d->num_games || A != d->action_space_size || W != d->tape_words || W < 1) {
+  if (m->num_games != d->num_games || m->action_space_size != d->action_space_size || m->tape_words != d->tape_words || m->tape_words < 1) {
     set_error("%s: the move and the draws disagree on num_games / action_space_size / tape_words (>= 1)", who);
     return MZX_ERR_INVALID;
   }
@@ -1279,43 +1098,10 @@ int mzx_selfplay_move_device(mzx_search* s, const mzx_move* m, const mzx_draws* 
     return MZX_ERR_INVALID;
   }
   if (!io.d_tape || !io.d_visit_counts) { set_error("%s: io.d_tape / io.d_visit_counts missing", who); return MZX_ERR_INVALID; }
-  int32_t* h_legal = (int32_t*)move_host(io.d_legal_actions, m->d_in, m->h_in, m->in_bytes);
-  int32_t* h_to_play = (int32_t*)move_host(io.d_to_play, m->d_in, m->h_in, m->in_bytes);
-  float* h_obs = (float*)move_host(io.d_observation, m->d_in, m->h_in, m->in_bytes);
-  if (!h_legal || !h_to_play || (m->observation && !h_obs) || (!m->observation && !io.d_observation)) {
-    set_error("%s: io fields must lie inside the staged input block", who);
-    return MZX_ERR_INVALID;
-  }
-  for (int k = 0; k < B; ++k) {      // self_play.py:296-301 on the padded lists, as mzx_selfplay_search
-    const int32_t* row = m->legal_actions + (size_t)k * A;
-    int n = 0;
-    while (n < A && row[n] >= 0) ++n;
-    if (n == 0) { set_error("Legal actions should not be an empty array. Got [] (game %d).", k); return MZX_ERR_INVALID; }
-    for (int j = 0; j < A; ++j)
-      if (j < n ? row[j] >= A : row[j] >= 0) {
-        set_error("Legal actions should be a subset of the action space (padded with -1 at the end); game %d.", k);
-        return MZX_ERR_INVALID;
-      }
-    n_legal[k] = n;
-  }
-  memcpy(h_legal, m->legal_actions, sizeof(int32_t) * (size_t)B * A);
-  memcpy(h_to_play, m->to_play, sizeof(int32_t) * (size_t)B);
-  if (m->observation) memcpy(h_obs, m->observation, sizeof(float) * (size_t)B * m->observation_floats);
-  if (m->h_in != m->d_in) MZX_TRY_LAUNCH(copy_h2d(m->d_in, m->h_in, (size_t)m->in_bytes, (stream_t)stream));
-  mzx_draws dd = *d;                 // the move's own arrays: legal rows, noise and tape of the search
-  dd.d_legal_actions = io.d_legal_actions; dd.d_n = nullptr; dd.d_noise = (double*)io.d_noise; dd.d_tape = (uint32_t*)io.d_tape;
-  dd.dirichlet_alpha = m->dirichlet_alpha;
-  rc = mzx_selfplay_draws(&dd, stream);
-  if (rc) return rc;
-  rc = mzx_search_run(s, &io, d_arena, arena_bytes, stream);
-  if (rc) return rc;
-  if (sel) {
-    sp.legal = io.d_legal_actions; sp.visits = io.d_visit_counts;
-    MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(SelfplaySelectBody{sp}, (stream_t)stream));
-  }
-  if (m->h_out != m->d_out) MZX_TRY_LAUNCH(copy_d2h(m->h_out, m->d_out, (size_t)m->out_bytes, (stream_t)stream));
-  if (!(m->flags & MZX_MOVE_NO_SYNC)) MZX_TRY_LAUNCH(stream_sync((stream_t)stream));
-  return MZX_OK;
+  rc = move_stage(m, n_legal, who, false);
+  if (rc == MZX_OK) rc = move_upload(m, stream);
+  if (rc == MZX_OK) rc = actor_queue_device_move(s, m, d, sel, d_arena, arena_bytes, stream);
+  return rc ? rc : move_finish(m, stream);
 }
 
 // ------------------------------------------------------------- replay hand-off: initial PER priorities on the device
@@ -1768,14 +1554,7 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
   return MZX_OK;
 }
 
-}  // extern "C"
-
 // ------------------------------------------------------------- natively stepped games + the round loop of a shard
-#include "mzx_actor.h"
-#include "mzx_games_device.h"
-#include "mzx_resident.h"
-
-extern "C" {
 
 int mzx_game_create(const char* kind, int32_t num_games, const uint32_t* seeds, const int32_t* observation_shape,
                     int32_t action_space_size, int32_t num_players, mzx_game** out) {
@@ -1834,8 +1613,6 @@ int mzx_game_step(mzx_game* g, const int64_t* actions, const uint8_t* active, do
   return MZX_OK;
 }
 
-static void resident_free(mzx_actor* a);      // (resident rounds, below)
-
 // ---- the device-resident twin of a game object (mzx_games_device.h)
 
 int mzx_game_device_create(const mzx_game* host, mzx_game_device** out) {
@@ -1852,16 +1629,9 @@ int mzx_game_device_create(const mzx_game* host, mzx_game_device** out) {
     return MZX_ERR_RUNTIME;
   }
   game_device_point(&d->v, (char*)d->block, L);
-  int rc = 0;
-  if (h.kind == 0) {
-    rc = copy_h2d_blocking(d->v.seeds, h.seeds, 4 * (size_t)h.num_games);
-  } else {
-    rc = copy_h2d_blocking((void*)d->v.lines, h.lines, 4 * (size_t)h.num_lines * h.k);
-  }
-  std::vector<void*> src;
-  game_state_arrays(h, [&](void* p, size_t) { src.push_back(p); });
-  size_t q = 0;
-  game_state_arrays(d->v, [&](void* p, size_t bytes) { if (rc == 0) rc = copy_h2d_blocking(p, src[q], bytes); ++q; });
+  int rc = h.kind == 0 ? copy_h2d_blocking(d->v.seeds, h.seeds, 4 * (size_t)h.num_games)
+                       : copy_h2d_blocking((void*)d->v.lines, h.lines, 4 * (size_t)h.num_lines * h.k);
+  game_state_copy(d->v, h, [&](void* to, void* from, size_t bytes) { if (rc == 0) rc = copy_h2d_blocking(to, from, bytes); });
   if (rc != 0) {
     device_free(d->block);
     delete d;
@@ -1907,11 +1677,8 @@ int mzx_game_device_download(const mzx_game_device* d, mzx_game* host, void* str
     set_error("mzx_game_device_download: the host object is not the kind and size of game the device state was created from");
     return MZX_ERR_INVALID;
   }
-  std::vector<void*> dst;
-  game_state_arrays(h, [&](void* p, size_t) { dst.push_back(p); });
   int rc = 0;
-  size_t q = 0;
-  game_state_arrays(d->v, [&](void* p, size_t bytes) { if (rc == 0) rc = copy_d2h(dst[q], p, bytes, (stream_t)stream); ++q; });
+  game_state_copy(h, d->v, [&](void* to, void* from, size_t bytes) { if (rc == 0) rc = copy_d2h(to, from, bytes, (stream_t)stream); });
   const int waited = stream_sync((stream_t)stream);      // (also behind a failed copy: nothing stays in flight into the host object)
   if (rc == 0) rc = waited;
   if (rc != 0) { set_error("mzx_game_device_download: %s", runtime_error_string(rc)); return MZX_ERR_RUNTIME; }
@@ -1970,9 +1737,7 @@ int mzx_actor_set_device_draws(mzx_actor* a, uint64_t seed, uint64_t first_count
   for (int k = 1; k < a->B; ++k)
     if (a->streams[k] != a->streams[0] + k) { set_error("mzx_actor_set_device_draws: the group's streams must be consecutive slots"); return MZX_ERR_INVALID; }
   const mzx_move& m = a->move;
-  const ptrdiff_t t_off = (const char*)d_temperature - (const char*)m.d_in, a_off = (const char*)d_action - (const char*)m.d_out;
-  if (!d_temperature || !d_action || t_off < 0 || t_off + (ptrdiff_t)(sizeof(double) * a->B) > m.in_bytes || a_off < 0 ||
-      a_off + (ptrdiff_t)(sizeof(int64_t) * a->B) > m.out_bytes) {
+  if (!move_in(&m).holds(d_temperature, sizeof(double) * a->B) || !move_out(&m).holds(d_action, sizeof(int64_t) * a->B)) {
     set_error("mzx_actor_set_device_draws: d_temperature must lie inside the staged input block, d_action inside the output block");
     return MZX_ERR_INVALID;
   }
@@ -1993,16 +1758,6 @@ int mzx_actor_set_draw_counter(mzx_actor* a, uint64_t counter) {
 
 // ------------------------------------------------------------- resident rounds (mzx_resident.h)
 
-static void resident_free(mzx_actor* a) {
-  mzx_actor_resident* R = a->resident;
-  if (!R) return;
-  mzx_game_device_destroy(R->game);
-  if (R->block) device_free(R->block);
-  if (R->d_pack) device_free(R->d_pack);
-  delete R;
-  a->resident = nullptr;
-}
-
 int mzx_actor_set_resident(mzx_actor* a, int32_t chunk_rounds, int64_t max_log_bytes) {
   const char* who = "mzx_actor_set_resident";
   if (!a) { set_error("%s: null actor", who); return MZX_ERR_INVALID; }
@@ -2010,30 +1765,23 @@ int mzx_actor_set_resident(mzx_actor* a, int32_t chunk_rounds, int64_t max_log_b
   if (chunk_rounds < 1) { set_error("%s: chunk_rounds %d must be at least 1", who, chunk_rounds); return MZX_ERR_INVALID; }
   if (a->pending || a->round != 0) { set_error("%s: the group has played rounds already", who); return MZX_ERR_INVALID; }
   const mzx_move& m = a->move;
-  auto inside = [&](const void* p, size_t bytes, const void* base, int64_t total) {
-    const ptrdiff_t off = (const char*)p - (const char*)base;
-    return p && off >= 0 && off + (ptrdiff_t)bytes <= total;
-  };
+  const Block in = move_in(&m), out = move_out(&m);
   const size_t B = (size_t)a->B, A = (size_t)a->A, E = (size_t)a->E;
-  if (!inside(m.io.d_observation, 4 * B * E, m.d_in, m.in_bytes) || !inside(m.io.d_legal_actions, 4 * B * A, m.d_in, m.in_bytes) ||
-      !inside(m.io.d_to_play, 4 * B, m.d_in, m.in_bytes) || !inside(m.io.d_visit_counts, 4 * B * A, m.d_out, m.out_bytes) ||
-      !inside(m.io.d_root_value, 8 * B, m.d_out, m.out_bytes) || !inside(m.io.d_info, 16 * B, m.d_out, m.out_bytes)) {
+  if (!in.holds(m.io.d_observation, 4 * B * E) || !in.holds(m.io.d_legal_actions, 4 * B * A) || !in.holds(m.io.d_to_play, 4 * B) ||
+      !out.holds(m.io.d_visit_counts, 4 * B * A) || !out.holds(m.io.d_root_value, 8 * B) || !out.holds(m.io.d_info, 16 * B)) {
     set_error("%s: the move's observation, legal rows and to_play must lie inside the input block, its outputs inside the output block", who);
     return MZX_ERR_INVALID;
   }
   resident_free(a);
-  const int64_t cap = (int64_t)a->max_moves + chunk_rounds + 1;
   const bool masks = !a->game->always_all_legal;
   if (masks && a->game->view().kind != 1) { set_error("%s: a game with varying legal sets that is no board game", who); return MZX_ERR_INVALID; }
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t rows = (size_t)cap * B, cells = (size_t)chunk_rounds * B;
-  const size_t o_start = take(8 * B), o_temps = take(8 * B), o_obs = take(4 * rows * E), o_tp = take(4 * rows), o_act = take(8 * rows),
-               o_vis = take(4 * rows * A), o_val = take(8 * rows), o_rew = take(8 * rows), o_mask = take(masks ? rows * A : 0),
-               o_ctrl = take(4 * (RESIDENT_CTRL_WORDS + cells)), o_ftp = take(4 * cells), o_fobs = take(4 * cells * E);
-  if ((int64_t)at > max_log_bytes) {
+  ResidentDevice d;
+  d.B = a->B; d.A = a->A; d.E = (int32_t)a->E; d.max_moves = a->max_moves; d.chunk = chunk_rounds; d.masks = masks ? 1 : 0;
+  d.cap = (int64_t)a->max_moves + chunk_rounds + 1;
+  const ResidentLayout L = resident_layout(d);
+  if ((int64_t)L.total > max_log_bytes) {
     set_error("%s: the device log of this group takes %lld bytes (%lld rows of %d slots), more than max_log_bytes = %lld", who,
-              (long long)at, (long long)cap, a->B, (long long)max_log_bytes);
+              (long long)L.total, (long long)d.cap, a->B, (long long)max_log_bytes);
     return MZX_ERR_INVALID;
   }
   mzx_actor_resident* R = new (std::nothrow) mzx_actor_resident();
@@ -2041,27 +1789,20 @@ int mzx_actor_set_resident(mzx_actor* a, int32_t chunk_rounds, int64_t max_log_b
   a->resident = R;
   int rc = mzx_game_device_create(a->game, &R->game);
   if (rc) { resident_free(a); return rc; }
-  if (device_alloc(&R->block, at) != 0) {
+  if (device_alloc(&R->block, L.total) != 0) {
     R->block = nullptr;
     resident_free(a);
-    set_error("%s: device allocation of %lld bytes failed", who, (long long)at);
+    set_error("%s: device allocation of %lld bytes failed", who, (long long)L.total);
     return MZX_ERR_RUNTIME;
   }
-  R->block_bytes = (int64_t)at;
-  R->stats[5] = (int64_t)at;
-  char* base = (char*)R->block;
-  ResidentDevice& d = R->d;
+  R->block_bytes = R->stats[5] = (int64_t)L.total;
   d.game = R->game->v;
-  d.B = a->B; d.A = a->A; d.E = (int32_t)a->E; d.max_moves = a->max_moves; d.chunk = chunk_rounds; d.masks = masks ? 1 : 0; d.cap = cap;
-  d.start = (int64_t*)(base + o_start); d.temps = (double*)(base + o_temps); d.l_obs = (float*)(base + o_obs);
-  d.l_tp = (int32_t*)(base + o_tp); d.l_act = (int64_t*)(base + o_act); d.l_vis = (int32_t*)(base + o_vis);
-  d.l_val = (double*)(base + o_val); d.l_rew = (double*)(base + o_rew); d.l_mask = masks ? (uint8_t*)(base + o_mask) : nullptr;
-  d.ctrl = (int32_t*)(base + o_ctrl); d.fin_len = d.ctrl + RESIDENT_CTRL_WORDS; d.fin_tp = (int32_t*)(base + o_ftp);
-  d.fin_obs = (float*)(base + o_fobs);
+  resident_point(&d, (char*)R->block, L);
   d.in_obs = (float*)m.io.d_observation; d.in_legal = (int32_t*)m.io.d_legal_actions; d.in_to_play = (int32_t*)m.io.d_to_play;
   d.in_temperature = a->d_temperature;
   d.visits = m.io.d_visit_counts; d.root_value = m.io.d_root_value; d.action = a->d_action; d.info = m.io.d_info;
-  R->h_ctrl.assign(RESIDENT_CTRL_WORDS + cells, 0);
+  R->d = d;
+  R->h_ctrl.assign(RESIDENT_CTRL_WORDS + (size_t)chunk_rounds * B, 0);
   return MZX_OK;
 }
 
@@ -2071,308 +1812,6 @@ int mzx_actor_resident_stats(const mzx_actor* a, int64_t out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = a->resident->stats[k];
   return MZX_OK;
 }
-
-namespace {
-
-const int32_t RESIDENT_CTRL_CLEAR[RESIDENT_CTRL_WORDS] = {0, -1, 0, 0};
-
-struct ResidentPiece {            // the games one harvest of one group brought, not yet numbered
-  int group;
-  mzx_actor::Batch b;
-  std::vector<int64_t> round;     // round of the CALL each game ended in
-};
-
-int resident_fail(const char* what, int rc) {
-  set_error("mzx_selfplay_rounds (resident): %s: %s", what, runtime_error_string(rc));
-  return MZX_ERR_RUNTIME;
-}
-
-// draws -> search -> action choice of the group's next position under `counter`
-int resident_queue_search(mzx_actor* a, const RoundsArgs& args, uint64_t counter, void* stream) {
-  const mzx_move& m = a->move;
-  mzx_draws dd{};
-  dd.seed = a->draw_seed; dd.counter = counter; dd.first_stream = a->streams[0];
-  dd.num_games = a->B; dd.action_space_size = a->A; dd.tape_words = m.tape_words; dd.dirichlet_alpha = m.dirichlet_alpha;
-  dd.d_legal_actions = m.io.d_legal_actions; dd.d_noise = (double*)m.io.d_noise; dd.d_tape = (uint32_t*)m.io.d_tape;
-  int rc = mzx_selfplay_draws(&dd, stream);
-  if (rc) return rc;
-  rc = mzx_search_run(a->search, &m.io, a->d_arena, a->arena_bytes, stream);
-  if (rc) return rc;
-  mzx_draws_select sel{};
-  sel.d_legal_actions = m.io.d_legal_actions; sel.d_visit_counts = m.io.d_visit_counts;
-  sel.d_temperature = a->d_temperature; sel.d_action = a->d_action;
-  if (args.num_temperatures > 0) {
-    sel.d_pow_table = (const double*)a->d_pow;
-    sel.d_table_temperatures = (const double*)a->d_pow + (size_t)args.num_temperatures * args.table_stride;
-    sel.table_stride = args.table_stride; sel.num_temperatures = args.num_temperatures;
-  }
-  return mzx_selfplay_select_device(&dd, &sel, stream);
-}
-
-int resident_queue_commit(mzx_actor* a, const RoundsArgs& args, int64_t r, int q, int prime, void* stream) {
-  ResidentCommitBody body{a->resident->d, r, q, prime, args.temperature_threshold, args.temperature};
-  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(body, (stream_t)stream));
-  return MZX_OK;
-}
-
-// rounds [q0, q1) of the chunk for one group, the first one round a->round under a->draw_counter (the rest of a chunk behind a
-// repaired round); nothing is waited for
-int resident_queue_rounds(mzx_actor* a, const RoundsArgs& args, int q0, int q1, void* stream) {
-  mzx_actor_resident* R = a->resident;
-  for (int q = q0; q < q1; ++q) {
-    int rc = resident_queue_search(a, args, a->draw_counter + (uint64_t)(q - q0), stream);
-    if (rc) return rc;
-    MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(ResidentVoteBody{R->d, q}, (stream_t)stream));
-    rc = resident_queue_commit(a, args, a->round + (q - q0), q, 0, stream);
-    if (rc) return rc;
-  }
-  return MZX_OK;
-}
-
-// the downloads of a chunk's end: control block + finished lengths, and the game state into the host game object (so that
-// legal_actions() etc. are true between calls); queued behind the chunk's rounds, waited for by resident_wait
-int resident_queue_downloads(mzx_actor* a, int rounds_of_chunk, void* stream) {
-  mzx_actor_resident* R = a->resident;
-  const size_t bytes = sizeof(int32_t) * (RESIDENT_CTRL_WORDS + (size_t)rounds_of_chunk * a->B);
-  int rc = copy_d2h(R->h_ctrl.data(), R->d.ctrl, bytes, (stream_t)stream);
-  if (rc) return resident_fail("control block download", rc);
-  R->stats[4] += (int64_t)bytes;
-  const GameView h = a->game->view();
-  std::vector<void*> dst;
-  game_state_arrays(h, [&](void* p, size_t) { dst.push_back(p); });
-  size_t i = 0;
-  game_state_arrays(R->game->v, [&](void* p, size_t n) { if (rc == 0) { rc = copy_d2h(dst[i], p, n, (stream_t)stream); R->stats[4] += (int64_t)n; } ++i; });
-  if (rc) return resident_fail("game state download", rc);
-  return MZX_OK;
-}
-
-int resident_wait(mzx_actor* a, void* stream) {
-  const int rc = stream_sync((stream_t)stream);
-  a->resident->stats[3] += 1;
-  if (rc) return resident_fail("waiting for the group's stream", rc);
-  return MZX_OK;
-}
-
-// the games that ended in rounds [q0, q1) of the chunk (round q = round r_first + (q - q0) of the group, call_round0 + q of the
-// call): gathered on the device, downloaded, queued as one piece
-int resident_harvest(mzx_actor* a, int group, int q0, int q1, int64_t r_first, int64_t call_round0, void* stream,
-                     std::vector<ResidentPiece>& pieces) {
-  mzx_actor_resident* R = a->resident;
-  const int64_t B = a->B, A = a->A, E = a->E;
-  const int32_t* fin = R->h_ctrl.data() + RESIDENT_CTRL_WORDS;
-  std::vector<int64_t> table;
-  ResidentPiece piece;
-  piece.group = group;
-  mzx_actor::Batch& b = piece.b;
-  int64_t o1 = 0, o0 = 0;
-  for (int q = q0; q < q1; ++q)
-    for (int64_t s = 0; s < B; ++s) {
-      const int64_t n = fin[(size_t)q * B + s];
-      if (n == 0) continue;
-      const int64_t last = r_first + (q - q0);
-      if (n < 1 || n > a->max_moves || n > last + 1) {
-        set_error("mzx_selfplay_rounds (resident): slot %lld reports a game of %lld moves in round %lld", (long long)s, (long long)n, (long long)last);
-        return MZX_ERR_RUNTIME;
-      }
-      const int64_t row[5] = {last - n + 1, s, n, o1, o0};
-      table.insert(table.end(), row, row + 5);
-      b.slot.push_back(a->first_slot + (int32_t)s); b.n.push_back((int32_t)n); b.seq.push_back(0);
-      piece.round.push_back(call_round0 + q);
-      o1 += n + 1; o0 += n;
-    }
-  const int64_t k = (int64_t)b.slot.size();
-  if (k == 0) return MZX_OK;
-  const bool masks = R->d.masks != 0;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_table = take(8 * table.size()), o_obs = take(4 * (size_t)(o1 * E)), o_act = take(8 * (size_t)o1), o_tp = take(8 * (size_t)o1),
-               o_rew = take(8 * (size_t)o1), o_vis = take(4 * (size_t)(o0 * A)), o_val = take(8 * (size_t)o0), o_mask = take(masks ? (size_t)(o0 * A) : 0);
-  if ((int64_t)at > R->pack_bytes) {
-    if (R->d_pack) device_free(R->d_pack);
-    R->d_pack = nullptr; R->pack_bytes = 0;
-    const size_t want = std::max(at, (size_t)1 << 16) * 2;
-    if (device_alloc(&R->d_pack, want) != 0) { R->d_pack = nullptr; set_error("mzx_selfplay_rounds (resident): gather buffer of %lld bytes", (long long)want); return MZX_ERR_RUNTIME; }
-    R->pack_bytes = (int64_t)want;
-  }
-  char* base = (char*)R->d_pack;
-  int rc = copy_h2d(base + o_table, table.data(), 8 * table.size(), (stream_t)stream);
-  if (rc) return resident_fail("gather table upload", rc);
-  ResidentGatherBody body{R->d, (const int64_t*)(base + o_table), (int32_t)k, q0, r_first, (float*)(base + o_obs), (int64_t*)(base + o_act),
-                          (int64_t*)(base + o_tp), (double*)(base + o_rew), (int32_t*)(base + o_vis), (double*)(base + o_val),
-                          masks ? (uint8_t*)(base + o_mask) : nullptr};
-  MZX_TRY_LAUNCH(launch_waves<GAME_WAVES>(body, (stream_t)stream));
-  b.obs.resize((size_t)(o1 * E)); b.act.resize((size_t)o1); b.tp.resize((size_t)o1); b.rew.resize((size_t)o1);
-  b.vis.resize((size_t)(o0 * A)); b.val.resize((size_t)o0);
-  if (masks) b.mask.resize((size_t)(o0 * A));
-  struct { void* dst; const void* src; size_t bytes; } copies[7] = {
-      {b.obs.data(), base + o_obs, 4 * b.obs.size()}, {b.act.data(), base + o_act, 8 * b.act.size()}, {b.tp.data(), base + o_tp, 8 * b.tp.size()},
-      {b.rew.data(), base + o_rew, 8 * b.rew.size()}, {b.vis.data(), base + o_vis, 4 * b.vis.size()}, {b.val.data(), base + o_val, 8 * b.val.size()},
-      {b.mask.data(), base + o_mask, b.mask.size()}};
-  for (const auto& c : copies) {
-    if (c.bytes == 0) continue;
-    rc = copy_d2h(c.dst, c.src, c.bytes, (stream_t)stream);
-    if (rc) return resident_fail("finished games download", rc);
-    R->stats[4] += (int64_t)c.bytes;
-  }
-  rc = resident_wait(a, stream);
-  if (rc) return rc;
-  if (masks) {
-    bool any_illegal = false;
-    for (uint8_t x : b.mask) if (!x) { any_illegal = true; break; }
-    if (!any_illegal) { b.mask.clear(); b.mask.shrink_to_fit(); }
-  }
-  R->stats[6] += k;
-  pieces.push_back(std::move(piece));
-  return MZX_OK;
-}
-
-// the rare path: round a->round halted (a tree exhausted its tie-break tape).  The round is searched again under the same
-// counter and waited for, the flagged trees go through the retry callback and take their actions on the host (as
-// actor_consume does), the patched output block goes back and the round is committed.
-int resident_repair(mzx_actor* a, int group, const RoundsArgs& args, int q, void* stream) {
-  mzx_actor_resident* R = a->resident;
-  const mzx_move& m = a->move;
-  const int B = a->B, A = a->A;
-  const uint64_t counter = a->draw_counter;
-  int rc = resident_queue_search(a, args, counter, stream);
-  if (rc) return rc;
-  if (m.h_in != m.d_in) { rc = copy_d2h(m.h_in, m.d_in, (size_t)m.in_bytes, (stream_t)stream); R->stats[4] += m.in_bytes; }
-  if (rc == 0 && m.h_out != m.d_out) { rc = copy_d2h(m.h_out, m.d_out, (size_t)m.out_bytes, (stream_t)stream); R->stats[4] += m.out_bytes; }
-  if (rc) return resident_fail("download of the halted round", rc);
-  rc = resident_wait(a, stream);
-  if (rc) return rc;
-  a->draw_counter = counter + 1;        // (the retry callback reads mzx_actor_draw_counter - 1)
-  char* h_out = (char*)m.h_out;
-  const char* h_in = (const char*)m.h_in;
-  auto out_of = [&](const void* d) { return h_out + ((const char*)d - (const char*)m.d_out); };
-  auto in_of = [&](const void* d) { return h_in + ((const char*)d - (const char*)m.d_in); };
-  const int32_t* info = (const int32_t*)out_of(m.io.d_info);
-  std::vector<int32_t> redo;
-  for (int k = 0; k < B; ++k) if (info[4 * k + 1] & 1) redo.push_back(k);
-  if (!redo.empty()) {
-    if (!args.retry) { set_error("mzx_selfplay_rounds: a search exhausted its tie-break tape and no retry callback was given"); return MZX_ERR_RUNTIME; }
-    rc = args.retry(args.retry_ctx, group, (int32_t)redo.size(), redo.data());
-    if (rc) { set_error("mzx_selfplay_rounds: the tape-retry callback failed (%d)", rc); return MZX_ERR_RUNTIME; }
-  }
-  for (int k = 0; k < B; ++k)
-    if (info[4 * k + 1] != 0) { set_error("search flagged tree %d (flags %d): node arena exhausted", k, info[4 * k + 1]); return MZX_ERR_RUNTIME; }
-  if (!redo.empty()) {
-    SelfplaySelectParams sp{};
-    sp.seed = a->draw_seed; sp.counter = counter; sp.first_stream = a->streams[0];
-    sp.legal = (const int32_t*)in_of(m.io.d_legal_actions); sp.visits = (const int32_t*)out_of(m.io.d_visit_counts);
-    sp.temperature = (const double*)in_of(a->d_temperature); sp.pow_table = args.pow_table; sp.table_temperatures = args.table_temperatures;
-    sp.action = (int64_t*)out_of(a->d_action); sp.B = B; sp.A = A; sp.table_stride = args.table_stride; sp.num_temperatures = args.num_temperatures;
-    for (int32_t k : redo) sp.action[k] = draw_select_action(sp, (size_t)k);
-  }
-  if (m.h_out != m.d_out) {
-    rc = copy_h2d(m.d_out, m.h_out, (size_t)m.out_bytes, (stream_t)stream);
-    if (rc) return resident_fail("upload of the repaired round", rc);
-  }
-  rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)stream);
-  if (rc) return resident_fail("control block reset", rc);
-  rc = resident_queue_commit(a, args, a->round, q, 0, stream);
-  if (rc) return rc;
-  a->round += 1;
-  R->stats[0] += 1; R->stats[2] += 1;
-  return MZX_OK;
-}
-
-int resident_rounds(mzx_actor* const* groups, int num_groups, mzx_rounds* io, const RoundsArgs& args, const std::vector<void*>& streams,
-                    int64_t* out_finished, int64_t* out_rounds, int64_t* out_searches, int64_t* sequence) {
-  int rc = MZX_OK;
-  double* phase = io->phase_seconds;
-  int chunk = groups[0]->resident->d.chunk;
-  for (int k = 0; k < num_groups; ++k) chunk = std::min(chunk, (int)groups[k]->resident->d.chunk);
-  for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {      // the first search's inputs, written by the device from the games' state
-    mzx_actor* a = groups[k];
-    mzx_actor_resident* R = a->resident;
-    if (R->primed) continue;
-    const double t0 = actor_now();
-    void* st = streams[(size_t)k];
-    if ((rc = copy_h2d(R->d.start, a->start.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
-        (rc = copy_h2d(R->d.temps, a->temps.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
-        (rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)st)) != 0) {
-      rc = resident_fail("first upload", rc);
-      break;
-    }
-    rc = resident_queue_commit(a, args, a->round, 0, 1, st);
-    R->primed = rc == MZX_OK;
-    phase[0] += actor_now() - t0;
-  }
-  int64_t finished = 0, rounds = 0, searches = 0;
-  while (rc == MZX_OK && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
-    const int n = io->max_rounds < 0 ? chunk : (int)std::min<int64_t>(chunk, io->max_rounds - rounds);
-    std::vector<ResidentPiece> pieces;
-    double t0 = actor_now();
-    // the chunk's rounds, interleaved round by round so that every group's stream starts at once
-    for (int q = 0; q < n && rc == MZX_OK; ++q)
-      for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
-        mzx_actor* a = groups[k];
-        rc = resident_queue_search(a, args, a->draw_counter + (uint64_t)q, streams[(size_t)k]);
-        if (rc) break;
-        { const int e = launch_waves<GAME_WAVES>(ResidentVoteBody{a->resident->d, q}, (stream_t)streams[(size_t)k]); if (e) rc = resident_fail("vote launch", e); }
-        if (rc == MZX_OK) rc = resident_queue_commit(a, args, a->round + q, q, 0, streams[(size_t)k]);
-      }
-    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) rc = resident_queue_downloads(groups[k], n, streams[(size_t)k]);
-    phase[0] += actor_now() - t0;
-    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
-      mzx_actor* a = groups[k];
-      mzx_actor_resident* R = a->resident;
-      void* st = streams[(size_t)k];
-      // rounds of the chunk: [0, accounted) are committed and counted in a->round / a->draw_counter (a repaired round is,
-      // the moment resident_repair commits it), [0, harvested) have handed out their finished games
-      int accounted = 0, harvested = 0;
-      R->stats[1] += 1;
-      while (rc == MZX_OK) {
-        t0 = actor_now();
-        rc = resident_wait(a, st);
-        phase[1] += actor_now() - t0;
-        if (rc) break;
-        const bool halted = R->h_ctrl[0] != 0;
-        const int upto = halted ? R->h_ctrl[1] : n;       // the device committed rounds [accounted, upto) in this pass
-        if (upto < accounted || upto > n || (halted && upto >= n)) {
-          set_error("mzx_selfplay_rounds (resident): halt round %d outside the chunk's queued rounds [%d, %d)", upto, accounted, n);
-          rc = MZX_ERR_RUNTIME;
-          break;
-        }
-        t0 = actor_now();
-        rc = resident_harvest(a, k, harvested, upto, a->round - (accounted - harvested), rounds, st, pieces);
-        a->round += upto - accounted; a->draw_counter += (uint64_t)(upto - accounted); R->stats[0] += upto - accounted;
-        accounted = harvested = upto;
-        phase[3] += actor_now() - t0;
-        if (rc || !halted) break;
-        t0 = actor_now();
-        rc = resident_repair(a, k, args, upto, st);       // (commits round `upto`: harvested with the next pass)
-        accounted = upto + 1;
-        if (rc == MZX_OK) rc = resident_queue_rounds(a, args, accounted, n, st);
-        if (rc == MZX_OK) rc = resident_queue_downloads(a, n, st);
-        phase[4] += actor_now() - t0;
-      }
-    }
-    if (rc) break;
-    // sequence numbers in (round, group, slot) order across groups: the order the host loop finishes games in
-    struct Key { int64_t round; int group; int32_t slot; size_t piece, j; };
-    std::vector<Key> keys;
-    for (size_t p = 0; p < pieces.size(); ++p)
-      for (size_t j = 0; j < pieces[p].b.slot.size(); ++j) keys.push_back({pieces[p].round[j], pieces[p].group, pieces[p].b.slot[j], p, j});
-    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
-      return x.round != y.round ? x.round < y.round : x.group != y.group ? x.group < y.group : x.slot < y.slot;
-    });
-    for (const Key& key : keys) pieces[key.piece].b.seq[key.j] = (*sequence)++;
-    for (ResidentPiece& p : pieces) {
-      mzx_actor* a = groups[p.group];
-      std::lock_guard<std::mutex> lk(a->finished_lock);
-      a->finished.push_back(std::move(p.b));
-    }
-    finished += (int64_t)keys.size();
-    rounds += n;
-    for (int k = 0; k < num_groups; ++k) searches += (int64_t)n * groups[k]->B;
-  }
-  *out_finished = finished; *out_rounds = rounds; *out_searches = searches;
-  return rc;
-}
-
-}  // namespace
 
 int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds* io, void* stream) {
   if (!groups || num_groups < 1 || !io) { set_error("mzx_selfplay_rounds: missing argument"); return MZX_ERR_INVALID; }
@@ -2386,15 +1825,11 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
   }
   const double t_call = actor_now();
   for (double& x : io->phase_seconds) x = 0.0;
-  RoundsArgs args;
-  args.phase = io->phase_seconds;
-  args.temperature = io->temperature; args.temperature_threshold = io->temperature_threshold;
-  args.pow_table = io->pow_table; args.table_stride = io->table_stride; args.table_temperatures = io->table_temperatures;
-  args.num_temperatures = io->num_temperatures; args.retry = io->retry; args.retry_ctx = io->retry_ctx;
+  const RoundsArgs args{io->phase_seconds, io->temperature, io->temperature_threshold, io->pow_table, io->table_stride,
+                        io->table_temperatures, io->num_temperatures, io->retry, io->retry_ctx};
   int64_t finished = 0, rounds = 0, searches = 0, sequence = io->sequence;
   double search_seconds = 0.0;
   int rc = MZX_OK;
-  const bool pipelined = num_groups > 1;
   // Streams: the first group searches on the caller's stream, every further group on a stream of its own, ordered behind
   // whatever the caller queued before this call (a weight upload).  Half a shard of a small network fills half the chip
   // (C2: 2048 trees = two waves per CU), and such a search is latency-bound -- it takes as long as the whole shard's -- so
@@ -2418,22 +1853,8 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
     for (int k = 0; k < num_groups; ++k)
       if (groups[k]->pending) { set_error("mzx_selfplay_rounds: a search is in flight for resident group %d", k); rc = MZX_ERR_INVALID; }
     if (rc == MZX_OK) rc = resident_rounds(groups, num_groups, io, args, streams, &finished, &rounds, &searches, &sequence);
-  }
-  // SelfPlay._rounds_batched, statement for statement
-  while (rc == MZX_OK && !resident_groups && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
-    for (int k = 0; k < num_groups && rc == MZX_OK; ++k)
-      if (!groups[k]->pending) rc = actor_begin(groups[k], args, streams[(size_t)k], &search_seconds, io->phase_seconds);
-    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
-      rc = actor_consume(groups[k], k, args, &sequence, &finished, &search_seconds);
-      if (rc) break;
-      searches += groups[k]->B;
-      int64_t later = 0;
-      for (int j = k + 1; j < num_groups; ++j) later += groups[j]->B;
-      // certain to be consumed by this call: runs while the host plays the groups after it
-      if (pipelined && k + 1 < num_groups && finished + later < io->min_games && (io->max_rounds < 0 || rounds + 1 < io->max_rounds))
-        rc = actor_begin(groups[k], args, streams[(size_t)k], &search_seconds, io->phase_seconds);
-    }
-    ++rounds;
+  } else if (rc == MZX_OK) {
+    rc = actor_rounds(groups, num_groups, io, args, streams, &finished, &rounds, &searches, &sequence, &search_seconds);
   }
   if (rc != MZX_OK) {          // nothing stays in flight behind a failure
     for (int k = 0; k < num_groups; ++k) (void)stream_sync((stream_t)streams[(size_t)k]);

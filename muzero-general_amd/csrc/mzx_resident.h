@@ -22,6 +22,10 @@
 // in a round in which ANY tree of the group was flagged -- the host repairs the round as a whole.  After a halt at round r
 // the device state is the state before round r; the rounds queued behind it were no-ops (their draws and searches ran and
 // are discarded: their counters are not consumed).
+//
+// Here: the device state and the wave bodies (vote, commit, gather), then the host side of a group: the layout of its block,
+// a round queued (resident_queue_round), the chunk's downloads and harvest, the repair of a halted round and the loop of a
+// call (resident_rounds).  mzx_actor_set_resident and mzx_selfplay_rounds (mzx_lib.cpp) check arguments and call in here.
 #pragma once
 #include <algorithm>
 
@@ -179,3 +183,302 @@ struct mzx_actor_resident {
   int64_t pack_bytes = 0;
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+
+namespace mzx {
+
+// ---- the group's device block ------------------------------------------------------------------------------------------
+
+// byte offsets of the arrays of a group (sizes of `d` set) inside its one block, each 16-byte aligned; total: the block's size
+struct ResidentLayout { size_t start, temps, obs, tp, act, vis, val, rew, mask, ctrl, fin_tp, fin_obs, total; };
+inline ResidentLayout resident_layout(const ResidentDevice& d) {
+  const size_t B = (size_t)d.B, A = (size_t)d.A, E = (size_t)d.E, rows = (size_t)d.cap * B, cells = (size_t)d.chunk * B;
+  ResidentLayout L;
+  Carver c;
+  L.start = c.take(8 * B); L.temps = c.take(8 * B); L.obs = c.take(4 * rows * E); L.tp = c.take(4 * rows); L.act = c.take(8 * rows);
+  L.vis = c.take(4 * rows * A); L.val = c.take(8 * rows); L.rew = c.take(8 * rows); L.mask = c.take(d.masks ? rows * A : 0);
+  L.ctrl = c.take(4 * (RESIDENT_CTRL_WORDS + cells)); L.fin_tp = c.take(4 * cells); L.fin_obs = c.take(4 * cells * E);
+  L.total = c.at;
+  return L;
+}
+
+inline void resident_point(ResidentDevice* d, char* base, const ResidentLayout& L) {
+  d->start = (int64_t*)(base + L.start); d->temps = (double*)(base + L.temps); d->l_obs = (float*)(base + L.obs);
+  d->l_tp = (int32_t*)(base + L.tp); d->l_act = (int64_t*)(base + L.act); d->l_vis = (int32_t*)(base + L.vis);
+  d->l_val = (double*)(base + L.val); d->l_rew = (double*)(base + L.rew); d->l_mask = d->masks ? (uint8_t*)(base + L.mask) : nullptr;
+  d->ctrl = (int32_t*)(base + L.ctrl); d->fin_len = d->ctrl + RESIDENT_CTRL_WORDS; d->fin_tp = (int32_t*)(base + L.fin_tp);
+  d->fin_obs = (float*)(base + L.fin_obs);
+}
+
+inline void resident_free(mzx_actor* a) {
+  mzx_actor_resident* R = a->resident;
+  if (!R) return;
+  mzx_game_device_destroy(R->game);
+  if (R->block) device_free(R->block);
+  if (R->d_pack) device_free(R->d_pack);
+  delete R;
+  a->resident = nullptr;
+}
+
+// ---- the rounds of a call (mzx_selfplay_rounds with resident groups) -----------------------------------------------------
+
+constexpr int32_t RESIDENT_CTRL_CLEAR[RESIDENT_CTRL_WORDS] = {0, -1, 0, 0};
+
+struct ResidentPiece {            // the games one harvest of one group brought, not yet numbered
+  int group;
+  mzx_actor::Batch b;
+  std::vector<int64_t> round;     // round of the CALL each game ended in
+};
+
+inline int resident_fail(const char* what, int rc) {
+  set_error("mzx_selfplay_rounds (resident): %s: %s", what, runtime_error_string(rc));
+  return MZX_ERR_RUNTIME;
+}
+
+// draws -> search -> action choice of the group's next position under `counter`
+inline int resident_queue_search(mzx_actor* a, const RoundsArgs& args, uint64_t counter, void* stream) {
+  mzx_draws d; mzx_draws_select sel;
+  actor_draws(a, args, counter, &d, &sel);
+  return actor_queue_device_move(a->search, &a->move, &d, &sel, a->d_arena, a->arena_bytes, stream);
+}
+
+inline int resident_queue_commit(mzx_actor* a, const RoundsArgs& args, int64_t r, int q, int prime, void* stream) {
+  ResidentCommitBody body{a->resident->d, r, q, prime, args.temperature_threshold, args.temperature};
+  const int rc = launch_waves<GAME_WAVES>(body, (stream_t)stream);
+  return rc ? resident_fail("commit launch", rc) : MZX_OK;
+}
+
+// round r of the group as round q of the chunk, searched under `counter`: search -> vote -> commit, nothing waited for
+inline int resident_queue_round(mzx_actor* a, const RoundsArgs& args, int q, int64_t r, uint64_t counter, void* stream) {
+  int rc = resident_queue_search(a, args, counter, stream);
+  if (rc) return rc;
+  rc = launch_waves<GAME_WAVES>(ResidentVoteBody{a->resident->d, q}, (stream_t)stream);
+  if (rc) return resident_fail("vote launch", rc);
+  return resident_queue_commit(a, args, r, q, 0, stream);
+}
+
+// rounds [q0, q1) of the chunk for one group, the first one round a->round under a->draw_counter (the rest of a chunk behind a
+// repaired round)
+inline int resident_queue_rounds(mzx_actor* a, const RoundsArgs& args, int q0, int q1, void* stream) {
+  int rc = MZX_OK;
+  for (int q = q0; q < q1 && rc == MZX_OK; ++q)
+    rc = resident_queue_round(a, args, q, a->round + (q - q0), a->draw_counter + (uint64_t)(q - q0), stream);
+  return rc;
+}
+
+// the downloads of a chunk's end: control block + finished lengths, and the game state into the host game object (so that
+// legal_actions() etc. are true between calls); queued behind the chunk's rounds, waited for by resident_wait
+inline int resident_queue_downloads(mzx_actor* a, int rounds_of_chunk, void* stream) {
+  mzx_actor_resident* R = a->resident;
+  const size_t bytes = sizeof(int32_t) * (RESIDENT_CTRL_WORDS + (size_t)rounds_of_chunk * a->B);
+  int rc = copy_d2h(R->h_ctrl.data(), R->d.ctrl, bytes, (stream_t)stream);
+  if (rc) return resident_fail("control block download", rc);
+  R->stats[4] += (int64_t)bytes;
+  game_state_copy(a->game->view(), R->game->v, [&](void* to, void* from, size_t n) {
+    if (rc == 0) { rc = copy_d2h(to, from, n, (stream_t)stream); R->stats[4] += (int64_t)n; }
+  });
+  return rc ? resident_fail("game state download", rc) : MZX_OK;
+}
+
+inline int resident_wait(mzx_actor* a, void* stream) {
+  const int rc = stream_sync((stream_t)stream);
+  a->resident->stats[3] += 1;
+  return rc ? resident_fail("waiting for the group's stream", rc) : MZX_OK;
+}
+
+// the games that ended in rounds [q0, q1) of the chunk (round q = round r_first + (q - q0) of the group, call_round0 + q of the
+// call): gathered on the device, downloaded, queued as one piece
+inline int resident_harvest(mzx_actor* a, int group, int q0, int q1, int64_t r_first, int64_t call_round0, void* stream,
+                            std::vector<ResidentPiece>& pieces) {
+  mzx_actor_resident* R = a->resident;
+  const int64_t B = a->B, A = a->A, E = a->E;
+  const int32_t* fin = R->h_ctrl.data() + RESIDENT_CTRL_WORDS;
+  std::vector<int64_t> table;
+  ResidentPiece piece;
+  piece.group = group;
+  mzx_actor::Batch& b = piece.b;
+  int64_t o1 = 0, o0 = 0;
+  for (int q = q0; q < q1; ++q)
+    for (int64_t s = 0; s < B; ++s) {
+      const int64_t n = fin[(size_t)q * B + s];
+      if (n == 0) continue;
+      const int64_t last = r_first + (q - q0);
+      if (n < 1 || n > a->max_moves || n > last + 1) {
+        set_error("mzx_selfplay_rounds (resident): slot %lld reports a game of %lld moves in round %lld", (long long)s, (long long)n, (long long)last);
+        return MZX_ERR_RUNTIME;
+      }
+      const int64_t row[5] = {last - n + 1, s, n, o1, o0};
+      table.insert(table.end(), row, row + 5);
+      b.slot.push_back(a->first_slot + (int32_t)s); b.n.push_back((int32_t)n); b.seq.push_back(0);
+      piece.round.push_back(call_round0 + q);
+      o1 += n + 1; o0 += n;
+    }
+  const int64_t k = (int64_t)b.slot.size();
+  if (k == 0) return MZX_OK;
+  const bool masks = R->d.masks != 0;
+  Carver c;
+  const size_t o_table = c.take(8 * table.size()), o_obs = c.take(4 * (size_t)(o1 * E)), o_act = c.take(8 * (size_t)o1), o_tp = c.take(8 * (size_t)o1),
+               o_rew = c.take(8 * (size_t)o1), o_vis = c.take(4 * (size_t)(o0 * A)), o_val = c.take(8 * (size_t)o0), o_mask = c.take(masks ? (size_t)(o0 * A) : 0);
+  if ((int64_t)c.at > R->pack_bytes) {
+    if (R->d_pack) device_free(R->d_pack);
+    R->d_pack = nullptr; R->pack_bytes = 0;
+    const size_t want = std::max(c.at, (size_t)1 << 16) * 2;
+    if (device_alloc(&R->d_pack, want) != 0) { R->d_pack = nullptr; set_error("mzx_selfplay_rounds (resident): gather buffer of %lld bytes", (long long)want); return MZX_ERR_RUNTIME; }
+    R->pack_bytes = (int64_t)want;
+  }
+  char* base = (char*)R->d_pack;
+  int rc = copy_h2d(base + o_table, table.data(), 8 * table.size(), (stream_t)stream);
+  if (rc) return resident_fail("gather table upload", rc);
+  ResidentGatherBody body{R->d, (const int64_t*)(base + o_table), (int32_t)k, q0, r_first, (float*)(base + o_obs), (int64_t*)(base + o_act),
+                          (int64_t*)(base + o_tp), (double*)(base + o_rew), (int32_t*)(base + o_vis), (double*)(base + o_val),
+                          masks ? (uint8_t*)(base + o_mask) : nullptr};
+  rc = launch_waves<GAME_WAVES>(body, (stream_t)stream);
+  if (rc) return resident_fail("gather launch", rc);
+  b.obs.resize((size_t)(o1 * E)); b.act.resize((size_t)o1); b.tp.resize((size_t)o1); b.rew.resize((size_t)o1);
+  b.vis.resize((size_t)(o0 * A)); b.val.resize((size_t)o0);
+  if (masks) b.mask.resize((size_t)(o0 * A));
+  struct { void* dst; const void* src; size_t bytes; } copies[7] = {
+      {b.obs.data(), base + o_obs, 4 * b.obs.size()}, {b.act.data(), base + o_act, 8 * b.act.size()}, {b.tp.data(), base + o_tp, 8 * b.tp.size()},
+      {b.rew.data(), base + o_rew, 8 * b.rew.size()}, {b.vis.data(), base + o_vis, 4 * b.vis.size()}, {b.val.data(), base + o_val, 8 * b.val.size()},
+      {b.mask.data(), base + o_mask, b.mask.size()}};
+  for (const auto& cp : copies) {
+    if (cp.bytes == 0) continue;
+    rc = copy_d2h(cp.dst, cp.src, cp.bytes, (stream_t)stream);
+    if (rc) return resident_fail("finished games download", rc);
+    R->stats[4] += (int64_t)cp.bytes;
+  }
+  rc = resident_wait(a, stream);
+  if (rc) return rc;
+  if (masks) {
+    bool any_illegal = false;
+    for (uint8_t x : b.mask) if (!x) { any_illegal = true; break; }
+    if (!any_illegal) { b.mask.clear(); b.mask.shrink_to_fit(); }
+  }
+  R->stats[6] += k;
+  pieces.push_back(std::move(piece));
+  return MZX_OK;
+}
+
+// the rare path: round a->round halted (a tree exhausted its tie-break tape).  The round is searched again under the same
+// counter and waited for, the flagged trees go through actor_retry_flagged on the host mirrors of the move's blocks (as
+// actor_consume's do on its vectors), the patched output block goes back and the round is committed.
+inline int resident_repair(mzx_actor* a, int group, const RoundsArgs& args, int q, void* stream) {
+  mzx_actor_resident* R = a->resident;
+  const mzx_move* m = &a->move;
+  const uint64_t counter = a->draw_counter;
+  int rc = resident_queue_search(a, args, counter, stream);
+  if (rc) return rc;
+  if (m->h_in != m->d_in) { rc = copy_d2h(m->h_in, m->d_in, (size_t)m->in_bytes, (stream_t)stream); R->stats[4] += m->in_bytes; }
+  if (rc == 0 && m->h_out != m->d_out) { rc = copy_d2h(m->h_out, m->d_out, (size_t)m->out_bytes, (stream_t)stream); R->stats[4] += m->out_bytes; }
+  if (rc) return resident_fail("download of the halted round", rc);
+  rc = resident_wait(a, stream);
+  if (rc) return rc;
+  a->draw_counter = counter + 1;        // (the retry callback reads mzx_actor_draw_counter - 1)
+  std::vector<int32_t> redo;
+  rc = actor_retry_flagged(a, group, args, move_out_host(m, m->io.d_info), counter,
+                           ActorRows{move_in_host(m, m->io.d_legal_actions), move_out_host(m, m->io.d_visit_counts),
+                                     move_in_host(m, a->d_temperature), move_out_host(m, a->d_action)}, &redo);
+  if (rc) return rc;
+  if (m->h_out != m->d_out) {
+    rc = copy_h2d(m->d_out, m->h_out, (size_t)m->out_bytes, (stream_t)stream);
+    if (rc) return resident_fail("upload of the repaired round", rc);
+  }
+  rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)stream);
+  if (rc) return resident_fail("control block reset", rc);
+  rc = resident_queue_commit(a, args, a->round, q, 0, stream);
+  if (rc) return rc;
+  a->round += 1;
+  R->stats[0] += 1; R->stats[2] += 1;
+  return MZX_OK;
+}
+
+inline int resident_rounds(mzx_actor* const* groups, int num_groups, mzx_rounds* io, const RoundsArgs& args, const std::vector<void*>& streams,
+                           int64_t* out_finished, int64_t* out_rounds, int64_t* out_searches, int64_t* sequence) {
+  int rc = MZX_OK;
+  double* phase = io->phase_seconds;
+  int chunk = groups[0]->resident->d.chunk;
+  for (int k = 0; k < num_groups; ++k) chunk = std::min(chunk, (int)groups[k]->resident->d.chunk);
+  for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {      // the first search's inputs, written by the device from the games' state
+    mzx_actor* a = groups[k];
+    mzx_actor_resident* R = a->resident;
+    if (R->primed) continue;
+    const double t0 = actor_now();
+    void* st = streams[(size_t)k];
+    if ((rc = copy_h2d(R->d.start, a->start.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
+        (rc = copy_h2d(R->d.temps, a->temps.data(), 8 * (size_t)a->B, (stream_t)st)) != 0 ||
+        (rc = copy_h2d(R->d.ctrl, RESIDENT_CTRL_CLEAR, sizeof(RESIDENT_CTRL_CLEAR), (stream_t)st)) != 0) {
+      rc = resident_fail("first upload", rc);
+      break;
+    }
+    rc = resident_queue_commit(a, args, a->round, 0, 1, st);
+    R->primed = rc == MZX_OK;
+    phase[0] += actor_now() - t0;
+  }
+  int64_t finished = 0, rounds = 0, searches = 0;
+  while (rc == MZX_OK && finished < io->min_games && (io->max_rounds < 0 || rounds < io->max_rounds)) {
+    const int n = io->max_rounds < 0 ? chunk : (int)std::min<int64_t>(chunk, io->max_rounds - rounds);
+    std::vector<ResidentPiece> pieces;
+    double t0 = actor_now();
+    // the chunk's rounds, interleaved round by round so that every group's stream starts at once
+    for (int q = 0; q < n && rc == MZX_OK; ++q)
+      for (int k = 0; k < num_groups && rc == MZX_OK; ++k)
+        rc = resident_queue_round(groups[k], args, q, groups[k]->round + q, groups[k]->draw_counter + (uint64_t)q, streams[(size_t)k]);
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) rc = resident_queue_downloads(groups[k], n, streams[(size_t)k]);
+    phase[0] += actor_now() - t0;
+    for (int k = 0; k < num_groups && rc == MZX_OK; ++k) {
+      mzx_actor* a = groups[k];
+      mzx_actor_resident* R = a->resident;
+      void* st = streams[(size_t)k];
+      // rounds of the chunk: [0, accounted) are committed and counted in a->round / a->draw_counter (a repaired round is,
+      // the moment resident_repair commits it), [0, harvested) have handed out their finished games
+      int accounted = 0, harvested = 0;
+      R->stats[1] += 1;
+      while (rc == MZX_OK) {
+        t0 = actor_now();
+        rc = resident_wait(a, st);
+        phase[1] += actor_now() - t0;
+        if (rc) break;
+        const bool halted = R->h_ctrl[0] != 0;
+        const int upto = halted ? R->h_ctrl[1] : n;       // the device committed rounds [accounted, upto) in this pass
+        if (upto < accounted || upto > n || (halted && upto >= n)) {
+          set_error("mzx_selfplay_rounds (resident): halt round %d outside the chunk's queued rounds [%d, %d)", upto, accounted, n);
+          rc = MZX_ERR_RUNTIME;
+          break;
+        }
+        t0 = actor_now();
+        rc = resident_harvest(a, k, harvested, upto, a->round - (accounted - harvested), rounds, st, pieces);
+        a->round += upto - accounted; a->draw_counter += (uint64_t)(upto - accounted); R->stats[0] += upto - accounted;
+        accounted = harvested = upto;
+        phase[3] += actor_now() - t0;
+        if (rc || !halted) break;
+        t0 = actor_now();
+        rc = resident_repair(a, k, args, upto, st);       // (commits round `upto`: harvested with the next pass)
+        accounted = upto + 1;
+        if (rc == MZX_OK) rc = resident_queue_rounds(a, args, accounted, n, st);
+        if (rc == MZX_OK) rc = resident_queue_downloads(a, n, st);
+        phase[4] += actor_now() - t0;
+      }
+    }
+    if (rc) break;
+    // sequence numbers in (round, group, slot) order across groups: the order the host loop finishes games in
+    struct Key { int64_t round; int group; int32_t slot; size_t piece, j; };
+    std::vector<Key> keys;
+    for (size_t p = 0; p < pieces.size(); ++p)
+      for (size_t j = 0; j < pieces[p].b.slot.size(); ++j) keys.push_back({pieces[p].round[j], pieces[p].group, pieces[p].b.slot[j], p, j});
+    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
+      return x.round != y.round ? x.round < y.round : x.group != y.group ? x.group < y.group : x.slot < y.slot;
+    });
+    for (const Key& key : keys) pieces[key.piece].b.seq[key.j] = (*sequence)++;
+    for (ResidentPiece& p : pieces) {
+      mzx_actor* a = groups[p.group];
+      std::lock_guard<std::mutex> lk(a->finished_lock);
+      a->finished.push_back(std::move(p.b));
+    }
+    finished += (int64_t)keys.size();
+    rounds += n;
+    for (int k = 0; k < num_groups; ++k) searches += (int64_t)n * groups[k]->B;
+  }
+  *out_finished = finished; *out_rounds = rounds; *out_searches = searches;
+  return rc;
+}
+
+}  // namespace mzx

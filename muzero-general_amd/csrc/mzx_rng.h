@@ -160,10 +160,6 @@ struct Mt19937 {
   }
 };
 
-}  // namespace mzx
-
-namespace mzx {
-
 // A few persistent worker threads: the per-move draws of a shard (4 096 Dirichlet samples, ~2 us each) are worth
 // spreading over cores, but creating and joining std::threads on every move costs more than the draws themselves
 // (~30 us per thread).  A self-play round is two or three such regions of 20 - 100 us each, a fraction of a millisecond
@@ -244,6 +240,24 @@ struct mzx_rng {
 };
 
 namespace mzx {
+
+// game k + 1 of a per-game loop over [.., hi): its generator state on the way into cache (2.5 KB each: a shard's bank
+// does not stay there)
+inline void rng_prefetch_next(const mzx_rng* r, const int32_t* idx, int k, int hi) {
+  if (k + 1 >= hi) return;
+  const Mt19937& nx = r->streams[idx[k + 1]];
+  __builtin_prefetch(&nx.pos);
+  __builtin_prefetch(&nx.key[nx.pos < 624 ? nx.pos : 0]);
+}
+
+// RandomState.dirichlet([alpha] * n) into out[0, n), zeros up to A: gammas, then multiplication by 1 / sum
+inline void dirichlet_row(Mt19937& m, double alpha, int n, int A, double* out) {
+  double acc = 0.0;
+  for (int j = 0; j < n; ++j) { out[j] = m.standard_gamma(alpha); acc = acc + out[j]; }
+  const double invacc = 1 / acc;
+  for (int j = 0; j < n; ++j) out[j] = out[j] * invacc;
+  for (int j = n; j < A; ++j) out[j] = 0.0;
+}
 
 template <class Fn>
 inline void rng_parallel(mzx_rng* r, int count, int n_threads, Fn fn) {
