@@ -117,6 +117,32 @@ template <int K>
 __device__ __forceinline__ int bcast_i(int v) { return dpp_i<DPP_BCAST0 + K>(v); }
 template <int K>
 __device__ __forceinline__ double bcast_d(double v) { return dpp_d<DPP_BCAST0 + K>(v); }
+// binary64 row broadcast as ONE v_mov_b64_dpp.  row_newbcast is the only control gfx950 takes on a 64-bit DPP operand
+// (quad_perm, the mirrors and row_shl stay pairs of 32-bit moves: dpp_d, shl1_d), and the only 64-bit instructions
+// with a DPP form are v_mov_b64 and v_fmac_f64 (add_bcast_d).  Same whole-row convention as dpp_i.  Used by the two-action
+// instantiations of fc2_search_kernel only (mzx_fused_fc2.h): the lone wave of C2 gains 2.5 % by the 64-bit forms, the
+// tile kernel of C5 (four-lane records, several waves beside MFMAs) measured 0.6 % slower with them and keeps bcast_d.
+template <int K>
+__device__ __forceinline__ double bcast_d64(double v) {
+  const long long zero = 0, src = __builtin_bit_cast(long long, v);
+  const long long r = __builtin_amdgcn_update_dpp(zero, src, DPP_BCAST0 + K, 0xF, 0xF, true);
+  return __builtin_bit_cast(double, r);
+}
+// bcast_d<K>(r) + m in one instruction: v_fmac_f64_dpp m, r, 1.0 computes fma(r[lane K], 1.0, m) -- the product with one
+// is exact, so the single rounding is the addition's, signed zeros included (binary64 has no add with a DPP operand).
+// `one` is a register pair holding 1.0 (a VOP2 DPP operand cannot be a literal).  The statement owns its hazard: `r`
+// must have been written at least two wait states before (dpp_ready_d); the accumulator `m` is an ordinary operand.
+template <int K>
+__device__ __forceinline__ double add_bcast_d(double r, double m, double one) {
+  asm("v_fmac_f64_dpp %[m], %[r], %[o] row_newbcast:%[k] row_mask:0xf bank_mask:0xf"
+      : [m] "+v"(m) : [r] "v"(r), [o] "v"(one), [k] "n"(K));
+  return m;
+}
+// Two wait states behind the VALU instruction that wrote `v`, once, for any number of add_bcast_d that read it.
+__device__ __forceinline__ double dpp_ready_d(double v) {
+  asm("s_nop 1" : "+v"(v));
+  return v;
+}
 
 // canonical butterfly (mzx_tree.h): xor 1, xor 2, half-mirror, mirror; own + partner
 __device__ __forceinline__ float row_sum(float v) {

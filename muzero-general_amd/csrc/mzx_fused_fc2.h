@@ -112,42 +112,69 @@ __device__ __forceinline__ double shl1_d(double v, double old) {
 // holds the row's final value.  Until a lane stops, its copy went through the same operations on the same operands as
 // every other copy of the row, hence the same bits as one row-uniform value.  `lim` = max(ld - sub, 0): the condition
 // is one unsigned compare of the lane constant J - 1 - sub against it -- a select, no exec-mask branch.
+// The reward arrives as the DPP operand of the addition (add_bcast_d: `r_eff` at row_newbcast:J, `one` = 1.0 in registers):
+// a step is mul, add, the compare of the step AFTER it, two selects -- with its own compare in front hipcc put an s_nop 0
+// between the asm statement and the selects of every step; the next step's compare takes that slot.  The first compare of
+// a group is made at its entry.  fc2_backprop readies `r_eff` for DPP reads once per chunk; no wait state per step.
 template <int J>
-__device__ __forceinline__ void chain_step2(double r_eff, double disc, unsigned lim, int sub, double& val) {
-  const bool on = (unsigned)(J - 1 - sub) < lim;
+__device__ __forceinline__ bool chain_on(unsigned lim, int sub) { return (unsigned)(J - 1 - sub) < lim; }
+template <int J, bool NEXT>
+__device__ __forceinline__ void chain_step2(double r_eff, double disc, double one, unsigned lim, int sub, bool& on, double& val) {
+  const bool now = on;
+  const double nv = add_bcast_d<J>(r_eff, disc * val, one);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (NEXT) on = chain_on<J - 1>(lim, sub);
+  __builtin_amdgcn_sched_barrier(0);
+  val = now ? nv : val;
+}
+// The same step with the reward broadcast by a pair of 32-bit moves and a plain addition (7 instructions): the form of the
+// instantiations that do not take 64-bit DPP operands (D64 = false below).
+template <int J>
+__device__ __forceinline__ void chain_step2_moves(double r_eff, double disc, unsigned lim, int sub, double& val) {
+  const bool on = chain_on<J>(lim, sub);
   __builtin_amdgcn_sched_barrier(0);
   const double rj = bcast_d<J>(r_eff);
   const double nv = rj + disc * val;
   val = on ? nv : val;
 }
+template <bool D64, int J, bool NEXT>
+__device__ __forceinline__ void chain_step(double r_eff, double disc, double one, unsigned lim, int sub, bool& on, double& val) {
+  if constexpr (D64) chain_step2<J, NEXT>(r_eff, disc, one, lim, sub, on, val);
+  else chain_step2_moves<J>(r_eff, disc, lim, sub, val);
+}
 // Steps 15 .. 7 in three groups guarded by the deepest row of the wave (wmax, wave-uniform: plain scalar branches, no
 // exec masking); a step above a row's own leaf is a no-op by its select, so a group may run a step too many.
-__device__ __forceinline__ void value_chain(double r_eff, double disc, int ld, int sub, int wmax, double& val) {
+template <bool D64>
+__device__ __forceinline__ void value_chain(double r_eff, double disc, double one, int ld, int sub, int wmax, double& val) {
   const int room = ld - sub;
   const unsigned lim = (unsigned)(room > 0 ? room : 0);
+  bool on6 = chain_on<6>(lim, sub);          // ahead of the guarded groups: ready when step 6 selects
   if (wmax >= 13) {
-    chain_step2<15>(r_eff, disc, lim, sub, val);
-    chain_step2<14>(r_eff, disc, lim, sub, val);
-    chain_step2<13>(r_eff, disc, lim, sub, val);
+    bool on = chain_on<15>(lim, sub);
+    chain_step<D64, 15, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 14, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 13, false>(r_eff, disc, one, lim, sub, on, val);
   }
   if (wmax >= 9) {
-    chain_step2<12>(r_eff, disc, lim, sub, val);
-    chain_step2<11>(r_eff, disc, lim, sub, val);
-    chain_step2<10>(r_eff, disc, lim, sub, val);
-    chain_step2<9>(r_eff, disc, lim, sub, val);
+    bool on = chain_on<12>(lim, sub);
+    chain_step<D64, 12, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 11, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 10, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 9, false>(r_eff, disc, one, lim, sub, on, val);
   }
   if (wmax >= 7) {
-    chain_step2<8>(r_eff, disc, lim, sub, val);
-    chain_step2<7>(r_eff, disc, lim, sub, val);
+    bool on = chain_on<8>(lim, sub);
+    chain_step<D64, 8, true>(r_eff, disc, one, lim, sub, on, val);
+    chain_step<D64, 7, false>(r_eff, disc, one, lim, sub, on, val);
   }
   // steps 6 .. 1 without a guard: of the waves of a C2 search (4096 trees x 50 simulations) 71 % reach depth 5 and 50 %
   // depth 6; a compare-and-branch pair per step cost more than the steps a shallow wave now runs for nothing
-  chain_step2<6>(r_eff, disc, lim, sub, val);
-  chain_step2<5>(r_eff, disc, lim, sub, val);
-  chain_step2<4>(r_eff, disc, lim, sub, val);
-  chain_step2<3>(r_eff, disc, lim, sub, val);
-  chain_step2<2>(r_eff, disc, lim, sub, val);
-  chain_step2<1>(r_eff, disc, lim, sub, val);
+  chain_step<D64, 6, true>(r_eff, disc, one, lim, sub, on6, val);
+  chain_step<D64, 5, true>(r_eff, disc, one, lim, sub, on6, val);
+  chain_step<D64, 4, true>(r_eff, disc, one, lim, sub, on6, val);
+  chain_step<D64, 3, true>(r_eff, disc, one, lim, sub, on6, val);
+  chain_step<D64, 2, true>(r_eff, disc, one, lim, sub, on6, val);
+  chain_step<D64, 1, false>(r_eff, disc, one, lim, sub, on6, val);
 }
 
 
@@ -200,8 +227,8 @@ __device__ __forceinline__ Fc2Walk fc2_walk(const Fc2Tree& T, Fc2Row& st, const 
       const double v = div_by(q - mn_e, dd_e, yd_e);
       const double wv = ps + v;
       const double sc = seen ? wv : ps;
-      const double a0 = bcast_d<0>(sc), a1 = bcast_d<1>(sc);
-      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);
+      const int c0 = bcast_i<0>(c), c1 = bcast_i<1>(c);     // ahead of the scores: two wait states behind sc's select
+      const double a0 = bcast_d64<0>(sc), a1 = bcast_d64<1>(sc);
       const bool up = a1 > a0;     // the child is selected by the comparison itself
       int sl = up ? 1 : 0;
       int cw = up ? c1 : c0;
@@ -348,6 +375,8 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
   double val = value;
   int carry_vc2 = 0, carry_pslot = -1;       // lane 0 of the chunk below (deeper), for lane 15 of this one
   double carry_inv = 0.0;
+  constexpr bool D64 = (AW == 2);            // 64-bit DPP operands: the two-action instantiations (see bcast_d64)
+  const double one = 1.0;                    // register operand of add_bcast_d
   for (int c = cmax; c >= 0; --c) {
     if (c != cmax) { wave_sync(); L = fc2_load_lane<AW>(T, w, c, sub); }
     const int d = c * 16 + sub;
@@ -355,14 +384,19 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
     const bool inner = d < depth;               // lanes at AND beyond the leaf carry the leaf's operands (fc2_load_lane)
     const double rr = inner ? L.rr : reward;
     const bool same = (L.tp == vtp);
-    const double r_eff = (P == 1 || !same) ? rr : -rr;   // value = (+-reward) + discount * value
+    // value = (+-reward) + discount * value; the selects that make it are VALU writes: two wait states once, ahead of
+    // every DPP read of it below (the chain's steps and the hand-over)
+    const double r_sel = (P == 1 || !same) ? rr : -rr;
+    const double r_eff = D64 ? dpp_ready_d(r_sel) : r_sel;
     const int wm = w.levels - c * 16;           // deepest leaf of the wave relative to this chunk (wave-uniform)
-    value_chain(r_eff, disc, ld, sub, wm > 15 ? 15 : (wm < 0 ? 0 : wm), val);
+    value_chain<D64>(r_eff, disc, one, ld, sub, wm > 15 ? 15 : (wm < 0 ? 0 : wm), val);
     const double my_in = val;                   // the value arriving at this lane's node (lane 0: the chunk's final value)
     // hand the value to the chunk above: lane 0's, through lane 0's node -- row-uniform again.  Behind a scalar branch:
     // the first chunk of a search no deeper than 15 plies (c == 0) issues none of it.
     if (c > 0) {
-      const double nv = bcast_d<0>(r_eff) + disc * bcast_d<0>(val);
+      double nv;
+      if constexpr (D64) nv = add_bcast_d<0>(r_eff, disc * bcast_d64<0>(val), one);
+      else nv = bcast_d<0>(r_eff) + disc * bcast_d<0>(val);
       val = (ld >= 0) ? nv : val;
     }
     const int vc2 = L.vc + 1;
@@ -409,7 +443,7 @@ __device__ __forceinline__ void fc2_backprop(const Fc2Tree& T, Fc2Row& st, const
         const double psc = prior_score(L.pb, L.sv, ns, iv, L.sprior[s]);
         sp[s].ps = (s < nslots) ? psc : -MZX_INF;
       }
-      carry_vc2 = bcast_i<0>(vc2); carry_pslot = bcast_i<0>(L.pslot); carry_inv = bcast_d<0>(L.inv_vc3);
+      carry_vc2 = bcast_i<0>(vc2); carry_pslot = bcast_i<0>(L.pslot); carry_inv = D64 ? bcast_d64<0>(L.inv_vc3) : bcast_d<0>(L.inv_vc3);
     } else {
       wave_sync();
       if (inner) {
