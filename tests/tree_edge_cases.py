@@ -235,23 +235,28 @@ def check_lockstep(backend, case, report=None):
 
 # ----------------------------------------------------------------------------- real networks that produce the situations
 
-NETWORK_KINDS = ("random", "flat", "last", "pair", "constant")
+NETWORK_KINDS = ("random", "flat", "last", "pair", "constant", "heads")
 
 
 def _last_bias(sd, head):
-    """Key of the bias of the last Linear layer of a head ('policy' / 'value'), fully connected or residual network."""
+    """Key of the bias of the last Linear layer of a head ('policy' / 'value' / 'reward'), fully connected or residual
+    network.  (The residual dynamics network names its reward layers plain `fc`.)"""
     keys = [k for k in sd if head in k and k.endswith(".bias") and sd[k].dim() == 1 and "bn" not in k]
+    if head == "reward":
+        keys += [k for k in sd if k.startswith("dynamics_network.") and ".fc." in k and k.endswith(".bias")]
     assert keys, (head, list(sd))
     return keys[-1]
 
 
-def network_weights(net, kind, A, seed=12, pair=None, value_bin=None):
+def network_weights(net, kind, A, seed=12, pair=None, value_bin=None, heads=None):
     """A state_dict for `net` that makes a search meet the situation `kind`:
        random    synthetic.fill_state_dict
        flat      every tensor zero: equal priors, zero values -- ties at every level
        last      zero, then +8 on the last policy layer's bias at A - 1: the walk takes the last slot at every level
        pair      zero, then +3 at the two bias indices `pair`: two equal maxima
-       constant  zero, then +20 on bin `value_bin` of the value head's last bias: every value the same c != 0"""
+       constant  zero, then +20 on bin `value_bin` of the value head's last bias: every value the same c != 0
+       heads     zero, then the last bias of the value head is the row heads[0] and the last bias of the reward head the row
+                 heads[1]: with zero weights both heads return exactly those logit rows at every node"""
     assert kind in NETWORK_KINDS, kind
     sd = net.state_dict()
     if kind == "random":
@@ -265,6 +270,12 @@ def network_weights(net, kind, A, seed=12, pair=None, value_bin=None):
     if kind == "constant":
         key = _last_bias(sd, "value")
         sd[key][value_bin] = 20.0
+    if kind == "heads":
+        for head, row in zip(("value", "reward"), heads):
+            key = _last_bias(sd, head)
+            row = torch.from_numpy(numpy.array(row, dtype=numpy.float32))
+            assert sd[key].shape == row.shape, (key, sd[key].shape, row.shape)
+            sd[key] = row.to(sd[key].device)
     return sd
 
 
