@@ -23,6 +23,7 @@ from . import _lib, draws
 from .history import ShardGameHistory, ShardGames, _ShardRecord, gc_paused
 from . import search as _search
 from .search import BatchedMCTS
+from .shard_play import SlotGroup
 
 
 def resident_wanted(config):
@@ -58,10 +59,12 @@ def usable(actor):
             and actor.engine.fused_move and len(actor.config.action_space) <= 4096)
 
 
-class _Group:
+class _Group(SlotGroup):
+    """A slot group whose rounds run inside the library: one ``mzx_actor`` over the group's game, engine and staging."""
+
     def __init__(self, actor, game, first, n, engine, temperature):
         cfg, lib = actor.config, actor.model.backend.lib
-        self.game, self.engine, self.first, self.n = game, engine, first, n
+        super().__init__(first, n, engine, game, owns_game=game is not actor.batched_game)
         A = len(cfg.action_space)
         obs_floats = int(numpy.prod(cfg.observation_shape))
         assert tuple(game.shape) == tuple(cfg.observation_shape), \
@@ -73,7 +76,6 @@ class _Group:
         c_vp = ctypes.c_void_p
         if device_draws:        # noise and tape are device scratch: nothing of them is uploaded (csrc/mzx_draws.h)
             pin = dict(pin, noise=st["draw_noise"].data_ptr(), tape=st["draw_tape"].data_ptr())
-        self.streams = numpy.arange(first, first + n, dtype=numpy.int32)
         self.tape_words = _search.TAPE_WORDS      # (of this group's handle and staging; the retries grow from it)
         self.arena = engine.arena(n)
         conf = _lib.ActorConfig()
@@ -108,14 +110,7 @@ class _Group:
         handle, self.handle = self.handle, None
         if handle:
             self.lib.mzx_actor_destroy(handle)
-
-    # the dict surface SelfPlay's bookkeeping reads from a slot group
-    def get(self, key, default=None):
-        return {"game": self.game, "pending": None, "n": self.n}.get(key, default)
-
-    def __getitem__(self, key):
-        return {"game": self.game, "engine": self.engine, "n": self.n, "slots": list(range(self.first, self.first + self.n)),
-                "pending": None}[key]
+        super().close()
 
 
 class NativeShard:
@@ -123,7 +118,7 @@ class NativeShard:
 
     def __init__(self, actor, temperature):
         cfg, B = actor.config, actor.num_games
-        spans = actor._batched_spans(B)
+        spans = actor._slot_spans(B, batched=True)
         self.groups = []
         for first, last in spans:
             single = len(spans) == 1
@@ -139,10 +134,6 @@ class NativeShard:
         self.error = None
         self._actor = actor
         self._retry = _lib.RETRY_FN(self._retry_flagged)      # (kept alive: the library calls it during a rounds call)
-
-    def close(self):
-        for g in self.groups:
-            g.close()
 
     def set_draw_counter(self, value):
         """Device draws: every group's next search takes this counter (``SelfPlay.draw_counter``)."""
@@ -237,9 +228,7 @@ class NativeShard:
             raise self.error
         lib.check(rc)
         self.sequence = int(io.sequence)
-        actor.stats["searches"] += int(io.searches)
-        actor.stats["simulations"] += int(io.searches) * engine.num_simulations
-        actor.stats["search_seconds"] += float(io.search_seconds)
+        actor._count_search(int(io.searches), engine, float(io.search_seconds))
         phases = actor.stats.setdefault("native_phase_seconds", [0.0] * 7)      # (diagnostics: where the host time of the calls went)
         for k in range(6):
             phases[k] += float(io.phase_seconds[k])

@@ -8,6 +8,7 @@ override_root_with, :275-277).  ``MCTS`` is the reference's single-root class on
 """
 import ctypes
 import math
+import types
 
 import numpy
 import torch
@@ -62,6 +63,30 @@ class PendingSearch:
         if self._complete is not None:
             self._result, self._complete = self._complete(), None
         return self._result
+
+
+class _MoveOutputs:
+    """
+    The outputs of a one-call move (``BatchedMCTS._fused_move``).  Calling it waits for the event behind an asynchronous
+    call and hands out host copies of visits, root values, predicted values and info, n_legal [B] and the noise the roots
+    got ([B][A] view of the staging block, or None: no noise, or device draws -- ``device_noise`` is then the tensor).
+    ``select`` (device draws with a temperature): the call also fills ``actions``.  (An object, not a closure with
+    attributes: a function that names itself is a reference cycle per search, left to the cyclic collector.)
+    """
+    select, actions, device_noise = False, None, None
+
+    def __init__(self, staging, shape, n_legal, done, host_noise, keep):
+        self.staging, self.shape, self.n_legal, self.done, self.host_noise, self.keep = staging, shape, n_legal, done, host_noise, keep
+
+    def __call__(self):
+        if self.done is not None:
+            self.done.synchronize()
+        st, (B, A) = self.staging, self.shape
+        vout = st["vout"]
+        if self.select:
+            self.actions = vout["action"].copy()
+        return (vout["visits"].reshape(B, A).copy(), vout["root_value"].copy(), vout["predicted"].copy(),
+                vout["info"].reshape(B, 4).copy(), self.n_legal, st["vin"]["noise"].reshape(B, A) if self.host_noise else None)
 
 
 def _validate(config):
@@ -569,34 +594,38 @@ class BatchedMCTS:
         return (vout["visits"].reshape(B, A).copy(), vout["root_value"].copy(), vout["predicted"].copy(),
                 vout["info"].reshape(B, 4).copy())
 
-    def _move_search(self, B, obs, legal, to_play, bank, bank_idx, with_noise, asynchronous=False):
+    def _fused_move(self, B, obs, legal, to_play, with_noise, asynchronous, call, bank=None, bank_idx=None):
         """
-        ``mzx_selfplay_search``: root draws of the bank straight into the pinned staging block, ONE upload, the search,
-        ONE download, the stream synchronisation -- the statements of ``StreamBank.root_draws`` + ``_launch`` behind one
-        call.  Returns a function that hands out host copies of the outputs, n_legal [B] and the noise the roots got
-        ([B][A] view, or None).  ``asynchronous``: the call returns once the download is queued (MZX_MOVE_NO_SYNC) and
-        the returned function first waits for an event recorded behind it -- the host is free in between (the staging
-        block of this (B, tape) geometry is in use until then: one search in flight per engine).
+        What the two one-call moves share (``_move_search``: bank draws; ``_move_search_device``: ``bank`` None, noise and
+        tape are device scratch): the pinned staging block, the ``Move`` struct (its fixed part filled once per geometry),
+        the observation read from the device or from the host, the library call ``call(st, mv, n_legal, arena)`` -- its
+        "Legal actions ..." failures raise AssertionError as self_play.py:296-301 does -- and the event behind an
+        ``asynchronous`` call, which returns once the download is queued (MZX_MOVE_NO_SYNC; the staging block of this
+        (B, tape) geometry is in use until then: one search in flight per engine).  Returns the move's ``_MoveOutputs``.
         """
-        lib, A = self.backend.lib, self.A
+        lib, A, be = self.backend.lib, self.A, self.backend
         obs_dev = obs if isinstance(obs, torch.Tensor) else None
         obs_floats = 0 if obs_dev is not None else int(obs.size // B)
-        st = self._staging(B, TAPE_WORDS, obs_floats, with_noise)
-        pin, pout = st["pin"], st["pout"]
+        st = self._staging(B, TAPE_WORDS, obs_floats, with_noise, device_draws=bank is None)
+        pin, pout, c_vp = st["pin"], st["pout"], ctypes.c_void_p
         mv = st.get("move")
         if mv is None:
-            c_vp = ctypes.c_void_p
             mv = st["move"] = _lib.Move()
             mv.num_games, mv.action_space_size, mv.tape_words = B, A, TAPE_WORDS
             mv.h_in, mv.d_in, mv.in_bytes = st["h_in"].data_ptr(), st["d_in"].data_ptr(), st["h_in"].numel()
             mv.h_out, mv.d_out, mv.out_bytes = st["h_out"].data_ptr(), st["d_out"].data_ptr(), st["h_out"].numel()
-            mv.io = _lib.SearchIO(c_vp(pin["obs"]), c_vp(pin["legal"]), c_vp(pin["to_play"]),
-                                  c_vp(pin["noise"]) if with_noise else c_vp(0), c_vp(pin["tape"]), c_vp(pout["visits"]),
+            if bank is None:
+                noise, tape = be.ptr(st["draw_noise"]), be.ptr(st["draw_tape"])
+            else:
+                noise, tape = c_vp(pin["noise"]) if with_noise else c_vp(0), c_vp(pin["tape"])
+            mv.io = _lib.SearchIO(c_vp(pin["obs"]), c_vp(pin["legal"]), c_vp(pin["to_play"]), noise, tape, c_vp(pout["visits"]),
                                   c_vp(pout["root_value"]), c_vp(pout["predicted"]), c_vp(pout["info"]))
         asynchronous = bool(asynchronous) and st["on_gpu"]
-        mv.num_threads = bank.threads
+        if bank is not None:
+            mv.num_threads = bank.threads
         mv.flags = _lib.MOVE_NO_SYNC if asynchronous else 0
-        mv.streams, mv.legal_actions, mv.to_play = bank_idx.ctypes.data, legal.ctypes.data, to_play.ctypes.data
+        mv.streams = None if bank is None else bank_idx.ctypes.data
+        mv.legal_actions, mv.to_play = legal.ctypes.data, to_play.ctypes.data
         mv.dirichlet_alpha, mv.add_exploration_noise = float(self.config.root_dirichlet_alpha), int(with_noise)
         if obs_dev is not None:
             mv.observation, mv.observation_floats = None, 0
@@ -604,9 +633,7 @@ class BatchedMCTS:
         else:
             mv.observation, mv.observation_floats = obs.ctypes.data, obs_floats
         n_legal = numpy.empty(B, numpy.int32)
-        arena = self.arena(B)
-        rc = lib.mzx_selfplay_search(self.handle(B, TAPE_WORDS), bank.handle, ctypes.byref(mv), n_legal.ctypes.data,
-                                     self.backend.ptr(arena), arena.numel(), self.backend.stream())
+        rc = call(st, mv, n_legal, self.arena(B))
         if rc != 0:
             message = lib.mzx_last_error().decode()
             if message.startswith("Legal actions"):       # self_play.py:296-301 raise AssertionError
@@ -617,17 +644,23 @@ class BatchedMCTS:
             done = st.get("event")
             if done is None:
                 done = st["event"] = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.backend.device))
-        keep = (obs, legal, to_play, bank_idx)      # the library read them during the call; the caller may reuse them after
+            done.record(torch.cuda.current_stream(be.device))
 
-        def outputs():
-            if done is not None:
-                done.synchronize()
-            vout = st["vout"]
-            return (vout["visits"].reshape(B, A).copy(), vout["root_value"].copy(), vout["predicted"].copy(),
-                    vout["info"].reshape(B, 4).copy(), n_legal, st["vin"]["noise"].reshape(B, A) if with_noise else None)
-        outputs.keep = keep
-        return outputs
+        # (keep: the library read these during the call; the caller may reuse them after)
+        return _MoveOutputs(st, (B, A), n_legal, done, with_noise and bank is not None, (obs, legal, to_play, bank_idx))
+
+    def _move_search(self, B, obs, legal, to_play, bank, bank_idx, with_noise, asynchronous=False):
+        """
+        ``mzx_selfplay_search``: root draws of the bank straight into the pinned staging block, ONE upload, the search,
+        ONE download, the stream synchronisation -- the statements of ``StreamBank.root_draws`` + ``_launch`` behind one
+        call.  Returns what ``_fused_move`` returns.
+        """
+        lib, be = self.backend.lib, self.backend
+
+        def call(st, mv, n_legal, arena):
+            return lib.mzx_selfplay_search(self.handle(B, TAPE_WORDS), bank.handle, ctypes.byref(mv), n_legal.ctypes.data,
+                                           be.ptr(arena), arena.numel(), be.stream())
+        return self._fused_move(B, obs, legal, to_play, with_noise, asynchronous, call, bank, bank_idx)
 
     def _power_table(self, temps):
         """Device copies of ``draws.power_table`` over every visit count a search of this engine can report."""
@@ -643,71 +676,31 @@ class BatchedMCTS:
         """
         ``mzx_selfplay_move_device``: the legal rows validated and staged, ONE upload, the draws, the search, the action
         choice (``temperature`` [B], or None: none), ONE download -- one library call, no host stream, no per-game loop.
-        Returns the function ``_move_search`` returns; its ``actions`` attribute hands out the chosen actions.
+        Returns what ``_fused_move`` returns; its ``actions`` attribute hands out the chosen actions.
         """
-        lib, A, be = self.backend.lib, self.A, self.backend
-        obs_dev = obs if isinstance(obs, torch.Tensor) else None
-        obs_floats = 0 if obs_dev is not None else int(obs.size // B)
-        st = self._staging(B, TAPE_WORDS, obs_floats, with_noise, device_draws=True)
-        pin, pout, c_vp = st["pin"], st["pout"], ctypes.c_void_p
-        mv = st.get("move")
-        if mv is None:
-            mv = st["move"] = _lib.Move()
-            mv.num_games, mv.action_space_size, mv.tape_words = B, A, TAPE_WORDS
-            mv.h_in, mv.d_in, mv.in_bytes = st["h_in"].data_ptr(), st["d_in"].data_ptr(), st["h_in"].numel()
-            mv.h_out, mv.d_out, mv.out_bytes = st["h_out"].data_ptr(), st["d_out"].data_ptr(), st["h_out"].numel()
-            mv.io = _lib.SearchIO(c_vp(pin["obs"]), c_vp(pin["legal"]), c_vp(pin["to_play"]), be.ptr(st["draw_noise"]),
-                                  be.ptr(st["draw_tape"]), c_vp(pout["visits"]), c_vp(pout["root_value"]),
-                                  c_vp(pout["predicted"]), c_vp(pout["info"]))
-        asynchronous = bool(asynchronous) and st["on_gpu"]
-        mv.flags = _lib.MOVE_NO_SYNC if asynchronous else 0
-        mv.streams, mv.legal_actions, mv.to_play = None, legal.ctypes.data, to_play.ctypes.data
-        mv.dirichlet_alpha, mv.add_exploration_noise = float(self.config.root_dirichlet_alpha), int(with_noise)
-        if obs_dev is not None:
-            mv.observation, mv.observation_floats = None, 0
-            mv.io.d_observation = obs_dev.data_ptr()
-        else:
-            mv.observation, mv.observation_floats = obs.ctypes.data, obs_floats
+        lib, A, be, c_vp = self.backend.lib, self.A, self.backend, ctypes.c_void_p
         streams, counter = ids
-        d = _lib.Draws(seed=self.draw_seed & (2 ** 64 - 1), counter=counter & (2 ** 64 - 1), num_games=B, action_space_size=A,
-                       tape_words=TAPE_WORDS, dirichlet_alpha=float(self.config.root_dirichlet_alpha))
-        if numpy.array_equal(streams, streams[0] + numpy.arange(B, dtype=numpy.int32)):
-            d.first_stream = int(streams[0])
-        else:
-            st["draw_streams"].copy_(torch.as_tensor(streams))
-            d.d_streams = be.ptr(st["draw_streams"])
-        sel, keep = None, (obs, legal, to_play)
-        if temperature is not None:
-            st["vin"]["temperature"][:] = temperature
-            table, distinct, _, _ = self._power_table(temperature)
-            sel = _lib.DrawsSelect(d_temperature=c_vp(pin["temperature"]), d_pow_table=be.ptr(table),
-                                   d_table_temperatures=be.ptr(distinct), table_stride=0 if table is None else table.shape[1],
-                                   num_temperatures=0 if table is None else table.shape[0], d_action=c_vp(pout["action"]))
-        n_legal = numpy.empty(B, numpy.int32)
-        arena = self.arena(B)
-        rc = lib.mzx_selfplay_move_device(self.handle(B, TAPE_WORDS), ctypes.byref(mv), ctypes.byref(d),
-                                          None if sel is None else ctypes.byref(sel), n_legal.ctypes.data, be.ptr(arena),
-                                          arena.numel(), be.stream())
-        if rc != 0:
-            message = lib.mzx_last_error().decode()
-            if message.startswith("Legal actions"):       # self_play.py:296-301 raise AssertionError
-                raise AssertionError(message)
-            lib.check(rc)
-        done = None
-        if asynchronous:
-            done = st.get("event")
-            if done is None:
-                done = st["event"] = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(be.device))
 
-        def outputs():
-            if done is not None:
-                done.synchronize()
-            vout = st["vout"]
-            outputs.actions = vout["action"].copy() if sel is not None else None
-            return (vout["visits"].reshape(B, A).copy(), vout["root_value"].copy(), vout["predicted"].copy(),
-                    vout["info"].reshape(B, 4).copy(), n_legal, None)
-        outputs.keep, outputs.device_noise, outputs.actions = keep, st["draw_noise"], None
+        def call(st, mv, n_legal, arena):
+            d = _lib.Draws(seed=self.draw_seed & (2 ** 64 - 1), counter=counter & (2 ** 64 - 1), num_games=B, action_space_size=A,
+                           tape_words=TAPE_WORDS, dirichlet_alpha=float(self.config.root_dirichlet_alpha))
+            if numpy.array_equal(streams, streams[0] + numpy.arange(B, dtype=numpy.int32)):
+                d.first_stream = int(streams[0])
+            else:
+                st["draw_streams"].copy_(torch.as_tensor(streams))
+                d.d_streams = be.ptr(st["draw_streams"])
+            sel = None
+            if temperature is not None:
+                st["vin"]["temperature"][:] = temperature
+                table, distinct, _, _ = self._power_table(temperature)
+                sel = _lib.DrawsSelect(d_temperature=c_vp(st["pin"]["temperature"]), d_pow_table=be.ptr(table),
+                                       d_table_temperatures=be.ptr(distinct), table_stride=0 if table is None else table.shape[1],
+                                       num_temperatures=0 if table is None else table.shape[0], d_action=c_vp(st["pout"]["action"]))
+            return lib.mzx_selfplay_move_device(self.handle(B, TAPE_WORDS), ctypes.byref(mv), ctypes.byref(d),
+                                                None if sel is None else ctypes.byref(sel), n_legal.ctypes.data, be.ptr(arena),
+                                                arena.numel(), be.stream())
+        outputs = self._fused_move(B, obs, legal, to_play, with_noise, asynchronous, call)
+        outputs.select, outputs.device_noise = temperature is not None, outputs.staging["draw_noise"]
         return outputs
 
     def run(self, observations, legal_actions, to_play, add_exploration_noise, rngs=None, _override=None, _defer_advance=False,
@@ -805,19 +798,22 @@ class BatchedMCTS:
             outputs = self._move_search(B, obs, legal, to_play, bank, bank_idx, bool(add_exploration_noise), _asynchronous)
         elif device_fused:
             outputs = self._move_search_device(B, obs, legal, to_play, ids, bool(add_exploration_noise), temperature, _asynchronous)
-        pending = PendingSearch(lambda: self._complete_run(
-            outputs, B, obs, legal, legal_actions, shared, to_play, n_legal, noise, tape, bank, bank_idx if bank is not None else None,
-            rngs, states if bank is None else None, _override, _defer_advance, ids, temperature))
+        job = types.SimpleNamespace(outputs=outputs, B=B, obs=obs, legal=legal, legal_actions=legal_actions, shared=shared,
+                                    to_play=to_play, n_legal=n_legal, noise=noise, tape=tape, bank=bank,
+                                    bank_idx=bank_idx if bank is not None else None, rngs=rngs, states=states, override=_override,
+                                    defer_advance=_defer_advance, ids=ids, temperature=temperature)
+        pending = PendingSearch(lambda: self._complete_run(job))
         return pending if _asynchronous else pending.result()
 
-    def _complete_run(self, outputs, B, obs, legal, legal_actions, shared, to_play, n_legal, noise, tape, bank, bank_idx, rngs,
-                      states, _override, _defer_advance, ids=None, temperature=None):
-        """The second half of ``run``: outputs of the (possibly still running) search, tape retries, the result record."""
+    def _complete_run(self, job):
+        """The second half of ``run``: outputs of the (possibly still running) search, tape retries, the result record.
+        ``job``: what ``run`` staged -- the inputs as the launch takes them, the draws or where they come from."""
         cfg, A = self.config, self.A
-        if outputs is not None:
-            visits, root_values, predicted, info, n_legal, noise = outputs()
+        B, n_legal, noise = job.B, job.n_legal, job.noise      # (the one-call moves hand n_legal and the noise out themselves)
+        if job.outputs is not None:
+            visits, root_values, predicted, info, n_legal, noise = job.outputs()
         else:
-            visits, root_values, predicted, info = self._launch(B, obs, legal, to_play, noise, tape, TAPE_WORDS, _override)
+            visits, root_values, predicted, info = self._launch(B, job.obs, job.legal, job.to_play, noise, job.tape, TAPE_WORDS, job.override)
         # A tree that exhausted its tie-break tape (a network with equal priors ties at every level) is searched
         # again with a longer tape: same roots, same noise, the stream peeked further -- the reference never
         # fails here (numpy.random.choice at self_play.py:371 simply keeps drawing).
@@ -830,58 +826,58 @@ class BatchedMCTS:
             redo = numpy.nonzero(info[:, 1] & 1)[0]
             redone[redo] = True
             self.tape_retries += len(redo)
-            if ids is not None:      # a longer tape under the same (stream, counter) begins with the shorter one
-                _, t_tape = draws.root_draws(self.backend, self.draw_seed, ids[1], len(redo), A, words, streams=ids[0][redo], noise=False)
+            if job.ids is not None:      # a longer tape under the same (stream, counter) begins with the shorter one
+                _, t_tape = draws.root_draws(self.backend, self.draw_seed, job.ids[1], len(redo), A, words, streams=job.ids[0][redo], noise=False)
                 long_tape = t_tape.cpu().numpy().view(numpy.uint32)
-                if noise is None and getattr(outputs, "device_noise", None) is not None:
-                    noise = outputs.device_noise.cpu().numpy()      # (read before _launch below draws anything)
-            elif bank is not None:
-                _, long_tape = bank.root_draws(bank_idx[redo], cfg.root_dirichlet_alpha, n_legal[redo], A, words,
+                if noise is None and getattr(job.outputs, "device_noise", None) is not None:
+                    noise = job.outputs.device_noise.cpu().numpy()      # (read before _launch below draws anything)
+            elif job.bank is not None:
+                _, long_tape = job.bank.root_draws(job.bank_idx[redo], cfg.root_dirichlet_alpha, n_legal[redo], A, words,
                                                with_noise=False)
             else:
                 long_tape = numpy.zeros((len(redo), words), numpy.uint32)
                 for k, i in enumerate(redo):
-                    rngs[i].set_state(states[i])
-                    long_tape[k] = rngs[i].randint(0, 2 ** 32, size=words, dtype=numpy.uint32)
-            ov = None if _override is None else {k: v[torch.as_tensor(redo, device=v.device)] for k, v in _override.items()}
-            sub_obs = obs[torch.as_tensor(redo, device=obs.device)] if isinstance(obs, torch.Tensor) else obs[redo]
-            v2, r2, p2, i2 = self._launch(len(redo), sub_obs, legal[redo], to_play[redo],
+                    job.rngs[i].set_state(job.states[i])
+                    long_tape[k] = job.rngs[i].randint(0, 2 ** 32, size=words, dtype=numpy.uint32)
+            ov = None if job.override is None else {k: v[torch.as_tensor(redo, device=v.device)] for k, v in job.override.items()}
+            sub_obs = job.obs[torch.as_tensor(redo, device=job.obs.device)] if isinstance(job.obs, torch.Tensor) else job.obs[redo]
+            v2, r2, p2, i2 = self._launch(len(redo), sub_obs, job.legal[redo], job.to_play[redo],
                                           None if noise is None else noise[redo], long_tape, words, ov)
             visits[redo], root_values[redo], predicted[redo], info[redo] = v2, r2, p2, i2
         self._carry = None      # (the re-runs used the arena at other shard sizes: the trees of this run are gone)
         if words == TAPE_WORDS:
-            self._note_searched(B, [list(legal[i, : int((legal[i] >= 0).sum())]) for i in range(B)], visits)
+            self._note_searched(B, [list(job.legal[i, : int((job.legal[i] >= 0).sum())]) for i in range(B)], visits)
         result = SearchResult(visits, root_values, predicted, info,
-                              legal_actions if isinstance(legal_actions, numpy.ndarray) else
-                              (shared if shared is not None else [list(a) for a in legal_actions]))
-        if shared is not None:
-            result.shared_legal = shared[0]
+                              job.legal_actions if isinstance(job.legal_actions, numpy.ndarray) else
+                              (job.shared if job.shared is not None else [list(a) for a in job.legal_actions]))
+        if job.shared is not None:
+            result.shared_legal = job.shared[0]
         if (info[:, 1] != 0).any():
             raise _lib.MzxError(f"search flagged trees {numpy.nonzero(info[:, 1])[0][:8]} (flags {set(info[:, 1])}): "
                                 "node arena exhausted")
         result.actions = None
-        if ids is not None:
-            result.legal_array, result.n_legal, result.streams = legal, n_legal, ids[0]
-            if temperature is not None:
-                result.actions = getattr(outputs, "actions", None)
+        if job.ids is not None:
+            result.legal_array, result.n_legal, result.streams = job.legal, n_legal, job.ids[0]
+            if job.temperature is not None:
+                result.actions = getattr(job.outputs, "actions", None)
                 again = numpy.arange(B) if result.actions is None else numpy.nonzero(redone)[0]
                 if again.size:       # the searches run again (and the given roots): the same select function over them
                     if result.actions is None:
                         result.actions = numpy.zeros(B, numpy.int64)
-                    _, _, table, distinct = self._power_table(temperature)
-                    result.actions[again] = draws.select(self.backend, self.draw_seed, ids[1], legal[again], visits[again],
-                                                         temperature[again], table, distinct, streams=ids[0][again]).cpu().numpy()
-        elif bank is not None:
-            result.legal_array, result.n_legal, result.streams = legal, n_legal, bank_idx
-            if _defer_advance and self.fused_move:     # (the numpy action draw of the A/B switch does not advance)
+                    _, _, table, distinct = self._power_table(job.temperature)
+                    result.actions[again] = draws.select(self.backend, self.draw_seed, job.ids[1], job.legal[again], visits[again],
+                                                         job.temperature[again], table, distinct, streams=job.ids[0][again]).cpu().numpy()
+        elif job.bank is not None:
+            result.legal_array, result.n_legal, result.streams = job.legal, n_legal, job.bank_idx
+            if job.defer_advance and self.fused_move:     # (the numpy action draw of the A/B switch does not advance)
                 result.pending_words = numpy.ascontiguousarray(info[:, 2], dtype=numpy.int32)
             else:
-                bank.advance(bank_idx, info[:, 2])   # consume exactly what the device consumed
+                job.bank.advance(job.bank_idx, info[:, 2])   # consume exactly what the device consumed
         else:
             for i in range(B):  # rewind, then consume exactly what the device consumed
-                rngs[i].set_state(states[i])
+                job.rngs[i].set_state(job.states[i])
                 if info[i, 2]:
-                    rngs[i].randint(0, 2 ** 32, size=int(info[i, 2]), dtype=numpy.uint32)
+                    job.rngs[i].randint(0, 2 ** 32, size=int(info[i, 2]), dtype=numpy.uint32)
         return result
 
 

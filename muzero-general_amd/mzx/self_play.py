@@ -25,7 +25,16 @@ process-global stream itself, so a single game reproduces the reference draw for
 draw.  Tie draws happen on the device from a tape of the stream's next raw
 words (numpy's masked rejection, exactly); the host then advances the stream by
 the number of words the device consumed.
+
+How the actor is laid out.  A move of a shard is written down in ONE place per protocol: ``_start_game`` / ``_log_moves``
+for per-object games (``_play_shard``, ``_rounds_shard`` and the stream-bank branch of ``_play``; the render / opponent /
+``Node`` branch of ``_play`` logs game by game as the reference does), ``shard_play.legal_mask_row`` /
+``shard_play.shard_views`` for the batched protocol (``_play_batched`` game-major, ``BatchedGroup`` in ring rows).  The
+rules they share are single functions: ``shard_play.move_temperature``, ``_count_search``, ``_slot_spans``.
+``play_rounds`` is ``_run_rounds`` over slot groups (``shard_play.SlotGroup``) with the protocol's own begin / consume and
+queue-ahead rule; ``_live`` is ``{"groups": [...]}`` (+ ``"native"``: the ``NativeShard``) while games are in progress.
 """
+import contextlib
 import ctypes
 import math
 import time
@@ -36,6 +45,7 @@ import torch
 
 from . import _lib, _rng, models, native_rounds, replay
 from . import observations as observations_mod
+from .shard_play import BatchedGroup as _BatchedGroup, ObjectGroup, SlotGroup, legal_mask_row, move_temperature, shard_views  # noqa: F401
 # round 6: the records / tree facades and the batched search live in modules of their own; every name stays importable
 # from here (the reference has them all in self_play.py)
 from .history import GameHistory, MinMaxStats, Node, ShardGameHistory, ShardGames, _ShardRecord, gc_paused  # noqa: F401
@@ -48,169 +58,6 @@ def _remote(method, *args):
         import ray
         return ray.get(method.remote(*args))
     return method(*args)
-
-
-class _BatchedGroup(dict):
-    """
-    A group of slots of a shard behind the batched plugin protocol (``SelfPlay._rounds_batched``): its game object,
-    engine, streams, frame store and the LOG of the games in progress -- ring arrays [row][slot], row = round % capacity,
-    a move is one contiguous row per field (a game lasts at most ``max_moves`` rounds, so its rows never collide; the
-    ring starts small and grows to that bound when a game outlasts it); a finished game's rows are copied out as they
-    lie (move-major) and viewed game by game -- no transposition on the actor's path.  A dict for the few fields the
-    actor's other methods read (``pending``, ``n``, ``slots``).
-    """
-
-    def __init__(self, actor, game, first, n, engine, temperature):
-        cfg = actor.config
-        obs = numpy.asarray(game.reset())
-        assert obs.shape == (n,) + tuple(cfg.observation_shape), \
-            f"Observation should match the observation_shape defined in MuZeroConfig. Expected {(n,) + tuple(cfg.observation_shape)} but got {obs.shape}."
-        super().__init__(game=game, first=first, n=n, engine=engine, slots=list(range(first, first + n)),
-                         streams=numpy.arange(first, first + n, dtype=numpy.int32), everyone=numpy.arange(n), obs=obs,
-                         tp=numpy.asarray(game.to_play()).astype(numpy.int64), start=numpy.zeros(n, numpy.int64),
-                         temps=numpy.full(n, float(temperature)), round=0, store=None, pending=None, legal=None,
-                         counter=int(actor.draw_counter))      # (device draws: the counter of the group's next search)
-        self.A, self.max_moves = len(cfg.action_space), int(cfg.max_moves)
-        self.ring, self.cap = None, 0
-        if cfg.stacked_observations > 0:   # frames stay in HBM; the stacked inputs are assembled there (csrc/mzx_obs.h)
-            whole = n == actor.num_games
-            self["store"] = actor._frame_store(n) if whole else observations_mod.FrameStore(cfg, n, actor.model.backend)
-            self["store"].push(obs, None)
-
-    def _row(self, r, obs, reward):
-        """Ring row of round ``r``; allocates / grows the ring so that the rounds of every running game keep their own."""
-        need = r - int(self["start"].min()) + 1
-        if need > self.cap:
-            row_bytes = max(1, obs.nbytes)      # (large observations: start with a ring of at most ~256 MB of frames)
-            first = max(2, min(16, (256 << 20) // row_bytes))
-            cap = min(max(2 * self.cap, need, first), self.max_moves + 1)
-            n, A = self["n"], self.A
-            obs_dtype, rew_dtype = obs.dtype, reward.dtype
-            if self.ring is not None:        # rows already logged keep their precision (a plugin may return floats in
-                # one round and ints in the next: the copy below must not truncate the earlier rows -- ADVICE r5)
-                obs_dtype = numpy.result_type(self.ring["obs"].dtype, obs_dtype)
-                rew_dtype = numpy.result_type(self.ring["rew"].dtype, rew_dtype)
-            ring = dict(obs=numpy.empty((cap, n) + obs.shape[1:], obs_dtype), tp=numpy.empty((cap, n), numpy.int64),
-                        act=numpy.empty((cap, n), numpy.int64), rew=numpy.empty((cap, n), rew_dtype),
-                        vis=numpy.empty((cap, n, A), numpy.int32), val=numpy.empty((cap, n), numpy.float64), mask=None)
-            if self.ring is not None:
-                if self.ring["mask"] is not None:
-                    ring["mask"] = numpy.ones((cap, n, A), bool)
-                for q in range(int(self["start"].min()), r):
-                    for name, arr in ring.items():
-                        if arr is not None:
-                            arr[q % cap] = self.ring[name][q % self.cap]
-            self.ring, self.cap = ring, cap
-        for name, value in (("obs", obs), ("rew", reward)):      # a plugin may return ints in one round and floats in another
-            have = self.ring[name].dtype
-            if value.dtype != have and numpy.result_type(value.dtype, have) != have:
-                self.ring[name] = self.ring[name].astype(numpy.result_type(value.dtype, have))
-        return r % self.cap
-
-    def move_temps(self, temperature_threshold):
-        """The temperature of every slot's next move (self_play.py:151-157)."""
-        temps = self["temps"]
-        if temperature_threshold:
-            temps = numpy.where(self["round"] - self["start"] + 1 < temperature_threshold, temps, 0.0)
-        return temps
-
-    def play(self, actor, result, temperature, temperature_threshold):
-        """One move of every slot after its search: action draw, game step, log, finished games out, slots refilled."""
-        cfg, g, n, A = actor.config, self["game"], self["n"], self.A
-        r, start, store, everyone = self["round"], self["start"], self["store"], self["everyone"]
-        legal = self["legal"]
-        moves_before = r - start                      # len(action_history) - 1 of every slot's game
-        if actor.device_draws:                        # drawn on the device behind the search (csrc/mzx_draws.h)
-            actions = numpy.asarray(result.actions, numpy.int64)
-        else:
-            actions = numpy.asarray(actor._select_actions_bank(result, self["streams"], self.move_temps(temperature_threshold)),
-                                    numpy.int64)
-        obs2, reward, done = g.step(actions, None)
-        obs2, reward = numpy.asarray(obs2), numpy.asarray(reward)
-        c = self._row(r, self["obs"], reward)
-        ring = self.ring
-        ring["obs"][c], ring["tp"][c], ring["act"][c], ring["rew"][c] = self["obs"], self["tp"], actions, reward
-        ring["vis"][c], ring["val"][c] = result.visit_counts, result.root_values
-        if isinstance(legal, numpy.ndarray) and (legal >= 0).all():
-            if ring["mask"] is not None:              # every action legal for every game
-                ring["mask"][c] = True
-        else:
-            if ring["mask"] is None:
-                ring["mask"] = numpy.ones((self.cap, n, A), bool)
-            mask = numpy.zeros((n, A), bool)
-            if isinstance(legal, numpy.ndarray):
-                mask[numpy.repeat(everyone, (legal >= 0).sum(1)), legal[legal >= 0]] = True
-            else:
-                for i, acts in enumerate(legal):
-                    mask[i, acts] = True
-            ring["mask"][c] = mask
-        tp2 = numpy.asarray(g.to_play()).astype(numpy.int64)
-        over = numpy.asarray(done, bool) | (moves_before + 2 > cfg.max_moves)     # len(action_history) <= max_moves, :129
-        pushed = actions
-        finished, slots = [], []
-        if over.any():
-            idx = numpy.nonzero(over)[0]
-            finished = self._harvest(idx, r, obs2[idx], tp2[idx])
-            slots = (idx + self["first"]).tolist()
-            if not obs2.flags.writeable or obs2 is self["obs"]:
-                obs2 = obs2.copy()
-            obs2[idx] = numpy.asarray(g.reset_games(idx))       # the slots' next games begin (self_play.py:31-52)
-            tp2 = numpy.asarray(g.to_play()).astype(numpy.int64)
-            start[idx] = r + 1
-            self["temps"][idx] = float(temperature)
-            pushed = actions.copy()
-            pushed[idx] = 0
-            if store is not None:
-                store.clear_history(idx)
-        if store is not None:
-            store.push(obs2, pushed)
-        self["obs"], self["tp"] = obs2, tp2
-        self["round"] = r + 1
-        return finished, slots
-
-    def _harvest(self, idx, r, final_obs, final_tp):
-        """GameHistory views of the games of slots ``idx`` that ended with round ``r`` (self_play.py:479-511)."""
-        A, ring, cap = self.A, self.ring, self.cap
-        out = [None] * len(idx)
-        starts = self["start"][idx]
-        for st in numpy.unique(starts):
-            where = numpy.nonzero(starts == st)[0]
-            slots = idx[where]
-            n = r - int(st) + 1
-            rows = numpy.arange(int(st), r + 1) % cap
-            everyone = slots.size == self["n"]
-            contiguous = rows[-1] - rows[0] == n - 1               # the game's rounds did not wrap around the ring
-            if everyone and contiguous:
-                take = lambda a: a[rows[0]: rows[0] + n]           # (a view: copied into the record's arrays below)
-            elif everyone:
-                take = lambda a: a[rows]
-            else:
-                take = lambda a: a[rows[:, None], slots[None, :]]
-            k = slots.size
-            obs_all = numpy.empty((n + 1, k) + ring["obs"].shape[2:], ring["obs"].dtype)
-            obs_all[:n], obs_all[n] = take(ring["obs"]), final_obs[where]
-            acts = numpy.zeros((n + 1, k), numpy.int64)
-            acts[1:] = take(ring["act"])
-            rews = numpy.zeros((n + 1, k), ring["rew"].dtype)
-            rews[1:] = take(ring["rew"])
-            tps = numpy.empty((n + 1, k), numpy.int64)
-            tps[:n], tps[n] = take(ring["tp"]), final_tp[where]
-            vis, vals = numpy.array(take(ring["vis"])), numpy.array(take(ring["val"]))      # [n][games][A], [n][games] (copies)
-            totals = vis.sum(2)
-            ratios = vis / numpy.maximum(totals, 1)[:, :, None]       # true division of small integers == Python's int / int
-            plain = totals > 0
-            legal_mask = None
-            if ring["mask"] is not None:
-                legal_mask = numpy.array(take(ring["mask"]))
-                plain = plain & legal_mask.all(2)
-            record = _ShardRecord(A, obs_all, acts, rews, tps, vis, vals, totals, ratios, plain.all(0), legal_mask, time_major=True)
-            with gc_paused():
-                views = [ShardGameHistory(record, j, n) for j in range(k)]
-            if k == len(idx):
-                return views
-            for j, w in enumerate(where):
-                out[w] = views[j]
-        return out
 
 
 class SelfPlay:
@@ -273,7 +120,7 @@ class SelfPlay:
         if self.device_draws and live is not None:
             if live.get("native") is not None:
                 return max(int(g.lib.mzx_actor_draw_counter(g.handle)) for g in live["groups"])
-            return max(int(g["counter"]) for g in live["groups"])
+            return max(int(g.counter) for g in live["groups"])
         return self._draw_counter
 
     @draw_counter.setter
@@ -286,7 +133,7 @@ class SelfPlay:
                 live["native"].set_draw_counter(self._draw_counter)
             else:
                 for g in live["groups"]:
-                    g["counter"] = self._draw_counter
+                    g.counter = self._draw_counter
 
     def _no_device_draws(self, what):
         if self.device_draws:
@@ -443,18 +290,20 @@ class SelfPlay:
         return self._play(list(range(self.num_games)), temperature, temperature_threshold, render, opponent,
                           muzero_player)
 
-    def _end_live(self):
-        """Ends the games in progress under ``play_rounds``: queued searches drained, the slot groups' own game objects
-        (and native actors) released."""
+    def _end_live(self, forget=True):
+        """Ends the games in progress under ``play_rounds``: queued searches drained, the slot groups closed (their own game
+        objects, native actors).  ``forget=False`` (``close_game``): the closed groups stay in ``_live``, where a finished run's
+        groups and their engines' counters are still looked at -- not ``draw_counter``: a native actor's is gone with its handle."""
         self._drain_searches()
-        if self.device_draws and self._live is not None:
-            self._draw_counter = self.draw_counter        # (the next shard's searches go on counting)
-        live, self._live = self._live, None
-        for group in (live or {}).get("groups", ()):      # (slot groups of the batched protocol own their game objects)
-            if group.get("game") is not None and group["game"] is not self.batched_game:
-                group["game"].close()
-        if live and live.get("native") is not None:
-            live["native"].close()
+        live = self._live
+        if live is None:
+            return
+        if forget:
+            if self.device_draws:
+                self._draw_counter = self.draw_counter        # (the next shard's searches go on counting)
+            self._live = None
+        for group in live["groups"]:
+            group.close()
 
     def _check_observation(self, observation):
         # self_play.py:132-137 (same messages); ndarray observations of the right shape take the fast exit
@@ -467,41 +316,96 @@ class SelfPlay:
         assert got == shape, \
             f"Observation should match the observation_shape defined in MuZeroConfig. Expected {shape} but got {got}."
 
+    def _count_search(self, n, engine, seconds):
+        """``stats``: ``n`` searches of ``engine`` that took ``seconds`` of this thread's time."""
+        stats = self.stats
+        stats["search_seconds"] += seconds
+        stats["searches"] += n
+        stats["simulations"] += n * engine.num_simulations
+
+    @staticmethod
+    def _move_temps(temperature, histories, slots, threshold):
+        """``move_temperature`` of the games of ``slots`` (their lengths are only read with a threshold)."""
+        return move_temperature(temperature, [len(histories[s].action_history) for s in slots] if threshold else None, threshold)
+
+    # ------------------------------------------------------------------ the ledger of per-object games
+    @property
+    def _record_legal(self):
+        """config.reanalyse_search: the legal actions of every searched position go into the history (``legal_actions``, one
+        list of ints per position) -- what DeviceGameStore(legal_masks=True) turns into the mask rows of its search sweep."""
+        return bool(getattr(self.config, "reanalyse_search", False))
+
+    def _start_game(self, s, batch, first=0):
+        """A new game on slot ``s`` (self_play.py:118-123): its history; the first observation lands in ``batch[s - first]``
+        (``batch`` None: nowhere)."""
+        game, gh = self.games[s], GameHistory()
+        observation = game.reset()
+        gh.action_history.append(0)
+        gh.observation_history.append(observation)
+        gh.reward_history.append(0)
+        gh.to_play_history.append(game.to_play())
+        if self._record_legal:
+            gh.legal_actions = []
+        self._check_observation(observation)
+        if batch is not None:
+            batch[s - first] = observation
+        return gh
+
+    def _log_moves(self, slots, histories, result, actions, legal, batch, first, on_over):
+        """
+        One searched move of the per-object games of ``slots`` (self_play.py:139-172): game ``slots[k]`` plays ``actions[k]``
+        and logs root ``k`` of ``result`` in ``histories[slots[k]]``; its new observation lands in ``batch[slots[k] - first]``.
+        ``legal``: the lists the search was given.  ``on_over(k, s)`` is called for a game that is over (:129).  Everything
+        that is not a call into a plugin object or an append to one of its history's lists is done once for the whole move:
+        child_visits rows (visit / total, self_play.py:496-511) and root values come from two array operations.
+        """
+        cfg, games = self.config, self.games
+        A, max_moves, record_legal = len(cfg.action_space), cfg.max_moves, self._record_legal
+        shape = cfg.observation_shape if isinstance(cfg.observation_shape, tuple) else tuple(cfg.observation_shape)
+        vis = result.visit_counts
+        totals = vis.sum(1)
+        rows = (vis / numpy.maximum(totals, 1)[:, None]).tolist()     # int / int true division, as Python's
+        values = result.root_values.tolist()
+        plain = bool((totals > 0).all()) and all(len(l) == A for l in result.legal_actions)
+        for k, s in enumerate(slots):
+            game, gh, action = games[s], histories[s], actions[k]
+            if record_legal:
+                gh.legal_actions.append([int(a) for a in legal[k]])
+            observation, reward, done = game.step(action)
+            if plain:
+                gh.child_visits.append(rows[k])
+                gh.root_values.append(values[k])
+            else:      # illegal actions get 0, an unvisited root reports value 0 (self_play.py:496-511, :446-449)
+                total, legal_set = int(totals[k]), set(result.legal_actions[k])
+                gh.child_visits.append([int(vis[k][a]) / total if a in legal_set else 0 for a in cfg.action_space])
+                gh.root_values.append(values[k] if total else 0)
+            gh.action_history.append(action)
+            gh.observation_history.append(observation)
+            gh.reward_history.append(reward)
+            gh.to_play_history.append(game.to_play())
+            if getattr(observation, "shape", None) != shape:
+                self._check_observation(observation)
+            batch[s - first] = observation
+            if done or len(gh.action_history) > max_moves:
+                on_over(k, s)
+
     def _play_shard(self, temperature, temperature_threshold):
         """
         play_game (self_play.py:110-183) for all games of the shard through the REFERENCE plugin surface (B
-        unmodified ``Game`` objects): self-play, no rendering, native stream bank.  Everything that is not a call
-        into a plugin object or an append to one of its GameHistory lists is done once per move for the whole
-        shard: observations land in one persistent float32 batch as they are produced, legal-action lists are
-        validated once per distinct list, actions / child_visits rows / root values come from array operations.
+        unmodified ``Game`` objects): self-play, no rendering, native stream bank.  Observations land in one persistent
+        float32 batch as they are produced, legal-action lists are validated once per distinct list, actions and the
+        history rows of a move come from array operations (``_log_moves``).
         Game by game the result equals the single-game actor's (tests/test_selfplay_shard.py).
         """
-        cfg, games = self.config, self.games
-        A, G = len(cfg.action_space), len(self.games)
-        shape = tuple(cfg.observation_shape)
-        cfg_shape_is_tuple = cfg.observation_shape if isinstance(cfg.observation_shape, tuple) else shape
+        cfg, games, G = self.config, self.games, len(self.games)
         batch = getattr(self, "_obs_batch", None)
-        if batch is None or batch.shape != (G,) + shape:
-            batch = self._obs_batch = numpy.empty((G,) + shape, numpy.float32)
-        histories = []
-        record_legal = bool(getattr(cfg, "reanalyse_search", False))      # GameHistory.legal_actions, as in _play
-        for s, game in enumerate(games):
-            gh = GameHistory()
-            observation = game.reset()
-            gh.action_history.append(0)
-            gh.observation_history.append(observation)
-            gh.reward_history.append(0)
-            gh.to_play_history.append(game.to_play())
-            if record_legal:
-                gh.legal_actions = []
-            self._check_observation(observation)
-            batch[s] = observation
-            histories.append(gh)
+        if batch is None or batch.shape != (G,) + tuple(cfg.observation_shape):
+            batch = self._obs_batch = numpy.empty((G,) + tuple(cfg.observation_shape), numpy.float32)
+        histories = [self._start_game(s, batch) for s in range(G)]
         store = None
         if cfg.stacked_observations > 0:
             store = self._frame_store(G)
             store.push(batch, None)
-        max_moves = cfg.max_moves
         active = list(range(G))
         moved = numpy.zeros(G, numpy.int32)
         while active:
@@ -514,95 +418,51 @@ class SelfPlay:
                 stacked = batch if everyone else batch[active]
             t0 = time.perf_counter()
             result = self.engine.run(stacked, legal, to_play, True, (self.bank, active))
-            self.stats["search_seconds"] += time.perf_counter() - t0
-            self.stats["searches"] += len(active)
-            self.stats["simulations"] += len(active) * self.engine.num_simulations
-            if temperature_threshold:
-                temps = [temperature if len(histories[s].action_history) < temperature_threshold else 0 for s in active]
-            else:
-                temps = temperature
-            actions = self._select_actions_bank(result, active, temps)
-            vis = result.visit_counts
-            totals = vis.sum(1)
-            rows = (vis / numpy.maximum(totals, 1)[:, None]).tolist()     # int / int true division, as Python's
-            values = result.root_values.tolist()
-            plain = bool((totals > 0).all()) and all(len(l) == A for l in result.legal_actions)
-            still = []
-            for j, s in enumerate(active):
-                game, gh, action = games[s], histories[s], actions[j]
-                if record_legal:
-                    gh.legal_actions.append([int(a) for a in legal[j]])
-                observation, reward, done = game.step(action)
-                if plain:
-                    gh.child_visits.append(rows[j])
-                    gh.root_values.append(values[j])
-                else:      # illegal actions get 0, an unvisited root reports value 0 (self_play.py:496-511, :446-449)
-                    total, legal_set = int(totals[j]), set(result.legal_actions[j])
-                    gh.child_visits.append([int(vis[j][a]) / total if a in legal_set else 0 for a in cfg.action_space])
-                    gh.root_values.append(values[j] if total else 0)
-                gh.action_history.append(action)
-                gh.observation_history.append(observation)
-                gh.reward_history.append(reward)
-                gh.to_play_history.append(game.to_play())
-                if getattr(observation, "shape", None) != cfg_shape_is_tuple:
-                    self._check_observation(observation)
-                batch[s] = observation
-                if not done and len(gh.action_history) <= max_moves:
-                    still.append(s)
+            self._count_search(len(active), self.engine, time.perf_counter() - t0)
+            actions = self._select_actions_bank(result, active, self._move_temps(temperature, histories, active, temperature_threshold))
+            over = set()
+            self._log_moves(active, histories, result, actions, legal, batch, 0, lambda k, s: over.add(s))
+            still = [s for s in active if s not in over]
             if store is not None and still:
-                for s in active:
-                    moved[s] = histories[s].action_history[-1]
+                moved[active] = actions
                 store.push(batch, moved)
             active = still
         return histories
 
     def _play(self, slots, temperature, temperature_threshold, render, opponent, muzero_player):
+        """play_game (self_play.py:110-183) for the games of ``slots``, opponents and rendering included.  Moves searched on
+        the stream bank are logged in bulk unless rendered; every other move goes through a ``Node`` as in the reference.
+        Within a move the bulk-logged games are stepped first, then the others in slot order: when a shard mixes searched
+        and opponent positions in one move, the plugin objects are not called in slot order (they are independent games)."""
         cfg = self.config
-        A = len(cfg.action_space)
-        histories = {}
-        observations = {}
-        # config.reanalyse_search: the legal actions of every position go into the history (GameHistory.legal_actions, one
-        # list per position) -- what DeviceGameStore(legal_masks=True) turns into the mask rows of its search sweep
-        record_legal = bool(getattr(cfg, "reanalyse_search", False))
+        A, G, record_legal = len(cfg.action_space), len(self.games), self._record_legal
+        # the slots' current frames, for the frame store and the bulk ledger; a lone game without either keeps none
+        with_store = cfg.stacked_observations > 0 and opponent == "self"
+        frame = numpy.zeros((G,) + tuple(cfg.observation_shape), numpy.float32) if with_store or self.bank is not None else None
+        histories = [None] * G
         for s in slots:
-            gh = GameHistory()
-            observation = self.games[s].reset()
-            gh.action_history.append(0)
-            gh.observation_history.append(observation)
-            gh.reward_history.append(0)
-            gh.to_play_history.append(self.games[s].to_play())
-            if record_legal:
-                gh.legal_actions = []
-            histories[s] = gh
-            observations[s] = observation
+            histories[s] = self._start_game(s, frame)
             if render:
                 self.games[s].render()
         # stacked observations of a self-play shard are assembled on the device from a frame store
         # (one upload of the new frames per move) instead of per-game numpy concatenations
         store = None
-        if cfg.stacked_observations > 0 and opponent == "self":
-            store = self._frame_store(len(self.games))
-            frame = numpy.zeros((len(self.games),) + tuple(cfg.observation_shape), numpy.float32)
-            for s in slots:
-                frame[s] = numpy.asarray(observations[s])
+        if with_store:
+            store = self._frame_store(G)
             store.push(frame, None)
         active = list(slots)
         while active:
             searching, stacked, stacked_by_slot = [], [], {}
             for s in active:
-                observation, gh = observations[s], histories[s]
-                # self_play.py:132-137
-                assert len(numpy.array(observation).shape) == 3, \
-                    f"Observation should be 3 dimensionnal instead of {len(numpy.array(observation).shape)} dimensionnal. Got observation of shape: {numpy.array(observation).shape}"
-                assert numpy.array(observation).shape == cfg.observation_shape, \
-                    f"Observation should match the observation_shape defined in MuZeroConfig. Expected {cfg.observation_shape} but got {numpy.array(observation).shape}."
+                gh = histories[s]
+                self._check_observation(gh.observation_history[-1])
                 st = None if store is not None else gh.get_stacked_observations(-1, cfg.stacked_observations, A)
                 if opponent == "self" or muzero_player == self.games[s].to_play():
                     searching.append(s)
                     stacked.append(st)
                 else:
                     stacked_by_slot[s] = st      # what THIS game's opponent sees (self_play.py:161-165)
-            result = None
+            result, batch_actions, over = None, None, set()
             if searching:
                 t0 = time.perf_counter()
                 legal_lists = [self.games[s].legal_actions() for s in searching]
@@ -612,34 +472,22 @@ class SelfPlay:
                     [self.games[s].to_play() for s in searching], True,
                     (self.bank, searching) if self.bank is not None else [self.rngs[s] for s in searching],
                 )
-                self.stats["search_seconds"] += time.perf_counter() - t0
-                self.stats["searches"] += len(searching)
-                self.stats["simulations"] += len(searching) * self.engine.num_simulations
-            still = []
+                self._count_search(len(searching), self.engine, time.perf_counter() - t0)
+                if self.bank is not None:
+                    batch_actions = self._select_actions_bank(
+                        result, searching, self._move_temps(temperature, histories, searching, temperature_threshold))
             position = {s: k for k, s in enumerate(searching)}
-            batch_actions = None
-            if self.bank is not None and searching:
-                temps = [temperature if not temperature_threshold or len(histories[s].action_history) < temperature_threshold
-                         else 0 for s in searching]
-                batch_actions = self._select_actions_bank(result, searching, temps)
-            # shard bookkeeping in bulk: with the stream bank the per-game Node objects are only needed for
-            # rendering; the child_visits rows (visit / total, 0 for illegal actions, self_play.py:496-511)
-            # and root values come from two array operations per move
-            fast_rows = None
-            if batch_actions is not None and not render:
-                vis = result.visit_counts
-                totals = vis.sum(1)
-                ratios = (vis / numpy.maximum(totals, 1)[:, None]).tolist()   # int / int true division, as Python's
-                fast_rows = (vis, totals, ratios)
+            # shard bookkeeping in bulk: with the stream bank the per-game Node objects are only needed for rendering
+            in_bulk = batch_actions is not None and not render
+            if in_bulk:
+                self._log_moves(searching, histories, result, batch_actions, legal_lists, frame, 0, lambda k, s: over.add(s))
             for s in active:
+                if in_bulk and s in position:
+                    continue
                 gh, game = histories[s], self.games[s]
-                root = None
-                if s in position and fast_rows is not None:
-                    k = position[s]
-                    action = batch_actions[k]
-                elif s in position:
+                if s in position:
                     root = result.root(position[s])
-                    t = temperature if not temperature_threshold or len(gh.action_history) < temperature_threshold else 0
+                    t = move_temperature(temperature, len(gh.action_history), temperature_threshold)
                     action = batch_actions[position[s]] if batch_actions is not None else self._select_action(root, t, self.rngs[s])
                     if render:
                         print(f'Tree depth: {result.max_tree_depth[position[s]]}')
@@ -652,29 +500,18 @@ class SelfPlay:
                 if render:
                     print(f"Played action: {game.action_to_string(action)}")
                     game.render()
-                if s in position and fast_rows is not None:
-                    vis, totals, ratios = fast_rows
-                    k, legal_k = position[s], result.legal_actions[position[s]]
-                    total = int(totals[k])
-                    if len(legal_k) == A and total:
-                        gh.child_visits.append(ratios[k])
-                    else:
-                        legal_set = set(legal_k)
-                        gh.child_visits.append([int(vis[k][a]) / total if a in legal_set else 0 for a in cfg.action_space])
-                    gh.root_values.append(float(result.root_values[k]) if total else 0)
-                else:
-                    gh.store_search_statistics(root, cfg.action_space)
+                gh.store_search_statistics(root, cfg.action_space)
                 gh.action_history.append(action)
                 gh.observation_history.append(observation)
                 gh.reward_history.append(reward)
                 gh.to_play_history.append(game.to_play())
-                observations[s] = observation
-                if not done and len(gh.action_history) <= cfg.max_moves:
-                    still.append(s)
+                if done or len(gh.action_history) > cfg.max_moves:
+                    over.add(s)
+            still = [s for s in active if s not in over]
             if store is not None and still:
-                moved = numpy.zeros(len(self.games), numpy.int32)
+                moved = numpy.zeros(G, numpy.int32)
                 for s in active:
-                    frame[s] = numpy.asarray(observations[s])
+                    frame[s] = numpy.asarray(histories[s].observation_history[-1])
                     moved[s] = histories[s].action_history[-1]
                 store.push(frame, moved)
             active = still
@@ -716,15 +553,13 @@ class SelfPlay:
                 legal = legal[idx] if isinstance(legal, numpy.ndarray) else [legal[i] for i in idx]
             to_play = tp_hist[-1] if everyone else tp_hist[-1][idx]
             t0 = time.perf_counter()
-            t = temperature if not temperature_threshold or move + 1 < temperature_threshold else 0
+            t = move_temperature(temperature, move + 1, temperature_threshold)
             if self.device_draws:       # one fused move: streams are the shard slots, one counter per move
                 result = self.engine.run(stacked, legal, to_play, True, None, streams=idx, counter=self._draw_counter, temperature=t)
                 self._draw_counter += 1
             else:
                 result = self.engine.run(stacked, legal, to_play, True, (self.bank, idx))
-            self.stats["search_seconds"] += time.perf_counter() - t0
-            self.stats["searches"] += len(idx)
-            self.stats["simulations"] += len(idx) * self.engine.num_simulations
+            self._count_search(len(idx), self.engine, time.perf_counter() - t0)
             chosen = result.actions if self.device_draws else self._select_actions_bank(result, idx, t)
             if everyone:
                 actions = numpy.asarray(chosen, numpy.int64)
@@ -737,17 +572,7 @@ class SelfPlay:
                 values = numpy.zeros(B, numpy.float64)
                 values[idx] = result.root_values
             obs, reward, done = g.step(actions, alive if everyone else alive.copy())
-            if isinstance(legal, numpy.ndarray) and (legal >= 0).all():
-                mask = None                                  # every action legal for every searched game
-            else:
-                mask = numpy.zeros((B, A), bool)
-                if isinstance(legal, numpy.ndarray):
-                    rows = numpy.repeat(idx, (legal >= 0).sum(1))
-                    mask[rows, legal[legal >= 0]] = True
-                else:
-                    for r, acts in zip(idx, legal):
-                        mask[r, acts] = True
-            visits_hist.append(visits); value_hist.append(values); legal_hist.append(mask)
+            visits_hist.append(visits); value_hist.append(values); legal_hist.append(legal_mask_row(legal, idx, B, A))
             obs_hist.append(numpy.asarray(obs)); act_hist.append(actions)
             if store is not None:
                 store.push(obs_hist[-1], actions)
@@ -761,25 +586,15 @@ class SelfPlay:
                 alive = alive & ~done
                 n_alive = int(alive.sum())
             move += 1
-        # ---- per-game records (self_play.py:479-511): transpose once to game-major, slice per game
-        n_moves = len(visits_hist)
+        # ---- per-game records: transpose once to game-major, a view per game
         by_game = lambda seq: numpy.ascontiguousarray(numpy.swapaxes(numpy.stack(seq), 0, 1))
-        acts, rews, tps, obs_all = by_game(act_hist), by_game(rew_hist), by_game(tp_hist), by_game(obs_hist)
-        record = _ShardRecord(A, obs_all, acts, rews, tps)
-        if n_moves:
-            vis = by_game(visits_hist)                    # [B][n_moves][A]
-            vals = by_game(value_hist)
-            totals = vis.sum(2)
-            # visit_count / total: true division of small integers == Python's int / int
-            ratios = vis / numpy.maximum(totals, 1)[:, :, None]
-            played = numpy.arange(n_moves)[None, :] < length[:, None]
-            plain = (totals > 0) | ~played
-            legal_mask = None
+        vis = vals = legal_mask = None
+        if visits_hist:
+            vis, vals = by_game(visits_hist), by_game(value_hist)              # [B][n_moves][A], [B][n_moves]
             if any(m is not None for m in legal_hist):
                 legal_mask = by_game([numpy.ones((B, A), bool) if m is None else m for m in legal_hist])
-                plain &= legal_mask.all(2)
-            record = _ShardRecord(A, obs_all, acts, rews, tps, vis, vals, totals, ratios, plain.all(1), legal_mask)
-        return [ShardGameHistory(record, i, n) for i, n in enumerate(length.tolist())]
+        return shard_views(A, by_game(obs_hist), by_game(act_hist), by_game(rew_hist), by_game(tp_hist), vis, vals, legal_mask,
+                           length.tolist())
 
     # ------------------------------------------------------------------ continuous play: finished slots are refilled
     def play_rounds(self, temperature, temperature_threshold, min_games=None, max_rounds=None):
@@ -812,87 +627,106 @@ class SelfPlay:
         self._no_device_draws("the per-object shard")
         return self._rounds_shard(temperature, temperature_threshold, min_games, max_rounds)
 
-    def _slot_groups(self, G):
+    def _slot_spans(self, G, batched):
         """
-        The slots of a shard of B ``Game`` objects as ONE group, or as TWO that take turns on the GPU: while the search of
-        one group runs (a worker thread inside the C call / the stream synchronisation, both of which release the GIL),
-        the host steps the other group's ``Game`` objects -- the Python work of the reference plugin surface (a third of
-        the wall for connect4 at 1024 games) hides behind the other half's search.  Slots are independent actors (own
-        ``Game``, own numpy stream) and the library searches a network on ONE arithmetic whatever the shard size (wide
-        residual networks: csrc/mzx_row_search.h wide_search_route), so which slots share a launch does not change what any of
-        them plays -- bit for bit, on the device too (tests/test_gpu_parity.py: 1024 connect4 games, two groups against one).
-        ``config.self_play_pipeline``: True / False; unset = from 1024 games on -- each half must still fill the chip: the
-        residual whole-search kernels run a workgroup per tree or pair of trees, so a search of fewer than ~512 trees takes as
-        long as one of 512 and two half searches would cost more than they hide.
+        The slots of a shard of G games as ONE group, or as several that take turns on the GPU: while the search of one
+        group runs, the host steps, draws and logs another.  Slots are independent actors (own game, own stream) and the
+        library searches a network on ONE arithmetic whatever the shard size (wide residual networks: csrc/mzx_row_search.h
+        wide_search_route), so which slots share a launch does not change what any of them plays -- bit for bit, on the
+        device too (tests/test_gpu_parity.py: 1024 connect4 games, two groups against one).
+        ``config.self_play_pipeline``: True / False; unset, the protocol's own threshold:
+          per-object games (``batched`` False): from 1024 games on.  The Python work of the reference plugin surface (a third
+            of the wall for connect4 at 1024 games) hides behind the other half's search, and each half still fills the
+            chip: the residual whole-search kernels run a workgroup per tree or pair of trees, so a search of fewer than
+            ~512 trees takes as long as one of 512 and two half searches would cost more than they hide.  Always two groups.
+          the batched protocol: when the host side of a move weighs as much as its search -- a fully connected network (one
+            whole-search launch of a fraction of a millisecond) from 2048 games on.  Residual networks are search-bound
+            (connect4 at 1024 games: 98 % of the wall is the search, and two searches of 512 trees cost 14 % more than one
+            of 1024): one group.  ``config.self_play_groups``: how many groups take turns (default two).  A round of k
+            groups lasts max(search + host work of ONE group, k x host work of a group), so a latency-bound search (C2:
+            0.2 ms for 1024 trees as for 4096) would want more, smaller groups -- measured on the natively played C2 shard
+            (profiles/r06_native_rounds.txt): four groups of 1024 on four streams 5.1 M steps/s against 10.3 M with two
+            (queueing a search took 97 us instead of 40).
         """
-        want = getattr(self.config, "self_play_pipeline", None)
+        cfg = self.config
+        want = getattr(cfg, "self_play_pipeline", None)
         if want is None:
-            want = G >= 1024
+            want = (cfg.network == "fullyconnected" and G >= 2048) if batched else G >= 1024
         if not want or G < 2:
             return [(0, G)]
-        half = (G + 1) // 2
-        return [(0, half), (half, G)]
+        groups = max(2, min(int(getattr(cfg, "self_play_groups", None) or 2), G)) if batched else 2
+        edges = [(G * g + groups - 1) // groups for g in range(groups + 1)]
+        return [(edges[g], edges[g + 1]) for g in range(groups) if edges[g + 1] > edges[g]]
 
     def _search_job(self, group, stacked, legal, to_play, stream):
-        """One search of a slot group (runs on the worker thread when the shard is pipelined)."""
-        device = self.model.backend.device
+        """One search of a slot group of per-object games (runs on the worker thread when the shard is pipelined, under the
+        submitting thread's device and stream: both are thread-local in torch)."""
         t0 = time.perf_counter()
-        if stream is not None:       # the submitting thread's device and stream (both are thread-local in torch)
-            torch.cuda.set_device(device)
-            with torch.cuda.stream(stream):
-                result = group["engine"].run(stacked, legal, to_play, True, (self.bank, group["slots"]))
-        else:
-            result = group["engine"].run(stacked, legal, to_play, True, (self.bank, group["slots"]))
+        if stream is not None:
+            torch.cuda.set_device(self.model.backend.device)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            result = group.engine.run(stacked, legal, to_play, True, (self.bank, group.slots))
         return result, time.perf_counter() - t0
 
+    def _run_rounds(self, groups, begin, consume, may_queue_ahead, min_games, max_rounds):
+        """
+        The round loop of ``play_rounds``: a round is one move of every slot -- every group without a pending search begins
+        one, then the groups are consumed in order -- until ``min_games`` games finished or ``max_rounds`` rounds were played.
+        ``begin(group, done, rounds)`` queues the group's next search (``group.pending``; ``done`` games finished so far in
+        round ``rounds`` of this call); ``consume(group)`` completes it, plays the group's move and returns the games that
+        ended.  Several groups take turns: right after its move a group's NEXT search is begun, so that it runs while the
+        host plays the groups after it, when another round can follow and ``may_queue_ahead(k, done)`` agrees.  The protocols
+        differ in that rule alone:
+          per-object games   queue unless this is KNOWN to be the last round (``done < min_games``).  The search may then
+                             wait across the end of the call: ``begin`` keeps the streams' states when the call may end
+                             first (``_drain_searches`` gives the draws back), ``_rounds_shard`` waits for the worker.
+          batched protocol   queue only when CERTAIN to be consumed in this call: even if every game of the groups still to
+                             play ended now, the call would go on.  Nothing is in flight between calls.
+        """
+        finished, rounds = [], 0
+        while len(finished) < min_games and (max_rounds is None or rounds < max_rounds):
+            for group in groups:
+                if group.pending is None:     # (a pipelined per-object shard may hold a search from the end of the last call)
+                    begin(group, len(finished), rounds)
+            for k, group in enumerate(groups):
+                finished.extend(consume(group))
+                if (k + 1 < len(groups) and (max_rounds is None or rounds + 1 < max_rounds)
+                        and may_queue_ahead(k, len(finished))):
+                    begin(group, len(finished), rounds)
+            rounds += 1
+        return finished
+
     def _rounds_shard(self, temperature, temperature_threshold, min_games, max_rounds):
-        """``play_rounds`` through the reference plugin surface (B ``Game`` objects); bookkeeping as ``_play_shard``."""
-        cfg, games = self.config, self.games
-        A, G = len(cfg.action_space), len(self.games)
-        shape = tuple(cfg.observation_shape)
-        cfg_shape_is_tuple = cfg.observation_shape if isinstance(cfg.observation_shape, tuple) else shape
+        """``play_rounds`` through the reference plugin surface (B ``Game`` objects); bookkeeping as ``_play_shard``.  Two
+        slot groups: the search of one runs on a worker thread (inside the C call / the stream synchronisation, both of
+        which release the GIL) while this thread steps the other group's ``Game`` objects."""
+        cfg, games, G = self.config, self.games, len(self.games)
         live = self._live
-
-        def start(s, group):
-            gh = GameHistory()
-            observation = games[s].reset()
-            gh.action_history.append(0)
-            gh.observation_history.append(observation)
-            gh.reward_history.append(0)
-            gh.to_play_history.append(games[s].to_play())
-            self._check_observation(observation)
-            group["batch"][s - group["first"]] = observation
-            live["histories"][s] = gh
-            live["temps"][s] = temperature
-
         if live is None:
-            live = self._live = dict(histories=[None] * G, temps=[temperature] * G, groups=[])
-            spans = self._slot_groups(G)
+            live = self._live = dict(histories=[None] * G, groups=[])
+            spans = self._slot_spans(G, batched=False)
             for first, last in spans:
                 n = last - first
-                group = dict(first=first, slots=list(range(first, last)), batch=numpy.empty((n,) + shape, numpy.float32),
-                             moved=numpy.zeros(n, numpy.int32), store=None, pending=None,
-                             engine=self.engine if len(spans) == 1 else BatchedMCTS(cfg, self.model, n))
+                group = ObjectGroup(first, n, self.engine if len(spans) == 1 else BatchedMCTS(cfg, self.model, n),
+                                    cfg.observation_shape, temperature)
                 live["groups"].append(group)
-                for s in group["slots"]:
-                    start(s, group)
+                for s in group.slots:
+                    live["histories"][s] = self._start_game(s, group.batch, first)
                 if cfg.stacked_observations > 0:
-                    group["store"] = (self._frame_store(G) if len(spans) == 1 else
-                                      observations_mod.FrameStore(cfg, n, self.model.backend))
-                    group["store"].push(group["batch"], None)
+                    group.store = (self._frame_store(G) if len(spans) == 1 else
+                                   observations_mod.FrameStore(cfg, n, self.model.backend))
+                    group.store.push(group.batch, None)
         histories, groups = live["histories"], live["groups"]
         pipelined = len(groups) > 1
         if pipelined and getattr(self, "_search_worker", None) is None:
             import concurrent.futures
             self._search_worker = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="mzx-search")
-        max_moves = cfg.max_moves
-        finished, rounds = [], 0
 
-        def submit(group):
-            slots = group["slots"]
+        def begin(group, done, rounds):
+            slots = group.slots
             legal = [games[s].legal_actions() for s in slots]
             to_play = [games[s].to_play() for s in slots]
-            stacked = group["store"].stacked(None) if group["store"] is not None else group["batch"]
+            stacked = group.store.stacked(None) if group.store is not None else group.batch
             if pipelined:
                 device = self.model.backend.device
                 stream = torch.cuda.current_stream(device) if device.type == "cuda" else None
@@ -900,100 +734,59 @@ class SelfPlay:
                 # close_game come instead, its result is dropped -- and the root noise / tie words it drew are given back
                 # (_drain_searches), so that the slots' streams stay those of lone actors.  The states are only kept when
                 # this call can actually end before the result is consumed.
-                may_be_last = (len(finished) + sum(len(g["slots"]) for g in groups) >= min_games
-                               or (max_rounds is not None and rounds + 2 >= max_rounds))
-                group["streams_before"] = [self.bank.get_state(s) for s in slots] if may_be_last else None
-                group["pending"] = self._search_worker.submit(self._search_job, group, stacked, legal, to_play, stream)
+                may_be_last = done + G >= min_games or (max_rounds is not None and rounds + 2 >= max_rounds)
+                group.streams_before = [self.bank.get_state(s) for s in slots] if may_be_last else None
+                group.pending = self._search_worker.submit(self._search_job, group, stacked, legal, to_play, stream)
             else:
-                group["pending"] = self._search_job(group, stacked, legal, to_play, None)
+                job = self._search_job(group, stacked, legal, to_play, None)
+                group.pending = PendingSearch(lambda: job)
 
         def consume(group):
-            pending, group["pending"] = group["pending"], None
-            result, seconds = pending.result() if pipelined else pending
-            slots, first, batch, moved, store = group["slots"], group["first"], group["batch"], group["moved"], group["store"]
-            n = len(slots)
-            self.stats["search_seconds"] += seconds
-            self.stats["searches"] += n
-            self.stats["simulations"] += n * group["engine"].num_simulations
-            slot_temps = live["temps"][first:first + n]
-            if temperature_threshold:
-                temps = [slot_temps[s - first] if len(histories[s].action_history) < temperature_threshold else 0 for s in slots]
-            elif slot_temps.count(slot_temps[0]) == n:
-                temps = slot_temps[0]
-            else:
-                temps = list(slot_temps)
-            actions = self._select_actions_bank(result, slots, temps)
-            vis = result.visit_counts
-            totals = vis.sum(1)
-            rows = (vis / numpy.maximum(totals, 1)[:, None]).tolist()     # int / int true division, as Python's
-            values = result.root_values.tolist()
-            plain = bool((totals > 0).all()) and all(len(l) == A for l in result.legal_actions)
-            restarted = []
-            for k, s in enumerate(slots):
-                game, gh, action = games[s], histories[s], actions[k]
-                observation, reward, done = game.step(action)
-                if plain:
-                    gh.child_visits.append(rows[k])
-                    gh.root_values.append(values[k])
-                else:      # illegal actions get 0, an unvisited root reports value 0 (self_play.py:496-511, :446-449)
-                    total, legal_set = int(totals[k]), set(result.legal_actions[k])
-                    gh.child_visits.append([int(vis[k][a]) / total if a in legal_set else 0 for a in cfg.action_space])
-                    gh.root_values.append(values[k] if total else 0)
-                gh.action_history.append(action)
-                gh.observation_history.append(observation)
-                gh.reward_history.append(reward)
-                gh.to_play_history.append(game.to_play())
-                if getattr(observation, "shape", None) != cfg_shape_is_tuple:
-                    self._check_observation(observation)
-                batch[k] = observation
-                moved[k] = action
-                if done or len(gh.action_history) > max_moves:     # self_play.py:129: the game is over
-                    finished.append(gh)
-                    self.finished_slots.append(s)
-                    start(s, group)                                # ... and the slot's next game begins (:31-52)
-                    moved[k] = 0
-                    restarted.append(k)
+            pending, group.pending = group.pending, None
+            result, seconds = pending.result()
+            slots, first, store = group.slots, group.first, group.store
+            self._count_search(group.n, group.engine, seconds)
+            actions = self._select_actions_bank(result, slots, self._move_temps(group.temps, histories, slots, temperature_threshold))
+            group.moved[:] = actions
+            finished, restarted = [], []
+
+            def over(k, s):     # self_play.py:129: the game is over ... and the slot's next game begins (:31-52)
+                finished.append(histories[s])
+                self.finished_slots.append(s)
+                histories[s] = self._start_game(s, group.batch, first)
+                group.temps[k], group.moved[k] = temperature, 0
+                restarted.append(k)
+
+            self._log_moves(slots, histories, result, actions, result.legal_actions, group.batch, first, over)
             if store is not None:
                 store.clear_history(restarted)
-                store.push(batch, moved)
+                store.push(group.batch, group.moved)
+            return finished
 
-        while len(finished) < min_games and (max_rounds is None or rounds < max_rounds):
-            for group in groups:
-                if group["pending"] is None:     # (a pipelined shard may hold a search from the end of the last call)
-                    submit(group)
-            for k, group in enumerate(groups):
-                consume(group)
-                # pipelined: this group's NEXT search is queued now, so that it runs while the host steps the groups
-                # after it -- unless this is known to be the last round of the call
-                if (pipelined and k + 1 < len(groups) and len(finished) < min_games
-                        and (max_rounds is None or rounds + 1 < max_rounds)):
-                    submit(group)
-            rounds += 1
-        if pipelined:
-            # nothing runs on the worker between calls (the caller may load new weights): a search queued for the next
-            # round finishes here, its result waits in the group (a round is one move of EVERY slot, so the call ends on
-            # a round boundary; the slots of that group have already drawn their root noise for the next move -- in the
-            # order a lone actor draws it)
-            for group in groups:
-                if group["pending"] is not None:
-                    group["pending"].result()
+        finished = self._run_rounds(groups, begin, consume, lambda k, done: done < min_games, min_games, max_rounds)
+        # nothing runs on the worker between calls (the caller may load new weights): a search queued for the next round
+        # finishes here, its result waits in the group (a round is one move of EVERY slot, so the call ends on a round
+        # boundary; the slots of that group have already drawn their root noise for the next move -- in the order a lone
+        # actor draws it)
+        for group in groups:
+            if group.pending is not None:
+                group.pending.result()
         return finished
 
     def _rounds_batched(self, temperature, temperature_threshold, min_games, max_rounds):
         """
         ``play_rounds`` behind the batched plugin protocol: per round and slot group ONE game call, ONE library call for
         the host side of the search (``mzx_selfplay_search``: draws, staging, upload, launch, download), ONE for the
-        streams' advance and the action draw (``mzx_selfplay_select``).  A move is logged as one column of a handful
-        of game-major arrays (``_BatchedGroup``); a finished game is a gather of its slot's columns, handed out as a
+        streams' advance and the action draw (``mzx_selfplay_select``).  A move is logged as one row of a handful
+        of ring arrays (``shard_play.BatchedGroup``); a finished game is a copy of its slot's rows, handed out as a
         ``ShardGameHistory`` view (games that started and ended together share one record).
 
-        Slot groups (``_batched_spans``): a large shard of a cheaply searched network runs as two groups with their own
+        Slot groups (``_slot_spans``): a large shard of a cheaply searched network runs as two groups with their own
         game object, engine and staging that take turns on the GPU -- the search of one group is queued, the host
         draws / steps / logs the other group, then waits for the first (an event behind the asynchronous library call;
         no worker thread).  Slots are independent actors with their own stream: which of them share a launch changes
         nothing any of them plays (tests/test_selfplay_refill.py, tests/test_selfplay_move.py); games finish in the
-        order (round, slot) either way.  A search is only queued ahead when the call cannot end before it is consumed,
-        so nothing is in flight between calls (weights may change there).
+        order (round, slot) either way.
         """
         cfg, B = self.config, self.num_games
         if native_rounds.usable(self):
@@ -1002,59 +795,42 @@ class SelfPlay:
             finished, slots = self._native_shard(temperature).play(temperature, temperature_threshold, min_games, max_rounds)
             self.finished_slots += slots
             return finished
-        live = self._live
-        if live is None:
-            spans = self._batched_spans(B)
+        if self._live is None:
+            spans = self._slot_spans(B, batched=True)
             groups = []
             for first, last in spans:
                 game = self.batched_game if len(spans) == 1 else type(self.batched_game)(self._game_seeds[first:last])
                 engine = self.engine if len(spans) == 1 else BatchedMCTS(cfg, self.model, last - first)
                 engine.draw_seed = self.draw_seed
                 groups.append(_BatchedGroup(self, game, first, last - first, engine, temperature))
-            live = self._live = dict(groups=groups)
-        groups = live["groups"]
-        pipelined = len(groups) > 1
-        finished, rounds = [], 0
+            self._live = dict(groups=groups)
+        groups = self._live["groups"]
 
-        def begin(group):
+        def begin(group, done, rounds):
             t0 = time.perf_counter()
-            legal = group["game"].legal_actions()
-            stacked = group["store"].stacked(None) if group["store"] is not None else group["obs"]
-            group["legal"] = legal
+            legal = group.legal = group.game.legal_actions()
+            stacked = group.store.stacked(None) if group.store is not None else group.obs
             if self.device_draws:     # the group's search number is its counter, its slots are the streams
-                group["pending"] = group["engine"].run(stacked, legal, group["tp"], True, None, streams=group["streams"],
-                                                       counter=group["counter"], _asynchronous=True,
-                                                       temperature=group.move_temps(temperature_threshold))
-                group["counter"] += 1
+                group.pending = group.engine.run(stacked, legal, group.tp, True, None, streams=group.streams,
+                                                 counter=group.counter, _asynchronous=True,
+                                                 temperature=group.move_temps(temperature_threshold))
+                group.counter += 1
             else:
-                group["pending"] = group["engine"].run(stacked, legal, group["tp"], True, (self.bank, group["streams"]),
-                                                       _defer_advance=True, _asynchronous=True)
-            self.stats["search_seconds"] += time.perf_counter() - t0
+                group.pending = group.engine.run(stacked, legal, group.tp, True, (self.bank, group.streams),
+                                                 _defer_advance=True, _asynchronous=True)
+            self._count_search(0, group.engine, time.perf_counter() - t0)
 
         def consume(group):
             t0 = time.perf_counter()
-            pending, group["pending"] = group["pending"], None
+            pending, group.pending = group.pending, None
             result = pending.result()
-            self.stats["search_seconds"] += time.perf_counter() - t0
-            n = group["n"]
-            self.stats["searches"] += n
-            self.stats["simulations"] += n * group["engine"].num_simulations
-            done_games, slots = group.play(self, result, temperature, temperature_threshold)
-            finished.extend(done_games)
+            self._count_search(group.n, group.engine, time.perf_counter() - t0)
+            finished, slots = group.play(self, result, temperature, temperature_threshold)
             self.finished_slots += slots
+            return finished
 
-        while len(finished) < min_games and (max_rounds is None or rounds < max_rounds):
-            for group in groups:
-                if group["pending"] is None:
-                    begin(group)
-            for k, group in enumerate(groups):
-                consume(group)
-                later = sum(g["n"] for g in groups[k + 1:])
-                if (pipelined and k + 1 < len(groups) and len(finished) + later < min_games
-                        and (max_rounds is None or rounds + 1 < max_rounds)):
-                    begin(group)      # certain to be consumed by this call: runs while the host plays the groups after it
-            rounds += 1
-        return finished
+        return self._run_rounds(groups, begin, consume,
+                                lambda k, done: done + sum(g.n for g in groups[k + 1:]) < min_games, min_games, max_rounds)
 
     def _native_shard(self, temperature):
         """The actors of a natively played shard (created with the first round; ``temperature``: of the games that start then)."""
@@ -1062,46 +838,6 @@ class SelfPlay:
             shard = native_rounds.NativeShard(self, temperature)
             self._live = dict(groups=shard.groups, native=shard)
         return self._live["native"]
-
-    def _batched_spans(self, B):
-        """
-        Slot groups of a shard behind the batched protocol.  ``config.self_play_pipeline`` True / False; unset: two groups
-        when the host side of a move weighs as much as its search -- a fully connected network (one whole-search launch
-        of a fraction of a millisecond) from 2048 games on.  Residual networks are search-bound (connect4 at 1024 games:
-        98 % of the wall is the search, and two searches of 512 trees cost 14 % more than one of 1024): one group.
-        """
-        want = getattr(self.config, "self_play_pipeline", None)
-        if want is None:
-            want = self.config.network == "fullyconnected" and B >= 2048
-        if not want or B < 2 or not hasattr(self, "_game_seeds"):
-            return [(0, B)]
-        # ``config.self_play_groups``: how many groups take turns (default two).  A round of k groups lasts max(search + host
-        # work of ONE group, k x host work of a group), so a latency-bound search (C2: 0.2 ms for 1024 trees as for 4096)
-        # would want more, smaller groups -- measured on the natively played C2 shard (profiles/r06_native_rounds.txt): four
-        # groups of 1024 on four streams 5.1 M steps/s against 10.3 M with two (queueing a search took 97 us instead of 40)
-        groups = max(2, min(int(getattr(self.config, "self_play_groups", None) or 2), B))
-        edges = [(B * g + groups - 1) // groups for g in range(groups + 1)]
-        return [(edges[g], edges[g + 1]) for g in range(groups) if edges[g + 1] > edges[g]]
-
-    @staticmethod
-    def _stacked_batch(obs_hist, act_hist, k, A):
-        """GameHistory.get_stacked_observations(-1, k, A) (self_play.py:513-550) for every game of the shard."""
-        current = obs_hist[-1]
-        if k == 0:
-            return current
-        index = len(obs_hist) - 1
-        B = current.shape[0]
-        plane_shape = (B, 1) + current.shape[2:]
-        pieces = [current]
-        for past in range(index - 1, index - 1 - k, -1):
-            if past >= 0:
-                pieces.append(obs_hist[past])
-                a = act_hist[past + 1].reshape((B,) + (1,) * (current.ndim - 1))
-                pieces.append(numpy.ones(plane_shape, current.dtype) * a / A)
-            else:
-                pieces.append(numpy.zeros_like(current))
-                pieces.append(numpy.zeros(plane_shape, current.dtype))
-        return numpy.concatenate(pieces, axis=1)
 
     def _frame_store(self, num_games):
         """The shard's device frame store: allocated once per actor, rewound for every game."""
@@ -1119,34 +855,27 @@ class SelfPlay:
         of the worker thread surfaces here instead of disappearing.
         """
         for group in (self._live or {}).get("groups", ()):
-            pending = group.get("pending")
-            if pending is None or not hasattr(pending, "result"):
+            pending, group.pending = group.pending, None
+            if pending is None:
                 continue
-            group["pending"] = None
-            if self.device_draws and "counter" in group:
-                group["counter"] -= 1        # (the dropped search's draws are a function of this counter: taken again)
+            if self.device_draws:
+                group.counter -= 1        # (the dropped search's draws are a function of this counter: taken again)
             try:
                 pending.result()
             except Exception as e:       # (the search is being discarded anyway; the failure is not)
                 warnings.warn(f"a queued self-play search failed on the worker thread: {e!r}")
-            before = group.get("streams_before")
+            before, group.streams_before = group.streams_before, None
             if before is not None and self.bank is not None:
-                for s, state in zip(group["slots"], before):
+                for s, state in zip(group.slots, before):
                     self.bank.set_state(s, state)
-            group["streams_before"] = None
 
     def close_game(self):
-        self._drain_searches()
-        if self._live and self._live.get("native") is not None:
-            self._live["native"].close()
+        self._end_live(forget=False)
         worker = getattr(self, "_search_worker", None)
         if worker is not None:
             worker.shutdown(wait=True)
             self._search_worker = None
         if self.batched_game is not None:
-            for group in (self._live or {}).get("groups", ()):
-                if group.get("game") is not None and group["game"] is not self.batched_game:
-                    group["game"].close()
             self.batched_game.close()
         for g in self.games:
             g.close()

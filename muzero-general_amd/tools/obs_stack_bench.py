@@ -19,7 +19,27 @@ import numpy
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mzx import _lib, configs, observations, self_play  # noqa: E402
+from mzx import _lib, configs, observations  # noqa: E402
+
+
+def stacked_batch(obs_hist, act_hist, k, A):
+    """GameHistory.get_stacked_observations(-1, k, A) (self_play.py:513-550) for every game of a shard, on the host."""
+    current = obs_hist[-1]
+    if k == 0:
+        return current
+    index = len(obs_hist) - 1
+    B = current.shape[0]
+    plane_shape = (B, 1) + current.shape[2:]
+    pieces = [current]
+    for past in range(index - 1, index - 1 - k, -1):
+        if past >= 0:
+            pieces.append(obs_hist[past])
+            a = act_hist[past + 1].reshape((B,) + (1,) * (current.ndim - 1))
+            pieces.append(numpy.ones(plane_shape, current.dtype) * a / A)
+        else:
+            pieces.append(numpy.zeros_like(current))
+            pieces.append(numpy.zeros(plane_shape, current.dtype))
+    return numpy.concatenate(pieces, axis=1)
 
 
 def main():
@@ -68,7 +88,7 @@ def main():
     t0 = time.perf_counter()
     reps = 3
     for _ in range(reps):
-        host = self_play.SelfPlay._stacked_batch(hist, acts, k, 4)
+        host = stacked_batch(hist, acts, k, 4)
         dev = torch.as_tensor(host).to(torch.float32).to(be.device)
     torch.cuda.synchronize()
     ms_host = (time.perf_counter() - t0) * 1e3 / reps

@@ -698,7 +698,7 @@ def _selfplay_rounds(backend, zero_weights):
         if zero_weights and native:
             assert shard.stats["native_phase_seconds"][4] > 0, "the retry callback ran"
         if zero_weights and not native:
-            assert sum(g["engine"].tape_retries for g in shard._live["groups"]) > 0, "the Python loop searched trees again"
+            assert sum(g.engine.tape_retries for g in shard._live["groups"]) > 0, "the Python loop searched trees again"
         shard.close_game()
     _same_games(runs["native"], runs["python"])
     if not zero_weights:
@@ -754,7 +754,7 @@ def check_actor_seed(backend):
         shard = _shard(backend, games.NATIVE["tictactoe"], cfg, weights, B, seed, native, True)
         assert shard.draw_seed == seed
         out = _play(shard, calls)
-        assert all(g["engine"].draw_seed == seed for g in shard._live["groups"])
+        assert all(g.engine.draw_seed == seed for g in shard._live["groups"])
         shard.close_game()
         return out
 

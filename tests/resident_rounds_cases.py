@@ -52,7 +52,7 @@ def positions(shard):
     """What every group's game object says between calls: legal rows, side to move, observation."""
     out = []
     for g in shard._live["groups"]:
-        game = g["game"]
+        game = g.game
         out.append((game.legal_actions(), numpy.asarray(game.to_play()), game._observation()))
     return out
 

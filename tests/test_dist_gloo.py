@@ -131,7 +131,7 @@ def _actor_worker(rank, world, port, out_dir, pipeline=False):
     cfg.ratio = None
     cfg.self_play_delay = 0
     cfg.PER, cfg.PER_alpha, cfg.td_steps = True, 0.5, 9      # games/tictactoe.py:87-96
-    cfg.self_play_pipeline = bool(pipeline)   # True: two slot groups take turns, searches on a worker thread (SelfPlay._slot_groups)
+    cfg.self_play_pipeline = bool(pipeline)   # True: two slot groups take turns, searches on a worker thread (SelfPlay._slot_spans)
     G = 3
     template = models.MuZeroNetwork(cfg, _backend=be).state_dict()
     wa, wb = synthetic.fill_state_dict(template, 1), synthetic.fill_state_dict(template, 2)
@@ -367,7 +367,7 @@ def _world4_worker(rank, world, port, out_dir):
 
     def recording_refresh(model, *a, **kw):
         live = actor._live or {}
-        queued_at_refresh.append(any(g.get("pending") is not None for g in live.get("groups", ())))
+        queued_at_refresh.append(any(g.pending is not None for g in live.get("groups", ())))
         before = model.flat_weights().clone()
         out = refresh(model, *a, **kw)
         if not torch.equal(before, model.flat_weights()):

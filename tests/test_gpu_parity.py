@@ -191,8 +191,8 @@ def test_pipelined_shard_of_1024_connect4_games_plays_what_one_group_plays(backe
         by_slot = {}
         for gh, slot in zip(shard.play_rounds(1.0, None, min_games=1 << 60, max_rounds=14), shard.finished_slots):
             by_slot.setdefault(slot, []).append(gh)
-        groups = [g["engine"] for g in shard._live["groups"]]
-        kernels = sorted({e.kernel_name(len(g["slots"])) for e, g in zip(groups, shard._live["groups"])})
+        groups = [g.engine for g in shard._live["groups"]]
+        kernels = sorted({e.kernel_name(len(g.slots)) for e, g in zip(groups, shard._live["groups"])})
         shard.close_game()
         return by_slot, kernels
 

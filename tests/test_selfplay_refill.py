@@ -81,11 +81,11 @@ def test_slot_games_equal_a_lone_actor_s_sequence(backend, name, protocol):
             lengths.add(len(want[k].action_history))
     assert len(lengths) > 1, "games should end at different moves for this test to mean anything"
     if protocol.endswith("pipelined"):
-        assert len(shard._live["groups"]) == 2 and [len(g["slots"]) for g in shard._live["groups"]] == [3, 2]
+        assert len(shard._live["groups"]) == 2 and [len(g.slots) for g in shard._live["groups"]] == [3, 2]
     if protocol == "per-object-pipelined":
-        assert all(g["pending"] is None or g["pending"].done() for g in shard._live["groups"])   # nothing runs between calls
+        assert all(g.pending is None or g.pending.done() for g in shard._live["groups"])   # nothing runs between calls
     if protocol == "batched-pipelined":      # the batched protocol never leaves a search queued across calls
-        assert all(g["pending"] is None for g in shard._live["groups"])
+        assert all(g.pending is None for g in shard._live["groups"])
     if protocol == "batched":
         assert len(shard._live["groups"]) == 1
     shard.close_game()
@@ -197,7 +197,7 @@ def test_dropped_queued_search_gives_its_draws_back(backend):
         # (fixed-length games: all eight end in one round; the first group's four leave the call short of five games, so its
         # next search is queued before the second group's four end the call)
         shard.play_rounds(1.0, None, min_games=5)
-        queued = any(g.get("pending") is not None for g in shard._live["groups"])
+        queued = any(g.pending is not None for g in shard._live["groups"])
         shard._drain_searches()
         states = [shard.bank.get_state(s) for s in range(8)]
         shard.close_game()
@@ -236,3 +236,101 @@ def test_reward_dtype_change_across_a_ring_growth_keeps_earlier_rows(backend):
         assert len(rewards) == 41 and rewards[0] == 0.0
         assert all(x in (0.25, 0.75) for x in rewards[1:11]), rewards[:12]
         assert all(x in (0.0, 1.0) for x in rewards[11:])
+
+
+@pytest.mark.parametrize("pipeline", [False, True])
+def test_per_object_rounds_record_legal_actions_for_reanalyse_search(backend, pipeline):
+    """config.reanalyse_search: per-object play_rounds records GameHistory.legal_actions as play_games does -- one list of
+    ints per searched position, the lone actor's lists -- so a store built with legal_masks=True gets the positions' real
+    mask rows and not the all-ones rows of a history without the attribute."""
+    from mzx import replay
+
+    cfg = configs.tictactoe(num_simulations=4, td_steps=4, num_unroll_steps=3, PER=False)      # (the store reads these)
+    cfg.reanalyse_search = True
+    cfg.self_play_pipeline = pipeline
+    Game = games.TicTacToe
+    weights = synthetic.fill_state_dict(models.MuZeroNetwork(cfg, _backend=backend).state_dict(), 21)
+    B, seed = 3, 40
+    shard = self_play.SelfPlay({"weights": weights}, Game, cfg, seed, num_games=B, _backend=backend)
+    by_slot = {s: [] for s in range(B)}
+    finished = 0
+    while finished < 4:
+        out = shard.play_rounds(1.0, None, min_games=1)
+        finished += len(out)
+        for gh, slot in zip(out, shard.finished_slots):
+            by_slot[slot].append(gh)
+    assert len(shard._live["groups"]) == (2 if pipeline else 1)
+    shard.close_game()
+    store = replay.DeviceGameStore(cfg, backend, 64, legal_masks=True)
+    for s in range(B):
+        want = _lone_actor_games(weights, Game, cfg, seed + s, 1.0, len(by_slot[s]), backend)
+        for got, lone in zip(by_slot[s], want):
+            assert getattr(got, "legal_actions", None) is not None, s
+            assert len(got.legal_actions) == len(got.root_values)
+            assert all(type(a) is int for acts in got.legal_actions for a in acts)
+            assert got.legal_actions == lone.legal_actions, s
+            rows = store._mask_rows(got, len(got.root_values)).view(numpy.uint32)
+            assert not (rows[:-1] == 0xFFFFFFFF).all()
+
+
+class _FirstMoveExpert(games.TicTacToe):
+    """Tic-tac-toe with a deterministic expert (the plugin surface's ``expert_agent``): the first legal action."""
+
+    def expert_agent(self):
+        return self.legal_actions()[0]
+
+
+def _same_with_opponent(got, want, where):
+    """``_same`` for games with opponent moves: the opponent's positions log no root value (None)."""
+    assert [v is None for v in got.root_values] == [v is None for v in want.root_values], where
+    assert any(v is None for v in want.root_values) and any(v is not None for v in want.root_values), where
+    for gh in (got, want):
+        gh.root_values = [float("nan") if v is None else v for v in gh.root_values]
+    _same(got, want, where)
+
+
+@pytest.mark.parametrize("stacked", [0, 2])
+def test_shard_against_an_opponent_equals_lone_actors(backend, stacked):
+    """play_games of a shard of per-object games against an opponent (``SelfPlay._play`` with the stream bank, no
+    rendering): the searched moves are logged in bulk, the opponent's one by one; stacked observations are assembled
+    on the host (the frame store serves self-play only).  Game i equals the game of a lone actor seeded ``seed + i``."""
+    cfg = configs.tictactoe(num_simulations=6, stacked_observations=stacked)
+    weights = synthetic.fill_state_dict(models.MuZeroNetwork(cfg, _backend=backend).state_dict(), 17)
+    B, seed = 3, 90
+    shard = self_play.SelfPlay({"weights": weights}, _FirstMoveExpert, cfg, seed, num_games=B, _backend=backend)
+    out = shard.play_games(1.0, 2, False, "expert", 0)
+    assert len(out) == B
+    for i in range(B):
+        lone = self_play.SelfPlay({"weights": weights}, _FirstMoveExpert, cfg, seed + i, num_games=1, _backend=backend)
+        _same_with_opponent(out[i], lone.play_game(1.0, 2, False, "expert", 0), (stacked, i))
+
+
+def test_play_game_on_a_shard_plays_slot_0(backend):
+    """play_game of an actor with num_games = 3: slot 0 alone, on its bank stream -- game 0 of play_games."""
+    cfg = configs.tictactoe(num_simulations=6)
+    weights = synthetic.fill_state_dict(models.MuZeroNetwork(cfg, _backend=backend).state_dict(), 17)
+    make = lambda: self_play.SelfPlay({"weights": weights}, games.TicTacToe, cfg, 33, num_games=3, _backend=backend)
+    got = make().play_game(1.0, 3, False, "self", 0)
+    want = make().play_games(1.0, 3, False, "self", 0)[0]
+    _same(got, want, "slot 0")
+
+
+def test_slot_groups_still_answer_the_dict_spelling(backend):
+    """Slot groups were dicts before they became objects: ``g["slots"]`` and ``g.get("pending")`` still read the attribute
+    of that name, on every group type (per-object, batched, native), and an unknown key behaves as a dict's does."""
+    cfg = configs.tictactoe(num_simulations=4)
+    cfg.self_play_pipeline = True
+    weights = synthetic.fill_state_dict(models.MuZeroNetwork(cfg, _backend=backend).state_dict(), 2)
+    games.NativeBatchedGame.backend = backend
+    for Game in (games.TicTacToe, games.TicTacToeBatched, games.TicTacToeNative):
+        shard = self_play.SelfPlay({"weights": weights}, Game, cfg, 5, num_games=4, _backend=backend)
+        shard.play_rounds(1.0, None, max_rounds=1, min_games=1 << 60)
+        groups = shard._live["groups"]
+        assert len(groups) == 2
+        for g in groups:
+            for key in ("first", "n", "slots", "engine", "game", "store", "pending"):
+                assert g[key] is getattr(g, key) and g.get(key) is getattr(g, key)
+            assert g.get("no such field") is None and g.get("no such field", 3) == 3
+            with pytest.raises(KeyError):
+                g["no such field"]
+        shard.close_game()
