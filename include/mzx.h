@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 5
+#define MZX_ABI_VERSION 6
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -789,6 +789,47 @@ int mzx_replay_ingest(const mzx_replay_pool* pool, const mzx_replay_sampler* sam
                       int64_t mask_rows, const mzx_replay_ingest_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Export of resident games (DeviceGameStore.download_games; csrc/mzx_replay.h): the inverse of the ingest, for reading
+ * games back.  num_games games (d_base[g], d_len[g] = T) of the pool are packed on the device, game-major and ragged, in
+ * the ingest's staged layout; the caller downloads the packed arrays, one copy per column whatever the number of games.
+ * Stateless; every pointer is a device pointer; nothing of the pool is written.
+ * Game g's packed rows start at d_dst1[g] in the arrays of T + 1 entries per game and at d_dst0[g] in those of T entries:
+ * the exclusive prefixes of len + 1 and of len, computed by the CALLER; total_rows = sum(len + 1).  Packed arrays:
+ *   d_observations [total_rows][channels * height * width] f32 (the frames), d_actions [total_rows] i64 and d_to_play
+ *   [total_rows] i64 (the pool's i32 widened), d_rewards [total_rows] f64; d_child_visits [sum T][A] f64 -- the pool's
+ *   quotients as they lie, NOT visit counts --, d_root_values [sum T] f64 (the pool's column: 0.0 for an unvisited root,
+ *   the reanalysed value after a sweep).
+ *   Optional: d_legal_mask [sum T][A] u8, 1 where bit a of the row of d_pool_legal_mask (u32 [mask_rows][ceil(A / 32)],
+ *   mask_rows must equal pool->rows) is set; d_priorities [sum T] f32, the rows of sampler->d_priorities (only that column
+ *   and sampler->rows, which must equal pool->rows, are read).  The padding row base + T contributes to the arrays of T + 1
+ *   entries only.
+ * One launch on the caller's stream, a wavefront per packed row.  num_games == 0 succeeds and launches nothing.
+ * MZX_ERR_INVALID, before anything is launched: a NULL required pointer, num_games < 0 or total_rows < num_games,
+ *   d_legal_mask without d_pool_legal_mask or with mask_rows other than pool->rows, d_priorities without a sampler column
+ *   of pool->rows rows.
+ * A game whose rows would leave the pool (base < 0, T < 0 or base + T >= rows) is passed over: its packed rows keep what
+ *   they held.  That d_dst1 / d_dst0 are the prefixes of d_len is the caller's contract, as d_src1 / d_src0 of the ingest.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_replay_export_io {
+  const int64_t* d_base;           /* [num_games] pool row of the game */
+  const int32_t* d_len;            /* [num_games] T */
+  const int64_t* d_dst1;           /* [num_games] exclusive prefix of len + 1 */
+  const int64_t* d_dst0;           /* [num_games] exclusive prefix of len */
+  float* d_observations;
+  int64_t* d_actions;
+  double* d_rewards;
+  int64_t* d_to_play;
+  double* d_child_visits;
+  double* d_root_values;
+  uint8_t* d_legal_mask;           /* nullable */
+  float* d_priorities;             /* nullable */
+  int64_t total_rows;              /* sum(len + 1) */
+  int32_t num_games, reserved;
+} mzx_replay_export_io;
+int mzx_replay_export(const mzx_replay_pool* pool, const mzx_replay_sampler* sampler, const uint32_t* d_pool_legal_mask,
+                      int64_t mask_rows, const mzx_replay_export_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The loss head of the trainer (mzx.trainer; csrc/mzx_trainer.h): what Trainer.update_weights computes between the
  * network's logits and loss.backward() (trainer.py:161-258).  Stateless; every pointer is a device pointer, fp32.
  * mzx_scalar_to_support = models.scalar_to_support (models.py:669-689) of `rows` scalars -> d_out [rows][2 * support_size
@@ -1009,13 +1050,48 @@ int mzx_actor_set_draw_counter(mzx_actor* actor, uint64_t counter);
  * per slot and the chunk's finished list) is refused above `max_log_bytes` with a message that states its size.
  * phase_seconds of a resident call: 0 queueing, 1 waiting, 2 unused (0), 3 harvest, 4 repairs, 5 the rest.
  * mzx_actor_resident_stats: out[0] rounds committed, 1 chunks, 2 repair rounds, 3 host synchronisations (stream waits),
- * 4 bytes downloaded, 5 bytes of device log, 6 games harvested, 7 reserved. */
+ * 4 bytes the rounds calls downloaded, 5 bytes of device log, 6 games harvested, 7 bytes kept on the device in pieces (the
+ * device hand-off below; 0 without it). */
 int mzx_actor_set_resident(mzx_actor* actor, int32_t chunk_rounds, int64_t max_log_bytes);
 int mzx_actor_resident_stats(const mzx_actor* actor, int64_t out[8]);
 int mzx_actor_finished(mzx_actor* a, int64_t before_sequence, int64_t out[3]);
 int mzx_actor_take(mzx_actor* a, int64_t before_sequence, int32_t* slot, int32_t* length, int64_t* sequence, float* observations, int64_t* actions,
                    double* rewards, int64_t* to_play, int32_t* visit_counts, double* root_values, uint8_t* legal_mask,
                    int32_t* any_illegal);
+
+/* The DEVICE HAND-OFF of a resident group (csrc/mzx_resident.h; opt-in, mzx_actor_set_device_handoff(actor, 1)): the
+ * finished games of a chunk are packed on the device and STAY there -- the rounds call downloads nothing of them (out[4] of
+ * mzx_actor_resident_stats counts the control blocks and game states only) -- so that mzx_replay_ingest can read them
+ * where they lie.  Refused (MZX_ERR_INVALID) for a group that is not resident or that has finished games pending.
+ * Harvest: one pack launch per chunk and group, a wavefront per packed row, into a PIECE: a device buffer the actor owns,
+ *   holding the packed arrays in the staged layout of mzx_replay_ingest_io -- observations f32 [sum(len + 1)][E], actions /
+ *   to_play i64 and rewards f64 [sum(len + 1)], visit counts i32 [sum len][A], root values f64 [sum len], and for a game
+ *   whose legal sets vary the legal mask u8 [sum len][A] -- and the columns len i32, src1 / src0 i64 [games] (the
+ *   ingest's d_len / d_src1 / d_src0).  Every pack launch has completed when mzx_selfplay_rounds returns.  Sequence
+ *   numbers, halts and repairs are those of the default path; the piece's slot / length / sequence stay on the host.
+ *   Piece buffers are recycled: a steady-state chunk allocates nothing.  The device log plus the piece buffers the actor
+ *   holds are refused above the group's max_log_bytes, with a message that states the sizes.
+ * mzx_actor_finished_device: out[0] pieces, out[1] games queued with sequence numbers below before_sequence (-1: all).
+ *   A piece belongs to one chunk of one call, so it lies wholly on one side of a call's boundary.
+ * mzx_actor_take_device: hands out those pieces, oldest first, while they fit max_pieces / max_games: per piece a row of
+ *   MZX_PIECE_INFO_WORDS i64 in piece_info -- token, games, sum len, 1 if a legal mask is present, then the DEVICE addresses
+ *   of len, src1, src0, observations, actions, rewards, to_play, visit counts, root values, legal mask (0: none), the
+ *   buffer's bytes, 0 -- and per game slot / length / sequence (host arrays, pieces concatenated).  out[0] pieces, out[1]
+ *   games handed out.  mzx_actor_finished / mzx_actor_take on such a group return MZX_ERR_INVALID.
+ * mzx_actor_download_device: the packed arrays of a taken, unreleased piece into host arrays (NULL: that array is skipped),
+ *   one copy per array on `stream`, waited for.  For consumers that need a game on the host after all.
+ * mzx_actor_release_device: the piece's buffer may be reused once the work queued on `stream` so far has finished -- the
+ *   library records an event there; the host does not wait.  A harvest that finds the event still pending takes another
+ *   buffer.  The token is dead afterwards.
+ * mzx_actor_destroy waits for the device before it frees the piece buffers, taken ones included. */
+#define MZX_PIECE_INFO_WORDS 16
+int mzx_actor_set_device_handoff(mzx_actor* actor, int32_t on);
+int mzx_actor_finished_device(mzx_actor* actor, int64_t before_sequence, int64_t out[2]);
+int mzx_actor_take_device(mzx_actor* actor, int64_t before_sequence, int32_t max_pieces, int64_t max_games, int64_t* piece_info,
+                          int32_t* slot, int32_t* length, int64_t* sequence, int64_t out[2]);
+int mzx_actor_download_device(mzx_actor* actor, int64_t token, float* observations, int64_t* actions, double* rewards,
+                              int64_t* to_play, int32_t* visit_counts, double* root_values, uint8_t* legal_mask, void* stream);
+int mzx_actor_release_device(mzx_actor* actor, int64_t token, void* stream);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,8 @@ inline int stream_sync(stream_t) { return 0; }
 inline int event_record(void** ev, stream_t) { *ev = (void*)1; return 0; }
 inline int event_wait(void*) { return 0; }
 inline void event_destroy(void*) {}
+inline bool event_done(void*) { return true; }
+inline void device_sync() {}
 inline int stream_create(void** out) { *out = nullptr; return 0; }
 inline void stream_destroy(void*) {}
 inline int stream_wait_event(stream_t, void*) { return 0; }
@@ -146,6 +148,13 @@ inline int event_record(void** ev, stream_t stream) {
 }
 inline int event_wait(void* ev) { return ev ? (int)hipEventSynchronize((hipEvent_t)ev) : 0; }
 inline void event_destroy(void* ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }
+// whether the work an event was recorded behind has finished: a query, never a wait (an error counts as not finished)
+inline bool event_done(void* ev) {
+  if (!ev || hipEventQuery((hipEvent_t)ev) == hipSuccess) return true;
+  (void)hipGetLastError();      // ("not ready" must not surface as the next launch's error)
+  return false;
+}
+inline void device_sync() { (void)hipDeviceSynchronize(); }
 // a library-owned stream (the second slot group of a natively played shard searches on its own: two searches of half a shard
 // each fill half the chip -- they run side by side instead of one after the other)
 inline int stream_create(void** out) {

@@ -1439,6 +1439,56 @@ int mzx_replay_ingest(const mzx_replay_pool* pool, const mzx_replay_sampler* sam
   return MZX_OK;
 }
 
+int mzx_replay_export(const mzx_replay_pool* pool, const mzx_replay_sampler* sampler, const uint32_t* d_pool_legal_mask,
+                      int64_t mask_rows, const mzx_replay_export_io* io, void* stream) {
+  if (!pool || !io) { set_error("mzx_replay_export: null argument"); return MZX_ERR_INVALID; }
+  if (io->num_games < 0 || io->total_rows < io->num_games) {
+    set_error("mzx_replay_export: num_games %d must not be negative, total_rows %lld at least num_games", io->num_games,
+              (long long)io->total_rows);
+    return MZX_ERR_INVALID;
+  }
+  if (pool->rows < 1 || pool->action_space_size < 1 || pool->channels < 1 || pool->height < 1 || pool->width < 1) {
+    set_error("mzx_replay_export: the pool's rows, action space and observation shape must be positive");
+    return MZX_ERR_INVALID;
+  }
+  const int64_t frame_floats = (int64_t)pool->channels * pool->height * pool->width;
+  if (frame_floats >= ((int64_t)1 << 31)) { set_error("mzx_replay_export: frame too large"); return MZX_ERR_INVALID; }
+  if (io->d_legal_mask && (!d_pool_legal_mask || mask_rows != pool->rows)) {
+    set_error("mzx_replay_export: the legal mask needs the pool's mask column: it has %lld rows, the pool %lld",
+              (long long)(d_pool_legal_mask ? mask_rows : 0), (long long)pool->rows);
+    return MZX_ERR_INVALID;
+  }
+  if (io->d_priorities && (!sampler || !sampler->d_priorities || sampler->rows != pool->rows)) {
+    set_error("mzx_replay_export: the priorities need the sampler's column: it has %lld rows, the pool %lld",
+              (long long)(sampler && sampler->d_priorities ? sampler->rows : 0), (long long)pool->rows);
+    return MZX_ERR_INVALID;
+  }
+  if (io->num_games == 0) return MZX_OK;
+  if (!pool->d_frames || !pool->d_actions || !pool->d_rewards || !pool->d_to_play || !pool->d_root_values || !pool->d_child_visits) {
+    set_error("mzx_replay_export: missing pool column");
+    return MZX_ERR_INVALID;
+  }
+  if (!io->d_base || !io->d_len || !io->d_dst1 || !io->d_dst0 || !io->d_observations || !io->d_actions || !io->d_rewards ||
+      !io->d_to_play || !io->d_child_visits || !io->d_root_values) {
+    set_error("mzx_replay_export: missing packed array");
+    return MZX_ERR_INVALID;
+  }
+  ReplayExportParams p;
+  p.base = io->d_base; p.len = io->d_len; p.dst1 = io->d_dst1; p.dst0 = io->d_dst0;
+  p.pool_frames = pool->d_frames; p.pool_actions = pool->d_actions; p.pool_rewards = pool->d_rewards;
+  p.pool_to_play = pool->d_to_play; p.pool_root_values = pool->d_root_values; p.pool_child_visits = pool->d_child_visits;
+  p.pool_mask = io->d_legal_mask ? d_pool_legal_mask : nullptr;
+  p.pool_priorities = io->d_priorities ? sampler->d_priorities : nullptr;
+  p.observations = io->d_observations; p.actions = io->d_actions; p.rewards = io->d_rewards; p.to_play = io->d_to_play;
+  p.child_visits = io->d_child_visits; p.root_values = io->d_root_values; p.legal = io->d_legal_mask;
+  p.priorities = io->d_priorities;
+  p.rows = pool->rows; p.total_rows = io->total_rows; p.G = io->num_games; p.A = pool->action_space_size;
+  p.frame_floats = (int32_t)frame_floats;
+  p.vec = frame_floats % 4 == 0 && ((uintptr_t)io->d_observations % 16) == 0 && ((uintptr_t)pool->d_frames % 16) == 0;
+  MZX_TRY_LAUNCH(launch_waves<SAMPLER_WAVES>(ReplayExportRowBody{p}, (stream_t)stream));
+  return MZX_OK;
+}
+
 // ------------------------------------------------------------- the trainer's loss head (csrc/mzx_trainer.h)
 
 int mzx_scalar_to_support(const float* d_x, int32_t rows, int32_t support_size, float* d_out, void* stream) {
@@ -1796,6 +1846,7 @@ int mzx_actor_set_resident(mzx_actor* a, int32_t chunk_rounds, int64_t max_log_b
     return MZX_ERR_RUNTIME;
   }
   R->block_bytes = R->stats[5] = (int64_t)L.total;
+  R->max_log_bytes = max_log_bytes;
   d.game = R->game->v;
   resident_point(&d, (char*)R->block, L);
   d.in_obs = (float*)m.io.d_observation; d.in_legal = (int32_t*)m.io.d_legal_actions; d.in_to_play = (int32_t*)m.io.d_to_play;
@@ -1867,8 +1918,123 @@ int mzx_selfplay_rounds(mzx_actor* const* groups, int32_t num_groups, mzx_rounds
   return rc;
 }
 
+// ------------------------------------------------------------- the device hand-off of a resident group (mzx_resident.h)
+
+int mzx_actor_set_device_handoff(mzx_actor* a, int32_t on) {
+  const char* who = "mzx_actor_set_device_handoff";
+  if (!a) { set_error("%s: null actor", who); return MZX_ERR_INVALID; }
+  if (!a->resident) { set_error("%s: not a resident group (mzx_actor_set_resident first)", who); return MZX_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(a->finished_lock);
+  if (!a->finished.empty() || !a->resident->queued.empty()) {
+    set_error("%s: the group has finished games pending: take them first", who);
+    return MZX_ERR_INVALID;
+  }
+  a->resident->handoff = on != 0;
+  return MZX_OK;
+}
+
+static int handoff_group(const char* who, const mzx_actor* a) {
+  if (!a) { set_error("%s: null actor", who); return MZX_ERR_INVALID; }
+  if (!a->resident || !a->resident->handoff) { set_error("%s: not a group on the device hand-off (mzx_actor_set_device_handoff)", who); return MZX_ERR_INVALID; }
+  return MZX_OK;
+}
+
+int mzx_actor_finished_device(mzx_actor* a, int64_t before_sequence, int64_t out[2]) {
+  const int rc = handoff_group("mzx_actor_finished_device", a);
+  if (rc) return rc;
+  if (!out) { set_error("mzx_actor_finished_device: null"); return MZX_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(a->finished_lock);
+  out[0] = out[1] = 0;
+  for (const mzx_actor_piece* p : a->resident->queued) {
+    if (before_sequence >= 0 && !p->seq.empty() && p->seq[0] >= before_sequence) break;
+    out[0] += 1; out[1] += p->games;
+  }
+  return MZX_OK;
+}
+
+int mzx_actor_take_device(mzx_actor* a, int64_t before_sequence, int32_t max_pieces, int64_t max_games, int64_t* piece_info,
+                          int32_t* slot, int32_t* length, int64_t* sequence, int64_t out[2]) {
+  const int rc = handoff_group("mzx_actor_take_device", a);
+  if (rc) return rc;
+  if (max_pieces < 0 || max_games < 0 || !out || (max_pieces > 0 && !piece_info) || (max_games > 0 && (!slot || !length || !sequence))) {
+    set_error("mzx_actor_take_device: missing buffer or negative capacity");
+    return MZX_ERR_INVALID;
+  }
+  mzx_actor_resident* R = a->resident;
+  std::lock_guard<std::mutex> lk(a->finished_lock);
+  int64_t pieces = 0, games = 0;
+  while (!R->queued.empty() && pieces < max_pieces) {
+    mzx_actor_piece* p = R->queued.front();
+    if (before_sequence >= 0 && !p->seq.empty() && p->seq[0] >= before_sequence) break;
+    if (games + p->games > max_games) break;
+    const char* base = (const char*)p->buf;
+    const int64_t row[MZX_PIECE_INFO_WORDS] = {
+        p->token, p->games, p->rows0, p->mask ? 1 : 0, (int64_t)(intptr_t)(base + p->o_len), (int64_t)(intptr_t)(base + p->o_src1),
+        (int64_t)(intptr_t)(base + p->o_src0), (int64_t)(intptr_t)(base + p->o_obs), (int64_t)(intptr_t)(base + p->o_act),
+        (int64_t)(intptr_t)(base + p->o_rew), (int64_t)(intptr_t)(base + p->o_tp), (int64_t)(intptr_t)(base + p->o_vis),
+        (int64_t)(intptr_t)(base + p->o_val), p->mask ? (int64_t)(intptr_t)(base + p->o_mask) : 0, p->bytes, 0};
+    memcpy(piece_info + MZX_PIECE_INFO_WORDS * pieces, row, sizeof(row));
+    memcpy(slot + games, p->slot.data(), sizeof(int32_t) * (size_t)p->games);
+    memcpy(length + games, p->n.data(), sizeof(int32_t) * (size_t)p->games);
+    memcpy(sequence + games, p->seq.data(), sizeof(int64_t) * (size_t)p->games);
+    p->state = mzx_actor_piece::TAKEN;
+    R->queued.pop_front();
+    pieces += 1; games += p->games;
+  }
+  out[0] = pieces; out[1] = games;
+  return MZX_OK;
+}
+
+int mzx_actor_download_device(mzx_actor* a, int64_t token, float* observations, int64_t* actions, double* rewards, int64_t* to_play,
+                              int32_t* visit_counts, double* root_values, uint8_t* legal_mask, void* stream) {
+  const char* who = "mzx_actor_download_device";
+  if (!a || !a->resident) { set_error("%s: not a resident group", who); return MZX_ERR_INVALID; }
+  const mzx_actor_piece* p;
+  {
+    std::lock_guard<std::mutex> lk(a->finished_lock);
+    p = resident_piece_find(a->resident, token, mzx_actor_piece::TAKEN);
+  }
+  if (!p) { set_error("%s: no piece with token %lld is taken and unreleased", who, (long long)token); return MZX_ERR_INVALID; }
+  const size_t A = (size_t)a->A, E = (size_t)a->E, n1 = (size_t)(p->rows0 + p->games), n0 = (size_t)p->rows0;
+  if (legal_mask && !p->mask) { set_error("%s: the piece carries no legal mask", who); return MZX_ERR_INVALID; }
+  const char* base = (const char*)p->buf;
+  struct { void* dst; const void* src; size_t bytes; } copies[7] = {
+      {observations, base + p->o_obs, 4 * n1 * E}, {actions, base + p->o_act, 8 * n1}, {rewards, base + p->o_rew, 8 * n1},
+      {to_play, base + p->o_tp, 8 * n1}, {visit_counts, base + p->o_vis, 4 * n0 * A}, {root_values, base + p->o_val, 8 * n0},
+      {legal_mask, base + p->o_mask, n0 * A}};
+  int rc = 0;
+  for (const auto& cp : copies)
+    if (cp.dst && cp.bytes && rc == 0) rc = copy_d2h(cp.dst, cp.src, cp.bytes, (stream_t)stream);
+  const int waited = stream_sync((stream_t)stream);      // (also behind a failed copy: nothing stays in flight into the host arrays)
+  if (rc == 0) rc = waited;
+  if (rc) { set_error("%s: %s", who, runtime_error_string(rc)); return MZX_ERR_RUNTIME; }
+  return MZX_OK;
+}
+
+int mzx_actor_release_device(mzx_actor* a, int64_t token, void* stream) {
+  const char* who = "mzx_actor_release_device";
+  if (!a || !a->resident) { set_error("%s: not a resident group", who); return MZX_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(a->finished_lock);
+  mzx_actor_piece* p = resident_piece_find(a->resident, token, mzx_actor_piece::TAKEN);
+  if (!p) { set_error("%s: no piece with token %lld is taken and unreleased", who, (long long)token); return MZX_ERR_INVALID; }
+  const int rc = event_record(&p->event, (stream_t)stream);
+  if (rc) { set_error("%s: event record failed: %s", who, runtime_error_string(rc)); return MZX_ERR_RUNTIME; }
+  p->event_pending = true;
+  p->state = mzx_actor_piece::FREE;
+  return MZX_OK;
+}
+
+static int no_handoff_group(const char* who, const mzx_actor* a) {
+  if (a && a->resident && a->resident->handoff) {
+    set_error("%s: the group is on the device hand-off: its games are taken with mzx_actor_take_device", who);
+    return MZX_ERR_INVALID;
+  }
+  return MZX_OK;
+}
+
 int mzx_actor_finished(mzx_actor* a, int64_t before_sequence, int64_t out[3]) {
   if (!a || !out) { set_error("mzx_actor_finished: null"); return MZX_ERR_INVALID; }
+  if (no_handoff_group("mzx_actor_finished", a)) return MZX_ERR_INVALID;
   std::lock_guard<std::mutex> lk(a->finished_lock);
   out[0] = out[1] = out[2] = 0;
   for (const mzx_actor::Batch& b : a->finished) {
@@ -1886,6 +2052,7 @@ int mzx_actor_take(mzx_actor* a, int64_t before_sequence, int32_t* slot, int32_t
     set_error("mzx_actor_take: missing buffer");
     return MZX_ERR_INVALID;
   }
+  if (no_handoff_group("mzx_actor_take", a)) return MZX_ERR_INVALID;
   // the batches to hand out leave the queue under its lock (a rounds call on another thread may be appending); the copies
   // run outside it
   std::deque<mzx_actor::Batch> mine;

@@ -819,4 +819,84 @@ struct ReplayIngestSlotBody {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Export (mzx_replay_export, include/mzx.h): the inverse of the ingest's row launch, for reading games back.  Games
+// (base[g], len[g]) of the pool are packed game-major and ragged in the ingest's staged layout: packed row r of the arrays
+// with T + 1 entries per game belongs to the LAST game g with dst1[g] <= r, index i = r - dst1[g]; its row of the arrays
+// with T entries is dst0[g] + i.  One launch, a wavefront per packed row; copies only -- the child visits are the pool's
+// quotients as they lie, actions / to_play widened to i64, a mask row expanded to one byte per action.
+struct ReplayExportParams {
+  const int64_t* base;          // [G]
+  const int32_t* len;           // [G]
+  const int64_t* dst1;          // [G]
+  const int64_t* dst0;          // [G]
+  const float* pool_frames;     // the pool's columns
+  const int32_t* pool_actions;
+  const double* pool_rewards;
+  const int32_t* pool_to_play;
+  const double* pool_root_values;
+  const double* pool_child_visits;
+  const uint32_t* pool_mask;    // null without `legal`
+  const float* pool_priorities; // null without `priorities`
+  float* observations;          // packed, see include/mzx.h
+  int64_t* actions;
+  double* rewards;
+  int64_t* to_play;
+  double* child_visits;
+  double* root_values;
+  uint8_t* legal;               // nullable
+  float* priorities;            // nullable
+  int64_t rows, total_rows;
+  int32_t G, A, frame_floats, vec;
+};
+
+struct ReplayExportRowBody {
+  ReplayExportParams p;
+  MZX_HD size_t size() const { return (size_t)p.total_rows; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int64_t r = (int64_t)e;
+    int lo = 0, hi = p.G - 1;            // dst1[lo] <= r always (dst1[0] == 0); the same search in every lane
+    while (lo < hi) {
+      const int mid = lo + (hi - lo + 1) / 2;
+      if (p.dst1[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    const int g = lo;
+    const int T = p.len[g];
+    const int64_t i = r - p.dst1[g], b = p.base[g];
+    if (i < 0 || i > T || b < 0 || b + T >= p.rows) return;      // (a game whose rows leave the pool is passed over)
+    const int64_t row = b + i;
+    const int A = p.A;
+
+    if (p.vec) {
+      const f32x4* __restrict__ src = (const f32x4*)(p.pool_frames + row * p.frame_floats);
+      f32x4* __restrict__ dst = (f32x4*)(p.observations + r * p.frame_floats);
+      WAVE_FOR(j, p.frame_floats / 4) dst[j] = src[j];
+    } else {
+      const float* __restrict__ src = p.pool_frames + row * p.frame_floats;
+      float* __restrict__ dst = p.observations + r * p.frame_floats;
+      WAVE_FOR(j, p.frame_floats) dst[j] = src[j];
+    }
+    if (lane == 0) {
+      p.actions[r] = (int64_t)p.pool_actions[row];
+      p.rewards[r] = p.pool_rewards[row];
+      p.to_play[r] = (int64_t)p.pool_to_play[row];
+    }
+    if (i == T) return;                  // the padding row has no entry in the arrays of T per game
+
+    const int64_t r0 = p.dst0[g] + i;
+    const double* __restrict__ cv = p.pool_child_visits + row * A;
+    double* __restrict__ out = p.child_visits + r0 * A;
+    WAVE_FOR(a, A) out[a] = cv[a];
+    if (p.legal) {
+      const uint32_t* __restrict__ m = p.pool_mask + row * ((A + 31) / 32);
+      uint8_t* __restrict__ ok = p.legal + r0 * A;
+      WAVE_FOR(a, A) ok[a] = (uint8_t)((m[a >> 5] >> (a & 31)) & 1u);
+    }
+    if (lane == 0) {
+      p.root_values[r0] = p.pool_root_values[row];
+      if (p.priorities) p.priorities[r0] = p.pool_priorities[row];
+    }
+  }
+};
+
 }  // namespace mzx

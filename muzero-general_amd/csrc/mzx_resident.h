@@ -169,7 +169,73 @@ struct ResidentGatherBody {
   }
 };
 
+// The hand-off's gather (mzx_actor_set_device_handoff): the same packed arrays, one wavefront per packed ROW -- work item e
+// is row e of the (len + 1)-long arrays and finds its game by binary search over the table's offset column, as
+// ReplayIngestRowBody (mzx_replay.h) does; no game's moves are walked one after another.  Row 0 of a game also writes the
+// game's entries of the three columns mzx_replay_ingest reads straight from the device: len i32, src1 / src0 i64.
+struct ResidentPackBody {
+  ResidentDevice d;
+  const int64_t* table;                // [count][5] as the gather's; column 3 strictly increasing from 0
+  int32_t count, q_first;
+  int64_t r_first, total_rows;         // total_rows = sum(len + 1)
+  float* obs; int64_t* act; int64_t* tp; double* rew; int32_t* vis; double* val; uint8_t* mask;
+  int32_t* len; int64_t* src1; int64_t* src0;
+  MZX_HD size_t size() const { return (size_t)total_rows; }
+  MZX_WAVE_FN void operator()(size_t e, int lane) const {
+    const int64_t r = (int64_t)e;
+    int lo = 0, hi = count - 1;        // table[lo][3] <= r always; the same search in every lane
+    while (lo < hi) {
+      const int mid = lo + (hi - lo + 1) / 2;
+      if (table[5 * (size_t)mid + 3] <= r) lo = mid; else hi = mid - 1;
+    }
+    const int64_t* t = table + 5 * (size_t)lo;
+    const int64_t st = t[0], s = t[1], n = t[2], q1 = t[3], q0 = t[4];
+    const int64_t m = r - q1;
+    if (m < 0 || m > n) return;
+    const int A = d.A, E = d.E, B = d.B;
+    if (m < n) {
+      const size_t row = (size_t)((st + m) % d.cap) * B + (size_t)s;
+      WAVE_FOR(j, E) obs[(size_t)r * E + j] = d.l_obs[row * E + j];
+      WAVE_FOR(j, A) vis[(size_t)(q0 + m) * A + j] = d.l_vis[row * A + j];
+      if (mask) WAVE_FOR(j, A) mask[(size_t)(q0 + m) * A + j] = d.l_mask[row * A + j];
+      if (lane == 0) {
+        tp[r] = d.l_tp[row];
+        act[r + 1] = d.l_act[row];
+        rew[r + 1] = d.l_rew[row];
+        val[q0 + m] = d.l_val[row];
+      }
+    } else {                           // the position after the last move closes the record
+      const size_t cell = (size_t)((st + n - 1 - r_first) + q_first) * B + (size_t)s;
+      WAVE_FOR(j, E) obs[(size_t)r * E + j] = d.fin_obs[cell * E + j];
+      if (lane == 0) tp[r] = d.fin_tp[cell];
+    }
+    if (m == 0 && lane == 0) {
+      act[q1] = 0; rew[q1] = 0.0;      // action_history / reward_history start with 0 (self_play.py:118-120)
+      len[lo] = (int32_t)n; src1[lo] = q1; src0[lo] = q0;
+    }
+  }
+};
+
 }  // namespace mzx
+
+// A piece: the finished games one harvest of a hand-off group packed, kept ON THE DEVICE in a buffer the actor owns -- the
+// packed arrays in the staged layout of mzx_replay_ingest and the len / src1 / src0 columns -- with the per-game slot /
+// length / sequence on the host.  free -> (harvest) queued -> (mzx_actor_take_device) taken -> (mzx_actor_release_device)
+// free again once the event recorded at the release has passed.
+struct mzx_actor_piece {
+  enum State { FREE, FILLING, QUEUED, TAKEN };
+  int64_t token = 0;
+  void* buf = nullptr;
+  int64_t bytes = 0;
+  State state = FREE;
+  void* event = nullptr;               // recorded by the release behind the consumer's work
+  bool event_pending = false;
+  int64_t games = 0, rows0 = 0;        // rows0 = sum len
+  bool mask = false;
+  size_t o_len = 0, o_src1 = 0, o_src0 = 0, o_obs = 0, o_act = 0, o_tp = 0, o_rew = 0, o_vis = 0, o_val = 0, o_mask = 0;
+  std::vector<int32_t> slot, n;
+  std::vector<int64_t> seq;
+};
 
 // the host side of a resident group
 struct mzx_actor_resident {
@@ -182,6 +248,11 @@ struct mzx_actor_resident {
   void* d_pack = nullptr;              // gather table + packed arrays (grown on demand)
   int64_t pack_bytes = 0;
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // the device hand-off (mzx_actor_set_device_handoff); pieces / queued / piece_bytes under the actor's finished_lock
+  bool handoff = false;
+  int64_t max_log_bytes = 0, next_token = 1, piece_bytes = 0;
+  std::vector<std::unique_ptr<mzx_actor_piece>> pieces;
+  std::deque<mzx_actor_piece*> queued;
 };
 
 namespace mzx {
@@ -215,8 +286,69 @@ inline void resident_free(mzx_actor* a) {
   mzx_game_device_destroy(R->game);
   if (R->block) device_free(R->block);
   if (R->d_pack) device_free(R->d_pack);
+  if (!R->pieces.empty()) device_sync();        // (a consumer's launch may still be reading a piece)
+  for (auto& p : R->pieces) {
+    event_destroy(p->event);
+    if (p->buf) device_free(p->buf);
+  }
   delete R;
   a->resident = nullptr;
+}
+
+// ---- the pieces of a hand-off group ---------------------------------------------------------------------------------------
+
+inline void resident_piece_drop(mzx_actor_resident* R, size_t index) {
+  mzx_actor_piece* p = R->pieces[index].get();
+  event_destroy(p->event);
+  if (p->buf) device_free(p->buf);
+  R->piece_bytes -= p->bytes;
+  R->stats[7] = R->piece_bytes;
+  R->pieces.erase(R->pieces.begin() + (long)index);
+}
+
+// A buffer of at least `need` bytes for the next piece: a free one whose release event has passed (a pending event is
+// queried, never waited for), else a fresh allocation.  Device log plus pieces stay within the group's max_log_bytes: free
+// buffers that are too small are given back first, and what still does not fit is refused with the sizes.
+inline int resident_piece_acquire(mzx_actor* a, size_t need, mzx_actor_piece** out) {
+  mzx_actor_resident* R = a->resident;
+  std::lock_guard<std::mutex> lk(a->finished_lock);
+  for (auto& p : R->pieces)
+    if (p->state == mzx_actor_piece::FREE && (size_t)p->bytes >= need && (!p->event_pending || event_done(p->event))) {
+      p->event_pending = false;
+      p->state = mzx_actor_piece::FILLING;
+      *out = p.get();
+      return MZX_OK;
+    }
+  size_t want = std::max(need, (size_t)1 << 16) * 2;
+  if (R->block_bytes + R->piece_bytes + (int64_t)want > R->max_log_bytes) {
+    for (size_t i = R->pieces.size(); i-- > 0;) {
+      mzx_actor_piece* p = R->pieces[i].get();
+      if (p->state == mzx_actor_piece::FREE && (!p->event_pending || event_done(p->event))) resident_piece_drop(R, i);
+    }
+    want = (need + 15) / 16 * 16;
+  }
+  if (R->block_bytes + R->piece_bytes + (int64_t)want > R->max_log_bytes) {
+    set_error("mzx_selfplay_rounds (resident): the device log (%lld bytes) and the pieces kept on the device (%lld bytes) leave no room "
+              "for a piece of %lld bytes within max_log_bytes = %lld: release pieces (mzx_actor_release_device) or raise the bound",
+              (long long)R->block_bytes, (long long)R->piece_bytes, (long long)want, (long long)R->max_log_bytes);
+    return MZX_ERR_INVALID;
+  }
+  std::unique_ptr<mzx_actor_piece> p(new (std::nothrow) mzx_actor_piece());
+  if (!p) { set_error("out of host memory"); return MZX_ERR_RUNTIME; }
+  if (device_alloc(&p->buf, want) != 0) { set_error("mzx_selfplay_rounds (resident): piece buffer of %lld bytes", (long long)want); return MZX_ERR_RUNTIME; }
+  p->bytes = (int64_t)want;
+  p->state = mzx_actor_piece::FILLING;
+  R->piece_bytes += p->bytes;
+  R->stats[7] = R->piece_bytes;
+  *out = p.get();
+  R->pieces.push_back(std::move(p));
+  return MZX_OK;
+}
+
+inline mzx_actor_piece* resident_piece_find(mzx_actor_resident* R, int64_t token, mzx_actor_piece::State state) {
+  for (auto& p : R->pieces)
+    if (p->token == token && p->state == state) return p.get();
+  return nullptr;
 }
 
 // ---- the rounds of a call (mzx_selfplay_rounds with resident groups) -----------------------------------------------------
@@ -225,7 +357,8 @@ constexpr int32_t RESIDENT_CTRL_CLEAR[RESIDENT_CTRL_WORDS] = {0, -1, 0, 0};
 
 struct ResidentPiece {            // the games one harvest of one group brought, not yet numbered
   int group;
-  mzx_actor::Batch b;
+  mzx_actor::Batch b;             // (a hand-off group: slot / n / seq only -- the arrays stay on the device, in `device`)
+  mzx_actor_piece* device = nullptr;
   std::vector<int64_t> round;     // round of the CALL each game ended in
 };
 
@@ -315,6 +448,42 @@ inline int resident_harvest(mzx_actor* a, int group, int q0, int q1, int64_t r_f
   const int64_t k = (int64_t)b.slot.size();
   if (k == 0) return MZX_OK;
   const bool masks = R->d.masks != 0;
+  if (R->handoff) {
+    // the pack into a piece: nothing of it is downloaded; the launch has completed when this returns
+    Carver c;
+    mzx_actor_piece L;
+    const size_t o_table = c.take(8 * table.size());
+    L.o_len = c.take(4 * (size_t)k); L.o_src1 = c.take(8 * (size_t)k); L.o_src0 = c.take(8 * (size_t)k);
+    L.o_obs = c.take(4 * (size_t)(o1 * E)); L.o_act = c.take(8 * (size_t)o1); L.o_tp = c.take(8 * (size_t)o1);
+    L.o_rew = c.take(8 * (size_t)o1); L.o_vis = c.take(4 * (size_t)(o0 * A)); L.o_val = c.take(8 * (size_t)o0);
+    L.o_mask = c.take(masks ? (size_t)(o0 * A) : 0);
+    mzx_actor_piece* p = nullptr;
+    int rc = resident_piece_acquire(a, c.at, &p);
+    if (rc) return rc;
+    p->games = k; p->rows0 = o0; p->mask = masks;
+    p->o_len = L.o_len; p->o_src1 = L.o_src1; p->o_src0 = L.o_src0; p->o_obs = L.o_obs; p->o_act = L.o_act; p->o_tp = L.o_tp;
+    p->o_rew = L.o_rew; p->o_vis = L.o_vis; p->o_val = L.o_val; p->o_mask = L.o_mask;
+    char* base = (char*)p->buf;
+    rc = copy_h2d(base + o_table, table.data(), 8 * table.size(), (stream_t)stream);
+    if (rc == 0) {
+      ResidentPackBody body{R->d, (const int64_t*)(base + o_table), (int32_t)k, q0, r_first, o1, (float*)(base + p->o_obs),
+                            (int64_t*)(base + p->o_act), (int64_t*)(base + p->o_tp), (double*)(base + p->o_rew), (int32_t*)(base + p->o_vis),
+                            (double*)(base + p->o_val), masks ? (uint8_t*)(base + p->o_mask) : nullptr, (int32_t*)(base + p->o_len),
+                            (int64_t*)(base + p->o_src1), (int64_t*)(base + p->o_src0)};
+      rc = launch_waves<GAME_WAVES>(body, (stream_t)stream);
+    }
+    const int waited = rc ? rc : resident_wait(a, stream);      // (the table is a local: it must outlive its upload)
+    if (rc || waited) {
+      if (rc) (void)stream_sync((stream_t)stream);
+      std::lock_guard<std::mutex> lk(a->finished_lock);
+      p->state = mzx_actor_piece::FREE;
+      return rc ? resident_fail("pack upload / launch", rc) : waited;
+    }
+    piece.device = p;
+    R->stats[6] += k;
+    pieces.push_back(std::move(piece));
+    return MZX_OK;
+  }
   Carver c;
   const size_t o_table = c.take(8 * table.size()), o_obs = c.take(4 * (size_t)(o1 * E)), o_act = c.take(8 * (size_t)o1), o_tp = c.take(8 * (size_t)o1),
                o_rew = c.take(8 * (size_t)o1), o_vis = c.take(4 * (size_t)(o0 * A)), o_val = c.take(8 * (size_t)o0), o_mask = c.take(masks ? (size_t)(o0 * A) : 0);
@@ -458,7 +627,11 @@ inline int resident_rounds(mzx_actor* const* groups, int num_groups, mzx_rounds*
         phase[4] += actor_now() - t0;
       }
     }
-    if (rc) break;
+    if (rc) {                 // (the pieces packed so far are not handed out: their buffers are free again)
+      for (ResidentPiece& p : pieces)
+        if (p.device) { std::lock_guard<std::mutex> lk(groups[p.group]->finished_lock); p.device->state = mzx_actor_piece::FREE; }
+      break;
+    }
     // sequence numbers in (round, group, slot) order across groups: the order the host loop finishes games in
     struct Key { int64_t round; int group; int32_t slot; size_t piece, j; };
     std::vector<Key> keys;
@@ -471,7 +644,14 @@ inline int resident_rounds(mzx_actor* const* groups, int num_groups, mzx_rounds*
     for (ResidentPiece& p : pieces) {
       mzx_actor* a = groups[p.group];
       std::lock_guard<std::mutex> lk(a->finished_lock);
-      a->finished.push_back(std::move(p.b));
+      if (p.device) {
+        p.device->slot.swap(p.b.slot); p.device->n.swap(p.b.n); p.device->seq.swap(p.b.seq);
+        p.device->token = a->resident->next_token++;
+        p.device->state = mzx_actor_piece::QUEUED;
+        a->resident->queued.push_back(p.device);
+      } else {
+        a->finished.push_back(std::move(p.b));
+      }
     }
     finished += (int64_t)keys.size();
     rounds += n;

@@ -14,8 +14,9 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 MOVE_NO_SYNC = 1
+PIECE_INFO_WORDS = 16
 
 c_i32, c_i64, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
 
@@ -174,6 +175,15 @@ class ReplayIngestIO(ctypes.Structure):
     ]
 
 
+class ReplayExportIO(ctypes.Structure):
+    """``mzx_replay_export_io``: the games and packed outputs of one mzx_replay_export call (DeviceGameStore.download_games)."""
+    _fields_ = [
+        ("d_base", c_vp), ("d_len", c_vp), ("d_dst1", c_vp), ("d_dst0", c_vp), ("d_observations", c_vp), ("d_actions", c_vp),
+        ("d_rewards", c_vp), ("d_to_play", c_vp), ("d_child_visits", c_vp), ("d_root_values", c_vp), ("d_legal_mask", c_vp),
+        ("d_priorities", c_vp), ("total_rows", c_i64), ("num_games", c_i32), ("reserved", c_i32),
+    ]
+
+
 class TrainerLossIO(ctypes.Structure):
     """``mzx_trainer_loss_io``: the inputs and outputs of one mzx_trainer_loss call (mzx.trainer)."""
     _fields_ = [
@@ -284,6 +294,8 @@ PROTOTYPES = {
     "mzx_replay_update_priorities": (ctypes.c_int, [ctypes.POINTER(ReplaySampler), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mzx_replay_ingest": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplaySampler), c_vp, c_i64,
                                          ctypes.POINTER(ReplayIngestIO), c_vp]),
+    "mzx_replay_export": (ctypes.c_int, [ctypes.POINTER(ReplayPool), ctypes.POINTER(ReplaySampler), c_vp, c_i64,
+                                         ctypes.POINTER(ReplayExportIO), c_vp]),
     "mzx_scalar_to_support": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mzx_trainer_loss_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "mzx_trainer_loss": (ctypes.c_int, [ctypes.POINTER(TrainerLossIO), c_vp]),
@@ -314,6 +326,11 @@ PROTOTYPES = {
     "mzx_actor_resident_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64 * 8)]),
     "mzx_actor_finished": (ctypes.c_int, [c_vp, c_i64, ctypes.POINTER(c_i64 * 3)]),
     "mzx_actor_take": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32)]),
+    "mzx_actor_set_device_handoff": (ctypes.c_int, [c_vp, c_i32]),
+    "mzx_actor_finished_device": (ctypes.c_int, [c_vp, c_i64, ctypes.POINTER(c_i64 * 2)]),
+    "mzx_actor_take_device": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64 * 2)]),
+    "mzx_actor_download_device": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mzx_actor_release_device": (ctypes.c_int, [c_vp, c_i64, c_vp]),
     "mzx_selfplay_select": (ctypes.c_int, [c_vp, ctypes.POINTER(Move), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32,
                                            c_vp]),
 }

@@ -179,6 +179,8 @@ class ShardGameHistory(GameHistory):
             return value
         if name == "legal_actions":       # one list per position from the record's legal mask (absent: every action legal)
             view = self.__dict__.get("_view")       # (a restored history has no view: it carries the lists or has none)
+            if view is not None and getattr(view[0], "store", None) is not None and view[0].on_device:
+                view = (view[0]._game(view[1], view[2]), 0, view[2])      # (store-backed: this game's own record)
             if view is not None and view[0].legal_mask is not None:
                 source, i, n = view
                 return [numpy.nonzero(source.legal_mask[i, t])[0].tolist() for t in range(n)]
@@ -257,6 +259,109 @@ class _ShardRecord:
             else:
                 out.append(float(self.vals[i, t]) if total else 0)
         return out
+
+
+def shard_record_fields(A, shape, G, n, rows_n, off1, off0, obs, acts, rews, tps, vis, vals, mask):
+    """The arguments of a ``_ShardRecord`` for the games ``rows_n`` (all of n moves) of G games packed game-major and ragged
+    (``off1`` / ``off0``: their first rows in the arrays of n + 1 and of n entries per game): the arrays as they lie when
+    every game has this length, one gather per array otherwise; visit totals, the quotients ``child_visits`` holds
+    (self_play.py:496-511), which games are "every action legal, every root visited" throughout.  ``mask``: the legal mask
+    u8 [sum n][A] when some action was illegal, else None."""
+    k = int(rows_n.size)
+    if k == G:          # one length (fixed-length games, or a single game): the arrays as they lie
+        take1 = lambda a: a.reshape((k, n + 1) + a.shape[1:])
+        take0 = lambda a: a.reshape((k, n) + a.shape[1:])
+    else:
+        i1 = (off1[rows_n][:, None] + numpy.arange(n + 1)[None, :])
+        i0 = (off0[rows_n][:, None] + numpy.arange(n)[None, :])
+        take1, take0 = (lambda a: a[i1]), (lambda a: a[i0])
+    v, vl = take0(vis), take0(vals)
+    if A <= 8:          # (numpy's reduction over a short last axis is slow: a few strided adds instead)
+        totals = v[:, :, 0].astype(numpy.int64)
+        for x in range(1, A):
+            totals += v[:, :, x]
+    else:
+        totals = v.sum(2)
+    ratios = v / numpy.maximum(totals, 1)[:, :, None]       # true division of small integers == Python's int / int
+    plain = totals > 0
+    legal_mask = None
+    if mask is not None:
+        legal_mask = take0(mask).astype(bool)
+        plain = plain & legal_mask.all(2)
+    return (A, take1(obs).reshape((k, n + 1) + tuple(shape)), take1(acts), take1(rews), take1(tps), v, vl, totals, ratios,
+            plain.all(1), legal_mask)
+
+
+class _PieceRecord(_ShardRecord):
+    """
+    A shard record whose arrays are NOT on the host (``config.device_handoff``): the games ``rows_n`` (n moves each) of a
+    piece a resident group keeps on the device (``mzx.native_rounds._Piece``).  It is a ``_ShardRecord`` to its views, with
+    the arrays fetched on first touch:
+
+      * PIECE-BACKED, from ``collect`` until the hand-off: the first touch of any array downloads the piece -- once, one
+        copy per column, converted exactly as ``collect`` converts -- and releases it; the record is an ordinary host
+        record from then on.  Nothing is downloaded for a record nobody touches.
+      * STORE-BACKED, after ``ReplayBuffer.save_games`` ingested the piece on the device (``bind``): a view materialises
+        its fields from the pool (``DeviceGameStore.download_games`` of its game: ``mzx_replay_export``).  The pool keeps
+        the quotients and the root values (0.0 for an unvisited root), not the counts: ``vis`` / ``totals`` are not
+        available then.  A view whose game has left the store raises ``LookupError`` naming the game id.
+
+    ``priorities`` stay None: the ingest computes them, the device columns are authoritative.
+    """
+    _FETCHED = frozenset(("obs", "acts", "rews", "tps", "vis", "vals", "totals", "ratios", "simple", "legal_mask"))
+
+    def __init__(self, A, shape, piece, rows_n, n):
+        self.A, self.shape, self.piece, self.rows_n, self.n = A, tuple(shape), piece, rows_n, n
+        self._lists = {}
+        self.priorities = self.game_priority = None
+        self.store, self.game_ids, self._games = None, {}, {}
+
+    @property
+    def on_device(self):
+        """Whether the games' data is still only on the device (an unfetched piece, or the store's pool)."""
+        return "obs" not in self.__dict__
+
+    @property
+    def live(self):
+        """Piece-backed with the piece untouched: what the device path of ``save_games`` takes."""
+        return self.store is None and self.on_device and self.piece.live
+
+    def __getattr__(self, name):          # reached only while the arrays have not been fetched
+        if name in _PieceRecord._FETCHED:
+            if self.__dict__.get("store") is not None:
+                raise AttributeError(f"{name}: the record's games live in the device store (its views read them game by game)")
+            self.__dict__.update(self.piece.record_fields(self.rows_n, self.n))
+            return self.__dict__[name]
+        raise AttributeError(name)
+
+    def bind(self, store, game_ids, obs_dtype, integer_rewards):
+        """The piece was ingested into ``store``: row i of the record is game ``game_ids[i]`` there (rows that were
+        evicted again within the hand-off are simply not resident)."""
+        self.store, self.obs_dtype, self.integer_rewards = store, obs_dtype, integer_rewards
+        self.game_ids.update(game_ids)
+
+    def _game(self, i, n):
+        """Row i as a host record of one game, exported from the pool once."""
+        record = self._games.get(i)
+        if record is None:
+            game_id = self.game_ids.get(i)
+            if game_id is None or self.store.games.get(game_id, (None, None))[1] != n:
+                raise LookupError(f"game {game_id} has left the device store: its history was handed over on the device and "
+                                  f"never materialised on the host")
+            record = self._games[i] = self.store.game_record(game_id, self.obs_dtype, self.integer_rewards)
+        return record
+
+    def field(self, name, i, n):
+        if self.__dict__.get("store") is None or "obs" in self.__dict__:
+            return super().field(name, i, n)
+        return self._game(i, n).field(name, 0, n)
+
+
+def positions_of(game_history):
+    """``len(game_history.root_values)`` without materialising a view that has not been touched."""
+    d = game_history.__dict__
+    view = d.get("_view")
+    return view[2] if view is not None and "root_values" not in d else len(game_history.root_values)
 
 
 class ShardGames(list):

@@ -20,7 +20,7 @@ import ctypes
 import numpy
 
 from . import _lib, draws
-from .history import ShardGameHistory, ShardGames, _ShardRecord, gc_paused
+from .history import ShardGameHistory, ShardGames, _PieceRecord, _ShardRecord, gc_paused, shard_record_fields
 from . import search as _search
 from .search import BatchedMCTS
 from .shard_play import SlotGroup
@@ -29,6 +29,95 @@ from .shard_play import SlotGroup
 def resident_wanted(config):
     """``config.device_games``: the shard's games, move log and bookkeeping stay on the device (csrc/mzx_resident.h)."""
     return bool(getattr(config, "device_games", False))
+
+
+def handoff_wanted(config):
+    """``config.device_handoff``: a resident shard's finished games stay on the device until the replay store ingests them."""
+    return bool(getattr(config, "device_handoff", False))
+
+
+def check_handoff(actor):
+    """``config.device_handoff`` sits on top of ``config.device_games``: anything else is an error, no silent fall-back."""
+    if not resident_wanted(actor.config):
+        raise NotImplementedError("config.device_handoff: config.device_games is off (only resident rounds keep their finished "
+                                  "games on the device)")
+
+
+def check_handoff_buffer(config, replay_buffer):
+    """``continuous_self_play`` with ``config.device_handoff``: nothing on the host may need the histories to sample, so the
+    buffer must be local, with a device store and the device sampler."""
+    if not handoff_wanted(config):
+        return
+    why = None
+    if hasattr(getattr(replay_buffer, "save_game", None), "remote"):
+        why = "the replay buffer is remote (the games cannot leave the device's process)"
+    elif getattr(replay_buffer, "device_store", None) is None:
+        why = "the replay buffer has no device store"
+    elif not getattr(replay_buffer, "_sampler", False):
+        why = "the replay buffer has no device sampler (the host draws would read the histories)"
+    if why is not None:
+        raise NotImplementedError(f"config.device_handoff: {why}")
+
+
+class _Piece:
+    """A piece of a hand-off group (include/mzx.h ``mzx_actor_take_device``): the finished games of one chunk, packed on the
+    device in a buffer the actor owns.  ``ptr``: the device addresses ``mzx_replay_ingest`` reads; ``length`` per game on
+    the host.  ``fetch`` downloads it -- once, one copy per column, converted as ``collect`` converts -- and releases it."""
+
+    def __init__(self, group, backend, info, length, A, shape):
+        self.group, self.backend, self.A, self.shape = group, backend, A, tuple(shape)
+        self.token, self.games, self.rows0, self.has_mask = int(info[0]), int(info[1]), int(info[2]), bool(info[3])
+        names = ("len", "src1", "src0", "obs", "acts", "rews", "tps", "vis", "vals", "mask")
+        self.ptr = {name: int(info[4 + j]) or None for j, name in enumerate(names)}
+        self.bytes = int(info[14])
+        self.length = length
+        self.columns, self.released, self.downloads = None, False, 0
+
+    @property
+    def live(self):
+        return self.columns is None and not self.released
+
+    def release(self, stream=None):
+        """The buffer may be reused once the work queued on ``stream`` (default: the backend's) so far has finished."""
+        if not self.released:
+            g = self.group
+            g.lib.check(g.lib.mzx_actor_release_device(g.handle, self.token, self.backend.stream() if stream is None else stream))
+            self.released = True
+            g.pieces.remove(self)
+
+    def fetch(self):
+        if self.columns is None:
+            if self.released:
+                raise LookupError("the piece was handed over on the device and released: its games are read from the replay store")
+            g, A, E = self.group, self.A, int(numpy.prod(self.shape))
+            rows, G = self.rows0, self.games
+            obs = numpy.empty((rows + G, E), numpy.float32)
+            acts, tps = numpy.empty(rows + G, numpy.int64), numpy.empty(rows + G, numpy.int64)
+            rews = numpy.empty(rows + G, numpy.float64)
+            vis, vals = numpy.empty((rows, A), numpy.int32), numpy.empty(rows, numpy.float64)
+            mask = numpy.empty((rows, A), numpy.uint8) if self.has_mask else None
+            g.lib.check(g.lib.mzx_actor_download_device(g.handle, self.token, obs.ctypes.data, acts.ctypes.data, rews.ctypes.data,
+                                                        tps.ctypes.data, vis.ctypes.data, vals.ctypes.data,
+                                                        None if mask is None else mask.ctypes.data, self.backend.stream()))
+            self.downloads += 1
+            game = g.game
+            if game.obs_dtype != numpy.float32:
+                obs = obs.astype(game.obs_dtype)
+            if game.reward_dtype is numpy.int64:
+                rews = rews.astype(numpy.int64)
+            if mask is not None and mask.all():       # (every action legal throughout: the record carries no mask)
+                mask = None
+            self.columns = (obs, acts, rews, tps, vis, vals, mask)
+            self.release()
+        return self.columns
+
+    def record_fields(self, rows_n, n):
+        obs, acts, rews, tps, vis, vals, mask = self.fetch()
+        length = self.length
+        off1, off0 = numpy.cumsum(length + 1) - (length + 1), numpy.cumsum(length) - length
+        names = ("A", "obs", "acts", "rews", "tps", "vis", "vals", "totals", "ratios", "simple", "legal_mask")
+        return dict(zip(names, shard_record_fields(self.A, self.shape, self.games, n, rows_n, off1, off0, obs, acts, rews, tps,
+                                                   vis, vals, mask)))
 
 
 def check_resident(actor):
@@ -100,6 +189,11 @@ class _Group(SlotGroup):
         if self.resident:       # games, move log and bookkeeping on the device; the host returns once per chunk of rounds
             lib.check(lib.mzx_actor_set_resident(self.handle, int(getattr(cfg, "device_games_chunk", 16)),
                                                  int(getattr(cfg, "device_games_max_bytes", 2 << 30))))
+        self.handoff = self.resident and handoff_wanted(cfg)
+        self.pieces = []        # the pieces taken and not released yet (the device hand-off)
+        self.backend = actor.model.backend
+        if self.handoff:        # finished games stay on the device, in pieces the actor owns
+            lib.check(lib.mzx_actor_set_device_handoff(self.handle, 1))
 
     def resident_stats(self):
         out = (ctypes.c_int64 * 8)()
@@ -107,6 +201,8 @@ class _Group(SlotGroup):
         return list(out)
 
     def close(self):
+        for piece in list(self.pieces):       # (their buffers go with the actor: what nobody ingested comes to the host)
+            piece.fetch()
         handle, self.handle = self.handle, None
         if handle:
             self.lib.mzx_actor_destroy(handle)
@@ -234,17 +330,56 @@ class NativeShard:
             phases[k] += float(io.phase_seconds[k])
         return self.sequence
 
+    def _collect_pieces(self, g, before, A, shape, views_all, seq_all, slot_all, records):
+        """``collect`` for a group on the device hand-off: its pieces numbered below ``before``, every (piece, length) a
+        ``_PieceRecord`` whose arrays are fetched on first touch."""
+        lib = g.lib
+        counts = (ctypes.c_int64 * 2)()
+        lib.check(lib.mzx_actor_finished_device(g.handle, int(before), ctypes.byref(counts)))
+        P, G = int(counts[0]), int(counts[1])
+        if G == 0:
+            return
+        info = numpy.zeros((P, _lib.PIECE_INFO_WORDS), numpy.int64)
+        slot, length, seq = numpy.empty(G, numpy.int32), numpy.empty(G, numpy.int32), numpy.empty(G, numpy.int64)
+        lib.check(lib.mzx_actor_take_device(g.handle, int(before), P, G, info.ctypes.data, slot.ctypes.data, length.ctypes.data,
+                                            seq.ctypes.data, ctypes.byref(counts)))
+        assert (int(counts[0]), int(counts[1])) == (P, G)
+        lo = 0
+        for row in info:
+            k_piece = int(row[1])
+            sl = slice(lo, lo + k_piece)
+            lo += k_piece
+            piece = _Piece(g, g.backend, row, length[sl].copy(), A, shape)
+            g.pieces.append(piece)
+            for n in numpy.unique(piece.length).tolist():
+                rows_n = numpy.nonzero(piece.length == n)[0]
+                k = int(rows_n.size)
+                record = _PieceRecord(A, shape, piece, rows_n, n)
+                with gc_paused():
+                    views = ShardGameHistory.make_many(record, k, n)
+                views_all += views
+                seq_all.append(seq[sl][rows_n])
+                slot_all.append(slot[sl][rows_n])
+                records.append((record, n, views))
+
     def collect(self, before=-1, priorities_for=None):
         """The finished games of every group (numbered below ``before``; -1: all) as ``ShardGameHistory`` views, in the order
         they finished; their slots.  ``priorities_for`` (a configuration with PER on; ``continuous_self_play``'s hand-off):
         the initial PER priorities of every record are computed on the device right here and every view is created with its
-        row -- the buffer's save_game reads them for every game."""
+        row -- the buffer's save_game reads them for every game.
+
+        ``config.device_handoff``: the same ``ShardGames``, but every record is piece-backed (``_PieceRecord``: its arrays
+        are fetched on first touch, nothing is downloaded for a record nobody touches) and ``priorities_for`` is ignored --
+        ``ReplayBuffer.save_games`` ingests the pieces on the device, and the ingest computes the priorities."""
         actor = self._actor
         lib, A = actor.model.backend.lib, len(actor.config.action_space)
         shape = tuple(actor.config.observation_shape)
         E = int(numpy.prod(shape))
         views_all, seq_all, slot_all, records = [], [], [], []
         for g in self.groups:
+            if g.handoff:       # piece-backed records: nothing of the games is downloaded (priorities_for: the ingest's)
+                self._collect_pieces(g, before, A, shape, views_all, seq_all, slot_all, records)
+                continue
             counts = (ctypes.c_int64 * 3)()
             lib.check(lib.mzx_actor_finished(g.handle, int(before), ctypes.byref(counts)))
             G, rows = int(counts[0]), int(counts[1])
@@ -270,28 +405,9 @@ class NativeShard:
             for n in numpy.unique(length).tolist():
                 rows_n = numpy.nonzero(length == n)[0]
                 k = int(rows_n.size)
-                if k == G:          # one length (fixed-length games, or a single game): the arrays as they lie
-                    take1 = lambda a: a.reshape((k, n + 1) + a.shape[1:])
-                    take0 = lambda a: a.reshape((k, n) + a.shape[1:])
-                else:
-                    i1 = (off1[rows_n][:, None] + numpy.arange(n + 1)[None, :])
-                    i0 = (off0[rows_n][:, None] + numpy.arange(n)[None, :])
-                    take1, take0 = (lambda a: a[i1]), (lambda a: a[i0])
-                v, vl = take0(vis), take0(vals)
-                if A <= 8:          # (numpy's reduction over a short last axis is slow: a few strided adds instead)
-                    totals = v[:, :, 0].astype(numpy.int64)
-                    for x in range(1, A):
-                        totals += v[:, :, x]
-                else:
-                    totals = v.sum(2)
-                ratios = v / numpy.maximum(totals, 1)[:, :, None]       # true division of small integers == Python's int / int
-                plain = totals > 0
-                legal_mask = None
-                if mask is not None and illegal.value:
-                    legal_mask = take0(mask).astype(bool)
-                    plain = plain & legal_mask.all(2)
-                record = _ShardRecord(A, take1(obs).reshape((k, n + 1) + shape), take1(acts), take1(rews), take1(tps), v, vl,
-                                      totals, ratios, plain.all(1), legal_mask)
+                record = _ShardRecord(*shard_record_fields(A, shape, G, n, rows_n, off1, off0, obs, acts, rews, tps, vis, vals,
+                                                           mask if mask is not None and illegal.value else None))
+                vl, totals = record.vals, record.totals
                 if priorities_for is not None and getattr(priorities_for, "PER", False) and n > 0:
                     from . import replay
                     record.priorities, record.game_priority = replay.device_priorities(

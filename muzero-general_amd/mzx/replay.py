@@ -32,7 +32,7 @@ import numpy
 import torch
 
 from . import _lib, models, observations
-from .history import ShardGameHistory, gc_paused
+from .history import ShardGameHistory, _PieceRecord, _ShardRecord, gc_paused, positions_of
 
 # DeviceGameStore.reanalyse: the stacked observations of one chunk of positions stay within this many bytes (the network's
 # activations scale with the same count), and within the 64-lane groups one mzx_replay_batch gather accepts
@@ -153,6 +153,12 @@ def fill_initial_priorities_many(histories, config, backend=None):
     filled, views, plain = 0, {}, {}
     jobs = []
     grouped = getattr(histories, "records", None)
+    if grouped and any(getattr(record, "on_device", False) for record, _, _ in grouped):
+        # records whose games are still on the device (config.device_handoff): the ingest computes their priorities there,
+        # nothing of them is fetched for it; whatever else the hand-off holds goes game by game
+        skip = {id(h) for record, _, members in grouped if getattr(record, "on_device", False) for h in members}
+        rest = [h for h in histories if id(h) not in skip]
+        return fill_initial_priorities_many(rest, config, backend) if rest else 0
     if (grouped and all(record.priorities is not None for record, _, _ in grouped)
             and sum(len(members) for _, _, members in grouped) == len(histories)):
         return 0        # (every record came with its priorities: the views were created with their rows)
@@ -320,6 +326,7 @@ class DeviceGameStore:
         # add_records: the pinned staging block, its device twin and the event recorded behind the last ingest that read it
         self._stage = self._stage_dev = self._stage_event = None
         self.ingest_calls = 0         # mzx_replay_ingest calls so far (add_records: one per staged chunk)
+        self.export_calls = 0         # mzx_replay_export calls so far (download_games: one per call)
         self.max_games = None if max_games is None else int(max_games)
         self.sampler = None
         if self.max_games is not None:
@@ -728,6 +735,114 @@ class DeviceGameStore:
             if self._stage_event is None:
                 self._stage_event = torch.cuda.Event()
             self._stage_event.record(torch.cuda.current_stream(be.device))
+
+    # ---- the device hand-off
+    def ingest_piece(self, piece, bases, game_ids):
+        """
+        The games of a piece a resident shard kept on the device (``mzx.native_rounds._Piece``, ``config.device_handoff``)
+        become pool rows without touching the host: ONE small upload -- ``bases`` / ``game_ids`` per game of the piece, in
+        the piece's order, base -1 for a game that is not to be stored (evicted again within its hand-off: the ingest passes
+        it over) -- and ONE ``mzx_replay_ingest`` whose d_len / d_src1 / d_src0 and staged arrays point into the piece;
+        then the piece is released behind the ingest.  The rows were reserved by ``_reserve``; the priorities are computed
+        by the kernel.
+        """
+        be, lib = self.backend, self.backend.lib
+        G = piece.games
+        table = numpy.empty((2, G), numpy.int64)
+        table[0], table[1] = bases, game_ids
+        if self.sampler is not None:
+            for base, game_id in zip(table[0].tolist(), table[1].tolist()):
+                if base >= 0:        # (the kernel writes these slots: a pending entry must not overwrite them later)
+                    self._slot_dirty.pop(game_id % self.max_games, None)
+            self._flush_slots()
+        d_table = self._up(table)
+        ptr = piece.ptr
+        io = _lib.ReplayIngestIO()
+        io.d_len, io.d_src1, io.d_src0 = ptr["len"], ptr["src1"], ptr["src0"]
+        io.d_base, io.d_game_id = d_table.data_ptr(), d_table.data_ptr() + 8 * G
+        io.d_observations, io.d_actions, io.d_rewards, io.d_to_play = ptr["obs"], ptr["acts"], ptr["rews"], ptr["tps"]
+        io.d_visits, io.d_root_values, io.d_legal_mask, io.d_priorities = ptr["vis"], ptr["vals"], ptr["mask"], None
+        per = self.sampler is not None and bool(self.config.PER)
+        io.d_discount_pow, io.per_alpha = self._discount_pow.data_ptr(), float(getattr(self.config, "PER_alpha", 1.0))
+        io.total_rows, io.num_games, io.td_steps, io.per, io.action_space_size = piece.rows0 + G, G, int(self.config.td_steps), int(per), self.A
+        io.channels, io.height, io.width = self.shape
+        lib.check(lib.mzx_replay_ingest(ctypes.byref(self.pool), None if self.sampler is None else ctypes.byref(self.sampler),
+                                        be.ptr(self.legal_mask), self.rows if self.legal_mask is not None else 0,
+                                        ctypes.byref(io), be.stream()))
+        self.ingest_calls += 1
+        piece.release(be.stream())
+        del d_table      # (torch's caching allocator keeps the block for this stream: the ingest reads it in stream order)
+
+    def game_record(self, game_id, obs_dtype=None, integer_rewards=False):
+        """A resident game as a host ``_ShardRecord`` of one game (``download_games``: one export): observations in
+        ``obs_dtype``, rewards as integers where the game's are, ``ratios`` the pool's quotients and ``vals`` its root
+        values -- the visit counts are not kept, so every row counts as visited and the record hands out its own rows."""
+        got = self.download_games([game_id], legal_mask=self.legal_mask is not None, priorities=False)
+        T = int(got["lengths"][0])
+        obs = got["observations"]
+        if obs_dtype is not None and numpy.dtype(obs_dtype) != numpy.float32:
+            obs = obs.astype(obs_dtype)
+        rews = got["rewards"].astype(numpy.int64) if integer_rewards else got["rewards"]
+        mask = got.get("legal_mask")
+        legal = None if mask is None or mask.all() else mask.astype(bool)[None]
+        return _ShardRecord(self.A, obs[None], got["actions"][None], rews[None], got["to_play"][None], None, got["root_values"][None],
+                            numpy.ones((1, T), numpy.int64), got["child_visits"][None], numpy.ones(1, bool), legal)
+
+    # ---- reading games back
+    def download_games(self, game_ids, legal_mask=None, priorities=None):
+        """
+        The resident games ``game_ids`` as host arrays: ONE ``mzx_replay_export`` (a launch that packs their pool rows
+        game-major and ragged, the ingest's staged layout) and one download per column, whatever the number of games.
+        Returns a dict: ``lengths`` i32 [G]; ``first1`` / ``first0`` i64 [G], the first packed row of every game in the
+        arrays of T + 1 and of T entries per game; ``observations`` f32 [sum(T + 1)] + observation_shape, ``actions`` /
+        ``to_play`` i64 and ``rewards`` f64 [sum(T + 1)]; ``child_visits`` f64 [sum T][A] -- the pool's quotients, bit
+        for bit --, ``root_values`` f64 [sum T] (the pool's column: the reanalysed values after a sweep); and, where the
+        store holds the column (``legal_mask`` / ``priorities``: None takes what is there, True insists), ``legal_mask``
+        u8 [sum T][A] and ``priorities`` f32 [sum T].  A game that is not resident raises ``LookupError`` naming its id
+        before anything is launched.
+        """
+        be, lib = self.backend, self.backend.lib
+        ids = [int(g) for g in game_ids]
+        for g in ids:
+            if g not in self.games:
+                raise LookupError(f"game {g} is not resident in the device store")
+        with_mask = self.legal_mask is not None if legal_mask is None else bool(legal_mask)
+        with_priorities = self.sampler is not None if priorities is None else bool(priorities)
+        if with_mask and self.legal_mask is None:
+            raise ValueError("this DeviceGameStore was built without legal_masks")
+        if with_priorities:
+            self._need_sampler()
+        entries = [self.games[g] for g in ids]
+        lens = numpy.array([T for _, T in entries], dtype=numpy.int64)
+        G, R0 = len(ids), int(lens.sum())
+        R1, n0 = R0 + G, max(R0, 1)       # (games without a position: the arrays of T entries still need an address)
+        first1, first0 = numpy.cumsum(lens + 1) - (lens + 1), numpy.cumsum(lens) - lens
+        table = numpy.empty((3, G), numpy.int64)
+        table[0], table[1], table[2] = [b for b, _ in entries], first1, first0
+        d_table, d_len = self._up(table), self._up(lens.astype(numpy.int32))
+        out = {"observations": be.empty((R1,) + self.shape, torch.float32), "actions": be.empty((R1,), torch.int64),
+               "rewards": be.empty((R1,), torch.float64), "to_play": be.empty((R1,), torch.int64),
+               "child_visits": be.empty((n0, self.A), torch.float64), "root_values": be.empty((n0,), torch.float64)}
+        if with_mask:
+            out["legal_mask"] = be.empty((n0, self.A), torch.uint8)
+        if with_priorities:
+            out["priorities"] = be.empty((n0,), torch.float32)
+        io = _lib.ReplayExportIO()
+        io.d_base, io.d_dst1, io.d_dst0 = (d_table.data_ptr() + 8 * G * i for i in range(3))
+        io.d_len = d_len.data_ptr()
+        io.d_observations, io.d_actions, io.d_rewards = (out[n].data_ptr() for n in ("observations", "actions", "rewards"))
+        io.d_to_play, io.d_child_visits, io.d_root_values = (out[n].data_ptr() for n in ("to_play", "child_visits", "root_values"))
+        io.d_legal_mask = out["legal_mask"].data_ptr() if with_mask else None
+        io.d_priorities = out["priorities"].data_ptr() if with_priorities else None
+        io.total_rows, io.num_games = R1, G
+        lib.check(lib.mzx_replay_export(ctypes.byref(self.pool), None if self.sampler is None else ctypes.byref(self.sampler),
+                                        be.ptr(self.legal_mask), self.rows if self.legal_mask is not None else 0,
+                                        ctypes.byref(io), be.stream()))
+        self.export_calls += 1
+        whole = ("observations", "actions", "rewards", "to_play")
+        out = {name: t.cpu().numpy()[:R1 if name in whole else R0] for name, t in out.items()}
+        out["lengths"], out["first1"], out["first0"] = lens.astype(numpy.int32), first1, first0
+        return out
 
     # ---- the sampler's state
     def _priority_rows(self, gh, T):
@@ -1190,7 +1305,7 @@ class ReplayBuffer:
         """The capacity bound in positions: the stock buffer's eviction (replay_buffer.py:59-61), applied once more."""
         store, stock = self._store, self._stock
         del_id = stock.num_played_games - len(stock.buffer)
-        stock.total_samples -= len(stock.buffer[del_id].root_values)
+        stock.total_samples -= positions_of(stock.buffer[del_id])
         del stock.buffer[del_id]
         self._arrays.pop(del_id, None)
         if del_id in store:
@@ -1259,7 +1374,7 @@ class ReplayBuffer:
         if store is None:
             return
         targets = store.download_targets([g for g in self._stock.buffer if g in store])
-        odd = [g for g, (_, roots) in targets.items() if len(self._stock.buffer[g].root_values) != len(roots)]
+        odd = [g for g, (_, roots) in targets.items() if positions_of(self._stock.buffer[g]) != len(roots)]
         if odd:
             raise ValueError(f"sync_targets: games {odd[:8]} changed length since they entered the device store")
         for game_id, (visits, roots) in targets.items():
@@ -1326,29 +1441,67 @@ class ReplayBuffer:
             if T + 1 > store.rows:
                 raise StoreFull(f"a game of {T} positions exceeds the device store's {store.rows} rows")
             views.append(view)
+        # the device hand-off: a fresh view of a LIVE piece-backed record never comes to the host -- provided the hand-off
+        # brings every game of its piece (a piece is ingested whole); any other piece is fetched, and its records are
+        # ordinary host records from here on
+        covered = {}
+        for view in views:
+            if view is not None and isinstance(view[0], _PieceRecord) and view[0].live:
+                covered[id(view[0].piece)] = covered.get(id(view[0].piece), 0) + 1
+        for record, _, _ in records:
+            if isinstance(record, _PieceRecord) and record.live and covered.get(id(record.piece), 0) != record.piece.games:
+                record.piece.fetch()
+        on_device = [view is not None and isinstance(view[0], _PieceRecord) and view[0].live for view in views]
         fill_initial_priorities_many(histories, config, backend=store.backend)
         for game_id in [g for g in store.games if g not in stock.buffer]:
             store.drop(game_id)
-        pending = []           # reserved fresh views whose rows are not filled yet: (game_id, game_history), view
+        pending = []           # reserved fresh views whose rows are not filled yet: (game_id, game_history), view, on the device
 
         def flush():
-            live = [(item, view) for item, view in pending if item[0] in store.games]
+            host = [(item, view) for item, view, device in pending if item[0] in store.games and not device]
+            pieces = {}          # id(piece) -> piece, base and game id per game of the piece, the records' rows -> game id
+            for (game_id, _), (record, row, _) in [(item, view) for item, view, device in pending if device]:
+                piece = record.piece
+                entry = pieces.get(id(piece))
+                if entry is None:
+                    entry = pieces[id(piece)] = (piece, numpy.full(piece.games, -1, numpy.int64), numpy.full(piece.games, -1, numpy.int64), {})
+                j = int(record.rows_n[row])
+                entry[1][j] = store.games[game_id][0] if game_id in store.games else -1
+                entry[2][j] = game_id
+                entry[3].setdefault(id(record), (record, {}))[1][row] = game_id
             del pending[:]
-            store._stage_views([item for item, _ in live], [view for _, view in live])
+            store._stage_views([item for item, _ in host], [view for _, view in host])
+            for piece, bases, ids, bound in pieces.values():
+                store.ingest_piece(piece, bases, ids)
+                game = piece.group.game
+                for record, rows in bound.values():
+                    record.bind(store, rows, game.obs_dtype, game.reward_dtype is numpy.int64)
 
         try:
-            for game_history, view in zip(histories, views):
+            for game_history, view, device in zip(histories, views, on_device):
                 if view is None:                  # any other game: the per-game path, behind the games before it
                     flush()
                     self.save_game(game_history, None)
                     continue
                 oldest = next(iter(stock.buffer), None)
-                stock.save_game(game_history, None)
+                if device:
+                    # the stock buffer's bookkeeping, replay_buffer.py:53-61, with T from the hand-off's lengths (its PER
+                    # branch :34-51 would read the game: the device columns are authoritative)
+                    stock.buffer[stock.num_played_games] = game_history
+                    stock.num_played_games += 1
+                    stock.num_played_steps += view[2]
+                    stock.total_samples += view[2]
+                    if config.replay_buffer_size < len(stock.buffer):
+                        del_id = stock.num_played_games - len(stock.buffer)
+                        stock.total_samples -= positions_of(stock.buffer[del_id])
+                        del stock.buffer[del_id]
+                else:
+                    stock.save_game(game_history, None)
                 if oldest is not None and oldest not in stock.buffer and oldest in store:      # evicted by replay_buffer_size
                     store.drop(oldest)
                 game_id = stock.num_played_games - 1
                 self._store_reserve(game_id, view[2])
-                pending.append(((game_id, game_history), view))
+                pending.append(((game_id, game_history), view, device))
         finally:
             flush()
         if self._arrays and stock.buffer:

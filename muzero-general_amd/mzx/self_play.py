@@ -151,6 +151,7 @@ class SelfPlay:
         exchange by every rank, ``finish`` drains the sequence.  This rank's games are seeded ``seed + i`` with ``seed`` =
         ``shard_seeds(config.seed, num_games)[0]`` (muzero.py:185).
         """
+        native_rounds.check_handoff_buffer(self.config, replay_buffer)      # (config.device_handoff: a local device buffer)
         sharded = hasattr(shared_storage, "refresh")
         get = (shared_storage.get_info if sharded else (lambda key: _remote(shared_storage.get_info, key)))
         if sharded:
@@ -615,6 +616,8 @@ class SelfPlay:
         Batched games need the optional ``reset_games(idx)`` hook; without it, and for a single-game actor, this falls
         back to ``play_games``.
         """
+        if native_rounds.handoff_wanted(self.config):
+            native_rounds.check_handoff(self)       # (NotImplementedError without config.device_games)
         if native_rounds.resident_wanted(self.config):
             native_rounds.check_resident(self)      # (NotImplementedError for what the resident loop does not cover)
         if self.bank is None or (self.batched_game is not None and not hasattr(self.batched_game, "reset_games")):
