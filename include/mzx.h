@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 6
+#define MZX_ABI_VERSION 7
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -919,6 +919,54 @@ typedef struct mzx_train_fc_io {
 int mzx_train_fc_supported(const mzx_net* net, int32_t batch, int32_t steps);
 int64_t mzx_train_fc_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps);
 int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * One training step of a RESIDUAL network up to and including loss.backward() (csrc/mzx_train_resnet.h):
+ * Trainer.update_weights (trainer.py:168-262) for MuZeroResidualNetwork (models.py:300-623, downsample = False) in
+ * TRAINING mode -- BatchNorm normalises with the statistics of the batch, per application of a shared network -- as
+ * launches on one stream, no atomics: the same bits on every run.  The convolutions and Linear layers are implicit GEMMs
+ * on the FP32 matrix pipes.  The fields of mzx_train_fc_io keep their meaning (d_observation [B][C_in][H][W]); in addition
+ *   out: d_stats [mzx_train_resnet_stat_floats(net)]: the running statistics AFTER the step, computed from those in
+ *        d_flat: for BatchNorm i in the order of the state_dict, running_mean [C_i] then running_var [C_i], the
+ *        BatchNorms behind one another.  The applications of a network fold in forward order (momentum 0.1, the
+ *        variance unbiased); a network that is not applied (steps = 1: dynamics) keeps its bits.
+ *   d_grad_flat holds exact zeros in the spans of running_mean / running_var.
+ *   min / max of the state normalisation hand their gradient to the lowest index on an exact tie.
+ * mzx_train_resnet_supported: 0 for a fully connected network, a network with a downsample stem, a network without
+ * residual blocks, and batch x board < 2 (BatchNorm needs more than one value per channel).
+ * mzx_train_resnet_launches: how many launches (kernels and small device-to-device copies) a step makes; 0 if unsupported.
+ * mzx_train_resnet_commit_stats: scatter d_stats into the running_mean / running_var spans of d_flat_out (the step after
+ * optimizer.step(): whatever the optimizer did to those spans is overwritten); follow it with mzx_net_set_weights.
+ * mzx_train_resnet_step returns MZX_ERR_INVALID -- before anything is launched -- for batch / steps < 1, a missing
+ * required pointer, a short or misaligned scratch buffer or an unsupported network.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_train_resnet_io {
+  const float* d_flat;
+  const float* d_observation;
+  const int32_t* d_action;
+  const float* d_target_value;
+  const float* d_target_reward;
+  const float* d_target_policy;
+  const float* d_gradient_scale;
+  const float* d_weight;           /* nullable */
+  int32_t batch, steps;
+  double value_loss_weight, per_alpha;
+  float* d_grad_flat;
+  float* d_losses;
+  float* d_priorities;
+  float* d_value_logits;           /* nullable */
+  float* d_reward_logits;          /* nullable */
+  float* d_policy_logits;          /* nullable */
+  void* d_scratch;
+  int64_t scratch_bytes;
+  float* d_stats;
+} mzx_train_resnet_io;
+int mzx_train_resnet_supported(const mzx_net* net, int32_t batch, int32_t steps);
+int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps);
+int64_t mzx_train_resnet_stat_floats(const mzx_net* net);
+int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps);
+int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, void* stream);
+int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of

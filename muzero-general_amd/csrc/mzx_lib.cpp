@@ -19,6 +19,7 @@
 #include "mzx_selfplay.h"
 #include "mzx_trainer.h"
 #include "mzx_train_fc.h"
+#include "mzx_train_resnet.h"
 #include "mzx_tree_carry.h"
 #ifndef MZX_HOSTCHECK
 #include "mzx_fused_fc.h"
@@ -1601,6 +1602,95 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
   if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
   MZX_TRY_LAUNCH(fct_launch(p, 1, (stream_t)stream));
   MZX_TRY_LAUNCH(launch_waves<FCT_WAVES>(FctWgradBody{p}, (stream_t)stream));
+  return MZX_OK;
+}
+
+// ------------------------------------------------------------- a training step of a residual network (csrc/mzx_train_resnet.h)
+
+int mzx_train_resnet_supported(const mzx_net* net, int32_t batch, int32_t steps) {
+  RtnPlan plan;
+  return rtn_plan(net, batch, steps, true, true, true, plan) ? 1 : 0;
+}
+
+int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps) {
+  RtnPlan plan;
+  if (!rtn_plan(net, batch, steps, true, true, true, plan)) return 0;
+  return plan.total_floats * 4;
+}
+
+int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat_floats(net) : 0; }
+
+int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) {
+  RtnPlan plan;
+  if (!rtn_plan(net, batch, steps, true, true, true, plan)) return 0;
+  RtnRun run;
+  memset((void*)&run, 0, sizeof(run));
+  run.P = &plan; run.dry = true;
+  run.forward();
+  run.backward();
+  return run.launched + 2;      // (the two launches of the loss head)
+}
+
+int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, void* stream) {
+  if (!net || !io) { set_error("mzx_train_resnet_step: null argument"); return MZX_ERR_INVALID; }
+  if (io->batch < 1 || io->steps < 1) {
+    set_error("mzx_train_resnet_step: batch %d and steps %d must be positive", io->batch, io->steps);
+    return MZX_ERR_INVALID;
+  }
+  if (!io->d_flat || !io->d_observation || !io->d_action || !io->d_target_value || !io->d_target_reward || !io->d_target_policy ||
+      !io->d_gradient_scale || !io->d_grad_flat || !io->d_losses || !io->d_priorities || !io->d_scratch || !io->d_stats) {
+    set_error("mzx_train_resnet_step: missing buffer");
+    return MZX_ERR_INVALID;
+  }
+  RtnPlan P;
+  std::string why;
+  if (!rtn_plan(net, io->batch, io->steps, !io->d_value_logits, !io->d_reward_logits, !io->d_policy_logits, P, &why)) {
+    set_error("mzx_train_resnet_step: %s", why.c_str());
+    return MZX_ERR_INVALID;
+  }
+  if (io->scratch_bytes < P.total_floats * 4 || ((uintptr_t)io->d_scratch % 16) != 0) {
+    set_error("mzx_train_resnet_step: scratch needs %lld bytes, 16-byte aligned",
+              (long long)mzx_train_resnet_scratch_bytes(net, io->batch, io->steps));
+    return MZX_ERR_INVALID;
+  }
+  if (P.A < 1 || net->cfg.support_size < 0 || (int64_t)io->batch * io->steps >= ((int64_t)1 << 31)) {
+    set_error("mzx_train_resnet_step: shape out of range");
+    return MZX_ERR_INVALID;
+  }
+  float* scratch = (float*)io->d_scratch;
+  RtnRun run;
+  memset((void*)&run, 0, sizeof(run));
+  run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
+  run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
+  run.vlog = io->d_value_logits ? io->d_value_logits : scratch + P.off_vlog;
+  run.rlog = io->d_reward_logits ? io->d_reward_logits : scratch + P.off_rlog;
+  run.plog = io->d_policy_logits ? io->d_policy_logits : scratch + P.off_plog;
+  mzx_trainer_loss_io lio;
+  memset(&lio, 0, sizeof(lio));
+  lio.d_value_logits = run.vlog; lio.d_reward_logits = run.rlog; lio.d_policy_logits = run.plog;
+  lio.d_target_value = io->d_target_value; lio.d_target_reward = io->d_target_reward; lio.d_target_policy = io->d_target_policy;
+  lio.d_gradient_scale = io->d_gradient_scale; lio.d_weight = io->d_weight;
+  lio.batch = io->batch; lio.steps = io->steps; lio.support_size = net->cfg.support_size; lio.num_actions = P.A;
+  lio.value_loss_weight = io->value_loss_weight; lio.per_alpha = io->per_alpha;
+  lio.d_losses = io->d_losses; lio.d_priorities = io->d_priorities;
+  lio.d_grad_value = scratch + P.off_gv; lio.d_grad_reward = scratch + P.off_gr; lio.d_grad_policy = scratch + P.off_gp;
+  lio.d_scratch = scratch + P.off_loss; lio.scratch_bytes = mzx_trainer_loss_scratch_bytes(io->batch, io->steps);
+  run.forward();
+  MZX_TRY_LAUNCH(run.rc);
+  if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
+  run.backward();
+  MZX_TRY_LAUNCH(run.rc);
+  return MZX_OK;
+}
+
+int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream) {
+  if (!net || !d_stats || !d_flat_out) { set_error("mzx_train_resnet_commit_stats: null argument"); return MZX_ERR_INVALID; }
+  int64_t at = 0;
+  for (const BnRef& b : net->bns) {
+    if (b.var != b.mean + b.channels) { set_error("mzx_train_resnet_commit_stats: unexpected weight table"); return MZX_ERR_INVALID; }
+    MZX_TRY_LAUNCH(copy_d2d(d_flat_out + b.mean, d_stats + at, sizeof(float) * 2 * b.channels, (stream_t)stream));
+    at += 2 * (int64_t)b.channels;
+  }
   return MZX_OK;
 }
 

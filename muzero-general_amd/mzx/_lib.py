@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 6
+ABI_VERSION = 7
 MOVE_NO_SYNC = 1
 PIECE_INFO_WORDS = 16
 
@@ -206,6 +206,11 @@ class TrainFcIO(ctypes.Structure):
     ]
 
 
+class TrainResnetIO(ctypes.Structure):
+    """``mzx_train_resnet_io``: ``mzx_train_fc_io`` plus the output of the running statistics after the step."""
+    _fields_ = TrainFcIO._fields_ + [("d_stats", c_vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mzx.h declares
 PROTOTYPES = {
     "mzx_abi_version": (ctypes.c_int, []),
@@ -302,6 +307,12 @@ PROTOTYPES = {
     "mzx_train_fc_supported": (ctypes.c_int, [c_vp, c_i32, c_i32]),
     "mzx_train_fc_scratch_bytes": (c_i64, [c_vp, c_i32, c_i32]),
     "mzx_train_fc_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TrainFcIO), c_vp]),
+    "mzx_train_resnet_supported": (ctypes.c_int, [c_vp, c_i32, c_i32]),
+    "mzx_train_resnet_scratch_bytes": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_train_resnet_stat_floats": (c_i64, [c_vp]),
+    "mzx_train_resnet_launches": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_train_resnet_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TrainResnetIO), c_vp]),
+    "mzx_train_resnet_commit_stats": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

@@ -11,10 +11,11 @@ Same names, arguments and return conventions as /root/reference/models.py:
 All arithmetic runs in the gfx950 kernels behind include/mzx.h; this module only
 owns device buffers (torch tensors) and the flat weight buffer that RCCL
 broadcasts.  Training: ``parameters()`` yields that buffer as ONE leaf parameter, so a
-torch optimizer updates the weights self-play searches on; for fully connected networks
-``mzx.trainer.update_weights`` / ``train_step`` fill its ``.grad`` with one
-``mzx_train_fc_step`` call (csrc/mzx_train_fc.h).  There is no autograd graph through
-``initial_inference`` / ``recurrent_inference``; residual networks train through torch.
+torch optimizer updates the weights self-play searches on; ``mzx.trainer.update_weights`` /
+``train_step`` fill its ``.grad`` with one ``mzx_train_fc_step`` call (csrc/mzx_train_fc.h) for
+fully connected networks, one ``mzx_train_resnet_step`` call (csrc/mzx_train_resnet.h, BatchNorm
+on batch statistics) for residual ones.  There is no autograd graph through
+``initial_inference`` / ``recurrent_inference``.
 """
 import collections
 import ctypes
@@ -260,6 +261,10 @@ class HipNetwork:
     def eval(self):
         return self
 
+    def train(self, mode=True):
+        """trainer.py:29 -- the training kernels always use batch statistics, inference always the running ones."""
+        return self
+
     def parameters(self):
         """The flat weight buffer as ONE ``torch.nn.Parameter`` (it shares ``flat_weights()``'s storage).  Adam and SGD
         are elementwise and the reference applies weight decay to every tensor, so an optimizer over this parameter
@@ -269,6 +274,10 @@ class HipNetwork:
     def train_fc_supported(self, batch, steps):
         """Whether ``mzx_train_fc_step`` runs this network at ``batch`` samples x ``steps`` (= num_unroll_steps + 1)."""
         return bool(self.backend.lib.mzx_train_fc_supported(self.handle, int(batch), int(steps)))
+
+    def train_resnet_supported(self, batch, steps):
+        """Whether ``mzx_train_resnet_step`` runs this network at ``batch`` samples x ``steps`` (= num_unroll_steps + 1)."""
+        return bool(self.backend.lib.mzx_train_resnet_supported(self.handle, int(batch), int(steps)))
 
     def state_dict(self):
         out = collections.OrderedDict()

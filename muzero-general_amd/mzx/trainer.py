@@ -22,7 +22,10 @@ of the package there is no CPU execution path: without the library or a GPU the 
 With a ``mzx.models.HipNetwork`` of a fully connected configuration as ``model`` the network is the library's too: the
 prediction loop, the loss head and ``loss.backward()`` are ONE ``mzx_train_fc_step`` call (csrc/mzx_train_fc.h, five
 launches) that writes ``.grad`` of the network's flat parameter; ``optimizer.step()`` then updates the very buffer self-play
-searches on and RCCL broadcasts.  ``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
+searches on and RCCL broadcasts.  A residual ``HipNetwork`` (no downsample stem) takes the same route through
+``mzx_train_resnet_step`` (csrc/mzx_train_resnet.h): BatchNorm in training mode, the convolutions as implicit GEMMs on the
+FP32 matrix pipes; after ``optimizer.step()`` the new running statistics are committed into the flat buffer.
+``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
 convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """
 import collections
@@ -162,9 +165,9 @@ def update_weights(model, optimizer, batch, config, backend=None):
     the reference's, the 0.5 hook on the hidden state included; the loss head is ``muzero_loss``.  Returns the
     reference's tuple ``(priorities float32 numpy [batch, K + 1], loss, value_loss, reward_loss, policy_loss)`` after ONE
     download -- ``ReplayBuffer.update_priorities`` takes the array unchanged.  The caller advances ``training_step``.
-    A ``HipNetwork`` (fully connected) takes the native path: ``mzx_train_fc_step`` writes the gradient of its flat
-    parameter, then ``optimizer.step()`` and ``model.refresh_derived()``; one the kernels do not run raises
-    ``NotImplementedError``.
+    A ``HipNetwork`` takes the native path: ``mzx_train_fc_step`` (fully connected) or ``mzx_train_resnet_step``
+    (residual) writes the gradient of its flat parameter, then ``optimizer.step()`` and ``model.refresh_derived()``; one
+    the kernels do not run raises ``NotImplementedError``.
     """
     packed, batch_size = _sgd_step(model, optimizer, batch, config, backend)
     host = packed.cpu().numpy()
@@ -176,6 +179,16 @@ def _sgd_step(model, optimizer, batch, config, backend):
     """The prediction loop, ``muzero_loss`` and one optimizer step of ``update_weights``: (packed [4 + B * steps] on the
     device -- the four losses, then the priorities --, B).  Nothing is downloaded."""
     if isinstance(model, models.HipNetwork):
+        if model._cfg.network != 0:
+            # parameters() is the one flat leaf, running_mean / running_var included: their gradient spans are exact
+            # zeros, and the commit AFTER the optimizer step overwrites whatever it did to them (weight decay) with the
+            # statistics computed from the pre-step values -- the reference never decays a buffer
+            stats = {}
+            packed = train_resnet_gradients(model, batch, config, stats=stats)
+            optimizer.step()
+            commit_running_stats(model, stats["running"], stats["applications"])
+            model.refresh_derived()
+            return packed, len(batch[2])
         packed = train_fc_gradients(model, batch, config)
         optimizer.step()
         model.refresh_derived()
@@ -254,6 +267,86 @@ def train_fc_gradients(model, batch, config, logits=None):
     return packed
 
 
+TRAIN_SCRATCH_MAX_BYTES = 32 << 30
+
+
+def train_resnet_gradients(model, batch, config, logits=None, stats=None):
+    """
+    The twin of ``train_fc_gradients`` for a residual ``HipNetwork``: ``Trainer.update_weights`` lines 168-262 in
+    ``model.train()`` mode (BatchNorm on batch statistics) as one ``mzx_train_resnet_step`` call.  ``.grad`` of
+    ``next(model.parameters())`` is OVERWRITTEN (exact zeros in the spans of ``running_mean`` / ``running_var``).
+    Returns the packed device tensor [4 + B * steps].  ``logits``: an optional dict that receives the step-major logits.
+    ``stats``: an optional dict that receives ``running`` (the packed running statistics after the step, computed from
+    those in the flat buffer; ``commit_running_stats`` writes them into it) and ``applications`` (per network prefix, how
+    often it was applied: what ``num_batches_tracked`` rises by).  Nothing synchronises.  A step whose scratch exceeds
+    ``config.train_scratch_max_bytes`` (default 32 GiB) raises ``NotImplementedError``.
+    """
+    be, lib = model.backend, model.backend.lib
+    (observation, action, target_value, target_reward, target_policy, weight,
+     scale) = replay.trainer_tensors(batch, be.device)
+    if not config.PER:
+        weight = None
+    batch_size, steps = target_value.shape
+    if not lib.mzx_train_resnet_supported(model.handle, batch_size, steps):
+        cfg = model._cfg
+        limit = ("fully connected networks train through mzx_train_fc_step (residual networks only)" if cfg.network != 1 else
+                 "downsample stems (the strided convolutions and pools) are not trained natively" if cfg.downsample else
+                 "the training kernels need at least one residual block per network" if cfg.blocks < 1 else
+                 "BatchNorm in training mode needs more than one value per channel (batch x board >= 2)")
+        raise NotImplementedError(f"mzx_train_resnet_step does not run this network at batch {batch_size} x {steps} steps: {limit}")
+    scratch_bytes = int(lib.mzx_train_resnet_scratch_bytes(model.handle, batch_size, steps))
+    most = int(getattr(config, "train_scratch_max_bytes", TRAIN_SCRATCH_MAX_BYTES))
+    if scratch_bytes > most:
+        raise NotImplementedError(f"mzx_train_resnet_step at batch {batch_size} x {steps} steps keeps {scratch_bytes} bytes of "
+                                  f"activations, more than config.train_scratch_max_bytes = {most}")
+    observation = observation.reshape(batch_size, -1).contiguous()
+    actions = model.action_space_size
+    if (observation.shape[1] != model.input_size or action.numel() != batch_size * steps
+            or target_reward.shape != (batch_size, steps) or scale.shape != (batch_size, steps)
+            or target_policy.shape != (batch_size, steps, actions) or (weight is not None and weight.shape != (batch_size,))):
+        raise ValueError(f"batch: expected observation [batch, {model.input_size}], action / value / reward / gradient scale "
+                         f"[batch, steps], policy [batch, steps, {actions}], weight [batch]")
+    action = action.reshape(batch_size, steps).to(torch.int32).contiguous()
+    tensors = [t.contiguous() for t in (target_value, target_reward, target_policy, scale)]
+    param = next(model.parameters())
+    if param.grad is None:
+        param.grad = torch.zeros_like(model.flat_weights())
+    packed = be.empty((4 + batch_size * steps,), torch.float32)
+    scratch = be.empty((scratch_bytes // 4,), torch.float32)
+    running = be.empty((int(lib.mzx_train_resnet_stat_floats(model.handle)),), torch.float32)
+    io = _lib.TrainResnetIO()
+    io.d_flat, io.d_observation, io.d_action = model.flat_weights().data_ptr(), observation.data_ptr(), action.data_ptr()
+    io.d_target_value, io.d_target_reward, io.d_target_policy, io.d_gradient_scale = (t.data_ptr() for t in tensors)
+    io.d_weight = None if weight is None else weight.contiguous().data_ptr()
+    io.batch, io.steps = batch_size, steps
+    io.value_loss_weight, io.per_alpha = float(config.value_loss_weight), float(config.PER_alpha)
+    io.d_grad_flat, io.d_losses, io.d_priorities = param.grad.data_ptr(), packed.data_ptr(), packed[4:].data_ptr()
+    if logits is not None:
+        width = model.full_support_size
+        logits["value"], logits["reward"] = (be.empty((steps, batch_size, width), torch.float32) for _ in range(2))
+        logits["policy"] = be.empty((steps, batch_size, actions), torch.float32)
+        io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (logits[k].data_ptr() for k in ("value", "reward", "policy"))
+    io.d_scratch, io.scratch_bytes = scratch.data_ptr(), scratch_bytes
+    io.d_stats = running.data_ptr()
+    lib.check(lib.mzx_train_resnet_step(model.handle, ctypes.byref(io), be.stream()))
+    if stats is not None:
+        stats["running"] = running
+        stats["applications"] = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
+    return packed
+
+
+def commit_running_stats(model, running, applications):
+    """Write the running statistics of ``train_resnet_gradients`` into the flat buffer (``mzx_train_resnet_commit_stats``) and
+    raise every ``num_batches_tracked`` by its network's application count.  Call ``model.refresh_derived()`` after it."""
+    be, lib = model.backend, model.backend.lib
+    lib.check(lib.mzx_train_resnet_commit_stats(model.handle, be.ptr(running), be.ptr(model.flat_weights()), be.stream()))
+    for key, *_ in model._tensors:
+        if key.endswith(".running_var"):
+            nbt = key[: -len("running_var")] + "num_batches_tracked"
+            count = next(n for prefix, n in applications.items() if key.startswith(prefix))
+            model._num_batches_tracked[nbt] = model._num_batches_tracked.get(nbt, torch.zeros((), dtype=torch.int64)) + count
+
+
 def update_lr(optimizer, config, training_step):
     """``Trainer.update_lr`` (trainer.py:275-283) with ``self`` unbound."""
     lr = config.lr_init * config.lr_decay_rate ** (training_step / config.lr_decay_steps)
@@ -262,8 +355,10 @@ def update_lr(optimizer, config, training_step):
 
 
 def _tensor_table(net):
-    """(key, offset, numel, shape) of every tensor of the flat buffer (``mzx_net_tensor_info``)."""
-    return list(net._tensors)
+    """(key, offset, numel, shape) of every tensor of the flat buffer (``mzx_net_tensor_info``) that is a PARAMETER in the
+    reference: ``running_mean`` / ``running_var`` are buffers there, so index i below is the reference's ``parameters()``
+    index (a fully connected network has no buffers)."""
+    return [t for t in net._tensors if not t[0].endswith((".running_mean", ".running_var"))]
 
 
 def optimizer_state(optimizer, net):
@@ -305,7 +400,7 @@ def load_optimizer_state(optimizer, net, state_dict):
         entry = collections.OrderedDict()
         for key, first in per_param[0].items():
             if torch.is_tensor(first) and tuple(first.shape) == tuple(table[0][3]) and first.dim() > 0:
-                joined = torch.empty(net.num_params, dtype=first.dtype, device=device)
+                joined = torch.zeros(net.num_params, dtype=first.dtype, device=device)      # (the buffers' spans: no state)
                 for i, (_, off, numel, shape) in enumerate(table):
                     piece = per_param[i][key]
                     if tuple(piece.shape) != tuple(shape):

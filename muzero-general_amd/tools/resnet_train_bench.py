@@ -1,0 +1,100 @@
+"""
+One training step of a residual network (Adam) on the GPU, at the shipped batch shapes of tic-tac-toe (64 x 21 steps) and
+connect4 (64 x 43 steps):
+
+  torch_ms    the only path before the native one: mzx.trainer.update_weights with the torch restatement of the network
+              (tests/resnet_train_cases.ResNetwork, training mode) on the device -- torch's convolutions forward and
+              backward, the fused loss head, torch Adam over the per-tensor parameters;
+  native_ms   mzx.trainer.update_weights with a residual HipNetwork: mzx_train_resnet_step, torch Adam on the flat
+              parameter, the statistics commit, refresh_derived.
+
+    python muzero-general_amd/tools/resnet_train_bench.py [--out profiles/resnet_train_bench.log] [--quick] [--shape NAME]
+
+Both legs run in one process and alternate block by block (host clock around calls that end in update_weights' one
+download, i.e. a synchronise); medians of 7 blocks after a warm-up, with the minimum and maximum.  `launches` is what
+mzx_train_resnet_launches reports for the native step (kernels and the small statistics copies), `scratch_bytes` what
+mzx_train_resnet_scratch_bytes asks for.  A gain (either way) counts only beyond the larger of the two legs' spreads.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, "muzero-general_amd"), os.path.join(ROOT, "tests")]
+
+SHAPES = {"tictactoe": (64, 21), "connect4": (64, 43)}
+ADAM = dict(lr=0.003, weight_decay=1e-4)
+
+
+def legs(be, name):
+    import resnet_train_cases as cases
+    from mzx import configs, trainer
+
+    B, steps = SHAPES[name]
+    case = cases.case_of_config(getattr(configs, name)(), B, steps, name=name)
+    cfg = cases.config_of(case)
+    batch = tuple(None if x is None else torch.from_numpy(x).to(be.device) for x in cases.batch(case))
+    model = cases.load(cases.ResNetwork(case), cases.weights(case)).to(be.device).train()
+    opt_torch = torch.optim.Adam(model.parameters(), **ADAM)
+    net = cases.network(be, case)
+    opt_native = torch.optim.Adam(net.parameters(), **ADAM)
+    info = dict(launches=int(be.lib.mzx_train_resnet_launches(net.handle, B, steps)),
+                scratch_bytes=int(be.lib.mzx_train_resnet_scratch_bytes(net.handle, B, steps)))
+    return dict(torch=lambda: trainer.update_weights(model, opt_torch, batch, cfg),
+                native=lambda: trainer.update_weights(net, opt_native, batch, cfg)), info
+
+
+def measure(be, name, quick):
+    fns, info = legs(be, name)
+    blocks, iters = (3, 2) if quick else (7, 5)
+    times = dict(torch=[], native=[])
+    for leg in times:
+        for _ in range(2):
+            fns[leg]()
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for leg in times:
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fns[leg]()
+            torch.cuda.synchronize()
+            times[leg].append((time.perf_counter() - t0) * 1e3 / iters)
+    line = dict(shape=f"{name}_b{SHAPES[name][0]}_k{SHAPES[name][1]}", optimizer="Adam", blocks=blocks, steps_per_block=iters)
+    for leg, ts in times.items():
+        line[f"{leg}_ms"] = round(statistics.median(ts), 3)
+        line[f"{leg}_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+    line["torch_over_native"] = round(line["torch_ms"] / line["native_ms"], 3)
+    line.update(info)
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resnet_train_bench.log"))
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--shape", choices=sorted(SHAPES), action="append")
+    args = ap.parse_args()
+    from mzx import _lib
+
+    be = _lib.default_backend()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    head = (f"# resnet_train_bench: {torch.cuda.get_device_name(0)}, torch {torch.__version__}; one training step of the shipped "
+            "residual networks, Adam; torch_ms = update_weights with the torch network (training mode), native_ms = "
+            "update_weights with a HipNetwork (mzx_train_resnet_step); medians of alternating timed blocks [min, max], each "
+            "call ends in one download")
+    lines = [head]
+    print(head, flush=True)
+    for name in args.shape or ["tictactoe", "connect4"]:
+        lines.append(json.dumps(measure(be, name, args.quick)))
+        print(lines[-1], flush=True)
+    with open(args.out, "w") as log:
+        log.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

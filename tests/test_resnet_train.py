@@ -1,0 +1,282 @@
+"""
+Training a residual network natively (mzx_train_resnet_step, mzx.trainer.train_resnet_gradients / update_weights with a
+residual HipNetwork) on the serial test double of the ABI, against tests/golden/resnet_train.npz -- the unmodified
+reference's own step in .train() mode, float32 and binary64 (muzero-general_amd/tools/make_resnet_train_golden.py) -- and,
+where the reference tree is present, against it live.
+"""
+import ctypes
+
+import numpy
+import pytest
+import torch
+
+import fc_train_cases
+import hostcheck
+import resnet_train_cases as cases
+from mzx import _lib, configs, models, trainer
+from oracle import ref_shim
+
+
+@pytest.fixture(scope="module")
+def be():
+    return hostcheck.backend()
+
+
+@pytest.fixture(scope="module")
+def gold(golden_dir):
+    return cases.golden(golden_dir)
+
+
+@pytest.mark.parametrize("case", cases.CASES, ids=lambda c: c["name"])
+def test_logits_losses_priorities_gradients_statistics(be, gold, case):
+    cases.check_case(be, case, gold)
+
+
+def test_two_sgd_momentum_steps_weights_and_buffers(be, gold):
+    cases.check_sgd(be, cases.BY_NAME["c_b5_k4_stacked"], gold)
+
+
+def check_adam_bit_for_bit(be, case):
+    """Adam over the one flat parameter is Adam per tensor on the parameter spans, bit for bit; the spans of the running
+    statistics hold what the step committed, whatever Adam did to them."""
+    hp = dict(lr=0.02, weight_decay=1e-4)
+    net = cases.network(be, case)
+    before = net.flat_weights().clone()
+    optimizer = torch.optim.Adam(net.parameters(), **hp)
+    trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
+    grad = next(net.parameters()).grad
+    want = cases.adam_reference_step(net, grad, before, **hp)
+    state = net.state_dict()
+    committed = cases.run_native(be, case, cases.network(be, case))
+    for key, off, numel, shape in net._tensors:
+        got = state[key].cpu().numpy()
+        if cases.is_statistic(key):
+            assert numpy.array_equal(got.view(numpy.int32), committed["stat/" + key].view(numpy.int32)), key
+        else:
+            assert not torch.equal(state[key].cpu(), before[off:off + numel].reshape(shape).cpu()), key
+            assert numpy.array_equal(got.view(numpy.int32), want[key].cpu().numpy().view(numpy.int32)), key
+
+
+def test_adam_on_the_flat_parameter_is_adam_per_tensor(be):
+    check_adam_bit_for_bit(be, cases.BY_NAME["c_b5_k4_stacked"])
+
+
+def test_num_batches_tracked_and_train_returns_self(be):
+    case = cases.BY_NAME["b_b3_k3"]
+    net = cases.network(be, case)
+    assert net.train() is net and net.eval() is net
+    optimizer = torch.optim.SGD(net.parameters(), lr=0.01)
+    for _ in range(3):
+        trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
+    counts = {k: int(v) for k, v in net.get_weights().items() if k.endswith("num_batches_tracked")}
+    assert counts and len(counts) == sum(k.endswith("running_var") for k in net.get_weights())
+    for key, value in counts.items():
+        per_step = 1 if key.startswith("representation") else case["steps"] - 1 if key.startswith("dynamics") else case["steps"]
+        assert value == 3 * per_step, (key, value)
+
+
+def check_optimizer_state_round_trip(be, case, make):
+    net = cases.network(be, case)
+    optimizer = make(net.parameters())
+    for _ in range(2):
+        trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
+    state = trainer.optimizer_state(optimizer, net)
+    table = [t for t in net._tensors if not cases.is_statistic(t[0])]
+    assert len(table) < len(net._tensors)
+    assert sorted(state["state"]) == list(range(len(table)))
+    assert state["param_groups"][0]["params"] == list(range(len(table)))
+    for i, (_, _, _, shape) in enumerate(table):
+        for value in state["state"][i].values():
+            assert not torch.is_tensor(value) or value.dim() == 0 or tuple(value.shape) == tuple(shape)
+    twin_net = cases.network(be, case)
+    twin = make(twin_net.parameters())
+    trainer.load_optimizer_state(twin, twin_net, state)
+    again = trainer.optimizer_state(twin, twin_net)
+    assert again["param_groups"] == state["param_groups"] and sorted(again["state"]) == sorted(state["state"])
+    for i in state["state"]:
+        assert list(again["state"][i]) == list(state["state"][i])
+        for key, value in state["state"][i].items():
+            other = again["state"][i][key]
+            assert torch.equal(value, other) if torch.is_tensor(value) else value == other, (i, key)
+    return state
+
+
+@pytest.mark.parametrize("kind", ["sgd", "adam"])
+def test_optimizer_state_round_trip(be, kind):
+    make = ((lambda p: torch.optim.SGD(p, lr=0.05, momentum=0.9, weight_decay=1e-4)) if kind == "sgd" else
+            (lambda p: torch.optim.Adam(p, lr=0.02, weight_decay=1e-4)))
+    check_optimizer_state_round_trip(be, cases.BY_NAME["c_b5_k4_stacked"], make)
+
+
+def test_supported_shapes_and_the_limits(be):
+    lib = be.lib
+    for case in cases.CASES:
+        net = cases.network(be, case)
+        assert lib.mzx_train_resnet_supported(net.handle, case["B"], case["steps"]) == 1 and net.train_resnet_supported(case["B"], case["steps"])
+        assert lib.mzx_train_resnet_scratch_bytes(net.handle, case["B"], case["steps"]) > 0
+        assert lib.mzx_train_resnet_launches(net.handle, case["B"], case["steps"]) > 0
+        assert lib.mzx_train_resnet_stat_floats(net.handle) == sum(n for k, _, n, _ in net._tensors if cases.is_statistic(k))
+        assert lib.mzx_train_resnet_supported(net.handle, 0, 3) == 0 and lib.mzx_train_resnet_supported(net.handle, 3, 0) == 0
+        assert lib.mzx_train_fc_supported(net.handle, case["B"], case["steps"]) == 0          # the other entry keeps refusing
+    for game, B, steps in ((configs.tictactoe(), 64, 21), (configs.connect4(), 64, 43)):
+        assert models.MuZeroNetwork(game, _backend=be).train_resnet_supported(B, steps)
+    # a downsample stem, a fully connected network, one value per channel
+    breakout = models.MuZeroNetwork(configs.breakout(), _backend=be)
+    assert lib.mzx_train_resnet_supported(breakout.handle, 4, 3) == 0 and lib.mzx_train_resnet_scratch_bytes(breakout.handle, 4, 3) == 0
+    fc = fc_train_cases.network(be, fc_train_cases.CASES[1])
+    assert lib.mzx_train_resnet_supported(fc.handle, 3, 3) == 0 and lib.mzx_train_resnet_launches(fc.handle, 3, 3) == 0
+    with pytest.raises(NotImplementedError, match="fully connected"):
+        trainer.train_resnet_gradients(fc, fc_train_cases.batch(fc_train_cases.CASES[1]), fc_train_cases.config_of(fc_train_cases.CASES[1]))
+    one = dict(cases.BY_NAME["a_b2_k1"], B=1, obs=(2, 1, 1))
+    net = models.MuZeroNetwork(cases.config_of(one), _backend=be)
+    assert lib.mzx_train_resnet_supported(net.handle, 1, 1) == 0 and lib.mzx_train_resnet_supported(net.handle, 2, 1) == 1
+    with pytest.raises(NotImplementedError, match="more than one value per channel"):
+        trainer.update_weights(net, torch.optim.SGD(net.parameters(), lr=0.1), cases.batch(one), cases.config_of(one))
+    assert lib.mzx_train_resnet_supported(None, 4, 3) == 0
+
+
+def test_downsample_is_refused_by_name(be):
+    cfg = configs.breakout(PER=True, PER_alpha=0.5, value_loss_weight=0.25)
+    net = models.MuZeroNetwork(cfg, _backend=be)
+    case = cases.case_of_config(cfg, 2, 2)
+    with pytest.raises(NotImplementedError, match="downsample"):
+        trainer.update_weights(net, torch.optim.SGD(net.parameters(), lr=0.1), cases.batch(case), cfg)
+
+
+def test_scratch_limit_names_the_attribute(be):
+    case = cases.BY_NAME["b_b3_k3"]
+    net = cases.network(be, case)
+    need = int(be.lib.mzx_train_resnet_scratch_bytes(net.handle, case["B"], case["steps"]))
+    with pytest.raises(NotImplementedError, match="train_scratch_max_bytes"):
+        trainer.train_resnet_gradients(net, cases.batch(case), cases.config_of(case, train_scratch_max_bytes=need - 1))
+    trainer.train_resnet_gradients(net, cases.batch(case), cases.config_of(case, train_scratch_max_bytes=need))
+    # gomoku as shipped (512 x 122) is far beyond the default of 32 GiB
+    gomoku = models.MuZeroNetwork(configs.gomoku(), _backend=be)
+    assert int(be.lib.mzx_train_resnet_scratch_bytes(gomoku.handle, 512, 122)) > trainer.TRAIN_SCRATCH_MAX_BYTES
+
+
+@pytest.mark.reference
+def test_the_board_games_of_the_reference_are_supported_at_their_shipped_shapes(be):
+    for name in ("tictactoe", "twentyone", "connect4"):
+        cfg = ref_shim.muzero_config(name)
+        assert cfg.network == "resnet"
+        net = models.MuZeroNetwork(cfg, _backend=be)
+        assert net.train_resnet_supported(cfg.batch_size, cfg.num_unroll_steps + 1), name
+    assert not models.MuZeroNetwork(ref_shim.muzero_config("breakout"), _backend=be).train_resnet_supported(4, 3)
+
+
+def _io(be, case, net, keep):
+    """A complete mzx_train_resnet_io over host tensors, outputs pre-filled with 7."""
+    observation, action, tv, tr, tp, weight, scale = cases.batch(case)
+    B, steps = case["B"], case["steps"]
+    t = dict(observation=torch.from_numpy(observation).reshape(B, -1).contiguous(), action=torch.from_numpy(action).to(torch.int32),
+             tv=torch.from_numpy(tv), tr=torch.from_numpy(tr), tp=torch.from_numpy(tp), scale=torch.from_numpy(scale),
+             grad=torch.full((net.num_params,), 7.0), losses=torch.full((4,), 7.0), priorities=torch.full((B, steps), 7.0),
+             stats=torch.full((int(be.lib.mzx_train_resnet_stat_floats(net.handle)),), 7.0))
+    nbytes = int(be.lib.mzx_train_resnet_scratch_bytes(net.handle, B, steps))
+    t["scratch"] = torch.full((max(nbytes, 16) // 4,), 7.0)
+    keep.append(t)
+    io = _lib.TrainResnetIO()
+    io.d_flat, io.d_observation, io.d_action = net.flat_weights().data_ptr(), t["observation"].data_ptr(), t["action"].data_ptr()
+    io.d_target_value, io.d_target_reward, io.d_target_policy = t["tv"].data_ptr(), t["tr"].data_ptr(), t["tp"].data_ptr()
+    io.d_gradient_scale = t["scale"].data_ptr()
+    io.batch, io.steps, io.value_loss_weight, io.per_alpha = B, steps, case["vlw"], case["alpha"]
+    io.d_grad_flat, io.d_losses, io.d_priorities = t["grad"].data_ptr(), t["losses"].data_ptr(), t["priorities"].data_ptr()
+    io.d_scratch, io.scratch_bytes, io.d_stats = t["scratch"].data_ptr(), nbytes, t["stats"].data_ptr()
+    return io, t
+
+
+REQUIRED = ("d_flat", "d_observation", "d_action", "d_target_value", "d_target_reward", "d_target_policy", "d_gradient_scale",
+            "d_grad_flat", "d_losses", "d_priorities", "d_scratch", "d_stats")
+BAD = [(f, None) for f in REQUIRED] + [("batch", 0), ("batch", -1), ("steps", 0), ("steps", -2), ("scratch_bytes", 64),
+                                       ("d_scratch", "misaligned")]
+OUTPUTS = ("grad", "losses", "priorities", "scratch", "stats")
+
+
+@pytest.mark.parametrize("field,value", BAD, ids=[f"{f}={v}" for f, v in BAD])
+def test_abi_refusals(be, field, value):
+    case, keep = cases.BY_NAME["b_b3_k3"], []
+    net = cases.network(be, case)
+    io, t = _io(be, case, net, keep)
+    setattr(io, field, t["scratch"].data_ptr() + 4 if value == "misaligned" else value)
+    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), None) == -1        # MZX_ERR_INVALID
+    assert be.lib.mzx_last_error()
+    for key in OUTPUTS:                                                                    # nothing was launched
+        assert (t[key] == 7.0).all(), key
+    io, t = _io(be, case, net, keep)                                                       # (the untouched struct is accepted)
+    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), None) == 0
+    assert not (t["losses"] == 7.0).any() and not (t["grad"] == 7.0).any() and not (t["stats"] == 7.0).any()
+
+
+def test_abi_refuses_unsupported_networks_and_null_arguments(be):
+    case, keep = cases.BY_NAME["b_b3_k3"], []
+    net = cases.network(be, case)
+    io, t = _io(be, case, net, keep)
+    fc = fc_train_cases.network(be, fc_train_cases.CASES[1])
+    assert be.lib.mzx_train_resnet_step(fc.handle, ctypes.byref(io), None) == -1
+    assert "fully connected" in be.lib.mzx_last_error().decode()
+    breakout = models.MuZeroNetwork(configs.breakout(), _backend=be)
+    assert be.lib.mzx_train_resnet_step(breakout.handle, ctypes.byref(io), None) == -1
+    assert "downsample" in be.lib.mzx_last_error().decode()
+    assert be.lib.mzx_train_resnet_step(None, ctypes.byref(io), None) == -1
+    assert be.lib.mzx_train_resnet_step(net.handle, None, None) == -1
+    assert be.lib.mzx_train_resnet_commit_stats(net.handle, None, net.flat_weights().data_ptr(), None) == -1
+    for key in OUTPUTS:
+        assert (t[key] == 7.0).all(), key
+
+
+@pytest.mark.reference
+@pytest.mark.parametrize("case", [c for c in cases.CASES if c["steps"] > 1], ids=lambda c: c["name"])
+def test_torch_restatement_is_the_reference(case):
+    """resnet_train_cases.ResNetwork in training mode makes the gradients and the running statistics of the reference's
+    Trainer.update_weights on models.MuZeroNetwork, bit for bit, on this host."""
+    import types
+
+    import trainer_loss_cases
+
+    ref_models, _ = ref_shim.load()
+    import trainer as ref_trainer      # the reference's trainer.py, under the shim's ray stub
+    theirs = ref_models.MuZeroNetwork(cases.config_of(case)).train()
+    ours = cases.load(cases.ResNetwork(case), cases.weights(case)).train()
+    assert list(ours.state_dict()) == list(theirs.state_dict())
+    theirs.load_state_dict(ours.state_dict())
+
+    class NoOptimizer:
+        zero_grad = step = lambda self: None
+
+    me = types.SimpleNamespace(model=theirs, optimizer=NoOptimizer(), config=cases.config_of(case), training_step=0,
+                               loss_function=ref_trainer.Trainer.loss_function)
+    want = ref_trainer.Trainer.update_weights(me, cases.batch(case))
+    got = trainer_loss_cases.torch_update_weights(ours, NoOptimizer(), cases.batch(case), cases.config_of(case))
+    assert got[1] == want[1]
+    for (key, a), b in zip(ours.named_parameters(), theirs.parameters()):
+        assert numpy.array_equal(a.grad.numpy().view(numpy.int32), b.grad.numpy().view(numpy.int32)), key
+    for (key, a), b in zip(ours.named_buffers(), theirs.buffers()):
+        assert torch.equal(a, b), key
+
+
+@pytest.mark.reference
+def test_optimizer_state_keys_are_the_reference_optimizers(be):
+    case = cases.BY_NAME["c_b5_k4_stacked"]
+    ref_models, _ = ref_shim.load()
+    theirs = ref_models.MuZeroNetwork(cases.config_of(case))
+    for kind in ("sgd", "adam"):
+        make = ((lambda p: torch.optim.SGD(p, lr=0.05, momentum=0.9, weight_decay=1e-4)) if kind == "sgd" else
+                (lambda p: torch.optim.Adam(p, lr=0.02, weight_decay=1e-4)))
+        reference = make(theirs.parameters())
+        for p in theirs.parameters():
+            p.grad = torch.ones_like(p)
+        reference.step()
+        want = reference.state_dict()
+        got = check_optimizer_state_round_trip(be, case, make)
+        assert sorted(got["state"]) == sorted(want["state"])
+        assert got["param_groups"][0].keys() == want["param_groups"][0].keys()
+        assert got["param_groups"][0]["params"] == want["param_groups"][0]["params"]
+        for i in want["state"]:
+            assert list(got["state"][i]) == list(want["state"][i])
+            for key, value in want["state"][i].items():
+                mine = got["state"][i][key]
+                assert torch.is_tensor(mine) == torch.is_tensor(value)
+                if torch.is_tensor(value):
+                    assert mine.shape == value.shape and mine.dtype == value.dtype, (i, key)
+        reference.load_state_dict(got)          # and the reference's optimizer takes it
