@@ -528,6 +528,10 @@ struct LdsNet {
     W = (const float*)(smem + args.lds_weights);
     a = &args;
   }
+  // fc2_search_kernel's launch prologue (see SmallNet): the weights go through stage(), the observation is read layer by
+  // layer from global memory (its length is a launch argument, not a register count) -- nothing to hold in a lane
+  __device__ __forceinline__ void request(const FusedFcArgs&, int, const float*, bool) {}
+  __device__ __forceinline__ void attach(const FusedFcArgs& args, char* smem) { setup(args, smem, 0); }
 
   // One Linear layer for the neurons o0, o0 + 16, ..., o0 + 16 (G - 1) of this lane (G = 1, 2 or 4 by the layer's
   // width): the input value x[k] is loaded once and feeds G independent fmaf chains, so wide layers (the 64-wide
@@ -626,6 +630,9 @@ struct LdsNet {
     mlp(a->rep, obs, s0, s1, s4, sub, 0, 0);
     scale(s4, h_out, a->E, sub);
     heads(h_out, scr, sub, o);
+  }
+  __device__ __forceinline__ void initial_requested(const float* obs, float* h_out, float* scr, int sub, NetOut& o) const {
+    initial(obs, h_out, scr, sub, o);
   }
   __device__ __forceinline__ void recurrent(const float* h_in, int action, float* h_out, float* scr, int sub,
                                             NetOut& o) const {
@@ -787,10 +794,17 @@ __device__ __forceinline__ void dot2_bcast(float x, const float (&u)[K], const f
 
 template <int K>
 __device__ __forceinline__ void load_row(float (&w)[K], float& b, const float* flat, int woff, int boff, int o, int O) {
+  // No guard on the reads (the pattern of fc2_load_lane): a lane without a neuron reads the layer's LAST row, which is in
+  // range, and selects zeros -- the K + 1 requests of a row are straight-line code, no exec round trip per chunk.
   const bool ok = o < O;
+  const int r = ok ? o : O - 1;
 #pragma unroll
-  for (int k = 0; k < K; ++k) w[k] = ok ? flat[woff + o * K + k] : 0.f;
-  b = ok ? flat[boff + o] : 0.f;
+  for (int k = 0; k < K; ++k) {
+    const float v = flat[woff + r * K + k];
+    w[k] = ok ? v : 0.f;
+  }
+  const float bv = flat[boff + r];
+  b = ok ? bv : 0.f;
 }
 
 // rep: IN -> E (no hidden layer); dyn: E+A -> HD -> E; rew: E -> HR -> F; pol: E -> HP -> A; val: E -> HV -> F
@@ -803,6 +817,7 @@ struct SmallNet {
   float w_p1[E], b_p1, w_p2[HP], b_p2;
   float w_v1[E], b_v1, w_v2a[HV], b_v2a, w_v2b[HV], b_v2b;
   int support;
+  float obs_r[IN];   // the tree's observation row (request; fc2_search_kernel only)
 
   static bool matches(const FusedFcArgs& a) {
     const int Fa = 2 * a.p.support_size + 1;
@@ -827,6 +842,19 @@ struct SmallNet {
     load_row(w_v2a, b_v2a, f, a.val.w[1], a.val.b[1], sub, F);
     load_row(w_v2b, b_v2b, f, a.val.w[1], a.val.b[1], sub + 16, F);
   }
+  // fc2_search_kernel's launch prologue: everything this lane reads from global memory for the network -- the eleven
+  // weight rows with their biases and, for a fresh search (`fresh`, launch-uniform), the observation row at `obs` --
+  // requested back to back and waited for by the caller, once.  attach() is what is left behind the barrier.
+  __device__ __forceinline__ void request(const FusedFcArgs& a, int sub, const float* obs, bool fresh) {
+    setup(a, nullptr, sub);
+#pragma unroll
+    for (int k = 0; k < IN; ++k) obs_r[k] = 0.f;
+    if (fresh) {
+#pragma unroll
+      for (int k = 0; k < IN; ++k) obs_r[k] = obs[k];
+    }
+  }
+  __device__ __forceinline__ void attach(const FusedFcArgs&, char*) {}
 
   // min-max scale of the state held one element per lane (lanes >= E hold junk)
   __device__ __forceinline__ float scale(float s, int sub) const {
@@ -850,13 +878,23 @@ struct SmallNet {
   // lands in h_out[E .. 16) -- the hidden state of the NEXT node, which is written when that node is expanded and read only
   // after, or, for the last node, the dead tail the plans leave behind a tree's hidden states (fused_plan, fc2_plan).  The
   // export and the continued-search import copy n_nodes * E floats.
-  __device__ __forceinline__ void initial(const float* obs, float* h_out, float*, int sub, NetOut& o) const {
+  __device__ __forceinline__ void initial_row(const float (&x)[IN], float* h_out, int sub, NetOut& o) const {
     float acc = 0.f;
 #pragma unroll
-    for (int k = 0; k < IN; ++k) acc = fmaf(obs[k], w_rep[k], acc);
+    for (int k = 0; k < IN; ++k) acc = fmaf(x[k], w_rep[k], acc);
     const float hn = scale(acc + b_rep, sub);
     h_out[sub] = hn;
     heads(hn, sub, o);
+  }
+  __device__ __forceinline__ void initial(const float* obs, float* h_out, float*, int sub, NetOut& o) const {
+    float x[IN];
+#pragma unroll
+    for (int k = 0; k < IN; ++k) x[k] = obs[k];
+    initial_row(x, h_out, sub, o);
+  }
+  // the observation row request() holds
+  __device__ __forceinline__ void initial_requested(const float*, float* h_out, float*, int sub, NetOut& o) const {
+    initial_row(obs_r, h_out, sub, o);
   }
   __device__ __forceinline__ void recurrent(const float* h_in, int action, float* h_out, float*, int sub,
                                             NetOut& o) const {

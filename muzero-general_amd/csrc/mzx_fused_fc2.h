@@ -509,17 +509,50 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
     t_last = __builtin_readcyclecounter();
   }
 
-  // ---- stage tables (+ weights): the only workgroup-wide barrier
+  // ---- every global input of the launch is requested HERE, back to back, and waited for once ("Launch
+  // prologue"): the thread's table entry, the lane's weight rows and the tree's observation (Net::request), its legal
+  // action, player and noise, or the caller's root (OVERRIDE).  A continued search takes its root from the arena: tables
+  // and weights only.  The exit below comes AFTER these reads, so they index a clamped tree: a row that will exit reads
+  // the inputs of the launch's last tree and drops them (the row itself is below trees_per_block: the launch has
+  // trees_per_block rows of threads); a lane beyond A or E reads the row's last entry.
+  const int ntab = 2 * (NN + 1);
+  const double tab_r = a.f.tables[tid < ntab ? tid : ntab - 1];
+  const int tree_c = tree < a.f.p.num_trees ? tree : a.f.p.num_trees - 1;
+  const bool given = !CONT && a.ov_hidden != nullptr;   // (launch-uniform) the caller's roots: no initial_inference
+  const bool noisy = a.f.io.d_noise != nullptr;         // (launch-uniform)
   Net net;
+  net.request(a.f, sub, a.f.io.d_observation + (size_t)tree_c * a.f.in_size, !CONT && !given);
+  int32_t lg_r = -1, tp_r = 0;
+  double nz_r = 0.0, ovp_r = 0.0, ovr_r = 0.0;
+  float ovh_r = 0.f;
+  if constexpr (!CONT) {
+    const int ac = sub < A ? sub : A - 1;
+    lg_r = a.f.io.d_legal_actions[(size_t)tree_c * A + ac];
+    tp_r = a.f.io.d_to_play[tree_c];
+    if (noisy) nz_r = a.f.io.d_noise[(size_t)tree_c * A + ac];
+    if (given) {
+      ovh_r = a.ov_hidden[(size_t)tree_c * E + (sub < E ? sub : E - 1)];
+      ovp_r = a.ov_priors[(size_t)tree_c * A + ac];
+      ovr_r = a.ov_reward[tree_c];
+    }
+  }
+
+  // ---- stage tables (+ weights): the only workgroup-wide barrier.  The reciprocals are arithmetic behind the requests.
   double* tables = (double*)(smem + a.f.lds_tables);
   double* inv_y = (double*)(smem + a.lds_inv);   // [NN + 2]: refined reciprocal of the integer k >= 1
-  const int ntab = 2 * (NN + 1);
-  for (int i = tid; i < ntab; i += blockDim.x) tables[i] = a.f.tables[i];
   for (int i = tid; i < NN + 2; i += blockDim.x) inv_y[i] = recip_refined((double)(i > 0 ? i : 1));
   net.stage(a.f, smem, tid);
+  // The launch's one wait for global memory, as the instruction itself (vmcnt(0), the other counters left alone): the
+  // compiler's own wait insertion reads it, so no load above is waited for again at its first use -- which for most of
+  // the weight rows is inside the simulation loop, an issue slot per wait and simulation.  The empty statement pins the
+  // requests of this function above it.
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  asm volatile("" ::"v"(tab_r), "v"(lg_r), "v"(tp_r), "v"(nz_r), "v"(ovp_r), "v"(ovr_r), "v"(ovh_r));
+  if (tid < ntab) tables[tid] = tab_r;
+  for (int i = tid + blockDim.x; i < ntab; i += blockDim.x) tables[i] = a.f.tables[i];   // more entries than threads
   __syncthreads();
   if (row >= a.f.trees_per_block || tree >= a.f.p.num_trees) return;  // whole rows exit together
-  net.setup(a.f, smem, sub);
+  net.attach(a.f, smem);
   const double* pbc = tables;
   const double* sqt = tables + (NN + 1);
   // prior-score factor of a freshly expanded leaf's slots: the leaf has ONE visit after its own
@@ -561,25 +594,29 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
   // ---- initial_inference (models.py:172-190) + root expansion (self_play.py:286-314, :467-476)
   if constexpr (!CONT) {
     NetOut o;
-    const bool given = a.ov_hidden != nullptr;       // (launch-uniform) the caller's roots: no initial_inference
-    if (!given) net.initial(a.f.io.d_observation + (size_t)tree * a.f.in_size, hidden, scr, sub, o);
-    else
-      for (int e = sub; e < E; e += FUSED_ROW) hidden[e] = a.ov_hidden[(size_t)tree * E + e];
-    const int32_t* lg = a.f.io.d_legal_actions + (size_t)tree * A;
-    const double* nz = a.f.io.d_noise ? a.f.io.d_noise + (size_t)tree * A : nullptr;
-    while (root_n < A && lg[root_n] >= 0) ++root_n;
+    if (!given) net.initial_requested(a.f.io.d_observation + (size_t)tree * a.f.in_size, hidden, scr, sub, o);
+    else {
+      if (sub < E) hidden[sub] = ovh_r;
+      for (int e = sub + FUSED_ROW; e < E; e += FUSED_ROW) hidden[e] = a.ov_hidden[(size_t)tree * E + e];
+    }
+    // Root actions: the leading non-negative entries of the legal-action row, lane s holding entry s.  The serial scan
+    // `while (n < A && lg[n] >= 0) ++n` stops at the FIRST s with s == A or lg[s] < 0; bit s of the row's ballot is set
+    // exactly when s < A and lg[s] >= 0, so that s is the lowest clear bit -- the count of trailing ones -- whatever
+    // follows it (a negative entry with non-negative ones behind it ends the count as it ends the scan).  Bits 16 and
+    // up of the complement are set: the count is at most 16.
+    root_n = __builtin_ctz(~row_bits(__ballot(sub < A && lg_r >= 0), row_in_wave));
     if (!given && sub < A) scr[sub] = o.policy;
     wave_sync();
     const bool in = sub < root_n;
-    const float l = (in && !given) ? scr[lg[sub]] : -MZX_INF;   // logits gathered in the game's legal-action order
+    const float l = (in && !given) ? scr[lg_r] : -MZX_INF;   // logits gathered in the game's legal-action order
     const float m = row_max_w<AW>(l);
     const float e = (in && !given) ? mzx_expf(l - m) : 0.f;
     const float den = row_sum_w<AW>(e);
-    root_to_play = a.f.io.d_to_play[tree];
+    root_to_play = tp_r;
     if (sub == 0) {
       Fc2Node r;
       r.value_sum = 0.0; r.visit = 0; r.to_play = root_to_play;
-      r.reward = given ? a.ov_reward[tree] : (double)support_inverse_transform(0.0f);
+      r.reward = given ? ovr_r : (double)support_inverse_transform(0.0f);
       r.parent = -1; r.parent_slot = -1;
       nodes[0] = r;
       path[0] = make_int2(0, -1);
@@ -588,12 +625,12 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
     }
     if (sub < AW) {
       Fc2Slot s;
-      const double pr = !in ? 0.0 : (given ? a.ov_priors[(size_t)tree * A + sub] : (double)mzx_div(e, den));
-      s.prior = in ? root_noisy_prior(pr, nz, sub, a.f.p.exploration_fraction) : 0.0;
+      const double pr = !in ? 0.0 : (given ? ovp_r : (double)mzx_div(e, den));
+      s.prior = in ? root_noisy_prior(pr, noisy ? &nz_r : nullptr, 0, a.f.p.exploration_fraction) : 0.0;   // nz_r: this slot's noise
       s.q = 0.0; s.n = 0; s.child = -1;
       s.ps = in ? prior_score(pbc[0], sqt[0], 0, inv_y[1], s.prior) : -MZX_INF;   // root visit count 0
       slots[sub] = s;
-      roota[sub] = in ? lg[sub] : -1;
+      roota[sub] = in ? lg_r : -1;
     }
     wave_sync();
   }
@@ -607,6 +644,11 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
   st.n_nodes = n_nodes; st.tape_pos = tape_pos; st.flags = flags; st.ties = ties; st.max_depth = max_depth;
   st.sum_depth = sum_depth; st.root_n = root_n; st.root_to_play = root_to_play;
   const int num_sims = a.f.p.num_sims;
+  // The loop's code starts a fixed distance behind a 64-byte boundary (the directive pads with s_nop, run once), so its
+  // place no longer moves with the length of the prologue above.  A lone wave pays for where its branch targets lie in
+  // the fetch lines: the SAME loop shifted in steps of 4 bytes measured 1.79 to 1.88 G simulations/s on C2, and this
+  // change's shorter prologue had moved it from a good place to a bad one ("Launch prologue").
+  asm volatile(".p2align 6");
   for (int sim = 0; sim < num_sims; ++sim) {
     const Fc2Walk w = fc2_walk<AW>(T, st, tape, tape_words, sub, row_in_wave);
     MZX_PROF(2)
@@ -637,9 +679,21 @@ __global__ void __launch_bounds__(256) fc2_search_kernel(const Fc2Args a) {
   sum_depth = st.sum_depth;
 
   // ---- results (FinalizeOp)
+  if constexpr (AW <= 4) {
+    // each action's count written once, by the lane of that action: the count of the root slot that holds it (the last
+    // such slot, as the loop below would leave it), or zero.  roota is -1 beyond the root's slots.
+    if (sub < A) {
+      int c = 0;
+#pragma unroll
+      for (int s = 0; s < AW; ++s) c = (roota[s] == sub) ? slots[s].n : c;
+      a.f.io.d_visit_counts[(size_t)tree * A + sub] = c;
+    }
+  }
   if (sub == 0) {
-    for (int x = 0; x < A; ++x) a.f.io.d_visit_counts[(size_t)tree * A + x] = 0;
-    for (int s = 0; s < root_n; ++s) a.f.io.d_visit_counts[(size_t)tree * A + roota[s]] = slots[s].n;
+    if constexpr (AW > 4) {
+      for (int x = 0; x < A; ++x) a.f.io.d_visit_counts[(size_t)tree * A + x] = 0;
+      for (int s = 0; s < root_n; ++s) a.f.io.d_visit_counts[(size_t)tree * A + roota[s]] = slots[s].n;
+    }
     const int vc = nodes[0].visit;
     a.f.io.d_root_value[tree] = (vc == 0) ? 0.0 : nodes[0].value_sum / (double)vc;
     a.f.io.d_info[tree * 4 + 0] = max_depth;
