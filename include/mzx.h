@@ -932,7 +932,8 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
  *        variance unbiased); a network that is not applied (steps = 1: dynamics) keeps its bits.
  *   d_grad_flat holds exact zeros in the spans of running_mean / running_var.
  *   min / max of the state normalisation hand their gradient to the lowest index on an exact tie.
- * mzx_train_resnet_supported: 0 for a fully connected network, a network with a downsample stem, a network without
+ * mzx_train_resnet_supported: 0 for a fully connected network, a network with a downsample stem (unless
+ * mzx_net_set_train_stem, below, switched its training on), a network without
  * residual blocks, and batch x board < 2 (BatchNorm needs more than one value per channel).
  * mzx_train_resnet_launches: how many launches (kernels and small device-to-device copies) a step makes; 0 if unsupported.
  * mzx_train_resnet_commit_stats: scatter d_stats into the running_mean / running_var spans of d_flat_out (the step after
@@ -967,6 +968,28 @@ int64_t mzx_train_resnet_stat_floats(const mzx_net* net);
 int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps);
 int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, void* stream);
 int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Downsample stems (config.downsample = "resnet" / "CNN": games/breakout.py, games/atari.py) are trained natively only
+ * on request, per handle.  mzx_net_set_train_stem(net, 1) makes every mzx_train_resnet_* entry plan the stem of the
+ * representation network as well: DownSample's two strided 3 x 3 convolutions (no BatchNorm, no bias, no ReLU), its eight
+ * BatchNorm residual blocks at C/2 and C channels and its two AvgPool2d(3, 2, 1), or DownsampleCNN's two biased
+ * convolutions (+ ReLU), two MaxPool2d(3, 2) and AdaptiveAvgPool2d.  With the switch off (the default) the entries answer
+ * as before: supported / scratch_bytes / launches 0, step MZX_ERR_INVALID with "downsample stems ... are not trained
+ * natively" in mzx_last_error().  The setter returns MZX_ERR_INVALID for a null handle or a fully connected network; on a
+ * residual network without a stem it is accepted and changes nothing.  mzx_net_train_stem reads the switch (0 for null).
+ *   Tie rules of the pools (gather form, no atomics: an input element sums the windows that contain or chose it in
+ *   increasing window order): AvgPool2d(3, 2, 1) always divides by 9 (count_include_pad); MaxPool2d(3, 2) hands the
+ *   gradient to the FIRST maximum of a window in row-major order; window i of AdaptiveAvgPool2d spans
+ *   floor(i in / out) .. ceil((i + 1) in / out), overlapping when out > in.
+ *   representation_network.module.conv / .bn exist in the state_dict but a stem bypasses them: their spans of d_grad_flat
+ *   are exact zeros and their part of d_stats keeps the bits of d_flat (num_batches_tracked must not rise for them).
+ *   The input gradient of the layer that reads the observation is never computed.
+ * Still refused: networks without residual blocks, batch x board < 2 at ANY BatchNorm (the stem's included), and
+ * activations or weight-gradient partials beyond 2^31 elements.
+ * ------------------------------------------------------------------------- */
+int mzx_net_set_train_stem(mzx_net* net, int on);
+int mzx_net_train_stem(const mzx_net* net);
 
 /* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of

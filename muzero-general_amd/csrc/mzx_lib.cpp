@@ -1683,6 +1683,15 @@ int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, voi
   return MZX_OK;
 }
 
+int mzx_net_set_train_stem(mzx_net* net, int on) {
+  if (!net) { set_error("mzx_net_set_train_stem: null network handle"); return MZX_ERR_INVALID; }
+  if (net->cfg.network != 1) { set_error("mzx_net_set_train_stem: fully connected networks have no downsample stem"); return MZX_ERR_INVALID; }
+  net->train_stem = on ? 1 : 0;
+  return MZX_OK;
+}
+
+int mzx_net_train_stem(const mzx_net* net) { return net ? net->train_stem : 0; }
+
 int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream) {
   if (!net || !d_stats || !d_flat_out) { set_error("mzx_train_resnet_commit_stats: null argument"); return MZX_ERR_INVALID; }
   int64_t at = 0;

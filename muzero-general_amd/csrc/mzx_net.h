@@ -71,6 +71,7 @@ struct mzx_net {
   int32_t rz_waves = 0;    // 0: automatic, 4: force 256-thread workgroups (A/B measurements)
   int32_t rb_force = 0;    // 1: every program on the streamed engine (mzx_net_set_mode(3) / (4))
   int32_t rb_no_towers = 0;  // 1: the streamed engine runs layer by layer, no tower launches (mzx_net_set_mode(4): A/B)
+  int32_t train_stem = 0;  // 1: mzx_train_resnet_* plan the downsample stem (mzx_net_set_train_stem); 0: they refuse it by name
   mzx::RbPlan rb;          // streamed MFMA engine for residual networks the fused engine cannot hold (mzx_resnet_batched.h)
 };
 

@@ -51,6 +51,14 @@
 // [steps][B][C][HW] | weight-gradient chunk partials | per layer: z, y, dz [applications][B][Cout][HW], BatchNorm
 // mean / 1/sigma / variance [applications][3][C] and the two backward sums [applications][2][C].
 //
+// Downsample stems (cfg.downsample; planned only when mzx_net_set_train_stem switched the handle on, refused by name
+// otherwise): the head of prog_initial -- DownSample's two strided 3 x 3 convolutions without BatchNorm, its eight blocks
+// at C / 2 and C channels and its two AvgPool2d(3, 2, 1), or DownsampleCNN's two biased convolutions (+ ReLU), its two
+// MaxPool2d(3, 2) and its AdaptiveAvgPool2d -- joins the representation chain.  Layers carry their own channel count and
+// boards; RtnGemmBody<MODE, 1> is the general convolution geometry, the pools are element kernels in gather form (below),
+// the layer that reads the observation gets no input gradient, and representation_network.module.conv / .bn, which the
+// stem bypasses, keep zero gradients and their statistics (RtnPlan::idle).
+//
 // tests/hostcheck build: the same operator list; a GEMM tile is three plain loops over the same operand functions.
 #pragma once
 #include <string>
@@ -83,6 +91,8 @@ struct RtnGemm {
   const int32_t* action;   // [B][act_steps]; the virtual channel of sample bb is action[bb % B][act_t0 + bb / B] / num_actions
   int32_t nb, B, cin, creal, cout, H, W, taps, elu, act_steps, act_t0, num_actions;
   int32_t M, N, K, kchunk, nchunks, tiles_m, tiles_n;
+  // general geometry (RtnGemmBody<MODE, 1>, the stem of a downsample network): H x W is then the OUTPUT board
+  int32_t ksize, stride, pad, Hin, Win, relu;
 };
 
 struct RtnPos { int32_t bb, py, px, rem; };
@@ -151,12 +161,93 @@ MZX_HD inline void rtn_store(const RtnGemm& p, int m, int n, int chunk, float v)
   p.out[at] = v;
 }
 
+// ---- general geometry (any square kernel, stride, padding; the output board H x W differs from the input board Hin x Win):
+// the stem of a downsample network.  A template parameter of the body selects these, so the same-board path above keeps its
+// code.  taps = ksize^2; no action plane (creal == cin); the divisors (taps, ksize, stride, the boards) are wave-uniform.
+MZX_HD inline RtnPos rtng_pos(int pos, int h, int w) {
+  const int hw = h * w;
+  RtnPos s;
+  s.bb = pos / hw;
+  s.rem = pos - s.bb * hw;
+  s.py = s.rem / w;
+  s.px = s.rem - s.py * w;
+  return s;
+}
+// the input of channel ci that output position s reads through `tap` (zero in the padding)
+MZX_HD inline float rtng_im2col(const RtnGemm& p, const RtnPos& s, int ci, int tap) {
+  const int ky = tap / p.ksize, kx = tap - ky * p.ksize;
+  const int y = s.py * p.stride - p.pad + ky, x = s.px * p.stride - p.pad + kx;
+  if (y < 0 || y >= p.Hin || x < 0 || x >= p.Win) return 0.f;
+  return p.x[(((int64_t)s.bb * p.creal + ci) * p.Hin + y) * p.Win + x];
+}
+// `row`: FWD the output position m, DGRAD the INPUT position m
+template <int MODE>
+MZX_HD inline float rtng_a(const RtnGemm& p, int m, int k, const RtnPos& row) {
+  if (m >= p.M || k >= p.K) return 0.f;
+  if (MODE == RTN_WGRAD) {
+    const int hw = p.H * p.W, bb = k / hw;
+    return p.g[((int64_t)bb * p.cout + m) * hw + (k - bb * hw)];
+  }
+  const int c = k / p.taps, tap = k - c * p.taps;
+  if (MODE == RTN_FWD) return rtng_im2col(p, row, c, tap);
+  // DGRAD: the tap contributes where (y + pad - ky, x + pad - kx) is a multiple of the stride whose quotient is on the output board
+  const int ky = tap / p.ksize, kx = tap - ky * p.ksize;
+  const int ty = row.py + p.pad - ky, tx = row.px + p.pad - kx;
+  if (ty < 0 || tx < 0) return 0.f;
+  const int oy = ty / p.stride, ox = tx / p.stride;
+  if (oy * p.stride != ty || ox * p.stride != tx || oy >= p.H || ox >= p.W) return 0.f;
+  return p.g[(((int64_t)row.bb * p.cout + c) * p.H + oy) * p.W + ox];
+}
+template <int MODE>
+MZX_HD inline float rtng_b(const RtnGemm& p, int k, int n) {
+  if (n >= p.N || k >= p.K) return 0.f;
+  if (MODE == RTN_FWD) return p.w[(int64_t)n * p.K + k];
+  if (MODE == RTN_DGRAD) {
+    const int co = k / p.taps, tap = k - co * p.taps;
+    return p.w[((int64_t)co * p.cin + n) * p.taps + tap];
+  }
+  const int ci = n / p.taps, tap = n - ci * p.taps;      // (n is fixed per lane: hoisted out of the K loop)
+  return rtng_im2col(p, rtng_pos(k, p.H, p.W), ci, tap);
+}
+template <int MODE>
+MZX_HD inline void rtng_store(const RtnGemm& p, int m, int n, int chunk, float v) {
+  if (m >= p.M || n >= p.N) return;
+  if (MODE == RTN_WGRAD) { p.out[((int64_t)chunk * p.M + m) * p.N + n] = v; return; }
+  if (MODE == RTN_FWD) {
+    const RtnPos s = rtng_pos(m, p.H, p.W);
+    if (p.bias) v += p.bias[n];
+    if (p.relu) v = fmaxf(v, 0.f);
+    p.out[((int64_t)s.bb * p.cout + n) * (p.H * p.W) + s.rem] = v;
+    return;
+  }
+  const RtnPos s = rtng_pos(m, p.Hin, p.Win);
+  p.out[((int64_t)s.bb * p.creal + n) * (p.Hin * p.Win) + s.rem] = v;
+}
+template <int MODE, int GEO>
+MZX_HD inline RtnPos rtnx_row(const RtnGemm& p, int m) {
+  if (GEO == 1) return MODE == RTN_DGRAD ? rtng_pos(m, p.Hin, p.Win) : rtng_pos(m, p.H, p.W);
+  return rtn_pos(p, m);
+}
+template <int MODE, int GEO>
+MZX_HD inline float rtnx_a(const RtnGemm& p, int m, int k, const RtnPos& row) { return GEO == 1 ? rtng_a<MODE>(p, m, k, row) : rtn_a<MODE>(p, m, k, row); }
+template <int MODE, int GEO>
+MZX_HD inline float rtnx_b(const RtnGemm& p, int k, int n) { return GEO == 1 ? rtng_b<MODE>(p, k, n) : rtn_b<MODE>(p, k, n); }
+template <int MODE, int GEO>
+MZX_HD inline void rtnx_store(const RtnGemm& p, int m, int n, int chunk, float v) {
+  if (GEO == 1) rtng_store<MODE>(p, m, n, chunk, v); else rtn_store<MODE>(p, m, n, chunk, v);
+}
+
 #ifndef MZX_HOSTCHECK
 typedef float rtn_f32x4 __attribute__((ext_vector_type(4)));
 #endif
 
-// a wavefront per (chunk, 16 x 16 tile)
-template <int MODE>
+// a wavefront per (chunk, 16 x 16 tile).  GEO = 0: 1 or 9 taps, stride 1, one board, four binary32 accumulator chains over
+// the whole of K.  GEO = 1 (the general geometry) and GEO = 2 (the geometry of GEO = 0) are what a network with a downsample
+// stem runs, every GEMM of its step: its chain of BatchNorm layers is several times as deep (eight more blocks before the
+// representation tower), and what the binary32 chains round away reaches the first blocks' gradients amplified by every
+// 1 / sigma on the way -- so there every MFMA starts from zero (four products in binary32) and its result is added to a
+// binary64 accumulator, rounded once at the end, like every other long sum of this file.
+template <int MODE, int GEO = 0>
 struct RtnGemmBody {
   RtnGemm p;
   MZX_HD size_t size() const { return (size_t)p.tiles_m * p.tiles_n * p.nchunks; }
@@ -170,21 +261,54 @@ struct RtnGemmBody {
     for (int i = 0; i < 16; ++i) {
       const int m = m0 + i;
       if (m >= p.M) break;
-      const RtnPos row = (MODE == RTN_WGRAD) ? RtnPos{0, 0, 0, 0} : rtn_pos(p, m);
+      const RtnPos row = (MODE == RTN_WGRAD) ? RtnPos{0, 0, 0, 0} : rtnx_row<MODE, GEO>(p, m);
       for (int j = 0; j < 16; ++j) {
         const int n = n0 + j;
         if (n >= p.N) break;
+        if (GEO) {
+          double wide = 0.0;
+          for (int k = k0; k < k1; k += 16) {
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < 4; ++c)
+              for (int kc = k + 4 * c; kc < k + 4 * c + 4 && kc < k1; ++kc) t[c] = fmaf(rtnx_a<MODE, GEO>(p, m, kc, row), rtnx_b<MODE, GEO>(p, kc, n), t[c]);
+            for (int c = 0; c < 4; ++c) wide += (double)t[c];
+          }
+          rtnx_store<MODE, GEO>(p, m, n, chunk, (float)wide);
+          continue;
+        }
         float acc = 0.f;
-        for (int k = k0; k < k1; ++k) acc = fmaf(rtn_a<MODE>(p, m, k, row), rtn_b<MODE>(p, k, n), acc);
-        rtn_store<MODE>(p, m, n, chunk, acc);
+        for (int k = k0; k < k1; ++k) acc = fmaf(rtnx_a<MODE, GEO>(p, m, k, row), rtnx_b<MODE, GEO>(p, k, n), acc);
+        rtnx_store<MODE, GEO>(p, m, n, chunk, acc);
       }
     }
 #else
     const int r = lane & 15, q = lane >> 4;
     const int m = m0 + r, n = n0 + r;
-    const RtnPos row = (MODE == RTN_WGRAD || m >= p.M) ? RtnPos{0, 0, 0, 0} : rtn_pos(p, m);
+    const RtnPos row = (MODE == RTN_WGRAD || m >= p.M) ? RtnPos{0, 0, 0, 0} : rtnx_row<MODE, GEO>(p, m);
     // four accumulator chains: they hide the MFMA's dependent latency, and four short sums joined at the end round less
     // than one long one
+    if (GEO) {
+      double wide[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int k = k0; k < k1; k += 16) {
+        float a[4], b[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int kc = k + 4 * c + q;
+          a[c] = kc < k1 ? rtnx_a<MODE, GEO>(p, m, kc, row) : 0.f;
+          b[c] = kc < k1 ? rtnx_b<MODE, GEO>(p, kc, n) : 0.f;
+        }
+        rtn_f32x4 t[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], rtn_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) wide[i] += (double)t[c][i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) rtnx_store<MODE, GEO>(p, m0 + 4 * q + i, n, chunk, (float)wide[i]);
+      return;
+    }
     rtn_f32x4 acc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = rtn_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -193,15 +317,15 @@ struct RtnGemmBody {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int kc = k + 4 * c + q;
-        a[c] = kc < k1 ? rtn_a<MODE>(p, m, kc, row) : 0.f;
-        b[c] = kc < k1 ? rtn_b<MODE>(p, kc, n) : 0.f;
+        a[c] = kc < k1 ? rtnx_a<MODE, GEO>(p, m, kc, row) : 0.f;
+        b[c] = kc < k1 ? rtnx_b<MODE, GEO>(p, kc, n) : 0.f;
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc[c], 0, 0, 0);
     }
     const rtn_f32x4 acc0 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rtn_store<MODE>(p, m0 + 4 * q + i, n, chunk, acc0[i]);
+    for (int i = 0; i < 4; ++i) rtnx_store<MODE, GEO>(p, m0 + 4 * q + i, n, chunk, acc0[i]);
 #endif
   }
 };
@@ -245,6 +369,105 @@ struct RtnFillOp {
   MZX_HD void operator()(size_t i) const { y[i] = v; }
 };
 
+// out = g where the layer's ReLU passed (y nullable: a copy): d loss / d z of a stem convolution without BatchNorm
+struct RtnMaskCopyOp {
+  const float* g;
+  const float* y;
+  float* out;
+  int64_t n;
+  MZX_HD size_t size() const { return (size_t)n; }
+  MZX_HD void operator()(size_t i) const { out[i] = (!y || y[i] > 0.f) ? g[i] : 0.f; }
+};
+
+// ------------------------------------------------------------------------------------------------ the pools of the stems
+// Element kernels in gather form: an output element reads its window, an input element sums -- in increasing window order
+// (row-major over the output board) -- the gradients of the windows that contain it (the averages) or chose it (the maximum).
+//   OP_POOL           AvgPool2d(3, 2, 1): count_include_pad, and no window reaches past the padded board: the divisor is 9
+//   OP_MAXPOOL        MaxPool2d(3, 2): no padding; the gradient goes to the FIRST maximum in row-major window order (torch's
+//                     CPU kernel keeps it; windows of ReLU outputs tie at 0.0 all the time)
+//   OP_ADAPTIVE_POOL  AdaptiveAvgPool2d: window i spans floor(i in / out) .. ceil((i + 1) in / out), overlapping when out > in
+
+struct RtnPool {
+  const float* x;          // the pool's input [planes][Hin][Win] (backward: the maximum is found again)
+  const float* g;          // backward: d loss / d output [planes][H][W]
+  float* out;              // forward: [planes][H][W]; backward: d loss / d input [planes][Hin][Win]
+  int32_t kind, planes, Hin, Win, H, W;
+};
+MZX_HD inline int rtn_adaptive_lo(int i, int in, int out) { return (i * in) / out; }
+MZX_HD inline int rtn_adaptive_hi(int i, int in, int out) { return ((i + 1) * in + out - 1) / out; }
+// the first maximum of the 3 x 3 window at (2 oy, 2 ox), as an index into the plane
+MZX_HD inline int rtn_maxpool_at(const float* plane, int win, int oy, int ox, float* value) {
+  int at = (2 * oy) * win + 2 * ox;
+  float best = plane[at];
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx) {
+      const int k = (2 * oy + ky) * win + 2 * ox + kx;
+      const float v = plane[k];
+      if (v > best) { best = v; at = k; }
+    }
+  if (value) *value = best;
+  return at;
+}
+struct RtnPoolFwdOp {
+  RtnPool p;
+  MZX_HD size_t size() const { return (size_t)p.planes * p.H * p.W; }
+  MZX_HD void operator()(size_t i) const {
+    const int hw = p.H * p.W;
+    const int64_t plane = (int64_t)(i / hw);
+    const int rem = (int)(i - (size_t)plane * hw), oy = rem / p.W, ox = rem - oy * p.W;
+    const float* x = p.x + plane * p.Hin * p.Win;
+    float v = 0.f;
+    if (p.kind == OP_MAXPOOL) {
+      rtn_maxpool_at(x, p.Win, oy, ox, &v);
+    } else if (p.kind == OP_POOL) {
+      for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) {
+          const int y = 2 * oy - 1 + ky, xx = 2 * ox - 1 + kx;
+          if (y >= 0 && y < p.Hin && xx >= 0 && xx < p.Win) v += x[y * p.Win + xx];
+        }
+      v /= 9.0f;
+    } else {
+      const int y0 = rtn_adaptive_lo(oy, p.Hin, p.H), y1 = rtn_adaptive_hi(oy, p.Hin, p.H);
+      const int x0 = rtn_adaptive_lo(ox, p.Win, p.W), x1 = rtn_adaptive_hi(ox, p.Win, p.W);
+      for (int y = y0; y < y1; ++y)
+        for (int xx = x0; xx < x1; ++xx) v += x[y * p.Win + xx];
+      v /= (float)((y1 - y0) * (x1 - x0));
+    }
+    p.out[i] = v;
+  }
+};
+struct RtnPoolBwdOp {
+  RtnPool p;
+  MZX_HD size_t size() const { return (size_t)p.planes * p.Hin * p.Win; }
+  MZX_HD void operator()(size_t i) const {
+    const int hw = p.Hin * p.Win;
+    const int64_t plane = (int64_t)(i / hw);
+    const int rem = (int)(i - (size_t)plane * hw), iy = rem / p.Win, ix = rem - iy * p.Win;
+    const float* g = p.g + plane * p.H * p.W;
+    float v = 0.f;
+    if (p.kind == OP_MAXPOOL) {          // windows oy with 2 oy <= iy <= 2 oy + 2
+      const float* x = p.x + plane * hw;
+      const int oy0 = iy >= 2 ? (iy - 1) / 2 : 0, ox0 = ix >= 2 ? (ix - 1) / 2 : 0;
+      for (int oy = oy0; oy <= iy / 2 && oy < p.H; ++oy)
+        for (int ox = ox0; ox <= ix / 2 && ox < p.W; ++ox)
+          if (rtn_maxpool_at(x, p.Win, oy, ox, nullptr) == rem) v += g[oy * p.W + ox];
+    } else if (p.kind == OP_POOL) {      // windows oy with 2 oy - 1 <= iy <= 2 oy + 1
+      for (int oy = iy / 2; oy <= (iy + 1) / 2 && oy < p.H; ++oy)
+        for (int ox = ix / 2; ox <= (ix + 1) / 2 && ox < p.W; ++ox) v += g[oy * p.W + ox] / 9.0f;
+    } else {
+      for (int oy = 0; oy < p.H; ++oy) {
+        const int y0 = rtn_adaptive_lo(oy, p.Hin, p.H), y1 = rtn_adaptive_hi(oy, p.Hin, p.H);
+        if (iy < y0 || iy >= y1) continue;
+        for (int ox = 0; ox < p.W; ++ox) {
+          const int x0 = rtn_adaptive_lo(ox, p.Win, p.W), x1 = rtn_adaptive_hi(ox, p.Win, p.W);
+          if (ix >= x0 && ix < x1) v += g[oy * p.W + ox] / (float)((y1 - y0) * (x1 - x0));
+        }
+      }
+    }
+    p.out[i] = v;
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ BatchNorm, training mode
 
 struct RtnBn {
@@ -261,6 +484,12 @@ struct RtnBn {
   float* dgamma;
   float* dbeta;
   int32_t napps, B, C, HW;
+  // a network with a downsample stem (nullable otherwise; the float path above keeps its code and sums): the batch
+  // statistics and the backward sums are ALSO kept in binary64, and normalise / dz compute in binary64 and round once.  A
+  // mean or 1 / sigma rounded to binary32 shifts or scales a whole channel by one correlated error, which the sums of
+  // the next layers do not average away; behind nineteen BatchNorm layers that is what the gradients' error is made of.
+  double* saved64;         // [napps][3][C]
+  double* sums64;          // [napps][2][C]
 };
 
 struct RtnBnStatBody {
@@ -284,6 +513,10 @@ struct RtnBnStatBody {
     if (lane == 0) {
       float* sv = p.saved + (int64_t)app * 3 * p.C;
       sv[c] = (float)mean; sv[p.C + c] = (float)(1.0 / sqrt(var + (double)RTN_BN_EPS)); sv[2 * p.C + c] = (float)var;
+      if (p.saved64) {
+        double* sd = p.saved64 + (int64_t)app * 3 * p.C;
+        sd[c] = mean; sd[p.C + c] = 1.0 / sqrt(var + (double)RTN_BN_EPS); sd[2 * p.C + c] = var;
+      }
     }
   }
 };
@@ -309,6 +542,13 @@ struct RtnBnApplyOp {
   MZX_HD size_t size() const { return (size_t)p.napps * p.B * p.C * p.HW; }
   MZX_HD void operator()(size_t i) const {
     const int c = (int)((i / p.HW) % p.C), app = (int)(i / ((size_t)p.B * p.C * p.HW));
+    if (p.saved64) {
+      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
+      double w = ((double)p.z[i] - sd[c]) * sd[p.C + c] * (double)p.gamma[c] + (double)p.beta[c];
+      if (p.res) w += (double)p.res[i];
+      p.out[i] = fmaxf((float)w, 0.f);
+      return;
+    }
     const float* sv = p.saved + (int64_t)app * 3 * p.C;
     float v = (p.z[i] - sv[c]) * sv[p.C + c] * p.gamma[c] + p.beta[c];
     if (p.res) v += p.res[i];
@@ -326,6 +566,23 @@ struct RtnBnSumsBody {
     const float* sv = p.saved + (int64_t)app * 3 * p.C;
     const float mean = sv[c], inv = sv[p.C + c];
     double sg = 0.0, sgx = 0.0;
+    if (p.saved64) {
+      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
+      const double mean64 = sd[c], inv64 = sd[p.C + c];
+      for (int i = lane; i < n; i += WAVE_LANES) {
+        const int b = i / p.HW;
+        const int64_t at = base + (int64_t)b * p.C * p.HW + (i - b * p.HW);
+        const double g = p.y[at] > 0.f ? (double)p.g[at] : 0.0;
+        sg += g;
+        sgx += g * (((double)p.z[at] - mean64) * inv64);
+      }
+      sg = wave_sum_f64(sg); sgx = wave_sum_f64(sgx);
+      if (lane == 0) {
+        p.sums[(int64_t)app * 2 * p.C + c] = (float)sg; p.sums[(int64_t)app * 2 * p.C + p.C + c] = (float)sgx;
+        p.sums64[(int64_t)app * 2 * p.C + c] = sg; p.sums64[(int64_t)app * 2 * p.C + p.C + c] = sgx;
+      }
+      return;
+    }
     for (int i = lane; i < n; i += WAVE_LANES) {
       const int b = i / p.HW;
       const int64_t at = base + (int64_t)b * p.C * p.HW + (i - b * p.HW);
@@ -343,6 +600,15 @@ struct RtnBnDzOp {
   MZX_HD size_t size() const { return (size_t)p.napps * p.B * p.C * p.HW; }
   MZX_HD void operator()(size_t i) const {
     const int c = (int)((i / p.HW) % p.C), app = (int)(i / ((size_t)p.B * p.C * p.HW));
+    if (p.saved64) {
+      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
+      const double* sw = p.sums64 + (int64_t)app * 2 * p.C;
+      const double nn = (double)(p.B * p.HW);
+      const double gw = p.y[i] > 0.f ? (double)p.g[i] : 0.0;
+      const double xw = ((double)p.z[i] - sd[c]) * sd[p.C + c];
+      p.out[i] = (float)((double)p.gamma[c] * sd[p.C + c] * (gw - sw[c] / nn - xw * (sw[p.C + c] / nn)));
+      return;
+    }
     const float* sv = p.saved + (int64_t)app * 3 * p.C;
     const float* sm = p.sums + (int64_t)app * 2 * p.C;
     const float n = (float)(p.B * p.HW);
@@ -358,6 +624,11 @@ struct RtnBnParamGradOp {
   MZX_HD size_t size() const { return (size_t)p.C; }
   MZX_HD void operator()(size_t c) const {
     double dg = 0.0, db = 0.0;
+    if (p.sums64) {
+      for (int app = 0; app < p.napps; ++app) { db += p.sums64[(int64_t)app * 2 * p.C + c]; dg += p.sums64[(int64_t)app * 2 * p.C + p.C + c]; }
+      p.dgamma[c] = (float)dg; p.dbeta[c] = (float)db;
+      return;
+    }
     for (int app = 0; app < p.napps; ++app) { db += (double)p.sums[(int64_t)app * 2 * p.C + c]; dg += (double)p.sums[(int64_t)app * 2 * p.C + p.C + c]; }
     p.dgamma[c] = (float)dg; p.dbeta[c] = (float)db;
   }
@@ -440,12 +711,19 @@ struct RtnScaleBwdBody {
 
 // ------------------------------------------------------------------------------------------------ the plan (host)
 
+constexpr int RTN_PLAIN = 100;       // a layer kind beside OpKind: DownSample's strided 3 x 3 convolutions (no BatchNorm, no bias, no ReLU)
+inline bool rtn_is_pool(int kind) { return kind == OP_POOL || kind == OP_MAXPOOL || kind == OP_ADAPTIVE_POOL; }
+
 struct RtnLayer {
-  int kind = 0;                      // OP_CONV3 (+ BatchNorm [+ residual] + ReLU), OP_CONV1 (bias), OP_LINEAR (bias [+ ELU])
-  int32_t cin = 0, creal = 0, cout = 0, H = 1, W = 1, taps = 1, elu = 0, has_res = 0;
+  // OP_CONV3 (+ BatchNorm [+ residual] + ReLU), OP_CONV1 (bias), OP_LINEAR (bias [+ ELU]); in the stem of a downsample
+  // network also RTN_PLAIN, OP_CONVK (bias + ReLU) and the three pools (no weights: y only)
+  int kind = 0;
+  int32_t cin = 0, creal = 0, cout = 0, H = 1, W = 1, taps = 1, elu = 0, has_res = 0;      // H x W: the OUTPUT board
+  int32_t ksize = 1, stride = 1, pad = 0, Hin = 1, Win = 1, relu = 0, geo = 0;             // geo: RtnGemmBody<MODE, 1>
   int64_t w = -1, b = -1;            // flat offsets
   BnRef bn;
   int64_t stat = -1;                 // offset of this BatchNorm in the statistics output
+  int64_t saved64 = -1, sums64 = -1; // (a stem network: the same in binary64, offsets in floats)
   int64_t z = -1, y = -1, dz = -1, saved = -1, sums = -1;      // scratch offsets; y / dz = -1: the logits / the loss head's gradients
   int64_t per_app(int B) const { return (int64_t)B * cout * H * W; }
 };
@@ -453,10 +731,12 @@ enum RtnNetId { RTN_REP, RTN_DYN, RTN_PRED, RTN_REW, RTN_VAL, RTN_POL, RTN_NETS 
 struct RtnChain { std::vector<RtnLayer> l; int32_t napps = 0, t0 = 0; };
 struct RtnPlan {
   RtnChain net[RTN_NETS];
-  int32_t B = 0, steps = 0, C = 0, HW = 0, A = 0, F = 0, num_params = 0;
+  int32_t B = 0, steps = 0, C = 0, HW = 0, A = 0, F = 0, num_params = 0, stem = 0;
   int64_t state = 0;                 // B * C * HW
   int64_t off_loss = 0, off_gv = 0, off_gr = 0, off_gp = 0, off_vlog = -1, off_rlog = -1, off_plog = -1, off_h = 0, off_ghp = 0,
           off_grs = 0, off_gd = 0, off_ga = 0, off_gb = 0, off_partial = 0, total_floats = 0;
+  struct IdleBn { int64_t stat, mean; int32_t channels; };
+  std::vector<IdleBn> idle;          // BatchNorms no chain applies (the bypassed representation_network.module.bn of a stem)
 };
 
 inline int64_t rtn_stat_floats(const mzx_net* net) {
@@ -476,7 +756,8 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   auto no = [&](const char* msg) { if (why) *why = msg; return false; };
   if (!net) return no("null network handle");
   if (net->cfg.network != 1) return no("fully connected networks train through mzx_train_fc_step (residual networks only)");
-  if (net->cfg.downsample) return no("downsample stems (the strided convolutions and pools) are not trained natively");
+  const bool stem = net->cfg.downsample != 0;
+  if (stem && !net->train_stem) return no("downsample stems (the strided convolutions and pools) are not trained natively");
   if (B < 1 || steps < 1) return no("batch and steps must be positive");
   if (net->cfg.blocks < 1) return no("the training kernels need at least one residual block per network");
   if (net->num_params >= ((int64_t)1 << 30)) return no("too many parameters");
@@ -487,23 +768,46 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
     return no("batch x steps too large");
   P = RtnPlan();
   P.B = B; P.steps = steps; P.C = C; P.HW = HW; P.A = net->cfg.action_space_size; P.F = 2 * net->cfg.support_size + 1;
-  P.num_params = (int32_t)net->num_params; P.state = (int64_t)B * C * HW;
+  P.num_params = (int32_t)net->num_params; P.state = (int64_t)B * C * HW; P.stem = stem ? 1 : 0;
   const int napps[RTN_NETS] = {1, steps - 1, steps, steps - 1, steps, steps};
   const int t0[RTN_NETS] = {0, 1, 0, 1, 0, 0};
   for (int n = 0; n < RTN_NETS; ++n) { P.net[n].napps = napps[n]; P.net[n].t0 = t0[n]; }
 
+  bool in_stem = false;              // the operator being cut may be one of the stem's (the head of prog_initial)
   auto layer_of = [&](const OpDesc& d, RtnLayer& L) {
     L.kind = d.kind; L.w = d.w;
+    if (in_stem && (d.kind == OP_CONVK || (d.kind == OP_CONV3 && d.bn.channels == 0))) {
+      const bool k = d.kind == OP_CONVK;
+      if (d.w < 0 || d.use_action || d.res != -100 || (k ? d.b < 0 || !d.relu : d.relu != 0)) return false;
+      L.kind = k ? (int)OP_CONVK : RTN_PLAIN; L.b = k ? d.b : -1; L.relu = d.relu;
+      L.ksize = k ? d.ksize : 3; L.stride = d.stride; L.pad = k ? d.pad : 1;
+      L.cin = L.creal = d.cin; L.cout = d.cout; L.Hin = d.hin; L.Win = d.win; L.H = d.hout; L.W = d.wout;
+      L.taps = L.ksize * L.ksize; L.geo = 1;
+      return L.ksize >= 1 && L.stride >= 1 && L.pad >= 0 && L.H >= 1 && L.W >= 1 &&
+             L.H == (L.Hin + 2 * L.pad - L.ksize) / L.stride + 1 && L.W == (L.Win + 2 * L.pad - L.ksize) / L.stride + 1;
+    }
+    if (in_stem && rtn_is_pool(d.kind)) {
+      L.w = -1;
+      L.cin = L.creal = L.cout = d.cin; L.Hin = d.hin; L.Win = d.win; L.H = d.hout; L.W = d.wout;
+      if (L.H < 1 || L.W < 1) return false;
+      if (d.kind == OP_POOL) return L.H == (L.Hin - 1) / 2 + 1 && L.W == (L.Win - 1) / 2 + 1;
+      if (d.kind == OP_MAXPOOL) return L.Hin >= 3 && L.Win >= 3 && L.H == (L.Hin - 3) / 2 + 1 && L.W == (L.Win - 3) / 2 + 1;
+      return true;
+    }
     if (d.kind == OP_CONV3) {
       if (d.stride != 1 || !d.relu || d.bn.channels != d.cout || d.w < 0) return false;
       L.cin = d.cin; L.creal = d.use_action ? d.cin - 1 : d.cin; L.cout = d.cout; L.H = d.hin; L.W = d.win; L.taps = 9;
+      L.Hin = d.hin; L.Win = d.win; L.ksize = 3; L.pad = 1;
       L.has_res = d.res != -100; L.bn = d.bn;
       int64_t at = 0;
       for (const BnRef& b : net->bns) { if (b.weight == d.bn.weight) { L.stat = at; break; } at += 2 * (int64_t)b.channels; }
       // the statistics output of a BatchNorm is a copy of its [running_mean | running_var] span of the flat buffer
       return L.stat >= 0 && d.bn.var == d.bn.mean + d.bn.channels;
     }
-    if (d.kind == OP_CONV1) { L.cin = L.creal = d.cin; L.cout = d.cout; L.H = d.hin; L.W = d.win; L.b = d.b; return d.b >= 0; }
+    if (d.kind == OP_CONV1) {
+      L.cin = L.creal = d.cin; L.cout = d.cout; L.H = L.Hin = d.hin; L.W = L.Win = d.win; L.b = d.b;
+      return d.b >= 0;
+    }
     if (d.kind == OP_LINEAR) {
       if (d.use_action || d.w_stride != d.in_features) return false;
       L.cin = L.creal = d.in_features; L.cout = d.out_features; L.elu = d.elu; L.b = d.b;
@@ -515,7 +819,13 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   auto cut = [&](const std::vector<OpDesc>& prog, int tower, bool reward, bool keep_prediction) {
     size_t i = 0;
     RtnLayer L;
-    for (; i < prog.size() && prog[i].kind == OP_CONV3; ++i) { L = RtnLayer(); if (!layer_of(prog[i], L)) return false; P.net[tower].l.push_back(L); }
+    in_stem = stem && tower == RTN_REP;
+    for (; i < prog.size() && (prog[i].kind == OP_CONV3 || (in_stem && (prog[i].kind == OP_CONVK || rtn_is_pool(prog[i].kind)))); ++i) {
+      L = RtnLayer();
+      if (!layer_of(prog[i], L)) return false;
+      P.net[tower].l.push_back(L);
+    }
+    in_stem = false;
     if (i >= prog.size() || prog[i].kind != OP_SCALE || prog[i].groups_per_sample != C || prog[i].len != HW) return false;
     ++i;
     auto mlp = [&](int id, int out_buf) {
@@ -547,13 +857,58 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   };
   if (!cut(net->prog_initial, RTN_REP, false, true) || !cut(net->prog_recurrent, RTN_DYN, true, false))
     return no("unexpected operator program");
-  // towers: [stem] then blocks of two convolutions, the second with the block's input as its residual
+  // towers: [first convolution] then blocks of two convolutions, the second with the block's input as its residual; in the
+  // representation network of a downsample configuration, segments of blocks separated by a geometry-changing operator
+  // (a strided or biased convolution, a pool), the first of which reads the observation
   for (int n : {RTN_REP, RTN_DYN, RTN_PRED}) {
     const std::vector<RtnLayer>& l = P.net[n].l;
     if (l.empty() || l.back().cout != C || l.back().H * l.back().W != HW) return no("unexpected operator program");
     for (int i = (int)l.size() - 1; i >= 0;) {
-      if (l[i].has_res) { if (i < 1 || l[i - 1].has_res || (i == 1 && n != RTN_PRED)) return no("unexpected operator program"); i -= 2; }
-      else { if (i != 0 || n == RTN_PRED) return no("unexpected operator program"); i -= 1; }
+      if (l[i].has_res) {
+        if (i < 1 || l[i].kind != OP_CONV3 || l[i - 1].kind != OP_CONV3 || l[i - 1].has_res || (i == 1 && n != RTN_PRED))
+          return no("unexpected operator program");
+        if (l[i - 1].cin != l[i].cout || l[i - 1].cout != l[i].cout || l[i].cin != l[i].cout || l[i - 1].H != l[i].H || l[i - 1].W != l[i].W)
+          return no("unexpected operator program");
+        i -= 2;
+      } else if (l[i].kind == OP_CONV3) {
+        if (i != 0 || n == RTN_PRED) return no("unexpected operator program");
+        i -= 1;
+      } else {
+        if (n != RTN_REP || (i == 0 && rtn_is_pool(l[i].kind))) return no("unexpected operator program");
+        i -= 1;
+      }
+    }
+    for (size_t i = 1; i < l.size(); ++i)
+      if (l[i].creal != l[i - 1].cout || l[i].Hin != l[i - 1].H || l[i].Win != l[i - 1].W) return no("unexpected operator program");
+  }
+  if (stem) {
+    const std::vector<RtnLayer>& l = P.net[RTN_REP].l;
+    if (rtn_is_pool(l[0].kind) || l[0].kind == OP_CONV3 || (int64_t)l[0].cin * l[0].Hin * l[0].Win != net->input_size)
+      return no("unexpected operator program");
+    for (const RtnLayer& L : l) {
+      if (L.kind == OP_CONV3 && (int64_t)B * L.H * L.W < 2)
+        return no("BatchNorm in training mode needs more than one value per channel (batch x board >= 2)");
+      // the stem's activations (the largest is the first convolution's, B x C/2 x ceil(H/2) x ceil(W/2) in DownSample) and
+      // the chunk partials of its weight gradients are indexed with 32-bit positions
+      if ((int64_t)B * L.cout * L.H * L.W >= ((int64_t)1 << 31) || (int64_t)B * L.cin * L.Hin * L.Win >= ((int64_t)1 << 31))
+        return no("batch x steps too large");
+      if (!rtn_is_pool(L.kind) &&
+          (((int64_t)B * L.H * L.W + RTN_KCHUNK - 1) / RTN_KCHUNK) * L.cout * L.cin * L.taps >= ((int64_t)1 << 31))
+        return no("batch x steps too large");
+    }
+  }
+  // BatchNorms that no chain applies keep their statistics and have zero gradients
+  {
+    int64_t at = 0;
+    for (const BnRef& b : net->bns) {
+      bool applied = false;
+      for (int n : {RTN_REP, RTN_DYN, RTN_PRED})
+        for (const RtnLayer& L : P.net[n].l) applied |= (L.kind == OP_CONV3 && L.stat == at);
+      if (!applied) {
+        if (b.var != b.mean + b.channels) return no("unexpected operator program");
+        P.idle.push_back({at, b.mean, b.channels});
+      }
+      at += 2 * (int64_t)b.channels;
     }
   }
   if (P.net[RTN_DYN].l[0].creal != C || P.net[RTN_PRED].l[0].cin != C) return no("unexpected operator program");
@@ -570,7 +925,10 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   P.off_rlog = own_rlog ? take(rows * P.F) : -1;
   P.off_plog = own_plog ? take(rows * P.A) : -1;
   P.off_h = take(steps * P.state); P.off_ghp = take(steps * P.state); P.off_grs = take((steps - 1) * P.state);
-  P.off_gd = take(P.state); P.off_ga = take(steps * P.state); P.off_gb = take(steps * P.state);
+  // the two gradient buffers also carry d loss / d y down the stem, whose boards are larger than the hidden state's
+  int64_t gbuf = steps * P.state;
+  for (const RtnLayer& L : P.net[RTN_REP].l) if (L.per_app(B) > gbuf) gbuf = L.per_app(B);
+  P.off_gd = take(P.state); P.off_ga = take(gbuf); P.off_gb = take(gbuf);
   int64_t partial = 0;
   for (int n = 0; n < RTN_NETS; ++n) {
     RtnChain& ch = P.net[n];
@@ -579,7 +937,9 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
       const int64_t all = ch.napps * L.per_app(B);
       const bool head_out = n >= RTN_REW && i + 1 == ch.l.size();
       if (L.kind == OP_CONV3) { L.z = take(all); L.saved = take((int64_t)ch.napps * 3 * L.cout); L.sums = take((int64_t)ch.napps * 2 * L.cout); }
+      if (L.kind == OP_CONV3 && stem) { L.saved64 = take((int64_t)ch.napps * 6 * L.cout); L.sums64 = take((int64_t)ch.napps * 4 * L.cout); }
       L.y = head_out ? -1 : take(all);
+      if (rtn_is_pool(L.kind)) continue;
       L.dz = head_out ? -1 : take(all);
       const int chunks = rtn_wgrad_chunks(L, ch.napps, B);
       if (chunks > 1 && (int64_t)chunks * L.cout * L.cin * L.taps > partial) partial = (int64_t)chunks * L.cout * L.cin * L.taps;
@@ -654,16 +1014,29 @@ struct RtnRun {
     g.w = flat + L.w;
     g.action = action; g.act_steps = p.steps; g.act_t0 = p.net[n].t0 + app; g.num_actions = p.A;
     g.nb = napps * p.B; g.B = p.B; g.cin = L.cin; g.creal = L.creal; g.cout = L.cout; g.H = L.H; g.W = L.W; g.taps = L.taps;
+    g.ksize = L.ksize; g.stride = L.stride; g.pad = L.pad; g.Hin = L.Hin; g.Win = L.Win;
     const int positions = g.nb * L.H * L.W;
     if (mode == RTN_FWD) { g.M = positions; g.N = L.cout; g.K = L.cin * L.taps; }
-    else if (mode == RTN_DGRAD) { g.M = positions; g.N = L.creal; g.K = L.cout * L.taps; }
+    else if (mode == RTN_DGRAD) { g.M = L.geo ? g.nb * L.Hin * L.Win : positions; g.N = L.creal; g.K = L.cout * L.taps; }
     else { g.M = L.cout; g.N = L.cin * L.taps; g.K = positions; }
     g.kchunk = mode == RTN_WGRAD ? RTN_KCHUNK : g.K;
     g.nchunks = mode == RTN_WGRAD ? (g.K + RTN_KCHUNK - 1) / RTN_KCHUNK : 1;
     g.tiles_m = (g.M + 15) / 16; g.tiles_n = (g.N + 15) / 16;
     return g;
   }
-  void launch_gemm(const RtnGemm& g, int mode) {
+  void launch_gemm(const RtnGemm& g, int mode, int geo = 0) {
+    if (geo) {
+      if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD, 1>{g}, stream); });
+      else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD, 1>{g}, stream); });
+      else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD, 1>{g}, stream); });
+      return;
+    }
+    if (P->stem) {      // the geometry of the plain path, the block sums joined in binary64
+      if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD, 2>{g}, stream); });
+      else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD, 2>{g}, stream); });
+      else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD, 2>{g}, stream); });
+      return;
+    }
     if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD>{g}, stream); });
     else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD>{g}, stream); });
     else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD>{g}, stream); });
@@ -679,14 +1052,34 @@ struct RtnRun {
     b.saved = scratch + L.saved + (int64_t)app * 3 * L.cout; b.sums = scratch + L.sums + (int64_t)app * 2 * L.cout;
     b.running = stats + L.stat; b.dgamma = grad + L.bn.weight; b.dbeta = grad + L.bn.bias;
     b.napps = napps; b.B = p.B; b.C = L.cout; b.HW = L.H * L.W;
+    if (L.saved64 >= 0) {
+      b.saved64 = (double*)(scratch + L.saved64) + (int64_t)app * 3 * L.cout;
+      b.sums64 = (double*)(scratch + L.sums64) + (int64_t)app * 2 * L.cout;
+    }
     return b;
   }
 
+  // a pool of the stem: forward (g == nullptr) into its y, or backward from d loss / d y in `g` to d loss / d input in `out`
+  void launch_pool(int n, size_t i, int app, int napps, const float* g, float* out) {
+    const RtnLayer& L = P->net[n].l[i];
+    RtnPool q;
+    memset(&q, 0, sizeof(q));
+    q.x = x_of(n, i, app); q.g = g; q.out = g ? out : y_of(n, i, app);
+    q.kind = L.kind; q.planes = napps * P->B * L.cout; q.Hin = L.Hin; q.Win = L.Win; q.H = L.H; q.W = L.W;
+    if (g) go([&] { return launch<256>(RtnPoolBwdOp{q}, stream); });
+    else go([&] { return launch<256>(RtnPoolFwdOp{q}, stream); });
+  }
   // applications [app, app + napps) of a tower: conv -> batch statistics -> running statistics -> normalise (+ residual) + ReLU
   void tower_forward(int n, int app, int napps) {
     const std::vector<RtnLayer>& l = P->net[n].l;
     for (size_t i = 0; i < l.size(); ++i) {
+      if (rtn_is_pool(l[i].kind)) { launch_pool(n, i, app, napps, nullptr, nullptr); continue; }
       RtnGemm g = gemm(n, i, app, napps, RTN_FWD);
+      if (l[i].kind != OP_CONV3) {       // a stem convolution without BatchNorm: z is y
+        g.x = x_of(n, i, app); g.out = y_of(n, i, app); g.bias = l[i].b >= 0 ? flat + l[i].b : nullptr; g.relu = l[i].relu;
+        launch_gemm(g, RTN_FWD, l[i].geo);
+        continue;
+      }
       g.x = x_of(n, i, app); g.out = scratch + l[i].z + (int64_t)app * l[i].per_app(P->B);
       launch_gemm(g, RTN_FWD);
       RtnBn b = bn(n, i, app, napps);
@@ -747,12 +1140,29 @@ struct RtnRun {
         g1.g = dz_of(n, i - 1, app); g1.out = (i - 1 == 0) ? dest : cur; g1.add = cur; g1.mask = y_of(n, i, app);
         launch_gemm(g1, RTN_DGRAD);
         i -= 2;
-      } else {
+      } else if (l[i].kind == OP_CONV3) {
         bn_backward(n, i, app, napps, cur);
         if (dest) {
           RtnGemm g = gemm(n, i, app, napps, RTN_DGRAD);
           g.g = dz_of(n, i, app); g.out = dest;
           launch_gemm(g, RTN_DGRAD);
+        }
+        i -= 1;
+      } else if (rtn_is_pool(l[i].kind)) {
+        launch_pool(n, i, app, napps, cur, other);
+        float* t = cur; cur = other; other = t;
+        i -= 1;
+      } else {
+        // a stem convolution without BatchNorm: dz = d loss / d y (where its ReLU passed), kept for the weight gradient; the
+        // one that reads the observation sends nothing further
+        RtnMaskCopyOp m;
+        m.g = cur; m.y = l[i].relu ? y_of(n, i, app) : nullptr; m.n = (int64_t)napps * l[i].per_app(P->B);
+        m.out = scratch + l[i].dz + (int64_t)app * l[i].per_app(P->B);
+        go([&] { return launch<256>(m, stream); });
+        if (i > 0) {
+          RtnGemm g = gemm(n, i, app, napps, RTN_DGRAD);
+          g.g = dz_of(n, i, app); g.out = cur;
+          launch_gemm(g, RTN_DGRAD, l[i].geo);
         }
         i -= 1;
       }
@@ -765,10 +1175,11 @@ struct RtnRun {
     if (ch.napps < 1) return;
     for (size_t i = 0; i < ch.l.size(); ++i) {
       const RtnLayer& L = ch.l[i];
+      if (rtn_is_pool(L.kind)) continue;
       RtnGemm g = gemm(n, i, 0, ch.napps, RTN_WGRAD);
       g.x = x_of(n, i, 0); g.g = dz_of(n, i, 0);
       g.out = g.nchunks > 1 ? scratch + p.off_partial : grad + L.w;
-      launch_gemm(g, RTN_WGRAD);
+      launch_gemm(g, RTN_WGRAD, L.geo);
       if (g.nchunks > 1) {
         RtnWgradFinishOp f;
         f.partial = scratch + p.off_partial; f.out = grad + L.w; f.elements = g.M * g.N; f.nchunks = g.nchunks;
@@ -777,7 +1188,7 @@ struct RtnRun {
       if (L.kind == OP_CONV3) {
         const RtnBn b = bn(n, i, 0, ch.napps);
         go([&] { return launch<64>(RtnBnParamGradOp{b}, stream); });
-      } else {
+      } else if (L.b >= 0) {
         RtnBiasGradBody bg;
         bg.dz = dz_of(n, i, 0); bg.out = grad + L.b; bg.nb = ch.napps * p.B; bg.cout = L.cout; bg.hw = L.H * L.W;
         go([&] { return launch_waves<RTN_WAVES>(bg, stream); });
@@ -813,7 +1224,9 @@ struct RtnRun {
     // the statistics output starts as the running statistics of the flat buffer: one [mean | var] span per BatchNorm
     for (int n : {RTN_REP, RTN_DYN, RTN_PRED})
       for (const RtnLayer& L : p.net[n].l)
-        go([&] { return copy_d2d(stats + L.stat, flat + L.bn.mean, sizeof(float) * 2 * L.cout, stream); });
+        if (L.kind == OP_CONV3) go([&] { return copy_d2d(stats + L.stat, flat + L.bn.mean, sizeof(float) * 2 * L.cout, stream); });
+    for (const RtnPlan::IdleBn& b : p.idle)
+      go([&] { return copy_d2d(stats + b.stat, flat + b.mean, sizeof(float) * 2 * b.channels, stream); });
     go([&] { RtnFillOp f; f.y = grad; f.n = p.num_params; f.v = 0.f; return launch<256>(f, stream); });
     tower_forward(RTN_REP, 0, 1);
     scale_forward(0);

@@ -313,6 +313,8 @@ PROTOTYPES = {
     "mzx_train_resnet_launches": (c_i64, [c_vp, c_i32, c_i32]),
     "mzx_train_resnet_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TrainResnetIO), c_vp]),
     "mzx_train_resnet_commit_stats": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mzx_net_set_train_stem": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "mzx_net_train_stem": (ctypes.c_int, [c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

@@ -237,6 +237,8 @@ class HipNetwork:
         self._workspace = None
         self._ws_batch = 0
         self._num_batches_tracked = {}
+        if config.network == "resnet" and getattr(config, "train_downsample", False):
+            self.train_stem = True
         self.set_weights(self._initial_weights())
 
     def __del__(self):
@@ -278,6 +280,17 @@ class HipNetwork:
     def train_resnet_supported(self, batch, steps):
         """Whether ``mzx_train_resnet_step`` runs this network at ``batch`` samples x ``steps`` (= num_unroll_steps + 1)."""
         return bool(self.backend.lib.mzx_train_resnet_supported(self.handle, int(batch), int(steps)))
+
+    @property
+    def train_stem(self):
+        """Whether ``mzx_train_resnet_step`` trains the downsample stem of this network (``mzx_net_set_train_stem``; off by
+        default: a network with ``config.downsample`` is then refused by name; ``config.train_downsample = True`` switches
+        it on at construction).  Setting it on a fully connected network raises."""
+        return bool(self.backend.lib.mzx_net_train_stem(self.handle))
+
+    @train_stem.setter
+    def train_stem(self, on):
+        self.backend.lib.check(self.backend.lib.mzx_net_set_train_stem(self.handle, int(bool(on))))
 
     def state_dict(self):
         out = collections.OrderedDict()

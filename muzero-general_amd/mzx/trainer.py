@@ -25,6 +25,11 @@ launches) that writes ``.grad`` of the network's flat parameter; ``optimizer.ste
 searches on and RCCL broadcasts.  A residual ``HipNetwork`` (no downsample stem) takes the same route through
 ``mzx_train_resnet_step`` (csrc/mzx_train_resnet.h): BatchNorm in training mode, the convolutions as implicit GEMMs on the
 FP32 matrix pipes; after ``optimizer.step()`` the new running statistics are committed into the flat buffer.
+A configuration with a downsample stem (``downsample = "resnet"`` / ``"CNN"``: breakout, atari) is refused by name unless
+``config.train_downsample = True`` (read by ``models.MuZeroNetwork(config)``) or ``HipNetwork.train_stem = True`` switched
+the stem's training on for that handle (``mzx_net_set_train_stem``); then the strided and biased convolutions, the stem's
+BatchNorm blocks and its three kinds of pool are trained as well, and the ``representation_network.module.conv`` / ``.bn``
+the stem bypasses keep zero gradients, their statistics and their ``num_batches_tracked``.
 ``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
 convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """
@@ -185,7 +190,14 @@ def _sgd_step(model, optimizer, batch, config, backend):
             # statistics computed from the pre-step values -- the reference never decays a buffer
             stats = {}
             packed = train_resnet_gradients(model, batch, config, stats=stats)
+            # behind a downsample stem representation_network.module.conv / .bn are never applied: the reference's optimizer
+            # skips them (their .grad is None), so weight decay and Adam's moments must not move them here either
+            flat = model.flat_weights()
+            bypassed = [(off, numel, flat[off:off + numel].clone()) for key, off, numel, _ in model._tensors
+                        if key.startswith(_BYPASSED)] if model._cfg.downsample else []
             optimizer.step()
+            for off, numel, kept in bypassed:
+                flat[off:off + numel].copy_(kept)
             commit_running_stats(model, stats["running"], stats["applications"])
             model.refresh_derived()
             return packed, len(batch[2])
@@ -268,6 +280,7 @@ def train_fc_gradients(model, batch, config, logits=None):
 
 
 TRAIN_SCRATCH_MAX_BYTES = 32 << 30
+_BYPASSED = ("representation_network.module.conv.", "representation_network.module.bn.")      # with config.downsample
 
 
 def train_resnet_gradients(model, batch, config, logits=None, stats=None):
@@ -278,7 +291,8 @@ def train_resnet_gradients(model, batch, config, logits=None, stats=None):
     Returns the packed device tensor [4 + B * steps].  ``logits``: an optional dict that receives the step-major logits.
     ``stats``: an optional dict that receives ``running`` (the packed running statistics after the step, computed from
     those in the flat buffer; ``commit_running_stats`` writes them into it) and ``applications`` (per network prefix, how
-    often it was applied: what ``num_batches_tracked`` rises by).  Nothing synchronises.  A step whose scratch exceeds
+    often it was applied: what ``num_batches_tracked`` rises by; the first matching prefix counts, and the
+    ``representation_network.module.bn.`` a downsample stem bypasses comes first with 0).  Nothing synchronises.  A step whose scratch exceeds
     ``config.train_scratch_max_bytes`` (default 32 GiB) raises ``NotImplementedError``.
     """
     be, lib = model.backend, model.backend.lib
@@ -290,7 +304,8 @@ def train_resnet_gradients(model, batch, config, logits=None, stats=None):
     if not lib.mzx_train_resnet_supported(model.handle, batch_size, steps):
         cfg = model._cfg
         limit = ("fully connected networks train through mzx_train_fc_step (residual networks only)" if cfg.network != 1 else
-                 "downsample stems (the strided convolutions and pools) are not trained natively" if cfg.downsample else
+                 "downsample stems (the strided convolutions and pools) are not trained natively unless config.train_downsample "
+                 "/ HipNetwork.train_stem is set" if cfg.downsample and not model.train_stem else
                  "the training kernels need at least one residual block per network" if cfg.blocks < 1 else
                  "BatchNorm in training mode needs more than one value per channel (batch x board >= 2)")
         raise NotImplementedError(f"mzx_train_resnet_step does not run this network at batch {batch_size} x {steps} steps: {limit}")
@@ -332,6 +347,8 @@ def train_resnet_gradients(model, batch, config, logits=None, stats=None):
     if stats is not None:
         stats["running"] = running
         stats["applications"] = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
+        if model._cfg.downsample:      # the stem bypasses representation_network.module.conv / .bn (first match wins)
+            stats["applications"] = {"representation_network.module.bn.": 0, **stats["applications"]}
     return packed
 
 
