@@ -1623,12 +1623,41 @@ int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat
 int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) {
   RtnPlan plan;
   if (!rtn_plan(net, batch, steps, true, true, true, plan)) return 0;
-  RtnRun run;
+  RtnRun<false> run;      // (the launches of a step do not depend on its precision)
   memset((void*)&run, 0, sizeof(run));
   run.P = &plan; run.dry = true;
   run.forward();
   run.backward();
   return run.launched + 2;      // (the two launches of the loss head)
+}
+
+// forward pass, loss head, backward pass of a planned step
+extern "C++" template <bool WIDE>
+int rtn_step(const mzx_net* net, const mzx_train_resnet_io* io, const RtnPlan& P, void* stream) {
+  float* scratch = (float*)io->d_scratch;
+  RtnRun<WIDE> run;
+  memset((void*)&run, 0, sizeof(run));
+  run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
+  run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
+  run.vlog = io->d_value_logits ? io->d_value_logits : scratch + P.off_vlog;
+  run.rlog = io->d_reward_logits ? io->d_reward_logits : scratch + P.off_rlog;
+  run.plog = io->d_policy_logits ? io->d_policy_logits : scratch + P.off_plog;
+  mzx_trainer_loss_io lio;
+  memset(&lio, 0, sizeof(lio));
+  lio.d_value_logits = run.vlog; lio.d_reward_logits = run.rlog; lio.d_policy_logits = run.plog;
+  lio.d_target_value = io->d_target_value; lio.d_target_reward = io->d_target_reward; lio.d_target_policy = io->d_target_policy;
+  lio.d_gradient_scale = io->d_gradient_scale; lio.d_weight = io->d_weight;
+  lio.batch = io->batch; lio.steps = io->steps; lio.support_size = net->cfg.support_size; lio.num_actions = P.A;
+  lio.value_loss_weight = io->value_loss_weight; lio.per_alpha = io->per_alpha;
+  lio.d_losses = io->d_losses; lio.d_priorities = io->d_priorities;
+  lio.d_grad_value = scratch + P.off_gv; lio.d_grad_reward = scratch + P.off_gr; lio.d_grad_policy = scratch + P.off_gp;
+  lio.d_scratch = scratch + P.off_loss; lio.scratch_bytes = mzx_trainer_loss_scratch_bytes(io->batch, io->steps);
+  run.forward();
+  MZX_TRY_LAUNCH(run.rc);
+  if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
+  run.backward();
+  MZX_TRY_LAUNCH(run.rc);
+  return MZX_OK;
 }
 
 int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, void* stream) {
@@ -1657,30 +1686,7 @@ int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, voi
     set_error("mzx_train_resnet_step: shape out of range");
     return MZX_ERR_INVALID;
   }
-  float* scratch = (float*)io->d_scratch;
-  RtnRun run;
-  memset((void*)&run, 0, sizeof(run));
-  run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
-  run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
-  run.vlog = io->d_value_logits ? io->d_value_logits : scratch + P.off_vlog;
-  run.rlog = io->d_reward_logits ? io->d_reward_logits : scratch + P.off_rlog;
-  run.plog = io->d_policy_logits ? io->d_policy_logits : scratch + P.off_plog;
-  mzx_trainer_loss_io lio;
-  memset(&lio, 0, sizeof(lio));
-  lio.d_value_logits = run.vlog; lio.d_reward_logits = run.rlog; lio.d_policy_logits = run.plog;
-  lio.d_target_value = io->d_target_value; lio.d_target_reward = io->d_target_reward; lio.d_target_policy = io->d_target_policy;
-  lio.d_gradient_scale = io->d_gradient_scale; lio.d_weight = io->d_weight;
-  lio.batch = io->batch; lio.steps = io->steps; lio.support_size = net->cfg.support_size; lio.num_actions = P.A;
-  lio.value_loss_weight = io->value_loss_weight; lio.per_alpha = io->per_alpha;
-  lio.d_losses = io->d_losses; lio.d_priorities = io->d_priorities;
-  lio.d_grad_value = scratch + P.off_gv; lio.d_grad_reward = scratch + P.off_gr; lio.d_grad_policy = scratch + P.off_gp;
-  lio.d_scratch = scratch + P.off_loss; lio.scratch_bytes = mzx_trainer_loss_scratch_bytes(io->batch, io->steps);
-  run.forward();
-  MZX_TRY_LAUNCH(run.rc);
-  if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
-  run.backward();
-  MZX_TRY_LAUNCH(run.rc);
-  return MZX_OK;
+  return P.stem ? rtn_step<true>(net, io, P, stream) : rtn_step<false>(net, io, P, stream);
 }
 
 int mzx_net_set_train_stem(mzx_net* net, int on) {

@@ -14,17 +14,31 @@
 //     gradient -- runs ONCE over steps x B samples with per-application BatchNorm statistics, and
 //   * only the dynamics tower (and the state normalisation between its applications) is launched step by step.
 //
-// The three GEMMs (RtnGemmBody<MODE>, a wavefront per 16 x 16 output tile on v_mfma_f32_16x16x4_f32, operands gathered
+// One convolution geometry.  Every layer with weights is a convolution: a ksize x ksize kernel (taps = ksize^2) at `stride`
+// with `pad` zeros around the input board Hin x Win, giving the output board H x W.  The plan fills these fields for every
+// layer -- conv3x3 on one board: 3, 1, 1; conv1x1: 1, 1, 0; a Linear layer: 1, 1, 0 on a 1 x 1 board; the strided and padded
+// convolutions of a stem: their own -- and one set of operand functions (rtn_pos, rtn_im2col, rtn_a / rtn_b / rtn_store<MODE>)
+// serves them all, without a special case: the divisors (taps, kernel size, stride) are wave-uniform and known to the host,
+// which prepares a multiplier and a shift for each (RtnDiv), so a division costs every geometry one v_mul_hi_u32.
+//
+// The three GEMMs (RtnGemmBody<MODE, WIDE>, a wavefront per 16 x 16 output tile on v_mfma_f32_16x16x4_f32, operands gathered
 // on the fly, ragged tiles masked):
-//   forward          M = positions (sample, y, x)   N = Cout        K = Cin x taps    A = im2col(x), B = W^T
-//   input gradient   M = positions                  N = Cin (real)  K = Cout x taps   A = im2col(dz, flipped taps), B = W
-//   weight gradient  M = Cout                       N = Cin x taps  K = positions     A = dz^T, B = im2col(x)
-// A Linear layer is the 1-tap case on a 1 x 1 board, a conv1x1 the 1-tap case.  The action plane of the dynamics input
-// is one more (virtual) input channel, zero-padded like the others; the input gradient covers the real channels only.
+//   forward          M = output positions (sample, y, x)   N = Cout        K = Cin x taps    A = im2col(x), B = W^T
+//   input gradient   M = INPUT positions                   N = Cin (real)  K = Cout x taps   A = dz at the outputs a tap reaches, B = W
+//   weight gradient  M = Cout                              N = Cin x taps  K = output positions   A = dz^T, B = im2col(x)
+// The action plane of the dynamics input is one more (virtual) input channel, ci >= creal, zero in the padding like the
+// others; the input gradient covers the real channels only.  The epilogues, each nullable or a flag: bias, ELU or ReLU
+// (forward); ELU', an added gradient, its ReLU mask (input gradient).
 // The weight gradient cuts its reduction (all applications, all samples, the whole board) into chunks of RTN_KCHUNK
 // positions; chunk partials go to scratch and RtnWgradFinishOp sums them in increasing chunk order.  No atomics anywhere:
 // a second call reproduces every bit.  MFMA operand layout: lane l feeds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15],
 // and holds D[4 (l >> 4) + r][l & 15] in accumulator register r.
+//
+// One precision switch, bool WIDE: a template parameter of the step (RtnRun<WIDE>) and so of every GEMM and BatchNorm
+// kernel of it; true for a network with a downsample stem, false for every other.  WIDE = false: a GEMM keeps four binary32
+// accumulator chains over K, and BatchNorm keeps its batch statistics and backward sums, and normalises, in binary32.
+// WIDE = true: every MFMA starts from zero and is added to binary64 accumulators, and the statistics type S of RtnBn<S> is
+// double.  Only the accumulate step and the join of the GEMM differ, and the BatchNorm kernels are written once in S.
 //
 // BatchNorm in training mode, per application: RtnBnStatBody (a wavefront per (application, channel): mean, biased
 // variance in two passes), RtnBnFoldOp (running statistics, applications in forward order, unbiased variance),
@@ -49,19 +63,21 @@
 // pass | h [steps][B][C][HW] | d loss / d h from the prediction tower [steps][B][C][HW] | d loss / d s from the reward
 // head [steps - 1][B][C][HW] | d loss / d h from the next dynamics application [B][C][HW] | two gradient buffers
 // [steps][B][C][HW] | weight-gradient chunk partials | per layer: z, y, dz [applications][B][Cout][HW], BatchNorm
-// mean / 1/sigma / variance [applications][3][C] and the two backward sums [applications][2][C].
+// mean / 1/sigma / variance [applications][3][C] and the two backward sums [applications][2][C] (in S: doubles when WIDE).
 //
 // Downsample stems (cfg.downsample; planned only when mzx_net_set_train_stem switched the handle on, refused by name
 // otherwise): the head of prog_initial -- DownSample's two strided 3 x 3 convolutions without BatchNorm, its eight blocks
 // at C / 2 and C channels and its two AvgPool2d(3, 2, 1), or DownsampleCNN's two biased convolutions (+ ReLU), its two
 // MaxPool2d(3, 2) and its AdaptiveAvgPool2d -- joins the representation chain.  Layers carry their own channel count and
-// boards; RtnGemmBody<MODE, 1> is the general convolution geometry, the pools are element kernels in gather form (below),
+// boards (the one geometry above), the pools are element kernels in gather form (below),
 // the layer that reads the observation gets no input gradient, and representation_network.module.conv / .bn, which the
 // stem bypasses, keep zero gradients and their statistics (RtnPlan::idle).
 //
-// tests/hostcheck build: the same operator list; a GEMM tile is three plain loops over the same operand functions.
+// tests/hostcheck build: the same operator list; a GEMM tile is three plain loops over the same operand functions, in the
+// order of k that WIDE selects (one fmaf chain, or four 4-term chains per 16 values of k added to a double).
 #pragma once
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mzx_launch.h"
@@ -79,92 +95,42 @@ enum RtnMode { RTN_FWD, RTN_DGRAD, RTN_WGRAD };
 
 // ------------------------------------------------------------------------------------------------ the GEMMs
 
+// n / d for 0 <= n < 2^31 by one multiplication, for a divisor the host knows (Granlund & Montgomery 1994, figure 4.1:
+// mul = floor(2^32 (2^shift - d) / d) + 1 with shift = ceil(log2 d); n < 2^31 keeps the sum below from overflowing).  The
+// divisors of the geometry are wave-uniform but not compile-time constants, and the instruction sequence of a general
+// integer division per gathered element made the step 8 - 14 % slower (profiles/resnet_train_refactor_ab.txt).
+struct RtnDiv { uint32_t mul, shift; };
+inline RtnDiv rtn_div_by(int d) {
+  RtnDiv r;
+  r.shift = 0;
+  while (((int64_t)1 << r.shift) < d) ++r.shift;
+  r.mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << r.shift) - (uint64_t)d)) / (uint64_t)d + 1);
+  return r;
+}
+MZX_HD inline int rtn_div(int n, const RtnDiv& d) {
+  return (int)(((uint32_t)(((uint64_t)(uint32_t)n * d.mul) >> 32) + (uint32_t)n) >> d.shift);
+}
+
 struct RtnGemm {
-  const float* x;          // FWD / WGRAD: the layer's input [nb][creal][H][W]
+  const float* x;          // FWD / WGRAD: the layer's input [nb][creal][Hin][Win]
   const float* g;          // DGRAD / WGRAD: d loss / d z [nb][cout][H][W]
   const float* w;          // [cout][cin][taps]
-  const float* bias;       // FWD, nullable
+  const float* bias;       // FWD epilogue, nullable
   float* out;
   const float* add;        // DGRAD epilogue, nullable: out = acc + add (where mask > 0, when a mask is given)
   const float* mask;
   const float* elu_y;      // DGRAD epilogue, nullable: acc *= ELU'(z) from ELU(z)
   const int32_t* action;   // [B][act_steps]; the virtual channel of sample bb is action[bb % B][act_t0 + bb / B] / num_actions
-  int32_t nb, B, cin, creal, cout, H, W, taps, elu, act_steps, act_t0, num_actions;
+  int32_t nb, B, cin, creal, cout, elu, relu, act_steps, act_t0, num_actions;      // elu, relu: FWD epilogue flags
+  // the geometry: a ksize x ksize kernel (taps = ksize^2) at `stride`, `pad` zeros around the input board Hin x Win,
+  // the output board H x W.  All of it is wave-uniform.
+  int32_t ksize, taps, stride, pad, Hin, Win, H, W;
+  RtnDiv by_ksize, by_taps, by_stride;
   int32_t M, N, K, kchunk, nchunks, tiles_m, tiles_n;
-  // general geometry (RtnGemmBody<MODE, 1>, the stem of a downsample network): H x W is then the OUTPUT board
-  int32_t ksize, stride, pad, Hin, Win, relu;
 };
 
 struct RtnPos { int32_t bb, py, px, rem; };
-MZX_HD inline RtnPos rtn_pos(const RtnGemm& p, int pos) {
-  const int hw = p.H * p.W;
-  RtnPos s;
-  s.bb = pos / hw;
-  s.rem = pos - s.bb * hw;
-  s.py = s.rem / p.W;
-  s.px = s.rem - s.py * p.W;
-  return s;
-}
-// the input of channel ci at tap `tap` around a position (zero outside the board, the action plane included)
-MZX_HD inline float rtn_im2col(const RtnGemm& p, const RtnPos& s, int ci, int tap) {
-  int y = s.py, x = s.px;
-  if (p.taps == 9) {
-    y += tap / 3 - 1; x += tap % 3 - 1;
-    if (y < 0 || y >= p.H || x < 0 || x >= p.W) return 0.f;
-  }
-  if (ci >= p.creal) return (float)p.action[(int64_t)(s.bb % p.B) * p.act_steps + p.act_t0 + s.bb / p.B] / (float)p.num_actions;
-  return p.x[(((int64_t)s.bb * p.creal + ci) * p.H + y) * p.W + x];
-}
-// A[m][k]; `row` = rtn_pos(m) for the two modes whose rows are positions
-template <int MODE>
-MZX_HD inline float rtn_a(const RtnGemm& p, int m, int k, const RtnPos& row) {
-  if (m >= p.M || k >= p.K) return 0.f;
-  if (MODE == RTN_WGRAD) {
-    const int hw = p.H * p.W, bb = k / hw;
-    return p.g[((int64_t)bb * p.cout + m) * hw + (k - bb * hw)];
-  }
-  const int c = p.taps == 9 ? k / 9 : k, tap = p.taps == 9 ? k - c * 9 : 0;
-  if (MODE == RTN_FWD) return rtn_im2col(p, row, c, tap);
-  int y = row.py, x = row.px;          // DGRAD: the output position that read this input position through `tap`
-  if (p.taps == 9) {
-    y -= tap / 3 - 1; x -= tap % 3 - 1;
-    if (y < 0 || y >= p.H || x < 0 || x >= p.W) return 0.f;
-  }
-  return p.g[(((int64_t)row.bb * p.cout + c) * p.H + y) * p.W + x];
-}
-template <int MODE>
-MZX_HD inline float rtn_b(const RtnGemm& p, int k, int n) {
-  if (n >= p.N || k >= p.K) return 0.f;
-  if (MODE == RTN_FWD) return p.w[(int64_t)n * p.K + k];
-  if (MODE == RTN_DGRAD) {
-    const int co = p.taps == 9 ? k / 9 : k, tap = p.taps == 9 ? k - co * 9 : 0;
-    return p.w[((int64_t)co * p.cin + n) * p.taps + tap];
-  }
-  const int ci = p.taps == 9 ? n / 9 : n, tap = p.taps == 9 ? n - ci * 9 : 0;
-  return rtn_im2col(p, rtn_pos(p, k), ci, tap);
-}
-template <int MODE>
-MZX_HD inline void rtn_store(const RtnGemm& p, int m, int n, int chunk, float v) {
-  if (m >= p.M || n >= p.N) return;
-  if (MODE == RTN_WGRAD) { p.out[((int64_t)chunk * p.M + m) * p.N + n] = v; return; }
-  const RtnPos s = rtn_pos(p, m);
-  const int hw = p.H * p.W;
-  if (MODE == RTN_FWD) {
-    if (p.bias) v += p.bias[n];
-    if (p.elu) v = mzx_elu(v);
-    p.out[((int64_t)s.bb * p.cout + n) * hw + s.rem] = v;
-    return;
-  }
-  const int64_t at = ((int64_t)s.bb * p.creal + n) * hw + s.rem;
-  if (p.elu_y) { const float a = p.elu_y[at]; v *= (a > 0.f ? 1.0f : a + 1.0f); }
-  if (p.add && (!p.mask || p.mask[at] > 0.f)) v += p.add[at];
-  p.out[at] = v;
-}
-
-// ---- general geometry (any square kernel, stride, padding; the output board H x W differs from the input board Hin x Win):
-// the stem of a downsample network.  A template parameter of the body selects these, so the same-board path above keeps its
-// code.  taps = ksize^2; no action plane (creal == cin); the divisors (taps, ksize, stride, the boards) are wave-uniform.
-MZX_HD inline RtnPos rtng_pos(int pos, int h, int w) {
+MZX_HD inline RtnPos rtn_pos(int pos, int h, int w) {
   const int hw = h * w;
   RtnPos s;
   s.bb = pos / hw;
@@ -173,81 +139,75 @@ MZX_HD inline RtnPos rtng_pos(int pos, int h, int w) {
   s.px = s.rem - s.py * w;
   return s;
 }
-// the input of channel ci that output position s reads through `tap` (zero in the padding)
-MZX_HD inline float rtng_im2col(const RtnGemm& p, const RtnPos& s, int ci, int tap) {
-  const int ky = tap / p.ksize, kx = tap - ky * p.ksize;
+// the input of channel ci that output position s reads through `tap` (zero in the padding, the action plane included)
+MZX_HD inline float rtn_im2col(const RtnGemm& p, const RtnPos& s, int ci, int tap) {
+  const int ky = rtn_div(tap, p.by_ksize), kx = tap - ky * p.ksize;
   const int y = s.py * p.stride - p.pad + ky, x = s.px * p.stride - p.pad + kx;
   if (y < 0 || y >= p.Hin || x < 0 || x >= p.Win) return 0.f;
+  if (ci >= p.creal) return (float)p.action[(int64_t)(s.bb % p.B) * p.act_steps + p.act_t0 + s.bb / p.B] / (float)p.num_actions;
   return p.x[(((int64_t)s.bb * p.creal + ci) * p.Hin + y) * p.Win + x];
 }
-// `row`: FWD the output position m, DGRAD the INPUT position m
+// A[m][k]; `row`: FWD the output position m, DGRAD the INPUT position m
 template <int MODE>
-MZX_HD inline float rtng_a(const RtnGemm& p, int m, int k, const RtnPos& row) {
+MZX_HD inline float rtn_a(const RtnGemm& p, int m, int k, const RtnPos& row) {
   if (m >= p.M || k >= p.K) return 0.f;
   if (MODE == RTN_WGRAD) {
     const int hw = p.H * p.W, bb = k / hw;
     return p.g[((int64_t)bb * p.cout + m) * hw + (k - bb * hw)];
   }
-  const int c = k / p.taps, tap = k - c * p.taps;
-  if (MODE == RTN_FWD) return rtng_im2col(p, row, c, tap);
+  const int c = rtn_div(k, p.by_taps), tap = k - c * p.taps;
+  if (MODE == RTN_FWD) return rtn_im2col(p, row, c, tap);
   // DGRAD: the tap contributes where (y + pad - ky, x + pad - kx) is a multiple of the stride whose quotient is on the output board
-  const int ky = tap / p.ksize, kx = tap - ky * p.ksize;
+  const int ky = rtn_div(tap, p.by_ksize), kx = tap - ky * p.ksize;
   const int ty = row.py + p.pad - ky, tx = row.px + p.pad - kx;
   if (ty < 0 || tx < 0) return 0.f;
-  const int oy = ty / p.stride, ox = tx / p.stride;
+  const int oy = rtn_div(ty, p.by_stride), ox = rtn_div(tx, p.by_stride);
   if (oy * p.stride != ty || ox * p.stride != tx || oy >= p.H || ox >= p.W) return 0.f;
   return p.g[(((int64_t)row.bb * p.cout + c) * p.H + oy) * p.W + ox];
 }
 template <int MODE>
-MZX_HD inline float rtng_b(const RtnGemm& p, int k, int n) {
+MZX_HD inline float rtn_b(const RtnGemm& p, int k, int n) {
   if (n >= p.N || k >= p.K) return 0.f;
   if (MODE == RTN_FWD) return p.w[(int64_t)n * p.K + k];
   if (MODE == RTN_DGRAD) {
-    const int co = k / p.taps, tap = k - co * p.taps;
+    const int co = rtn_div(k, p.by_taps), tap = k - co * p.taps;
     return p.w[((int64_t)co * p.cin + n) * p.taps + tap];
   }
-  const int ci = n / p.taps, tap = n - ci * p.taps;      // (n is fixed per lane: hoisted out of the K loop)
-  return rtng_im2col(p, rtng_pos(k, p.H, p.W), ci, tap);
+  const int ci = rtn_div(n, p.by_taps), tap = n - ci * p.taps;      // (n is fixed per lane: hoisted out of the K loop)
+  return rtn_im2col(p, rtn_pos(k, p.H, p.W), ci, tap);
 }
 template <int MODE>
-MZX_HD inline void rtng_store(const RtnGemm& p, int m, int n, int chunk, float v) {
+MZX_HD inline void rtn_store(const RtnGemm& p, int m, int n, int chunk, float v) {
   if (m >= p.M || n >= p.N) return;
   if (MODE == RTN_WGRAD) { p.out[((int64_t)chunk * p.M + m) * p.N + n] = v; return; }
   if (MODE == RTN_FWD) {
-    const RtnPos s = rtng_pos(m, p.H, p.W);
+    const RtnPos s = rtn_pos(m, p.H, p.W);
     if (p.bias) v += p.bias[n];
+    if (p.elu) v = mzx_elu(v);
     if (p.relu) v = fmaxf(v, 0.f);
     p.out[((int64_t)s.bb * p.cout + n) * (p.H * p.W) + s.rem] = v;
     return;
   }
-  const RtnPos s = rtng_pos(m, p.Hin, p.Win);
-  p.out[((int64_t)s.bb * p.creal + n) * (p.Hin * p.Win) + s.rem] = v;
-}
-template <int MODE, int GEO>
-MZX_HD inline RtnPos rtnx_row(const RtnGemm& p, int m) {
-  if (GEO == 1) return MODE == RTN_DGRAD ? rtng_pos(m, p.Hin, p.Win) : rtng_pos(m, p.H, p.W);
-  return rtn_pos(p, m);
-}
-template <int MODE, int GEO>
-MZX_HD inline float rtnx_a(const RtnGemm& p, int m, int k, const RtnPos& row) { return GEO == 1 ? rtng_a<MODE>(p, m, k, row) : rtn_a<MODE>(p, m, k, row); }
-template <int MODE, int GEO>
-MZX_HD inline float rtnx_b(const RtnGemm& p, int k, int n) { return GEO == 1 ? rtng_b<MODE>(p, k, n) : rtn_b<MODE>(p, k, n); }
-template <int MODE, int GEO>
-MZX_HD inline void rtnx_store(const RtnGemm& p, int m, int n, int chunk, float v) {
-  if (GEO == 1) rtng_store<MODE>(p, m, n, chunk, v); else rtn_store<MODE>(p, m, n, chunk, v);
+  const RtnPos s = rtn_pos(m, p.Hin, p.Win);
+  const int64_t at = ((int64_t)s.bb * p.creal + n) * (p.Hin * p.Win) + s.rem;
+  if (p.elu_y) { const float a = p.elu_y[at]; v *= (a > 0.f ? 1.0f : a + 1.0f); }
+  if (p.add && (!p.mask || p.mask[at] > 0.f)) v += p.add[at];
+  p.out[at] = v;
 }
 
 #ifndef MZX_HOSTCHECK
 typedef float rtn_f32x4 __attribute__((ext_vector_type(4)));
 #endif
 
-// a wavefront per (chunk, 16 x 16 tile).  GEO = 0: 1 or 9 taps, stride 1, one board, four binary32 accumulator chains over
-// the whole of K.  GEO = 1 (the general geometry) and GEO = 2 (the geometry of GEO = 0) are what a network with a downsample
-// stem runs, every GEMM of its step: its chain of BatchNorm layers is several times as deep (eight more blocks before the
-// representation tower), and what the binary32 chains round away reaches the first blocks' gradients amplified by every
-// 1 / sigma on the way -- so there every MFMA starts from zero (four products in binary32) and its result is added to a
-// binary64 accumulator, rounded once at the end, like every other long sum of this file.
-template <int MODE, int GEO = 0>
+// a wavefront per (chunk, 16 x 16 tile).  WIDE = false: four binary32 accumulator chains over the whole of K, joined
+// (0 + 1) + (2 + 3): they hide the MFMA's dependent latency, and four short sums joined at the end round less than one long
+// one.  WIDE = true is what a network with a downsample stem runs, every GEMM of its step: its chain of BatchNorm layers is
+// several times as deep (eight more blocks before the representation tower), and what the binary32 chains round away
+// reaches the first blocks' gradients amplified by every 1 / sigma on the way -- so there every MFMA starts from zero (four
+// products in binary32) and its result is added to a binary64 accumulator, rounded once at the end, like every other long
+// sum of this file.  The serial build keeps its two orders: one fmaf chain over K, or per 16 values of k four 4-term chains
+// added to a double.
+template <int MODE, bool WIDE>
 struct RtnGemmBody {
   RtnGemm p;
   MZX_HD size_t size() const { return (size_t)p.tiles_m * p.tiles_n * p.nchunks; }
@@ -261,72 +221,56 @@ struct RtnGemmBody {
     for (int i = 0; i < 16; ++i) {
       const int m = m0 + i;
       if (m >= p.M) break;
-      const RtnPos row = (MODE == RTN_WGRAD) ? RtnPos{0, 0, 0, 0} : rtnx_row<MODE, GEO>(p, m);
+      const RtnPos row = row_of(m);
       for (int j = 0; j < 16; ++j) {
         const int n = n0 + j;
         if (n >= p.N) break;
-        if (GEO) {
-          double wide = 0.0;
-          for (int k = k0; k < k1; k += 16) {
-            float t[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int c = 0; c < 4; ++c)
-              for (int kc = k + 4 * c; kc < k + 4 * c + 4 && kc < k1; ++kc) t[c] = fmaf(rtnx_a<MODE, GEO>(p, m, kc, row), rtnx_b<MODE, GEO>(p, kc, n), t[c]);
-            for (int c = 0; c < 4; ++c) wide += (double)t[c];
-          }
-          rtnx_store<MODE, GEO>(p, m, n, chunk, (float)wide);
-          continue;
-        }
         float acc = 0.f;
-        for (int k = k0; k < k1; ++k) acc = fmaf(rtnx_a<MODE, GEO>(p, m, k, row), rtnx_b<MODE, GEO>(p, k, n), acc);
-        rtnx_store<MODE, GEO>(p, m, n, chunk, acc);
+        double wide = 0.0;
+        for (int k = k0; k < k1; k += 16) {
+          float t[4] = {0.f, 0.f, 0.f, 0.f};
+          for (int c = 0; c < 4; ++c) {
+            float& sum = WIDE ? t[c] : acc;
+            for (int kc = k + 4 * c; kc < k + 4 * c + 4 && kc < k1; ++kc) sum = fmaf(rtn_a<MODE>(p, m, kc, row), rtn_b<MODE>(p, kc, n), sum);
+          }
+          if (WIDE) for (int c = 0; c < 4; ++c) wide += (double)t[c];
+        }
+        rtn_store<MODE>(p, m, n, chunk, WIDE ? (float)wide : acc);
       }
     }
 #else
     const int r = lane & 15, q = lane >> 4;
     const int m = m0 + r, n = n0 + r;
-    const RtnPos row = (MODE == RTN_WGRAD || m >= p.M) ? RtnPos{0, 0, 0, 0} : rtnx_row<MODE, GEO>(p, m);
-    // four accumulator chains: they hide the MFMA's dependent latency, and four short sums joined at the end round less
-    // than one long one
-    if (GEO) {
-      double wide[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int k = k0; k < k1; k += 16) {
-        float a[4], b[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int kc = k + 4 * c + q;
-          a[c] = kc < k1 ? rtnx_a<MODE, GEO>(p, m, kc, row) : 0.f;
-          b[c] = kc < k1 ? rtnx_b<MODE, GEO>(p, kc, n) : 0.f;
-        }
-        rtn_f32x4 t[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) t[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], rtn_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) wide[i] += (double)t[c][i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rtnx_store<MODE, GEO>(p, m0 + 4 * q + i, n, chunk, (float)wide[i]);
-      return;
-    }
-    rtn_f32x4 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = rtn_f32x4{0.f, 0.f, 0.f, 0.f};
+    const RtnPos row = m >= p.M ? RtnPos{0, 0, 0, 0} : row_of(m);
+    const rtn_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    rtn_f32x4 acc[4] = {zero, zero, zero, zero};
+    double wide[4] = {0.0, 0.0, 0.0, 0.0};
     for (int k = k0; k < k1; k += 16) {
       float a[4], b[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int kc = k + 4 * c + q;
-        a[c] = kc < k1 ? rtnx_a<MODE, GEO>(p, m, kc, row) : 0.f;
-        b[c] = kc < k1 ? rtnx_b<MODE, GEO>(p, kc, n) : 0.f;
+        a[c] = kc < k1 ? rtn_a<MODE>(p, m, kc, row) : 0.f;
+        b[c] = kc < k1 ? rtn_b<MODE>(p, kc, n) : 0.f;
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc[c], 0, 0, 0);
-    }
-    const rtn_f32x4 acc0 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], WIDE ? zero : acc[c], 0, 0, 0);
+      if (WIDE) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rtnx_store<MODE, GEO>(p, m0 + 4 * q + i, n, chunk, acc0[i]);
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) wide[i] += (double)acc[c][i];
+      }
+    }
+    const rtn_f32x4 joined = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rtn_store<MODE>(p, m0 + 4 * q + i, n, chunk, WIDE ? (float)wide[i] : joined[i]);
 #endif
+  }
+  // the position of row m for the two modes whose rows are positions
+  MZX_HD RtnPos row_of(int m) const {
+    if (MODE == RTN_WGRAD) return RtnPos{0, 0, 0, 0};
+    return MODE == RTN_DGRAD ? rtn_pos(m, p.Hin, p.Win) : rtn_pos(m, p.H, p.W);
   }
 };
 
@@ -470,6 +414,11 @@ struct RtnPoolBwdOp {
 
 // ------------------------------------------------------------------------------------------------ BatchNorm, training mode
 
+// S, the type of the batch statistics, the backward sums and the arithmetic of normalise / dz: float, or double in a network
+// with a downsample stem (WIDE).  A mean or 1 / sigma rounded to binary32 shifts or scales a whole channel by one correlated
+// error, which the sums of the next layers do not average away; behind nineteen BatchNorm layers that is what the gradients'
+// error is made of.  The running statistics fold the binary32-rounded batch statistics in both.
+template <class S>
 struct RtnBn {
   const float* z;          // [napps][B][C][HW]
   const float* y;          // the layer's output (after residual and ReLU): the ReLU mask of the backward pass
@@ -478,22 +427,17 @@ struct RtnBn {
   float* out;              // forward: y; backward: dz
   const float* gamma;
   const float* beta;
-  float* saved;            // [napps][3][C]: mean, 1 / sigma, biased variance
-  float* sums;             // [napps][2][C]: sum g, sum g x^
+  S* saved;                // [napps][3][C]: mean, 1 / sigma, biased variance
+  S* sums;                 // [napps][2][C]: sum g, sum g x^
   float* running;          // [2][C]: running_mean, running_var of the statistics output
   float* dgamma;
   float* dbeta;
   int32_t napps, B, C, HW;
-  // a network with a downsample stem (nullable otherwise; the float path above keeps its code and sums): the batch
-  // statistics and the backward sums are ALSO kept in binary64, and normalise / dz compute in binary64 and round once.  A
-  // mean or 1 / sigma rounded to binary32 shifts or scales a whole channel by one correlated error, which the sums of
-  // the next layers do not average away; behind nineteen BatchNorm layers that is what the gradients' error is made of.
-  double* saved64;         // [napps][3][C]
-  double* sums64;          // [napps][2][C]
 };
 
+template <class S>
 struct RtnBnStatBody {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.napps * p.C; }
   MZX_WAVE_FN void operator()(size_t item, int lane) const {
     const int app = (int)(item / p.C), c = (int)(item % p.C);
@@ -511,124 +455,89 @@ struct RtnBnStatBody {
     }
     const double var = wave_sum_f64(s2) / (double)n;
     if (lane == 0) {
-      float* sv = p.saved + (int64_t)app * 3 * p.C;
-      sv[c] = (float)mean; sv[p.C + c] = (float)(1.0 / sqrt(var + (double)RTN_BN_EPS)); sv[2 * p.C + c] = (float)var;
-      if (p.saved64) {
-        double* sd = p.saved64 + (int64_t)app * 3 * p.C;
-        sd[c] = mean; sd[p.C + c] = 1.0 / sqrt(var + (double)RTN_BN_EPS); sd[2 * p.C + c] = var;
-      }
+      S* sv = p.saved + (int64_t)app * 3 * p.C;
+      sv[c] = (S)mean; sv[p.C + c] = (S)(1.0 / sqrt(var + (double)RTN_BN_EPS)); sv[2 * p.C + c] = (S)var;
     }
   }
 };
 
-// running <- 0.9 running + 0.1 batch (the variance unbiased), the applications in forward order
+// running <- 0.9 running + 0.1 batch (the variance unbiased), the applications in forward order; the batch statistics enter
+// rounded to binary32, whatever S keeps
+template <class S>
 struct RtnBnFoldOp {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.C; }
   MZX_HD void operator()(size_t c) const {
     const double n = (double)p.B * p.HW;
     double rm = p.running[c], rv = p.running[p.C + c];
     for (int app = 0; app < p.napps; ++app) {
-      const float* sv = p.saved + (int64_t)app * 3 * p.C;
-      rm = (double)(float)(RTN_BN_MOMENTUM * (double)sv[c] + (1.0 - RTN_BN_MOMENTUM) * rm);
-      rv = (double)(float)(RTN_BN_MOMENTUM * ((double)sv[2 * p.C + c] * n / (n - 1.0)) + (1.0 - RTN_BN_MOMENTUM) * rv);
+      const S* sv = p.saved + (int64_t)app * 3 * p.C;
+      const float mean = (float)sv[c], var = (float)sv[2 * p.C + c];
+      rm = (double)(float)(RTN_BN_MOMENTUM * (double)mean + (1.0 - RTN_BN_MOMENTUM) * rm);
+      rv = (double)(float)(RTN_BN_MOMENTUM * ((double)var * n / (n - 1.0)) + (1.0 - RTN_BN_MOMENTUM) * rv);
     }
     p.running[c] = (float)rm; p.running[p.C + c] = (float)rv;
   }
 };
 
+template <class S>
 struct RtnBnApplyOp {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.napps * p.B * p.C * p.HW; }
   MZX_HD void operator()(size_t i) const {
     const int c = (int)((i / p.HW) % p.C), app = (int)(i / ((size_t)p.B * p.C * p.HW));
-    if (p.saved64) {
-      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
-      double w = ((double)p.z[i] - sd[c]) * sd[p.C + c] * (double)p.gamma[c] + (double)p.beta[c];
-      if (p.res) w += (double)p.res[i];
-      p.out[i] = fmaxf((float)w, 0.f);
-      return;
-    }
-    const float* sv = p.saved + (int64_t)app * 3 * p.C;
-    float v = (p.z[i] - sv[c]) * sv[p.C + c] * p.gamma[c] + p.beta[c];
-    if (p.res) v += p.res[i];
-    p.out[i] = fmaxf(v, 0.f);
+    const S* sv = p.saved + (int64_t)app * 3 * p.C;
+    S v = ((S)p.z[i] - sv[c]) * sv[p.C + c] * (S)p.gamma[c] + (S)p.beta[c];
+    if (p.res) v += (S)p.res[i];
+    p.out[i] = fmaxf((float)v, 0.f);
   }
 };
 
+template <class S>
 struct RtnBnSumsBody {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.napps * p.C; }
   MZX_WAVE_FN void operator()(size_t item, int lane) const {
     const int app = (int)(item / p.C), c = (int)(item % p.C);
     const int n = p.B * p.HW;
     const int64_t base = ((int64_t)app * p.B * p.C + c) * p.HW;
-    const float* sv = p.saved + (int64_t)app * 3 * p.C;
-    const float mean = sv[c], inv = sv[p.C + c];
+    const S* sv = p.saved + (int64_t)app * 3 * p.C;
+    const S mean = sv[c], inv = sv[p.C + c];
     double sg = 0.0, sgx = 0.0;
-    if (p.saved64) {
-      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
-      const double mean64 = sd[c], inv64 = sd[p.C + c];
-      for (int i = lane; i < n; i += WAVE_LANES) {
-        const int b = i / p.HW;
-        const int64_t at = base + (int64_t)b * p.C * p.HW + (i - b * p.HW);
-        const double g = p.y[at] > 0.f ? (double)p.g[at] : 0.0;
-        sg += g;
-        sgx += g * (((double)p.z[at] - mean64) * inv64);
-      }
-      sg = wave_sum_f64(sg); sgx = wave_sum_f64(sgx);
-      if (lane == 0) {
-        p.sums[(int64_t)app * 2 * p.C + c] = (float)sg; p.sums[(int64_t)app * 2 * p.C + p.C + c] = (float)sgx;
-        p.sums64[(int64_t)app * 2 * p.C + c] = sg; p.sums64[(int64_t)app * 2 * p.C + p.C + c] = sgx;
-      }
-      return;
-    }
     for (int i = lane; i < n; i += WAVE_LANES) {
       const int b = i / p.HW;
       const int64_t at = base + (int64_t)b * p.C * p.HW + (i - b * p.HW);
-      const float g = p.y[at] > 0.f ? p.g[at] : 0.f;
+      const S g = p.y[at] > 0.f ? (S)p.g[at] : (S)0;
       sg += (double)g;
-      sgx += (double)g * (double)((p.z[at] - mean) * inv);
+      sgx += (double)g * (double)(((S)p.z[at] - mean) * inv);
     }
     sg = wave_sum_f64(sg); sgx = wave_sum_f64(sgx);
-    if (lane == 0) { p.sums[(int64_t)app * 2 * p.C + c] = (float)sg; p.sums[(int64_t)app * 2 * p.C + p.C + c] = (float)sgx; }
+    if (lane == 0) { p.sums[(int64_t)app * 2 * p.C + c] = (S)sg; p.sums[(int64_t)app * 2 * p.C + p.C + c] = (S)sgx; }
   }
 };
 
+template <class S>
 struct RtnBnDzOp {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.napps * p.B * p.C * p.HW; }
   MZX_HD void operator()(size_t i) const {
     const int c = (int)((i / p.HW) % p.C), app = (int)(i / ((size_t)p.B * p.C * p.HW));
-    if (p.saved64) {
-      const double* sd = p.saved64 + (int64_t)app * 3 * p.C;
-      const double* sw = p.sums64 + (int64_t)app * 2 * p.C;
-      const double nn = (double)(p.B * p.HW);
-      const double gw = p.y[i] > 0.f ? (double)p.g[i] : 0.0;
-      const double xw = ((double)p.z[i] - sd[c]) * sd[p.C + c];
-      p.out[i] = (float)((double)p.gamma[c] * sd[p.C + c] * (gw - sw[c] / nn - xw * (sw[p.C + c] / nn)));
-      return;
-    }
-    const float* sv = p.saved + (int64_t)app * 3 * p.C;
-    const float* sm = p.sums + (int64_t)app * 2 * p.C;
-    const float n = (float)(p.B * p.HW);
-    const float g = p.y[i] > 0.f ? p.g[i] : 0.f;
-    const float xh = (p.z[i] - sv[c]) * sv[p.C + c];
-    p.out[i] = p.gamma[c] * sv[p.C + c] * (g - sm[c] / n - xh * (sm[p.C + c] / n));
+    const S* sv = p.saved + (int64_t)app * 3 * p.C;
+    const S* sm = p.sums + (int64_t)app * 2 * p.C;
+    const S n = (S)(p.B * p.HW);
+    const S g = p.y[i] > 0.f ? (S)p.g[i] : (S)0;
+    const S xh = ((S)p.z[i] - sv[c]) * sv[p.C + c];
+    p.out[i] = (float)((S)p.gamma[c] * sv[p.C + c] * (g - sm[c] / n - xh * (sm[p.C + c] / n)));
   }
 };
 
 // d gamma = sum g x^, d beta = sum g, over the applications in increasing order
+template <class S>
 struct RtnBnParamGradOp {
-  RtnBn p;
+  RtnBn<S> p;
   MZX_HD size_t size() const { return (size_t)p.C; }
   MZX_HD void operator()(size_t c) const {
     double dg = 0.0, db = 0.0;
-    if (p.sums64) {
-      for (int app = 0; app < p.napps; ++app) { db += p.sums64[(int64_t)app * 2 * p.C + c]; dg += p.sums64[(int64_t)app * 2 * p.C + p.C + c]; }
-      p.dgamma[c] = (float)dg; p.dbeta[c] = (float)db;
-      return;
-    }
     for (int app = 0; app < p.napps; ++app) { db += (double)p.sums[(int64_t)app * 2 * p.C + c]; dg += (double)p.sums[(int64_t)app * 2 * p.C + p.C + c]; }
     p.dgamma[c] = (float)dg; p.dbeta[c] = (float)db;
   }
@@ -718,13 +627,14 @@ struct RtnLayer {
   // OP_CONV3 (+ BatchNorm [+ residual] + ReLU), OP_CONV1 (bias), OP_LINEAR (bias [+ ELU]); in the stem of a downsample
   // network also RTN_PLAIN, OP_CONVK (bias + ReLU) and the three pools (no weights: y only)
   int kind = 0;
-  int32_t cin = 0, creal = 0, cout = 0, H = 1, W = 1, taps = 1, elu = 0, has_res = 0;      // H x W: the OUTPUT board
-  int32_t ksize = 1, stride = 1, pad = 0, Hin = 1, Win = 1, relu = 0, geo = 0;             // geo: RtnGemmBody<MODE, 1>
+  int32_t cin = 0, creal = 0, cout = 0, elu = 0, relu = 0, has_res = 0;
+  // the geometry, a Linear layer's by default: a 1 x 1 kernel on a 1 x 1 board.  Hin x Win -> H x W
+  int32_t ksize = 1, taps = 1, stride = 1, pad = 0, Hin = 1, Win = 1, H = 1, W = 1;
   int64_t w = -1, b = -1;            // flat offsets
   BnRef bn;
   int64_t stat = -1;                 // offset of this BatchNorm in the statistics output
-  int64_t saved64 = -1, sums64 = -1; // (a stem network: the same in binary64, offsets in floats)
-  int64_t z = -1, y = -1, dz = -1, saved = -1, sums = -1;      // scratch offsets; y / dz = -1: the logits / the loss head's gradients
+  // scratch offsets in floats (saved / sums hold doubles in a stem network); y / dz = -1: the logits / the loss head's gradients
+  int64_t z = -1, y = -1, dz = -1, saved = -1, sums = -1;
   int64_t per_app(int B) const { return (int64_t)B * cout * H * W; }
 };
 enum RtnNetId { RTN_REP, RTN_DYN, RTN_PRED, RTN_REW, RTN_VAL, RTN_POL, RTN_NETS };
@@ -782,7 +692,7 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
       L.kind = k ? (int)OP_CONVK : RTN_PLAIN; L.b = k ? d.b : -1; L.relu = d.relu;
       L.ksize = k ? d.ksize : 3; L.stride = d.stride; L.pad = k ? d.pad : 1;
       L.cin = L.creal = d.cin; L.cout = d.cout; L.Hin = d.hin; L.Win = d.win; L.H = d.hout; L.W = d.wout;
-      L.taps = L.ksize * L.ksize; L.geo = 1;
+      L.taps = L.ksize * L.ksize;
       return L.ksize >= 1 && L.stride >= 1 && L.pad >= 0 && L.H >= 1 && L.W >= 1 &&
              L.H == (L.Hin + 2 * L.pad - L.ksize) / L.stride + 1 && L.W == (L.Win + 2 * L.pad - L.ksize) / L.stride + 1;
     }
@@ -936,8 +846,8 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
       RtnLayer& L = ch.l[i];
       const int64_t all = ch.napps * L.per_app(B);
       const bool head_out = n >= RTN_REW && i + 1 == ch.l.size();
-      if (L.kind == OP_CONV3) { L.z = take(all); L.saved = take((int64_t)ch.napps * 3 * L.cout); L.sums = take((int64_t)ch.napps * 2 * L.cout); }
-      if (L.kind == OP_CONV3 && stem) { L.saved64 = take((int64_t)ch.napps * 6 * L.cout); L.sums64 = take((int64_t)ch.napps * 4 * L.cout); }
+      const int wide = stem ? 2 : 1;      // floats per statistic
+      if (L.kind == OP_CONV3) { L.z = take(all); L.saved = take((int64_t)ch.napps * 3 * L.cout * wide); L.sums = take((int64_t)ch.napps * 2 * L.cout * wide); }
       L.y = head_out ? -1 : take(all);
       if (rtn_is_pool(L.kind)) continue;
       L.dz = head_out ? -1 : take(all);
@@ -952,7 +862,10 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
 
 // ------------------------------------------------------------------------------------------------ the step (host)
 
+// WIDE: the precision switch of every GEMM and BatchNorm kernel of the step (a network with a downsample stem)
+template <bool WIDE>
 struct RtnRun {
+  typedef typename std::conditional<WIDE, double, float>::type S;
   const RtnPlan* P;
   const float* flat;
   const float* obs;
@@ -1006,56 +919,39 @@ struct RtnRun {
   }
   const float* x_of(int n, size_t i, int app) const { return i == 0 ? input_of(n, app) : y_of(n, i - 1, app); }
 
-  RtnGemm gemm(int n, size_t i, int app, int napps, int mode) const {
+  template <int MODE>
+  RtnGemm gemm(int n, size_t i, int app, int napps) const {
     const RtnPlan& p = *P;
     const RtnLayer& L = p.net[n].l[i];
     RtnGemm g;
     memset(&g, 0, sizeof(g));
     g.w = flat + L.w;
     g.action = action; g.act_steps = p.steps; g.act_t0 = p.net[n].t0 + app; g.num_actions = p.A;
-    g.nb = napps * p.B; g.B = p.B; g.cin = L.cin; g.creal = L.creal; g.cout = L.cout; g.H = L.H; g.W = L.W; g.taps = L.taps;
-    g.ksize = L.ksize; g.stride = L.stride; g.pad = L.pad; g.Hin = L.Hin; g.Win = L.Win;
+    g.nb = napps * p.B; g.B = p.B; g.cin = L.cin; g.creal = L.creal; g.cout = L.cout;
+    g.ksize = L.ksize; g.taps = L.taps; g.stride = L.stride; g.pad = L.pad; g.Hin = L.Hin; g.Win = L.Win; g.H = L.H; g.W = L.W;
+    g.by_ksize = rtn_div_by(L.ksize); g.by_taps = rtn_div_by(L.taps); g.by_stride = rtn_div_by(L.stride);
     const int positions = g.nb * L.H * L.W;
-    if (mode == RTN_FWD) { g.M = positions; g.N = L.cout; g.K = L.cin * L.taps; }
-    else if (mode == RTN_DGRAD) { g.M = L.geo ? g.nb * L.Hin * L.Win : positions; g.N = L.creal; g.K = L.cout * L.taps; }
+    if (MODE == RTN_FWD) { g.M = positions; g.N = L.cout; g.K = L.cin * L.taps; }
+    else if (MODE == RTN_DGRAD) { g.M = g.nb * L.Hin * L.Win; g.N = L.creal; g.K = L.cout * L.taps; }
     else { g.M = L.cout; g.N = L.cin * L.taps; g.K = positions; }
-    g.kchunk = mode == RTN_WGRAD ? RTN_KCHUNK : g.K;
-    g.nchunks = mode == RTN_WGRAD ? (g.K + RTN_KCHUNK - 1) / RTN_KCHUNK : 1;
+    g.kchunk = MODE == RTN_WGRAD ? RTN_KCHUNK : g.K;
+    g.nchunks = MODE == RTN_WGRAD ? (g.K + RTN_KCHUNK - 1) / RTN_KCHUNK : 1;
     g.tiles_m = (g.M + 15) / 16; g.tiles_n = (g.N + 15) / 16;
     return g;
   }
-  void launch_gemm(const RtnGemm& g, int mode, int geo = 0) {
-    if (geo) {
-      if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD, 1>{g}, stream); });
-      else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD, 1>{g}, stream); });
-      else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD, 1>{g}, stream); });
-      return;
-    }
-    if (P->stem) {      // the geometry of the plain path, the block sums joined in binary64
-      if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD, 2>{g}, stream); });
-      else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD, 2>{g}, stream); });
-      else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD, 2>{g}, stream); });
-      return;
-    }
-    if (mode == RTN_FWD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_FWD>{g}, stream); });
-    else if (mode == RTN_DGRAD) go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_DGRAD>{g}, stream); });
-    else go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<RTN_WGRAD>{g}, stream); });
-  }
-  RtnBn bn(int n, size_t i, int app, int napps) const {
+  template <int MODE>
+  void launch_gemm(const RtnGemm& g) { go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<MODE, WIDE>{g}, stream); }); }
+  RtnBn<S> bn(int n, size_t i, int app, int napps) const {
     const RtnPlan& p = *P;
     const RtnLayer& L = p.net[n].l[i];
     const int64_t at = (int64_t)app * L.per_app(p.B);
-    RtnBn b;
+    RtnBn<S> b;
     memset(&b, 0, sizeof(b));
     b.z = scratch + L.z + at; b.y = scratch + L.y + at;
     b.gamma = flat + L.bn.weight; b.beta = flat + L.bn.bias;
-    b.saved = scratch + L.saved + (int64_t)app * 3 * L.cout; b.sums = scratch + L.sums + (int64_t)app * 2 * L.cout;
+    b.saved = (S*)(scratch + L.saved) + (int64_t)app * 3 * L.cout; b.sums = (S*)(scratch + L.sums) + (int64_t)app * 2 * L.cout;
     b.running = stats + L.stat; b.dgamma = grad + L.bn.weight; b.dbeta = grad + L.bn.bias;
     b.napps = napps; b.B = p.B; b.C = L.cout; b.HW = L.H * L.W;
-    if (L.saved64 >= 0) {
-      b.saved64 = (double*)(scratch + L.saved64) + (int64_t)app * 3 * L.cout;
-      b.sums64 = (double*)(scratch + L.sums64) + (int64_t)app * 2 * L.cout;
-    }
     return b;
   }
 
@@ -1074,20 +970,20 @@ struct RtnRun {
     const std::vector<RtnLayer>& l = P->net[n].l;
     for (size_t i = 0; i < l.size(); ++i) {
       if (rtn_is_pool(l[i].kind)) { launch_pool(n, i, app, napps, nullptr, nullptr); continue; }
-      RtnGemm g = gemm(n, i, app, napps, RTN_FWD);
+      RtnGemm g = gemm<RTN_FWD>(n, i, app, napps);
       if (l[i].kind != OP_CONV3) {       // a stem convolution without BatchNorm: z is y
         g.x = x_of(n, i, app); g.out = y_of(n, i, app); g.bias = l[i].b >= 0 ? flat + l[i].b : nullptr; g.relu = l[i].relu;
-        launch_gemm(g, RTN_FWD, l[i].geo);
+        launch_gemm<RTN_FWD>(g);
         continue;
       }
       g.x = x_of(n, i, app); g.out = scratch + l[i].z + (int64_t)app * l[i].per_app(P->B);
-      launch_gemm(g, RTN_FWD);
-      RtnBn b = bn(n, i, app, napps);
+      launch_gemm<RTN_FWD>(g);
+      RtnBn<S> b = bn(n, i, app, napps);
       if (l[i].has_res) b.res = x_of(n, i - 1, app);
       b.out = scratch + l[i].y + (int64_t)app * l[i].per_app(P->B);
-      go([&] { return launch_waves<RTN_WAVES>(RtnBnStatBody{b}, stream); });
-      go([&] { return launch<64>(RtnBnFoldOp{b}, stream); });
-      go([&] { return launch<256>(RtnBnApplyOp{b}, stream); });
+      go([&] { return launch_waves<RTN_WAVES>(RtnBnStatBody<S>{b}, stream); });
+      go([&] { return launch<64>(RtnBnFoldOp<S>{b}, stream); });
+      go([&] { return launch<256>(RtnBnApplyOp<S>{b}, stream); });
     }
   }
   // every application of a head at once: conv1x1 (bias) -> flatten -> Linear (+ ELU) ...
@@ -1095,9 +991,9 @@ struct RtnRun {
     const RtnChain& ch = P->net[n];
     if (ch.napps < 1) return;
     for (size_t i = 0; i < ch.l.size(); ++i) {
-      RtnGemm g = gemm(n, i, 0, ch.napps, RTN_FWD);
+      RtnGemm g = gemm<RTN_FWD>(n, i, 0, ch.napps);
       g.x = x_of(n, i, 0); g.out = y_of(n, i, 0); g.bias = flat + ch.l[i].b; g.elu = ch.l[i].elu;
-      launch_gemm(g, RTN_FWD);
+      launch_gemm<RTN_FWD>(g);
     }
   }
   // every application of a head: d loss / d logits -> dz of every layer -> d loss / d (tower output) in `dest`
@@ -1105,7 +1001,7 @@ struct RtnRun {
     const RtnChain& ch = P->net[n];
     if (ch.napps < 1) return;
     for (size_t i = ch.l.size() - 1;; --i) {
-      RtnGemm g = gemm(n, i, 0, ch.napps, RTN_DGRAD);
+      RtnGemm g = gemm<RTN_DGRAD>(n, i, 0, ch.napps);
       g.g = dz_of(n, i, 0);
       if (i > 0) {
         g.out = scratch + ch.l[i - 1].dz;
@@ -1114,15 +1010,15 @@ struct RtnRun {
         g.out = dest;
         if (accumulate) g.add = dest;
       }
-      launch_gemm(g, RTN_DGRAD);
+      launch_gemm<RTN_DGRAD>(g);
       if (i == 0) break;
     }
   }
   void bn_backward(int n, size_t i, int app, int napps, const float* g) {
-    RtnBn b = bn(n, i, app, napps);
+    RtnBn<S> b = bn(n, i, app, napps);
     b.g = g; b.out = scratch + P->net[n].l[i].dz + (int64_t)app * P->net[n].l[i].per_app(P->B);
-    go([&] { return launch_waves<RTN_WAVES>(RtnBnSumsBody{b}, stream); });
-    go([&] { return launch<256>(RtnBnDzOp{b}, stream); });
+    go([&] { return launch_waves<RTN_WAVES>(RtnBnSumsBody<S>{b}, stream); });
+    go([&] { return launch<256>(RtnBnDzOp<S>{b}, stream); });
   }
   // applications [app, app + napps) of a tower, from d loss / d (tower output) in `cur` (overwritten; `other` is scratch of
   // the same size) to d loss / d (tower input) in `dest` (nullable: the observation needs none)
@@ -1131,21 +1027,21 @@ struct RtnRun {
     for (int i = (int)l.size() - 1; i >= 0;) {
       if (l[i].has_res) {
         bn_backward(n, i, app, napps, cur);
-        RtnGemm g = gemm(n, i, app, napps, RTN_DGRAD);
+        RtnGemm g = gemm<RTN_DGRAD>(n, i, app, napps);
         g.g = dz_of(n, i, app); g.out = other;
-        launch_gemm(g, RTN_DGRAD);
+        launch_gemm<RTN_DGRAD>(g);
         bn_backward(n, i - 1, app, napps, other);
         // the block's input: through its two convolutions, and straight from its output where the ReLU passed
-        RtnGemm g1 = gemm(n, i - 1, app, napps, RTN_DGRAD);
+        RtnGemm g1 = gemm<RTN_DGRAD>(n, i - 1, app, napps);
         g1.g = dz_of(n, i - 1, app); g1.out = (i - 1 == 0) ? dest : cur; g1.add = cur; g1.mask = y_of(n, i, app);
-        launch_gemm(g1, RTN_DGRAD);
+        launch_gemm<RTN_DGRAD>(g1);
         i -= 2;
       } else if (l[i].kind == OP_CONV3) {
         bn_backward(n, i, app, napps, cur);
         if (dest) {
-          RtnGemm g = gemm(n, i, app, napps, RTN_DGRAD);
+          RtnGemm g = gemm<RTN_DGRAD>(n, i, app, napps);
           g.g = dz_of(n, i, app); g.out = dest;
-          launch_gemm(g, RTN_DGRAD);
+          launch_gemm<RTN_DGRAD>(g);
         }
         i -= 1;
       } else if (rtn_is_pool(l[i].kind)) {
@@ -1160,9 +1056,9 @@ struct RtnRun {
         m.out = scratch + l[i].dz + (int64_t)app * l[i].per_app(P->B);
         go([&] { return launch<256>(m, stream); });
         if (i > 0) {
-          RtnGemm g = gemm(n, i, app, napps, RTN_DGRAD);
+          RtnGemm g = gemm<RTN_DGRAD>(n, i, app, napps);
           g.g = dz_of(n, i, app); g.out = cur;
-          launch_gemm(g, RTN_DGRAD, l[i].geo);
+          launch_gemm<RTN_DGRAD>(g);
         }
         i -= 1;
       }
@@ -1176,18 +1072,18 @@ struct RtnRun {
     for (size_t i = 0; i < ch.l.size(); ++i) {
       const RtnLayer& L = ch.l[i];
       if (rtn_is_pool(L.kind)) continue;
-      RtnGemm g = gemm(n, i, 0, ch.napps, RTN_WGRAD);
+      RtnGemm g = gemm<RTN_WGRAD>(n, i, 0, ch.napps);
       g.x = x_of(n, i, 0); g.g = dz_of(n, i, 0);
       g.out = g.nchunks > 1 ? scratch + p.off_partial : grad + L.w;
-      launch_gemm(g, RTN_WGRAD, L.geo);
+      launch_gemm<RTN_WGRAD>(g);
       if (g.nchunks > 1) {
         RtnWgradFinishOp f;
         f.partial = scratch + p.off_partial; f.out = grad + L.w; f.elements = g.M * g.N; f.nchunks = g.nchunks;
         go([&] { return launch<256>(f, stream); });
       }
       if (L.kind == OP_CONV3) {
-        const RtnBn b = bn(n, i, 0, ch.napps);
-        go([&] { return launch<64>(RtnBnParamGradOp{b}, stream); });
+        const RtnBn<S> b = bn(n, i, 0, ch.napps);
+        go([&] { return launch<64>(RtnBnParamGradOp<S>{b}, stream); });
       } else if (L.b >= 0) {
         RtnBiasGradBody bg;
         bg.dz = dz_of(n, i, 0); bg.out = grad + L.b; bg.nb = ch.napps * p.B; bg.cout = L.cout; bg.hw = L.H * L.W;

@@ -3,26 +3,25 @@ Shared by the stem training tests (tests/test_resnet_stem_train.py, tests/test_g
 recipe (muzero-general_amd/tools/make_resnet_stem_train_golden.py) and the bench (tools/resnet_stem_train_bench.py): the
 case table of residual networks WITH a downsample stem ("resnet": DownSample, "CNN": DownsampleCNN), inputs and weights
 rebuilt from seeds, the residual network with either stem restated in plain torch.nn under the reference's state_dict
-keys, and the gates -- the rules of resnet_train_cases, whose helpers run here on this module's tables.
+keys, and the gates -- those of resnet_train_cases, bound to this module's tables.
 """
 import collections
+import functools
 import hashlib
 import json
 import math
 import os
+import sys
 
 import numpy
 import torch
 
-import fc_train_cases
 import resnet_train_cases as base
 import trainer_loss_cases
 from mzx import configs
 
-LOGIT_GATE = fc_train_cases.LOGIT_GATE
-LOSS_KEYS = fc_train_cases.LOSS_KEYS
-LOSS_ERROR_FLOOR = trainer_loss_cases.LOSS_ERROR_FLOOR
-DECODED_SCALAR_GATE = trainer_loss_cases.DECODED_SCALAR_GATE
+LOGIT_GATE = base.LOGIT_GATE
+LOSS_KEYS = base.LOSS_KEYS
 
 # The smallest shapes at which each mechanism of the stems can still go wrong; the hidden board is ceil(H/16) x ceil(W/16).
 CASES = [
@@ -209,7 +208,7 @@ def torch_step(case, dtype, device="cpu"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Running a case through the native path (any backend) and the gates.
+# Running a case through the native path (any backend).
 
 def golden(golden_dir):
     return numpy.load(os.path.join(golden_dir, "resnet_stem_train.npz"))
@@ -226,179 +225,29 @@ def network(be, case, **kw):
     return net
 
 
-def run_native(be, case, net=None):
-    """resnet_train_cases.run_native on this module's tables: ``grad_flat`` pre-filled with NaN."""
-    from mzx import trainer
-    net = net if net is not None else network(be, case)
-    param = next(net.parameters())
-    param.grad = torch.full_like(net.flat_weights(), float("nan"))
-    logits, stats = {}, {}
-    packed = trainer.train_resnet_gradients(net, batch(case), config_of(case), logits=logits, stats=stats)
-    host = packed.cpu().numpy()
-    out = dict(loss=host[0], value_loss=host[1], reward_loss=host[2], policy_loss=host[3],
-               priorities=host[4:].reshape(case["B"], case["steps"]).copy(),
-               value_logits=logits["value"].cpu().numpy(), reward_logits=logits["reward"].cpu().numpy(),
-               policy_logits=logits["policy"].cpu().numpy(), grad_flat=param.grad.cpu().numpy().copy(),
-               running=stats["running"].cpu().numpy().copy())
-    at = 0
-    for key, off, numel, shape in net._tensors:
-        out["grad/" + key] = out["grad_flat"][off:off + numel].reshape(shape)
-        if is_statistic(key):
-            out["stat/" + key] = out["running"][at:at + numel]
-            at += numel
-    assert at == out["running"].size
-    assert stats["applications"]["representation_network.module.bn."] == 0
-    return out
-
-
 # The floor of the per-tensor gate is resnet_train_cases.PARAM_GRAD_ERROR_FLOOR (1e-6).  MEASURED on the serial build
 # (tests/test_resnet_stem_train.py prints, per case, the largest error on a tensor that needs the floor): the largest is
 # 2.747e-7 (sc_b5_k2_stacked, representation_network.module.resblocks.0.bn2.weight).  Twice that, 5.5e-7, stays below 1e-6, so
 # the parent's floor holds here unchanged.
 PARAM_GRAD_ERROR_FLOOR = base.PARAM_GRAD_ERROR_FLOOR
-
-
-def tensor_gate(ref_error):
-    return max(4 * ref_error, PARAM_GRAD_ERROR_FLOOR)
-
-
-def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report=print):
-    """The gates of resnet_train_cases.check_against over this module's tensors."""
-    name = case["name"]
-    failures = []
-    for head in ("value", "reward", "policy"):
-        ours, ref = got[f"{head}_logits"], want32_logits[head]
-        assert ours.shape == ref.shape, (head, ours.shape, ref.shape)
-        finite = numpy.isfinite(ref)
-        assert numpy.array_equal(ours[~finite], ref[~finite]), head
-        err = float(numpy.max(numpy.abs(ours[finite].astype(numpy.float64) - ref[finite]))) if finite.any() else 0.0
-        report(f"{name} {head} logits: error {err:.3e} against the reference float32, gate {LOGIT_GATE:.1e}")
-        if not err <= LOGIT_GATE:
-            failures.append(head)
-    for key in LOSS_KEYS:
-        mine, ref = abs(float(got[key]) - float(ref64[key])), abs(float(f32_losses[key]) - float(ref64[key]))
-        gate = max(4 * ref, LOSS_ERROR_FLOOR)
-        report(f"{name} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
-        if not mine <= gate:
-            failures.append(key)
-    logits = torch.from_numpy(got["value_logits"]).to(be.device).reshape(-1, 2 * case["S"] + 1)
-    pred = be.empty((logits.shape[0],), torch.float32)
-    be.lib.check(be.lib.mzx_support_to_scalar(be.ptr(logits), logits.shape[0], case["S"], be.ptr(pred), be.stream()))
-    pred = pred.cpu().numpy().reshape(case["steps"], case["B"]).T.copy()
-    want = numpy.abs(pred - batch(case)[2]) ** case["alpha"]
-    assert want.dtype == numpy.float32
-    ulps = trainer_loss_cases.ulp_distance(want, got["priorities"])
-    report(f"{name} priorities: max ulp distance {ulps.max()} (alpha {case['alpha']})")
-    assert ulps.max() <= (0 if case["alpha"] == 1.0 else 1)
-    gap = numpy.abs(pred.astype(numpy.float64) - f32_pred)
-    report(f"{name} decoded value against the reference: {gap.max():.3e} (values up to {numpy.abs(pred).max():.2f})")
-    assert gap.max() <= DECODED_SCALAR_GATE
-    assert not numpy.isnan(got["grad_flat"]).any(), "d_grad_flat was not fully overwritten"
-    state = weights(case)
-    worst = (0.0, None)
-    for key in tensor_shapes(case):
-        if is_statistic(key):
-            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key      # exact zeros
-            kind, mine64 = "stat", got["stat/" + key]
-        else:
-            kind, mine64 = "grad", got["grad/" + key]
-        if is_bypassed(key):        # never applied: exact-zero gradients, the statistics keep their bits
-            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
-            if is_statistic(key):
-                assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].reshape(-1).view(numpy.int32)), key
-        ref = float(ref_errors[f"{kind}/{key}"])
-        gate = tensor_gate(ref)
-        mine = float(numpy.max(numpy.abs(mine64.astype(numpy.float64).reshape(-1) - numpy.asarray(ref64[f"{kind}/{key}"]).reshape(-1))))
-        report(f"{name} {kind} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
-        if 4 * ref < PARAM_GRAD_ERROR_FLOOR and mine > worst[0]:
-            worst = (mine, key)
-        if not mine <= gate:
-            failures.append(key)
-    report(f"{name} largest error on a tensor that needs the floor: {worst[0]:.3e} ({worst[1]})")
-    assert not failures, failures
-
-
-def check_case(be, case, gold, report=print):
-    """Every gate of one fixture case; returns (network, outputs).  Figures are printed before they are asserted."""
-    name = case["name"]
-    assert digest(case) == str(gold[f"{name}/digest"]), "this machine rebuilt other input bits than the fixture's"
-    net = network(be, case)
-    got = run_native(be, case, net)
-    keys = list(tensor_shapes(case))
-    ref64 = {k: gold[f"{name}/f64_{k}"] for k in LOSS_KEYS}
-    ref_errors = {}
-    tensors = split(case, gold[f"{name}/f64_tensors"])
-    for key, error in zip(keys, gold[f"{name}/f32_errors"]):
-        kind = "stat" if is_statistic(key) else "grad"
-        ref64[f"{kind}/{key}"] = tensors[key]
-        ref_errors[f"{kind}/{key}"] = error
-    check_against(case, got, {h: gold[f"{name}/f32_{h}_logits"] for h in ("value", "reward", "policy")}, ref64, ref_errors,
-                  {k: gold[f"{name}/f32_{k}"] for k in LOSS_KEYS}, gold[f"{name}/f32_pred"], be, report)
-    if case["steps"] == 1:      # no dynamics: exact zeros, statistics unchanged bit for bit
-        state = weights(case)
-        for key in keys:
-            if key.startswith("dynamics_"):
-                assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
-                if is_statistic(key):
-                    assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].view(numpy.int32)), key
-    again = run_native(be, case, net)
-    for key, value in got.items():
-        a, b = numpy.ascontiguousarray(value, numpy.float32), numpy.ascontiguousarray(again[key], numpy.float32)
-        assert numpy.array_equal(a.view(numpy.int32), b.view(numpy.int32)), key
-    return net, got
-
-
-def check_live(be, case, report=print):
-    """The gates of ``check_case`` against the torch restatement run here in binary64 and float32 (shapes the fixture does
-    not carry)."""
-    ref64, ref32 = torch_step(case, torch.float64), torch_step(case, torch.float32)
-    errors = {k: float(numpy.max(numpy.abs(ref32[k].astype(numpy.float64) - ref64[k]))) for k in ref64 if k[:5] in ("grad/", "stat/")}
-    net = network(be, case)
-    got = run_native(be, case, net)
-    check_against(case, got, {h: ref32[f"{h}_logits"] for h in ("value", "reward", "policy")}, ref64, errors,
-                  {k: ref32[k] for k in LOSS_KEYS}, ref32["pred"], be, report)
-    return net, got
-
-
-def sgd_reference(gold, case):
-    delta, initial = split(case, gold[f"{case['name']}/f64_sgd_delta"]), weights(case)
-    return {key: initial[key].astype(numpy.float64) + delta[key].astype(numpy.float64) for key in initial}
+tensor_gate = base.tensor_gate
 
 
 def tracked_after(key, case, updates):
     """``num_batches_tracked`` of a BatchNorm after ``updates`` steps."""
-    if is_bypassed(key):
-        return 0
-    per_step = 1 if key.startswith("representation") else case["steps"] - 1 if key.startswith("dynamics") else case["steps"]
-    return updates * per_step
+    return 0 if is_bypassed(key) else base.tracked_after(key, case, updates)
 
 
-def check_sgd(be, case, gold, report=print):
-    """resnet_train_cases.check_sgd: two ``update_weights`` steps with SGD-momentum and weight decay against the reference's
-    weights AND buffers after two steps, the same gates; ``num_batches_tracked`` rises for the stem's BatchNorms and stays 0
-    for the bypassed one."""
-    from mzx import trainer
-    name, hp = case["name"], case["sgd"]
-    net = network(be, case)
-    optimizer = torch.optim.SGD(net.parameters(), lr=hp["lr"], momentum=hp["momentum"], weight_decay=hp["weight_decay"])
-    for _ in range(2):
-        out = trainer.update_weights(net, optimizer, batch(case), config_of(case))
-        assert isinstance(out[0], numpy.ndarray) and out[0].dtype == numpy.float32 and out[0].shape == (case["B"], case["steps"])
-        assert all(type(v) is float for v in out[1:])
-    failures = []
-    state, want = net.get_weights(), sgd_reference(gold, case)
-    for key, error in zip(tensor_shapes(case), gold[f"{name}/f32_errors"]):
-        gate_of = tensor_gate(float(error))
-        gate = 2 * gate_of if is_statistic(key) else 2 * hp["lr"] * (1 + hp["momentum"]) * gate_of
-        err = float(numpy.max(numpy.abs(state[key].numpy().astype(numpy.float64) - want[key])))
-        report(f"{name} after two SGD steps {key}: error {err:.3e}, gate {gate:.3e}")
-        if not err <= gate:
-            failures.append(key)
-    seen = set()
-    for key, value in state.items():
-        if key.endswith("num_batches_tracked"):
-            assert int(value) == tracked_after(key, case, 2), (key, int(value))
-            seen.add("stem" if ".downsample_net." in key else "bypassed" if is_bypassed(key) else key.split(".")[0])
-    assert seen == {"stem", "bypassed", "representation_network", "dynamics_network", "prediction_network"}, seen
-    assert not failures, failures
-    return net, optimizer
+# the groups of BatchNorms whose ``num_batches_tracked`` check_sgd has to meet
+TRACKED = {"stem", "bypassed", "representation_network", "dynamics_network", "prediction_network"}
+
+# The gates: resnet_train_cases' own, on this module's tables.  Beyond what they hold a plain network to, the tables make
+# them assert exact-zero gradients and untouched statistic bits for the bypassed tensors, no counted application of the
+# bypassed BatchNorm, and ``num_batches_tracked`` of the stem's BatchNorms (``tracked_after``, every group of ``TRACKED``).
+THIS = sys.modules[__name__]
+run_native = functools.partial(base.run_native, tables=THIS)
+check_against = functools.partial(base.check_against, tables=THIS)
+check_case = functools.partial(base.check_case, tables=THIS)
+check_live = functools.partial(base.check_live, tables=THIS)
+sgd_reference = functools.partial(base.sgd_reference, tables=THIS)
+check_sgd = functools.partial(base.check_sgd, tables=THIS)

@@ -9,6 +9,7 @@ import collections
 import hashlib
 import json
 import os
+import sys
 
 import numpy
 import torch
@@ -281,7 +282,13 @@ def torch_step(case, dtype, device="cpu", steps_of_sgd=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Running a case through the native path (any backend) and the gates both test files apply.
+# Running a case through the native path (any backend) and the gates.  run_native, check_against, check_case, check_live
+# and check_sgd exist once, here; their last argument ``tables`` is the module whose case tables they run on (``network``,
+# ``batch``, ``config_of``, ``weights``, ``tensor_shapes``, ``split``, ``digest``, ``torch_step``, ``is_bypassed``,
+# ``tracked_after``, ``TRACKED``): this module, or resnet_stem_train_cases, which binds them to itself under the same names.
+
+THIS = sys.modules[__name__]
+
 
 def golden(golden_dir):
     return numpy.load(os.path.join(golden_dir, "resnet_train.npz"))
@@ -298,16 +305,31 @@ def network(be, case):
     return net
 
 
-def run_native(be, case, net=None):
+def is_bypassed(key):
+    """A tensor of the state_dict that no application reads (none here; behind a stem, the tower's first convolution)."""
+    return False
+
+
+def tracked_after(key, case, updates):
+    """``num_batches_tracked`` of a BatchNorm after ``updates`` steps."""
+    per_step = 1 if key.startswith("representation") else case["steps"] - 1 if key.startswith("dynamics") else case["steps"]
+    return updates * per_step
+
+
+# the groups of BatchNorms whose ``num_batches_tracked`` check_sgd has to meet
+TRACKED = {"representation_network", "dynamics_network", "prediction_network"}
+
+
+def run_native(be, case, net=None, tables=THIS):
     """mzx_train_resnet_step of a case through mzx.trainer.train_resnet_gradients -> dict of host arrays: losses,
     priorities, logits, grad/<key> per tensor and stat/<key> per running statistic after the step.  The gradient buffer
     is pre-filled with NaN: the call has to overwrite all of it."""
     from mzx import trainer
-    net = net if net is not None else network(be, case)
+    net = net if net is not None else tables.network(be, case)
     param = next(net.parameters())
     param.grad = torch.full_like(net.flat_weights(), float("nan"))
     logits, stats = {}, {}
-    packed = trainer.train_resnet_gradients(net, batch(case), config_of(case), logits=logits, stats=stats)
+    packed = trainer.train_resnet_gradients(net, tables.batch(case), tables.config_of(case), logits=logits, stats=stats)
     host = packed.cpu().numpy()
     out = dict(loss=host[0], value_loss=host[1], reward_loss=host[2], policy_loss=host[3],
                priorities=host[4:].reshape(case["B"], case["steps"]).copy(),
@@ -321,6 +343,9 @@ def run_native(be, case, net=None):
             out["stat/" + key] = out["running"][at:at + numel]
             at += numel
     assert at == out["running"].size
+    for key, *_ in net._tensors:      # a bypassed BatchNorm counts no application
+        if key.endswith(".running_var") and tables.is_bypassed(key):
+            assert stats["applications"][key[:-len("running_var")]] == 0, key
     return out
 
 
@@ -340,7 +365,7 @@ def tensor_gate(ref_error):
     return max(4 * ref_error, PARAM_GRAD_ERROR_FLOOR)
 
 
-def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report=print):
+def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report=print, tables=THIS):
     """The gates of one case.  ``ref64``: key -> binary64 arrays (losses, grad/<key>, stat/<key>); ``ref_errors``: key ->
     the reference's own float32 error against binary64 on that tensor."""
     name = case["name"]
@@ -364,7 +389,7 @@ def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_p
     pred = be.empty((logits.shape[0],), torch.float32)
     be.lib.check(be.lib.mzx_support_to_scalar(be.ptr(logits), logits.shape[0], case["S"], be.ptr(pred), be.stream()))
     pred = pred.cpu().numpy().reshape(case["steps"], case["B"]).T.copy()
-    want = numpy.abs(pred - batch(case)[2]) ** case["alpha"]
+    want = numpy.abs(pred - tables.batch(case)[2]) ** case["alpha"]
     assert want.dtype == numpy.float32
     ulps = trainer_loss_cases.ulp_distance(want, got["priorities"])
     report(f"{name} priorities: max ulp distance {ulps.max()} (alpha {case['alpha']})")
@@ -373,16 +398,21 @@ def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_p
     report(f"{name} decoded value against the reference: {gap.max():.3e} (values up to {numpy.abs(pred).max():.2f})")
     assert gap.max() <= trainer_loss_cases.DECODED_SCALAR_GATE
     assert not numpy.isnan(got["grad_flat"]).any(), "d_grad_flat was not fully overwritten"
+    state = tables.weights(case)
     worst = (0.0, None)
-    for key in tensor_shapes(case):
+    for key in tables.tensor_shapes(case):
         if is_statistic(key):
             assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key      # exact zeros
             kind, mine64 = "stat", got["stat/" + key]
         else:
             kind, mine64 = "grad", got["grad/" + key]
+        if tables.is_bypassed(key):        # never applied: exact-zero gradients, the statistics keep their bits
+            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
+            if is_statistic(key):
+                assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].reshape(-1).view(numpy.int32)), key
         ref = float(ref_errors[f"{kind}/{key}"])
         gate = tensor_gate(ref)
-        mine = float(numpy.max(numpy.abs(mine64.astype(numpy.float64) - ref64[f"{kind}/{key}"])))
+        mine = float(numpy.max(numpy.abs(mine64.astype(numpy.float64).reshape(-1) - numpy.asarray(ref64[f"{kind}/{key}"]).reshape(-1))))
         report(f"{name} {kind} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
         if 4 * ref < PARAM_GRAD_ERROR_FLOOR and mine > worst[0]:
             worst = (mine, key)
@@ -392,83 +422,86 @@ def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_p
     assert not failures, failures
 
 
-def check_case(be, case, gold, report=print):
+def check_case(be, case, gold, report=print, tables=THIS):
     """Every gate of one fixture case; returns (network, outputs).  Figures are printed before they are asserted."""
     name = case["name"]
-    assert digest(case) == str(gold[f"{name}/digest"]), "this machine rebuilt other input bits than the fixture's"
-    net = network(be, case)
-    got = run_native(be, case, net)
-    keys = list(tensor_shapes(case))
+    assert tables.digest(case) == str(gold[f"{name}/digest"]), "this machine rebuilt other input bits than the fixture's"
+    net = tables.network(be, case)
+    got = run_native(be, case, net, tables)
+    keys = list(tables.tensor_shapes(case))
     ref64 = {k: gold[f"{name}/f64_{k}"] for k in LOSS_KEYS}
     ref_errors = {}
-    tensors = split(case, gold[f"{name}/f64_tensors"])
+    tensors = tables.split(case, gold[f"{name}/f64_tensors"])
     for key, error in zip(keys, gold[f"{name}/f32_errors"]):
         kind = "stat" if is_statistic(key) else "grad"
         ref64[f"{kind}/{key}"] = tensors[key]
         ref_errors[f"{kind}/{key}"] = error
     check_against(case, got, {h: gold[f"{name}/f32_{h}_logits"] for h in ("value", "reward", "policy")}, ref64, ref_errors,
-                  {k: gold[f"{name}/f32_{k}"] for k in LOSS_KEYS}, gold[f"{name}/f32_pred"], be, report)
+                  {k: gold[f"{name}/f32_{k}"] for k in LOSS_KEYS}, gold[f"{name}/f32_pred"], be, report, tables)
     if case["steps"] == 1:      # no dynamics: exact zeros, statistics unchanged bit for bit
-        state = weights(case)
+        state = tables.weights(case)
         for key in keys:
             if key.startswith("dynamics_"):
                 assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
                 if is_statistic(key):
                     assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].view(numpy.int32)), key
-    again = run_native(be, case, net)
+    again = run_native(be, case, net, tables)
     for key, value in got.items():
         a, b = numpy.ascontiguousarray(value, numpy.float32), numpy.ascontiguousarray(again[key], numpy.float32)
         assert numpy.array_equal(a.view(numpy.int32), b.view(numpy.int32)), key
     return net, got
 
 
-def check_live(be, case, report=print):
+def check_live(be, case, report=print, tables=THIS):
     """The gates of ``check_case`` against the torch restatement run here in binary64 and float32 (shapes the fixture does
     not carry)."""
-    ref64, ref32 = torch_step(case, torch.float64), torch_step(case, torch.float32)
+    ref64, ref32 = tables.torch_step(case, torch.float64), tables.torch_step(case, torch.float32)
     errors = {k: float(numpy.max(numpy.abs(ref32[k].astype(numpy.float64) - ref64[k]))) for k in ref64 if k[:5] in ("grad/", "stat/")}
-    net = network(be, case)
-    got = run_native(be, case, net)
+    net = tables.network(be, case)
+    got = run_native(be, case, net, tables)
     check_against(case, got, {h: ref32[f"{h}_logits"] for h in ("value", "reward", "policy")}, ref64, errors,
-                  {k: ref32[k] for k in LOSS_KEYS}, ref32["pred"], be, report)
+                  {k: ref32[k] for k in LOSS_KEYS}, ref32["pred"], be, report, tables)
     return net, got
 
 
-def sgd_reference(gold, case):
+def sgd_reference(gold, case, tables=THIS):
     """key -> the reference's binary64 tensor after two SGD steps: the fixture stores its distance from the initial float32
     value."""
-    delta, initial = split(case, gold[f"{case['name']}/f64_sgd_delta"]), weights(case)
+    delta, initial = tables.split(case, gold[f"{case['name']}/f64_sgd_delta"]), tables.weights(case)
     return {key: initial[key].astype(numpy.float64) + delta[key].astype(numpy.float64) for key in initial}
 
 
-def check_sgd(be, case, gold, report=print):
+def check_sgd(be, case, gold, report=print, tables=THIS):
     """Two ``update_weights`` steps with SGD-momentum and weight decay on the flat parameter against the reference's weights
     AND buffers after two steps.  Parameters: within lr x (1 + momentum) x the gradient gate (the second step's gradient is
     taken at weights that differ by the first step's error: x 2); running statistics: within twice their gate -- an
     optimizer's decay of them (the last step alone moves a variance near 1 by lr x (1 + momentum) x 1e-4, about 1e-5)
-    would not pass."""
+    would not pass.  ``num_batches_tracked`` rises by each network's applications (a stem's BatchNorms with the
+    representation network, a bypassed one not at all), and every group of ``tables.TRACKED`` has to be met."""
     from mzx import trainer
     name, hp = case["name"], case["sgd"]
-    net = network(be, case)
+    net = tables.network(be, case)
     optimizer = torch.optim.SGD(net.parameters(), lr=hp["lr"], momentum=hp["momentum"], weight_decay=hp["weight_decay"])
     for _ in range(2):
-        out = trainer.update_weights(net, optimizer, batch(case), config_of(case))
+        out = trainer.update_weights(net, optimizer, tables.batch(case), tables.config_of(case))
         assert isinstance(out[0], numpy.ndarray) and out[0].dtype == numpy.float32 and out[0].shape == (case["B"], case["steps"])
         assert all(type(v) is float for v in out[1:])
     failures = []
-    state, want = net.get_weights(), sgd_reference(gold, case)
-    for key, error in zip(tensor_shapes(case), gold[f"{name}/f32_errors"]):
+    state, want = net.get_weights(), sgd_reference(gold, case, tables)
+    for key, error in zip(tables.tensor_shapes(case), gold[f"{name}/f32_errors"]):
         base = tensor_gate(float(error))
         gate = 2 * base if is_statistic(key) else 2 * hp["lr"] * (1 + hp["momentum"]) * base
         err = float(numpy.max(numpy.abs(state[key].numpy().astype(numpy.float64) - want[key])))
         report(f"{name} after two SGD steps {key}: error {err:.3e}, gate {gate:.3e}")
         if not err <= gate:
             failures.append(key)
-    assert not failures, failures
+    seen = set()
     for key, value in state.items():
         if key.endswith("num_batches_tracked"):
-            want = 2 * (1 if key.startswith("representation") else case["steps"] - 1 if key.startswith("dynamics") else case["steps"])
-            assert int(value) == want, (key, int(value), want)
+            assert int(value) == tables.tracked_after(key, case, 2), (key, int(value))
+            seen.add("stem" if ".downsample_net." in key else "bypassed" if tables.is_bypassed(key) else key.split(".")[0])
+    assert seen == tables.TRACKED, seen
+    assert not failures, failures
     return net, optimizer
 
 

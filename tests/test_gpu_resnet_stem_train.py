@@ -1,5 +1,5 @@
 """
-Training a residual network WITH a downsample stem natively on the device (wave_kernel<4, RtnGemmBody<MODE, 1 | 2>> on the
+Training a residual network WITH a downsample stem natively on the device (wave_kernel<4, RtnGemmBody<MODE, true>> on the
 FP32 matrix pipes, the pool element kernels, mzx_net_set_train_stem) against tests/golden/resnet_stem_train.npz with the
 gates and helpers of tests/test_resnet_stem_train.py, and breakout as shipped -- 96 x 96 -> 6 x 6, 9216 stem positions per
 sample pair, 18 weight-gradient chunks, the real 8 / 16 channels -- against the torch restatement in binary64.
