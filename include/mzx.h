@@ -925,7 +925,8 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
  * Trainer.update_weights (trainer.py:168-262) for MuZeroResidualNetwork (models.py:300-623, downsample = False) in
  * TRAINING mode -- BatchNorm normalises with the statistics of the batch, per application of a shared network -- as
  * launches on one stream, no atomics: the same bits on every run.  The convolutions and Linear layers are implicit GEMMs
- * on the FP32 matrix pipes.  The fields of mzx_train_fc_io keep their meaning (d_observation [B][C_in][H][W]); in addition
+ * on the FP32 matrix pipes.  The fields of mzx_train_fc_io keep their meaning (d_observation [B][C_in][H][W]) and their
+ * place: a layout-identical prefix, asserted in the library (csrc/mzx_train_step.h).  In addition
  *   out: d_stats [mzx_train_resnet_stat_floats(net)]: the running statistics AFTER the step, computed from those in
  *        d_flat: for BatchNorm i in the order of the state_dict, running_mean [C_i] then running_var [C_i], the
  *        BatchNorms behind one another.  The applications of a network fold in forward order (momentum 0.1, the

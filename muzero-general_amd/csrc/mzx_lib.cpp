@@ -20,6 +20,7 @@
 #include "mzx_trainer.h"
 #include "mzx_train_fc.h"
 #include "mzx_train_resnet.h"
+#include "mzx_train_step.h"
 #include "mzx_tree_carry.h"
 #ifndef MZX_HOSTCHECK
 #include "mzx_fused_fc.h"
@@ -1541,63 +1542,25 @@ int mzx_trainer_loss(const mzx_trainer_loss_io* io, void* stream) {
 }
 
 // ------------------------------------------------------------- a training step of a fully connected network (csrc/mzx_train_fc.h)
+// Both step entries refuse through train_step_front and call the loss head through train_head_io (csrc/mzx_train_step.h).
 
 int mzx_train_fc_supported(const mzx_net* net, int32_t batch, int32_t steps) {
-  FctPlan plan;
-  return fct_plan(net, batch, steps, true, true, true, plan) ? 1 : 0;
+  return (int)train_full_plan<FctPlan>(fct_plan, net, batch, steps, [](const FctPlan&) { return 1; });
 }
 
 int64_t mzx_train_fc_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps) {
-  FctPlan plan;
-  if (!fct_plan(net, batch, steps, true, true, true, plan)) return 0;
-  return plan.total_floats * 4;
+  return train_full_plan<FctPlan>(fct_plan, net, batch, steps, [](const FctPlan& P) { return P.total_floats * 4; });
 }
 
 int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* stream) {
-  if (!net || !io) { set_error("mzx_train_fc_step: null argument"); return MZX_ERR_INVALID; }
-  if (io->batch < 1 || io->steps < 1) {
-    set_error("mzx_train_fc_step: batch %d and steps %d must be positive", io->batch, io->steps);
-    return MZX_ERR_INVALID;
-  }
-  if (!io->d_flat || !io->d_observation || !io->d_action || !io->d_target_value || !io->d_target_reward || !io->d_target_policy ||
-      !io->d_gradient_scale || !io->d_grad_flat || !io->d_losses || !io->d_priorities || !io->d_scratch) {
-    set_error("mzx_train_fc_step: missing buffer");
-    return MZX_ERR_INVALID;
-  }
   FctParams p;
-  std::string why;
-  if (!fct_plan(net, io->batch, io->steps, !io->d_value_logits, !io->d_reward_logits, !io->d_policy_logits, p.plan, &why)) {
-    set_error("mzx_train_fc_step: %s", why.c_str());
-    return MZX_ERR_INVALID;
-  }
-  if (io->scratch_bytes < p.plan.total_floats * 4 || ((uintptr_t)io->d_scratch % 16) != 0) {
-    set_error("mzx_train_fc_step: scratch needs %lld bytes, 16-byte aligned", (long long)mzx_train_fc_scratch_bytes(net, io->batch, io->steps));
-    return MZX_ERR_INVALID;
-  }
-  const FctPlan& P = p.plan;
+  if (const int rc = train_step_front("mzx_train_fc_step", net, io, false, fct_plan, p.plan)) return rc;
   float* scratch = (float*)io->d_scratch;
+  const mzx_trainer_loss_io lio = train_head_io(io, p.plan, scratch, net->cfg.support_size, p.vlog, p.rlog, p.plog);
   p.flat = io->d_flat; p.obs = io->d_observation; p.action = io->d_action;
-  p.vlog = io->d_value_logits ? io->d_value_logits : scratch + P.off_vlog;
-  p.rlog = io->d_reward_logits ? io->d_reward_logits : scratch + P.off_rlog;
-  p.plog = io->d_policy_logits ? io->d_policy_logits : scratch + P.off_plog;
-  p.gv = scratch + P.off_gv; p.gr = scratch + P.off_gr; p.gp = scratch + P.off_gp;
+  p.gv = lio.d_grad_value; p.gr = lio.d_grad_reward; p.gp = lio.d_grad_policy;
   p.scratch = scratch; p.grad_flat = io->d_grad_flat;
   p.B = io->batch; p.steps = io->steps;
-  // the loss head's own argument checks, made here so that nothing is launched before a refusal
-  mzx_trainer_loss_io lio;
-  memset(&lio, 0, sizeof(lio));
-  lio.d_value_logits = p.vlog; lio.d_reward_logits = p.rlog; lio.d_policy_logits = p.plog;
-  lio.d_target_value = io->d_target_value; lio.d_target_reward = io->d_target_reward; lio.d_target_policy = io->d_target_policy;
-  lio.d_gradient_scale = io->d_gradient_scale; lio.d_weight = io->d_weight;
-  lio.batch = io->batch; lio.steps = io->steps; lio.support_size = net->cfg.support_size; lio.num_actions = P.A;
-  lio.value_loss_weight = io->value_loss_weight; lio.per_alpha = io->per_alpha;
-  lio.d_losses = io->d_losses; lio.d_priorities = io->d_priorities;
-  lio.d_grad_value = scratch + P.off_gv; lio.d_grad_reward = scratch + P.off_gr; lio.d_grad_policy = scratch + P.off_gp;
-  lio.d_scratch = scratch + P.off_loss; lio.scratch_bytes = mzx_trainer_loss_scratch_bytes(io->batch, io->steps);
-  if (P.A < 1 || net->cfg.support_size < 0 || (int64_t)io->batch * io->steps >= ((int64_t)1 << 31)) {
-    set_error("mzx_train_fc_step: shape out of range");
-    return MZX_ERR_INVALID;
-  }
   MZX_TRY_LAUNCH(fct_launch(p, 0, (stream_t)stream));
   if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
   MZX_TRY_LAUNCH(fct_launch(p, 1, (stream_t)stream));
@@ -1608,27 +1571,24 @@ int mzx_train_fc_step(const mzx_net* net, const mzx_train_fc_io* io, void* strea
 // ------------------------------------------------------------- a training step of a residual network (csrc/mzx_train_resnet.h)
 
 int mzx_train_resnet_supported(const mzx_net* net, int32_t batch, int32_t steps) {
-  RtnPlan plan;
-  return rtn_plan(net, batch, steps, true, true, true, plan) ? 1 : 0;
+  return (int)train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [](const RtnPlan&) { return 1; });
 }
 
 int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps) {
-  RtnPlan plan;
-  if (!rtn_plan(net, batch, steps, true, true, true, plan)) return 0;
-  return plan.total_floats * 4;
+  return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [](const RtnPlan& P) { return P.total_floats * 4; });
 }
 
 int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat_floats(net) : 0; }
 
 int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) {
-  RtnPlan plan;
-  if (!rtn_plan(net, batch, steps, true, true, true, plan)) return 0;
-  RtnRun<false> run;      // (the launches of a step do not depend on its precision)
-  memset((void*)&run, 0, sizeof(run));
-  run.P = &plan; run.dry = true;
-  run.forward();
-  run.backward();
-  return run.launched + 2;      // (the two launches of the loss head)
+  return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [](const RtnPlan& plan) {
+    RtnRun<false> run;      // (the launches of a step do not depend on its precision)
+    memset((void*)&run, 0, sizeof(run));
+    run.P = &plan; run.dry = true;
+    run.forward();
+    run.backward();
+    return run.launched + 2;      // (the two launches of the loss head)
+  });
 }
 
 // forward pass, loss head, backward pass of a planned step
@@ -1639,19 +1599,8 @@ int rtn_step(const mzx_net* net, const mzx_train_resnet_io* io, const RtnPlan& P
   memset((void*)&run, 0, sizeof(run));
   run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
   run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
-  run.vlog = io->d_value_logits ? io->d_value_logits : scratch + P.off_vlog;
-  run.rlog = io->d_reward_logits ? io->d_reward_logits : scratch + P.off_rlog;
-  run.plog = io->d_policy_logits ? io->d_policy_logits : scratch + P.off_plog;
-  mzx_trainer_loss_io lio;
-  memset(&lio, 0, sizeof(lio));
-  lio.d_value_logits = run.vlog; lio.d_reward_logits = run.rlog; lio.d_policy_logits = run.plog;
-  lio.d_target_value = io->d_target_value; lio.d_target_reward = io->d_target_reward; lio.d_target_policy = io->d_target_policy;
-  lio.d_gradient_scale = io->d_gradient_scale; lio.d_weight = io->d_weight;
-  lio.batch = io->batch; lio.steps = io->steps; lio.support_size = net->cfg.support_size; lio.num_actions = P.A;
-  lio.value_loss_weight = io->value_loss_weight; lio.per_alpha = io->per_alpha;
-  lio.d_losses = io->d_losses; lio.d_priorities = io->d_priorities;
-  lio.d_grad_value = scratch + P.off_gv; lio.d_grad_reward = scratch + P.off_gr; lio.d_grad_policy = scratch + P.off_gp;
-  lio.d_scratch = scratch + P.off_loss; lio.scratch_bytes = mzx_trainer_loss_scratch_bytes(io->batch, io->steps);
+  const mzx_trainer_loss_io lio = train_head_io(reinterpret_cast<const mzx_train_fc_io*>(io), P, scratch, net->cfg.support_size,
+                                                run.vlog, run.rlog, run.plog);
   run.forward();
   MZX_TRY_LAUNCH(run.rc);
   if (const int rc = mzx_trainer_loss(&lio, stream)) return rc;
@@ -1661,31 +1610,9 @@ int rtn_step(const mzx_net* net, const mzx_train_resnet_io* io, const RtnPlan& P
 }
 
 int mzx_train_resnet_step(const mzx_net* net, const mzx_train_resnet_io* io, void* stream) {
-  if (!net || !io) { set_error("mzx_train_resnet_step: null argument"); return MZX_ERR_INVALID; }
-  if (io->batch < 1 || io->steps < 1) {
-    set_error("mzx_train_resnet_step: batch %d and steps %d must be positive", io->batch, io->steps);
-    return MZX_ERR_INVALID;
-  }
-  if (!io->d_flat || !io->d_observation || !io->d_action || !io->d_target_value || !io->d_target_reward || !io->d_target_policy ||
-      !io->d_gradient_scale || !io->d_grad_flat || !io->d_losses || !io->d_priorities || !io->d_scratch || !io->d_stats) {
-    set_error("mzx_train_resnet_step: missing buffer");
-    return MZX_ERR_INVALID;
-  }
   RtnPlan P;
-  std::string why;
-  if (!rtn_plan(net, io->batch, io->steps, !io->d_value_logits, !io->d_reward_logits, !io->d_policy_logits, P, &why)) {
-    set_error("mzx_train_resnet_step: %s", why.c_str());
-    return MZX_ERR_INVALID;
-  }
-  if (io->scratch_bytes < P.total_floats * 4 || ((uintptr_t)io->d_scratch % 16) != 0) {
-    set_error("mzx_train_resnet_step: scratch needs %lld bytes, 16-byte aligned",
-              (long long)mzx_train_resnet_scratch_bytes(net, io->batch, io->steps));
-    return MZX_ERR_INVALID;
-  }
-  if (P.A < 1 || net->cfg.support_size < 0 || (int64_t)io->batch * io->steps >= ((int64_t)1 << 31)) {
-    set_error("mzx_train_resnet_step: shape out of range");
-    return MZX_ERR_INVALID;
-  }
+  if (const int rc = train_step_front("mzx_train_resnet_step", net, reinterpret_cast<const mzx_train_fc_io*>(io), true, rtn_plan, P))
+    return rc;
   return P.stem ? rtn_step<true>(net, io, P, stream) : rtn_step<false>(net, io, P, stream);
 }
 

@@ -48,10 +48,12 @@
 // tests/hostcheck build: the same per-sample functions with one lane (mzx_wave.h), one element per sample, the weights read
 // from the flat buffer; the weight gradients are the same wave body, rows in increasing order.
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "mzx_launch.h"
 #include "mzx_net.h"
+#include "mzx_train_step.h"
 #include "mzx_trainer.h"
 
 namespace mzx {
@@ -69,11 +71,12 @@ struct FctLayer {
   int64_t act, dz;              // scratch offsets of the output rows / the pre-activation gradients; -1: logits / their gradients
 };
 struct FctMlp { int32_t n, pad; FctLayer l[FCT_MAX_LAYERS]; };
-struct FctPlan {
+struct FctPlan : TrainHeadPlan {      // A, F and the loss head's scratch offsets
   FctMlp mlp[FCT_MLPS];
-  int32_t E, A, F, in_size, maxw, lds_weight_floats, wave_floats, num_params;
-  int64_t off_loss, off_gv, off_gr, off_gp, off_vlog, off_rlog, off_plog, off_h, total_floats;
+  int32_t E, in_size, maxw, lds_weight_floats, wave_floats, num_params;
+  int64_t off_h, total_floats;
 };
+static_assert(std::is_trivially_copyable<FctPlan>::value, "FctPlan travels to the kernels inside FctParams");
 
 struct FctParams {
   FctPlan plan;
@@ -140,11 +143,7 @@ inline bool fct_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   if (rows * maxw >= ((int64_t)1 << 40)) return no("batch x steps too large");
   int64_t o = 0;
   auto take = [&](int64_t floats) { const int64_t at = o; o += (floats + 3) & ~(int64_t)3; return at; };
-  P.off_loss = take(rows * (int64_t)(sizeof(TrainerLossRow) / 4));
-  P.off_gv = take(rows * P.F); P.off_gr = take(rows * P.F); P.off_gp = take(rows * P.A);
-  P.off_vlog = own_vlog ? take(rows * P.F) : -1;
-  P.off_rlog = own_rlog ? take(rows * P.F) : -1;
-  P.off_plog = own_plog ? take(rows * P.A) : -1;
+  train_head_take(P, take, rows, own_vlog, own_rlog, own_plog);
   P.off_h = take(rows * P.E);
   for (int m = 0; m < FCT_MLPS; ++m)
     for (int l = 0; l < P.mlp[m].n; ++l) {

@@ -82,6 +82,7 @@
 
 #include "mzx_launch.h"
 #include "mzx_net.h"
+#include "mzx_train_step.h"
 #include "mzx_trainer.h"
 #include "mzx_wave.h"
 
@@ -639,12 +640,11 @@ struct RtnLayer {
 };
 enum RtnNetId { RTN_REP, RTN_DYN, RTN_PRED, RTN_REW, RTN_VAL, RTN_POL, RTN_NETS };
 struct RtnChain { std::vector<RtnLayer> l; int32_t napps = 0, t0 = 0; };
-struct RtnPlan {
+struct RtnPlan : TrainHeadPlan {      // A, F and the loss head's scratch offsets
   RtnChain net[RTN_NETS];
-  int32_t B = 0, steps = 0, C = 0, HW = 0, A = 0, F = 0, num_params = 0, stem = 0;
+  int32_t B = 0, steps = 0, C = 0, HW = 0, num_params = 0, stem = 0;
   int64_t state = 0;                 // B * C * HW
-  int64_t off_loss = 0, off_gv = 0, off_gr = 0, off_gp = 0, off_vlog = -1, off_rlog = -1, off_plog = -1, off_h = 0, off_ghp = 0,
-          off_grs = 0, off_gd = 0, off_ga = 0, off_gb = 0, off_partial = 0, total_floats = 0;
+  int64_t off_h = 0, off_ghp = 0, off_grs = 0, off_gd = 0, off_ga = 0, off_gb = 0, off_partial = 0, total_floats = 0;
   struct IdleBn { int64_t stat, mean; int32_t channels; };
   std::vector<IdleBn> idle;          // BatchNorms no chain applies (the bypassed representation_network.module.bn of a stem)
 };
@@ -829,11 +829,7 @@ inline bool rtn_plan(const mzx_net* net, int32_t B, int32_t steps, bool own_vlog
   int64_t o = 0;
   auto take = [&](int64_t floats) { const int64_t at = o; o += (floats + 3) & ~(int64_t)3; return at; };
   const int64_t rows = (int64_t)B * steps;
-  P.off_loss = take(rows * (int64_t)(sizeof(TrainerLossRow) / 4));
-  P.off_gv = take(rows * P.F); P.off_gr = take(rows * P.F); P.off_gp = take(rows * P.A);
-  P.off_vlog = own_vlog ? take(rows * P.F) : -1;
-  P.off_rlog = own_rlog ? take(rows * P.F) : -1;
-  P.off_plog = own_plog ? take(rows * P.A) : -1;
+  train_head_take(P, take, rows, own_vlog, own_rlog, own_plog);
   P.off_h = take(steps * P.state); P.off_ghp = take(steps * P.state); P.off_grs = take((steps - 1) * P.state);
   // the two gradient buffers also carry d loss / d y down the stem, whose boards are larger than the hidden state's
   int64_t gbuf = steps * P.state;

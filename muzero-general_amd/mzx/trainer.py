@@ -228,25 +228,47 @@ def _sgd_step(model, optimizer, batch, config, backend):
     return packed, target_value.shape[0]
 
 
-def train_fc_gradients(model, batch, config, logits=None):
-    """
-    ``Trainer.update_weights`` lines 168-262 -- the unrolled predictions, the loss and ``loss.backward()`` -- for a fully
-    connected ``HipNetwork`` as one ``mzx_train_fc_step`` call on the network's backend and torch's current stream.
-    ``.grad`` of ``next(model.parameters())`` is OVERWRITTEN with d loss / d parameter (allocated once, then reused: no
-    ``zero_grad()`` is needed).  Returns the packed device tensor [4 + B * steps]: loss, value / reward / policy loss
-    means, then the priorities.  ``logits``: an optional dict that receives the step-major ``value`` / ``reward`` /
-    ``policy`` logits.  Nothing synchronises.
-    """
+def _fc_limit(model):
+    return ("residual networks train through torch (fully connected networks only)" if model._cfg.network != 0 else
+            "its weights and per-wave activations exceed the 160 KiB LDS budget of the training kernels")
+
+
+def _resnet_limit(model):
+    cfg = model._cfg
+    return ("fully connected networks train through mzx_train_fc_step (residual networks only)" if cfg.network != 1 else
+            "downsample stems (the strided convolutions and pools) are not trained natively unless config.train_downsample "
+            "/ HipNetwork.train_stem is set" if cfg.downsample and not model.train_stem else
+            "the training kernels need at least one residual block per network" if cfg.blocks < 1 else
+            "BatchNorm in training mode needs more than one value per channel (batch x board >= 2)")
+
+
+# the library entries of a network kind, its io struct, and the wording of its refusal
+_StepKind = collections.namedtuple("_StepKind", "name io limit")
+_FC = _StepKind("mzx_train_fc", _lib.TrainFcIO, _fc_limit)
+_RESNET = _StepKind("mzx_train_resnet", _lib.TrainResnetIO, _resnet_limit)
+TRAIN_SCRATCH_MAX_BYTES = 32 << 30
+_BYPASSED = ("representation_network.module.conv.", "representation_network.module.bn.")      # with config.downsample
+
+
+def _train_gradients(kind, model, batch, config, logits, stats=None):
+    """``train_fc_gradients`` / ``train_resnet_gradients``: one ``<kind.name>_step`` call.  Only the residual kind has a
+    scratch ceiling, the ``d_stats`` output and the ``applications`` table."""
     be, lib = model.backend, model.backend.lib
+    residual = kind is _RESNET
     (observation, action, target_value, target_reward, target_policy, weight,
      scale) = replay.trainer_tensors(batch, be.device)
     if not config.PER:
         weight = None
     batch_size, steps = target_value.shape
-    if not lib.mzx_train_fc_supported(model.handle, batch_size, steps):
-        limit = ("residual networks train through torch (fully connected networks only)" if model._cfg.network != 0 else
-                 "its weights and per-wave activations exceed the 160 KiB LDS budget of the training kernels")
-        raise NotImplementedError(f"mzx_train_fc_step does not run this network at batch {batch_size} x {steps} steps: {limit}")
+    if not getattr(lib, kind.name + "_supported")(model.handle, batch_size, steps):
+        raise NotImplementedError(f"{kind.name}_step does not run this network at batch {batch_size} x {steps} steps: "
+                                  f"{kind.limit(model)}")
+    scratch_bytes = int(getattr(lib, kind.name + "_scratch_bytes")(model.handle, batch_size, steps))
+    if residual:
+        most = int(getattr(config, "train_scratch_max_bytes", TRAIN_SCRATCH_MAX_BYTES))
+        if scratch_bytes > most:
+            raise NotImplementedError(f"{kind.name}_step at batch {batch_size} x {steps} steps keeps {scratch_bytes} bytes of "
+                                      f"activations, more than config.train_scratch_max_bytes = {most}")
     observation = observation.reshape(batch_size, -1).contiguous()
     actions = model.action_space_size
     if (observation.shape[1] != model.input_size or action.numel() != batch_size * steps
@@ -260,9 +282,8 @@ def train_fc_gradients(model, batch, config, logits=None):
     if param.grad is None:
         param.grad = torch.zeros_like(model.flat_weights())
     packed = be.empty((4 + batch_size * steps,), torch.float32)
-    scratch_bytes = int(lib.mzx_train_fc_scratch_bytes(model.handle, batch_size, steps))
     scratch = be.empty((scratch_bytes // 4,), torch.float32)
-    io = _lib.TrainFcIO()
+    io = kind.io()
     io.d_flat, io.d_observation, io.d_action = model.flat_weights().data_ptr(), observation.data_ptr(), action.data_ptr()
     io.d_target_value, io.d_target_reward, io.d_target_policy, io.d_gradient_scale = (t.data_ptr() for t in tensors)
     io.d_weight = None if weight is None else weight.contiguous().data_ptr()
@@ -275,12 +296,28 @@ def train_fc_gradients(model, batch, config, logits=None):
         logits["policy"] = be.empty((steps, batch_size, actions), torch.float32)
         io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (logits[k].data_ptr() for k in ("value", "reward", "policy"))
     io.d_scratch, io.scratch_bytes = scratch.data_ptr(), scratch_bytes
-    lib.check(lib.mzx_train_fc_step(model.handle, ctypes.byref(io), be.stream()))
+    if residual:
+        running = be.empty((int(lib.mzx_train_resnet_stat_floats(model.handle)),), torch.float32)
+        io.d_stats = running.data_ptr()
+    lib.check(getattr(lib, kind.name + "_step")(model.handle, ctypes.byref(io), be.stream()))
+    if residual and stats is not None:
+        stats["running"] = running
+        stats["applications"] = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
+        if model._cfg.downsample:      # the stem bypasses representation_network.module.conv / .bn (first match wins)
+            stats["applications"] = {"representation_network.module.bn.": 0, **stats["applications"]}
     return packed
 
 
-TRAIN_SCRATCH_MAX_BYTES = 32 << 30
-_BYPASSED = ("representation_network.module.conv.", "representation_network.module.bn.")      # with config.downsample
+def train_fc_gradients(model, batch, config, logits=None):
+    """
+    ``Trainer.update_weights`` lines 168-262 -- the unrolled predictions, the loss and ``loss.backward()`` -- for a fully
+    connected ``HipNetwork`` as one ``mzx_train_fc_step`` call on the network's backend and torch's current stream.
+    ``.grad`` of ``next(model.parameters())`` is OVERWRITTEN with d loss / d parameter (allocated once, then reused: no
+    ``zero_grad()`` is needed).  Returns the packed device tensor [4 + B * steps]: loss, value / reward / policy loss
+    means, then the priorities.  ``logits``: an optional dict that receives the step-major ``value`` / ``reward`` /
+    ``policy`` logits.  Nothing synchronises.
+    """
+    return _train_gradients(_FC, model, batch, config, logits)
 
 
 def train_resnet_gradients(model, batch, config, logits=None, stats=None):
@@ -295,61 +332,7 @@ def train_resnet_gradients(model, batch, config, logits=None, stats=None):
     ``representation_network.module.bn.`` a downsample stem bypasses comes first with 0).  Nothing synchronises.  A step whose scratch exceeds
     ``config.train_scratch_max_bytes`` (default 32 GiB) raises ``NotImplementedError``.
     """
-    be, lib = model.backend, model.backend.lib
-    (observation, action, target_value, target_reward, target_policy, weight,
-     scale) = replay.trainer_tensors(batch, be.device)
-    if not config.PER:
-        weight = None
-    batch_size, steps = target_value.shape
-    if not lib.mzx_train_resnet_supported(model.handle, batch_size, steps):
-        cfg = model._cfg
-        limit = ("fully connected networks train through mzx_train_fc_step (residual networks only)" if cfg.network != 1 else
-                 "downsample stems (the strided convolutions and pools) are not trained natively unless config.train_downsample "
-                 "/ HipNetwork.train_stem is set" if cfg.downsample and not model.train_stem else
-                 "the training kernels need at least one residual block per network" if cfg.blocks < 1 else
-                 "BatchNorm in training mode needs more than one value per channel (batch x board >= 2)")
-        raise NotImplementedError(f"mzx_train_resnet_step does not run this network at batch {batch_size} x {steps} steps: {limit}")
-    scratch_bytes = int(lib.mzx_train_resnet_scratch_bytes(model.handle, batch_size, steps))
-    most = int(getattr(config, "train_scratch_max_bytes", TRAIN_SCRATCH_MAX_BYTES))
-    if scratch_bytes > most:
-        raise NotImplementedError(f"mzx_train_resnet_step at batch {batch_size} x {steps} steps keeps {scratch_bytes} bytes of "
-                                  f"activations, more than config.train_scratch_max_bytes = {most}")
-    observation = observation.reshape(batch_size, -1).contiguous()
-    actions = model.action_space_size
-    if (observation.shape[1] != model.input_size or action.numel() != batch_size * steps
-            or target_reward.shape != (batch_size, steps) or scale.shape != (batch_size, steps)
-            or target_policy.shape != (batch_size, steps, actions) or (weight is not None and weight.shape != (batch_size,))):
-        raise ValueError(f"batch: expected observation [batch, {model.input_size}], action / value / reward / gradient scale "
-                         f"[batch, steps], policy [batch, steps, {actions}], weight [batch]")
-    action = action.reshape(batch_size, steps).to(torch.int32).contiguous()
-    tensors = [t.contiguous() for t in (target_value, target_reward, target_policy, scale)]
-    param = next(model.parameters())
-    if param.grad is None:
-        param.grad = torch.zeros_like(model.flat_weights())
-    packed = be.empty((4 + batch_size * steps,), torch.float32)
-    scratch = be.empty((scratch_bytes // 4,), torch.float32)
-    running = be.empty((int(lib.mzx_train_resnet_stat_floats(model.handle)),), torch.float32)
-    io = _lib.TrainResnetIO()
-    io.d_flat, io.d_observation, io.d_action = model.flat_weights().data_ptr(), observation.data_ptr(), action.data_ptr()
-    io.d_target_value, io.d_target_reward, io.d_target_policy, io.d_gradient_scale = (t.data_ptr() for t in tensors)
-    io.d_weight = None if weight is None else weight.contiguous().data_ptr()
-    io.batch, io.steps = batch_size, steps
-    io.value_loss_weight, io.per_alpha = float(config.value_loss_weight), float(config.PER_alpha)
-    io.d_grad_flat, io.d_losses, io.d_priorities = param.grad.data_ptr(), packed.data_ptr(), packed[4:].data_ptr()
-    if logits is not None:
-        width = model.full_support_size
-        logits["value"], logits["reward"] = (be.empty((steps, batch_size, width), torch.float32) for _ in range(2))
-        logits["policy"] = be.empty((steps, batch_size, actions), torch.float32)
-        io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (logits[k].data_ptr() for k in ("value", "reward", "policy"))
-    io.d_scratch, io.scratch_bytes = scratch.data_ptr(), scratch_bytes
-    io.d_stats = running.data_ptr()
-    lib.check(lib.mzx_train_resnet_step(model.handle, ctypes.byref(io), be.stream()))
-    if stats is not None:
-        stats["running"] = running
-        stats["applications"] = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
-        if model._cfg.downsample:      # the stem bypasses representation_network.module.conv / .bn (first match wins)
-            stats["applications"] = {"representation_network.module.bn.": 0, **stats["applications"]}
-    return packed
+    return _train_gradients(_RESNET, model, batch, config, logits, stats)
 
 
 def commit_running_stats(model, running, applications):

@@ -1,10 +1,12 @@
 """
 Shared by the fully connected training tests (tests/test_fc_train.py, tests/test_gpu_fc_train.py), the fixture recipe
-(muzero-general_amd/tools/make_fc_train_golden.py) and the bench (tools/fc_train_bench.py): the case table, the inputs
-rebuilt from seeds (numpy.random.RandomState, float32 only, so every machine builds the same bits), the gates, and the
-fully connected MuZero network restated with plain torch.nn modules under the reference's state_dict keys.
+(muzero-general_amd/tools/make_fc_train_golden.py) and the bench (tools/train_bench.py --family fc): the case table, the
+inputs rebuilt from seeds (numpy.random.RandomState, float32 only, so every machine builds the same bits), the gates, and
+the fully connected MuZero network restated with plain torch.nn modules under the reference's state_dict keys.  What the
+residual case modules need as well lives in train_cases_common.
 """
 import collections
+import functools
 import hashlib
 import json
 import os
@@ -12,6 +14,7 @@ import os
 import numpy
 import torch
 
+import train_cases_common as common
 import trainer_loss_cases
 from mzx import configs
 
@@ -83,21 +86,7 @@ def weights(case):
     return out
 
 
-def batch(case):
-    """A host batch in the layout of ``get_batch()``'s second element (observation, action, target value / reward /
-    policy, PER weight or None, gradient scale)."""
-    B, steps, A = case["B"], case["steps"], case["A"]
-    c, h, w = case["obs"]
-    rs = numpy.random.RandomState(case["seed"])
-    observation = rs.standard_normal((B, c * (case["stacked"] + 1) + case["stacked"], h, w)).astype(numpy.float32)
-    action = rs.randint(0, A, size=(B, steps)).astype(numpy.int64)
-    tv = (rs.standard_normal((B, steps)) * 4).astype(numpy.float32)
-    tr = (rs.standard_normal((B, steps)) * 2).astype(numpy.float32)
-    tp = rs.dirichlet(numpy.ones(A) * 0.7, size=(B, steps)).astype(numpy.float32)
-    K = max(steps - 1, 1)
-    scale = numpy.repeat((1 + numpy.arange(B) % K).astype(numpy.float32)[:, None], steps, 1)   # 1 .. K, one per sample
-    weight = (0.1 + 0.9 * rs.random_sample(B)).astype(numpy.float32) if case["per"] else None
-    return (observation, action, tv, tr, tp, weight, numpy.ascontiguousarray(scale))
+batch = common.batch
 
 
 def digest(case):
@@ -123,19 +112,10 @@ class _Replicated(torch.nn.Module):
 
 
 def _mlp(sizes):
-    layers = []
-    for i in range(len(sizes) - 1):
-        layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
-        layers.append(torch.nn.ELU() if i < len(sizes) - 2 else torch.nn.Identity())
-    return _Replicated(torch.nn.Sequential(*layers))
+    return _Replicated(common._mlp(sizes))
 
 
-def _unit_range(state):
-    low = state.min(1, keepdim=True)[0]
-    high = state.max(1, keepdim=True)[0]
-    span = high - low
-    span[span < 1e-5] += 1e-5
-    return (state - low) / span
+_unit_range = functools.partial(common._unit_range, dim=1)
 
 
 class FcNetwork(torch.nn.Module):
@@ -167,9 +147,7 @@ class FcNetwork(torch.nn.Module):
         return value, reward, policy, state
 
 
-def load(module, state):
-    module.load_state_dict({k: torch.from_numpy(numpy.ascontiguousarray(v)) for k, v in state.items()})
-    return module
+load = common.load
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -192,23 +170,10 @@ def network(be, case):
 
 
 def run_native(be, case, net=None):
-    """mzx_train_fc_step of a case through mzx.trainer.train_fc_gradients -> dict of host arrays: loss, value_loss,
-    reward_loss, policy_loss, priorities, value / reward / policy logits (step-major) and grad/<key> per tensor.  The
-    gradient buffer is pre-filled with NaN: the call has to overwrite all of it."""
+    """mzx_train_fc_step of a case through mzx.trainer.train_fc_gradients -> the dict of ``common.run_native``."""
     from mzx import trainer
     net = net if net is not None else network(be, case)
-    param = next(net.parameters())
-    param.grad = torch.full_like(net.flat_weights(), float("nan"))
-    logits = {}
-    packed = trainer.train_fc_gradients(net, batch(case), config_of(case), logits=logits)
-    host = packed.cpu().numpy()
-    out = dict(loss=host[0], value_loss=host[1], reward_loss=host[2], policy_loss=host[3],
-               priorities=host[4:].reshape(case["B"], case["steps"]).copy(),
-               value_logits=logits["value"].cpu().numpy(), reward_logits=logits["reward"].cpu().numpy(),
-               policy_logits=logits["policy"].cpu().numpy(), grad_flat=param.grad.cpu().numpy().copy())
-    for key, off, numel, shape in net._tensors:
-        out["grad/" + key] = out["grad_flat"][off:off + numel].reshape(shape)
-    return out
+    return common.run_native(net, case, lambda logits: trainer.train_fc_gradients(net, batch(case), config_of(case), logits=logits))
 
 
 LOGIT_GATE = 1e-4           # DESIGN.md section 2: the heads, against the reference's float32 results
@@ -314,10 +279,4 @@ def check_sgd(be, case, gold, report=print):
 
 def adam_reference_step(net, grad_flat, flat_before, **hp):
     """torch Adam applied PER TENSOR to the flat gradient split by mzx_net_tensor_info -> the flat weights after."""
-    params = []
-    for key, off, numel, shape in net._tensors:
-        p = torch.nn.Parameter(flat_before[off:off + numel].reshape(shape).clone())
-        p.grad = grad_flat[off:off + numel].reshape(shape).clone()
-        params.append(p)
-    torch.optim.Adam(params, **hp).step()
-    return torch.cat([p.detach().reshape(-1) for p in params])
+    return torch.cat([p.reshape(-1) for p in common.adam_reference_step(net, grad_flat, flat_before, **hp).values()])

@@ -1,6 +1,6 @@
 """
 Shared by the stem training tests (tests/test_resnet_stem_train.py, tests/test_gpu_resnet_stem_train.py), the fixture
-recipe (muzero-general_amd/tools/make_resnet_stem_train_golden.py) and the bench (tools/resnet_stem_train_bench.py): the
+recipe (muzero-general_amd/tools/make_resnet_stem_train_golden.py) and the bench (tools/train_bench.py --family stem): the
 case table of residual networks WITH a downsample stem ("resnet": DownSample, "CNN": DownsampleCNN), inputs and weights
 rebuilt from seeds, the residual network with either stem restated in plain torch.nn under the reference's state_dict
 keys, and the gates -- those of resnet_train_cases, bound to this module's tables.

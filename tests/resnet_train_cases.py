@@ -1,11 +1,12 @@
 """
 Shared by the residual training tests (tests/test_resnet_train.py, tests/test_gpu_resnet_train.py), the fixture recipe
-(muzero-general_amd/tools/make_resnet_train_golden.py) and the bench (tools/resnet_train_bench.py): the case table, the
-inputs and weights rebuilt from seeds (numpy.random.RandomState, float32 only), the gates, and the residual MuZero
+(muzero-general_amd/tools/make_resnet_train_golden.py) and the bench (tools/train_bench.py --family resnet): the case
+table, the inputs and weights rebuilt from seeds (numpy.random.RandomState, float32 only), the gates, and the residual MuZero
 network restated with plain torch.nn modules under the reference's state_dict keys (training mode: BatchNorm on batch
 statistics).
 """
 import collections
+import functools
 import hashlib
 import json
 import os
@@ -15,6 +16,7 @@ import numpy
 import torch
 
 import fc_train_cases
+import train_cases_common as common
 import trainer_loss_cases
 from mzx import configs
 
@@ -63,8 +65,7 @@ def case_of_config(config, B, steps, seed=50, name=None):
                 alpha=0.5, vlw=0.25, seed=seed)
 
 
-def input_channels(case):
-    return case["obs"][0] * (case["stacked"] + 1) + case["stacked"]
+input_channels = common.input_channels
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -79,12 +80,7 @@ def _conv3(cin, cout):
     return torch.nn.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, bias=False)
 
 
-def _mlp(sizes):
-    layers = []
-    for i in range(len(sizes) - 1):
-        layers.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
-        layers.append(torch.nn.ELU() if i < len(sizes) - 2 else torch.nn.Identity())
-    return torch.nn.Sequential(*layers)
+_mlp = common._mlp
 
 
 class _Block(torch.nn.Module):
@@ -136,13 +132,7 @@ class _Prediction(torch.nn.Module):
         return self.fc_policy(self.conv1x1_policy(x).flatten(1)), self.fc_value(self.conv1x1_value(x).flatten(1))
 
 
-def _unit_range(state):
-    flat = state.flatten(2)
-    low = flat.min(2, keepdim=True)[0].unsqueeze(-1)
-    high = flat.max(2, keepdim=True)[0].unsqueeze(-1)
-    span = high - low
-    span[span < 1e-5] += 1e-5
-    return (state - low) / span
+_unit_range = functools.partial(common._unit_range, dim=2)      # per channel, over its board
 
 
 class ResNetwork(torch.nn.Module):
@@ -179,8 +169,7 @@ def tensor_shapes(case):
                                    if not k.endswith("num_batches_tracked"))
 
 
-def is_statistic(key):
-    return key.endswith((".running_mean", ".running_var"))
+is_statistic = common.is_statistic
 
 
 def split(case, joined):
@@ -221,20 +210,7 @@ def weights(case):
     return out
 
 
-def batch(case):
-    """A host batch in the layout of ``get_batch()``'s second element."""
-    B, steps, A = case["B"], case["steps"], case["A"]
-    _, h, w = case["obs"]
-    rs = numpy.random.RandomState(case["seed"])
-    observation = rs.standard_normal((B, input_channels(case), h, w)).astype(numpy.float32)
-    action = rs.randint(0, A, size=(B, steps)).astype(numpy.int64)
-    tv = (rs.standard_normal((B, steps)) * 4).astype(numpy.float32)
-    tr = (rs.standard_normal((B, steps)) * 2).astype(numpy.float32)
-    tp = rs.dirichlet(numpy.ones(A) * 0.7, size=(B, steps)).astype(numpy.float32)
-    K = max(steps - 1, 1)
-    scale = numpy.repeat((1 + numpy.arange(B) % K).astype(numpy.float32)[:, None], steps, 1)
-    weight = (0.1 + 0.9 * rs.random_sample(B)).astype(numpy.float32) if case["per"] else None
-    return (observation, action, tv, tr, tp, weight, numpy.ascontiguousarray(scale))
+batch = common.batch
 
 
 def digest(case):
@@ -244,9 +220,7 @@ def digest(case):
     return h.hexdigest()
 
 
-def load(module, state):
-    module.load_state_dict({k: torch.from_numpy(numpy.ascontiguousarray(v)) for k, v in state.items()}, strict=False)
-    return module
+load = functools.partial(common.load, strict=False)
 
 
 def torch_step(case, dtype, device="cpu", steps_of_sgd=0):
@@ -326,19 +300,12 @@ def run_native(be, case, net=None, tables=THIS):
     is pre-filled with NaN: the call has to overwrite all of it."""
     from mzx import trainer
     net = net if net is not None else tables.network(be, case)
-    param = next(net.parameters())
-    param.grad = torch.full_like(net.flat_weights(), float("nan"))
-    logits, stats = {}, {}
-    packed = trainer.train_resnet_gradients(net, tables.batch(case), tables.config_of(case), logits=logits, stats=stats)
-    host = packed.cpu().numpy()
-    out = dict(loss=host[0], value_loss=host[1], reward_loss=host[2], policy_loss=host[3],
-               priorities=host[4:].reshape(case["B"], case["steps"]).copy(),
-               value_logits=logits["value"].cpu().numpy(), reward_logits=logits["reward"].cpu().numpy(),
-               policy_logits=logits["policy"].cpu().numpy(), grad_flat=param.grad.cpu().numpy().copy(),
-               running=stats["running"].cpu().numpy().copy())
+    stats = {}
+    out = common.run_native(net, case, lambda logits: trainer.train_resnet_gradients(
+        net, tables.batch(case), tables.config_of(case), logits=logits, stats=stats))
+    out["running"] = stats["running"].cpu().numpy().copy()
     at = 0
     for key, off, numel, shape in net._tensors:
-        out["grad/" + key] = out["grad_flat"][off:off + numel].reshape(shape)
         if is_statistic(key):      # the packed statistics: [running_mean | running_var] per BatchNorm, in state_dict order
             out["stat/" + key] = out["running"][at:at + numel]
             at += numel
@@ -505,14 +472,4 @@ def check_sgd(be, case, gold, report=print, tables=THIS):
     return net, optimizer
 
 
-def adam_reference_step(net, grad_flat, flat_before, **hp):
-    """torch Adam applied PER TENSOR to the parameters (not the running statistics) -> {key: tensor after}."""
-    params, keys = [], []
-    for key, off, numel, shape in net._tensors:
-        if is_statistic(key):
-            continue
-        p = torch.nn.Parameter(flat_before[off:off + numel].reshape(shape).clone())
-        p.grad = grad_flat[off:off + numel].reshape(shape).clone()
-        params.append(p), keys.append(key)
-    torch.optim.Adam(params, **hp).step()
-    return {k: p.detach() for k, p in zip(keys, params)}
+adam_reference_step = common.adam_reference_step

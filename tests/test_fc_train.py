@@ -12,7 +12,8 @@ import torch
 
 import fc_train_cases as cases
 import hostcheck
-from mzx import _lib, configs, models, trainer
+import train_cases_common as common
+from mzx import configs, models, trainer
 from oracle import ref_shim
 
 
@@ -35,21 +36,8 @@ def test_two_sgd_momentum_steps(be, gold):
     cases.check_sgd(be, cases.BY_NAME["b5_k4_stacked"], gold)
 
 
-def check_adam_bit_for_bit(be, case):
-    hp = dict(lr=0.02, weight_decay=1e-4)
-    net = cases.network(be, case)
-    before = net.flat_weights().clone()
-    optimizer = torch.optim.Adam(net.parameters(), **hp)
-    trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
-    grad = next(net.parameters()).grad
-    want = cases.adam_reference_step(net, grad, before, **hp)
-    got = net.flat_weights()
-    assert not torch.equal(got, before)
-    assert numpy.array_equal(got.cpu().numpy().view(numpy.int32), want.cpu().numpy().view(numpy.int32))
-
-
 def test_adam_on_the_flat_parameter_is_adam_per_tensor(be):
-    check_adam_bit_for_bit(be, cases.BY_NAME["b5_k4_stacked"])
+    common.check_adam_bit_for_bit(be, cases, cases.BY_NAME["b5_k4_stacked"])
 
 
 def test_parameters_is_one_leaf_over_the_flat_buffer(be):
@@ -61,27 +49,7 @@ def test_parameters_is_one_leaf_over_the_flat_buffer(be):
 
 
 def check_optimizer_state_round_trip(be, case, make):
-    net = cases.network(be, case)
-    optimizer = make(net.parameters())
-    for _ in range(2):
-        trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
-    state = trainer.optimizer_state(optimizer, net)
-    assert sorted(state["state"]) == list(range(len(net._tensors)))
-    assert state["param_groups"][0]["params"] == list(range(len(net._tensors)))
-    for i, (_, _, _, shape) in enumerate(net._tensors):
-        for value in state["state"][i].values():
-            assert not torch.is_tensor(value) or value.dim() == 0 or tuple(value.shape) == tuple(shape)
-    twin_net = cases.network(be, case)
-    twin = make(twin_net.parameters())
-    trainer.load_optimizer_state(twin, twin_net, state)
-    again = trainer.optimizer_state(twin, twin_net)
-    assert again["param_groups"] == state["param_groups"] and sorted(again["state"]) == sorted(state["state"])
-    for i in state["state"]:
-        assert list(again["state"][i]) == list(state["state"][i])
-        for key, value in state["state"][i].items():
-            other = again["state"][i][key]
-            assert torch.equal(value, other) if torch.is_tensor(value) else value == other, (i, key)
-    return state
+    return common.check_optimizer_state_round_trip(be, cases, case, make, lambda net: net._tensors)      # (no buffers: every tensor)
 
 
 @pytest.mark.parametrize("kind", ["sgd", "adam"])
@@ -129,61 +97,25 @@ def test_every_fully_connected_game_of_the_reference_is_supported(be):
         assert net.train_fc_supported(cfg.batch_size, cfg.num_unroll_steps + 1), name
 
 
-def _io(be, case, net, keep):
-    """A complete mzx_train_fc_io over host tensors, outputs pre-filled with 7."""
-    observation, action, tv, tr, tp, weight, scale = cases.batch(case)
-    B, steps = case["B"], case["steps"]
-    t = dict(observation=torch.from_numpy(observation).reshape(B, -1).contiguous(), action=torch.from_numpy(action).to(torch.int32),
-             tv=torch.from_numpy(tv), tr=torch.from_numpy(tr), tp=torch.from_numpy(tp), scale=torch.from_numpy(scale),
-             grad=torch.full((net.num_params,), 7.0), losses=torch.full((4,), 7.0), priorities=torch.full((B, steps), 7.0))
-    nbytes = int(be.lib.mzx_train_fc_scratch_bytes(net.handle, B, steps))
-    t["scratch"] = torch.full((max(nbytes, 16) // 4,), 7.0)
-    keep.append(t)
-    io = _lib.TrainFcIO()
-    io.d_flat, io.d_observation, io.d_action = net.flat_weights().data_ptr(), t["observation"].data_ptr(), t["action"].data_ptr()
-    io.d_target_value, io.d_target_reward, io.d_target_policy = t["tv"].data_ptr(), t["tr"].data_ptr(), t["tp"].data_ptr()
-    io.d_gradient_scale = t["scale"].data_ptr()
-    io.batch, io.steps, io.value_loss_weight, io.per_alpha = B, steps, case["vlw"], case["alpha"]
-    io.d_grad_flat, io.d_losses, io.d_priorities = t["grad"].data_ptr(), t["losses"].data_ptr(), t["priorities"].data_ptr()
-    io.d_scratch, io.scratch_bytes = t["scratch"].data_ptr(), nbytes
-    return io, t
-
-
-REQUIRED = ("d_flat", "d_observation", "d_action", "d_target_value", "d_target_reward", "d_target_policy", "d_gradient_scale",
-            "d_grad_flat", "d_losses", "d_priorities", "d_scratch")
-BAD = [(f, None) for f in REQUIRED] + [("batch", 0), ("batch", -1), ("steps", 0), ("steps", -2), ("scratch_bytes", 64)]
-
-
-def check_refusals(be, field, value):
-    case, keep = cases.CASES[1], []
-    net = cases.network(be, case)
-    io, t = _io(be, case, net, keep)
-    setattr(io, field, value)
-    assert be.lib.mzx_train_fc_step(net.handle, ctypes.byref(io), None) == -1        # MZX_ERR_INVALID
-    assert be.lib.mzx_last_error()
-    for key in ("grad", "losses", "priorities", "scratch"):                             # nothing was launched
-        assert (t[key] == 7.0).all(), key
-    return net, case, keep
+BAD = [(f, None) for f in common.REQUIRED] + [("batch", 0), ("batch", -1), ("steps", 0), ("steps", -2), ("scratch_bytes", 64),
+                                              ("d_scratch", "misaligned")]
 
 
 @pytest.mark.parametrize("field,value", BAD, ids=[f"{f}={v}" for f, v in BAD])
 def test_abi_refusals(be, field, value):
-    net, case, keep = check_refusals(be, field, value)
-    io, t = _io(be, case, net, keep)                                    # (and the untouched struct is accepted)
-    assert be.lib.mzx_train_fc_step(net.handle, ctypes.byref(io), None) == 0
-    assert not (t["losses"] == 7.0).any() and not (t["grad"] == 7.0).any()
+    common.check_abi_refusal(be, "fc", cases, cases.CASES[1], field, value)
 
 
 def test_abi_refuses_a_residual_network_and_null_arguments(be):
     case, keep = cases.CASES[1], []
     net = cases.network(be, case)
     residual = models.MuZeroNetwork(configs.tictactoe(), _backend=be)
-    io, t = _io(be, case, net, keep)
+    io, t = common.step_io(be, case, net, keep, "fc")
     assert be.lib.mzx_train_fc_step(residual.handle, ctypes.byref(io), None) == -1
     assert "residual" in be.lib.mzx_last_error().decode()
     assert be.lib.mzx_train_fc_step(None, ctypes.byref(io), None) == -1
     assert be.lib.mzx_train_fc_step(net.handle, None, None) == -1
-    for key in ("grad", "losses", "priorities", "scratch"):
+    for key in common.OUTPUTS["fc"]:
         assert (t[key] == 7.0).all(), key
 
 

@@ -1,8 +1,8 @@
 """
-Every output bit of mzx_train_resnet_step on the serial test double of the ABI, for the ten fixture cases of
-resnet_train_cases and resnet_stem_train_cases, against the `serial` section of tests/golden/resnet_train_bits.json
-(muzero-general_amd/tools/make_resnet_train_bits.py --family resnet; the section names the commit it was recorded at).  A
-difference is a changed sum or a changed contraction: find the expression, do not re-record.
+Every output bit of mzx_train_fc_step on the serial test double of the ABI, for the five cases of fc_train_cases, against
+the `serial` section of tests/golden/fc_train_bits.json (muzero-general_amd/tools/make_resnet_train_bits.py --family fc; the
+section names the commit it was recorded at).  A difference is a changed sum or a changed contraction: find the
+expression, do not re-record.
 """
 import json
 
@@ -12,7 +12,7 @@ import hostcheck
 import train_cases_common as common
 
 bits = common.bits
-FAMILY = "resnet"
+FAMILY = "fc"
 CASES = bits.fixture_cases(FAMILY)
 
 
@@ -33,7 +33,7 @@ def check_bits(be, case, tables, section):
 
 def test_the_fixture_pins_every_case_on_both_builds(pinned):
     names = [case["name"] for case, _ in CASES]
-    assert names == list(bits.PLAIN + bits.STEM) and len(names) == 10
+    assert names == list(bits.FC) and len(names) == 5
     for backend in ("serial", "device"):
         assert sorted(pinned[backend]["cases"]) == sorted(names) and pinned[backend]["commit"]
 

@@ -4,7 +4,6 @@ wave_kernel<4, FctWgradBody> behind mzx_train_fc_step; mzx.trainer with a HipNet
 gates of tests/test_fc_train.py (fc_train_cases.check_case), and the whole step -- device sampler, native gradients, Adam,
 priority feedback -- followed by a search on the trained buffer.
 """
-import ctypes
 import warnings
 
 import numpy
@@ -14,6 +13,7 @@ import torch
 import fc_train_cases as cases
 import replay_sampler_cases
 import test_fc_train as host_tests
+import train_cases_common as common
 import trainer_loss_cases
 from mzx import _lib, configs, models, replay, self_play, synthetic, trainer
 
@@ -41,7 +41,7 @@ def test_two_sgd_momentum_steps(be, gold):
 
 
 def test_adam_on_the_flat_parameter_is_adam_per_tensor(be):
-    host_tests.check_adam_bit_for_bit(be, cases.BY_NAME["b5_k4_stacked"])
+    common.check_adam_bit_for_bit(be, cases, cases.BY_NAME["b5_k4_stacked"])
 
 
 def test_optimizer_state_round_trip(be):
@@ -52,21 +52,8 @@ def test_optimizer_state_round_trip(be):
 @pytest.mark.parametrize("field,value", [("d_scratch", None), ("steps", 0), ("scratch_bytes", 64)],
                          ids=["d_scratch=None", "steps=0", "scratch_bytes=64"])
 def test_abi_refusals(be, field, value):
-    case, keep = cases.CASES[1], []
-    net = cases.network(be, case)
-    io, t = host_tests._io(be, case, net, keep)
-    dev = {k: v.to(be.device) for k, v in t.items()}
-    for name, key in (("d_observation", "observation"), ("d_action", "action"), ("d_target_value", "tv"), ("d_target_reward", "tr"),
-                      ("d_target_policy", "tp"), ("d_gradient_scale", "scale"), ("d_grad_flat", "grad"), ("d_losses", "losses"),
-                      ("d_priorities", "priorities"), ("d_scratch", "scratch")):
-        setattr(io, name, dev[key].data_ptr())
-    setattr(io, field, value)
-    residual = models.MuZeroNetwork(configs.tictactoe())
-    assert be.lib.mzx_train_fc_step(net.handle, ctypes.byref(io), be.stream()) == -1        # MZX_ERR_INVALID
-    assert be.lib.mzx_train_fc_step(residual.handle, ctypes.byref(io), be.stream()) == -1
-    torch.cuda.synchronize()
-    for key in ("grad", "losses", "priorities", "scratch"):                                    # nothing was launched
-        assert (dev[key] == 7.0).all(), key
+    common.check_abi_refusal(be, "fc", cases, cases.CASES[1], field, value, device=be.device, sync=torch.cuda.synchronize,
+                             others=[models.MuZeroNetwork(configs.tictactoe())])
 
 
 def test_train_step_on_the_device_then_search(be):

@@ -5,7 +5,6 @@ HipNetwork) against tests/golden/resnet_train.npz with the gates of tests/test_r
 and connect4 networks against the torch restatement in binary64, and the whole step -- resident self-play rounds, device
 hand-off, device sampler, native gradients, Adam, the statistics commit -- followed by a search on the trained buffer.
 """
-import ctypes
 import warnings
 
 import numpy
@@ -16,6 +15,7 @@ import device_handoff_cases
 import resident_rounds_cases as rr
 import resnet_train_cases as cases
 import test_resnet_train as host_tests
+import train_cases_common as common
 import trainer_loss_cases
 from mzx import _lib, configs, games, models, self_play, synthetic, trainer
 from oracle import net_oracle
@@ -44,7 +44,7 @@ def test_two_sgd_momentum_steps_weights_and_buffers(be, gold):
 
 
 def test_adam_on_the_flat_parameter_is_adam_per_tensor(be):
-    host_tests.check_adam_bit_for_bit(be, cases.BY_NAME["c_b5_k4_stacked"])
+    common.check_adam_bit_for_bit(be, cases, cases.BY_NAME["c_b5_k4_stacked"])
 
 
 def test_optimizer_state_round_trip(be):
@@ -63,21 +63,8 @@ def test_shipped_networks_against_the_restatement_in_binary64(be, game):
 @pytest.mark.parametrize("field,value", [("d_scratch", None), ("d_stats", None), ("steps", 0), ("scratch_bytes", 64)],
                          ids=["d_scratch=None", "d_stats=None", "steps=0", "scratch_bytes=64"])
 def test_abi_refusals(be, field, value):
-    case, keep = cases.BY_NAME["b_b3_k3"], []
-    net = cases.network(be, case)
-    io, t = host_tests._io(be, case, net, keep)
-    dev = {k: v.to(be.device) for k, v in t.items()}
-    for name, key in (("d_observation", "observation"), ("d_action", "action"), ("d_target_value", "tv"), ("d_target_reward", "tr"),
-                      ("d_target_policy", "tp"), ("d_gradient_scale", "scale"), ("d_grad_flat", "grad"), ("d_losses", "losses"),
-                      ("d_priorities", "priorities"), ("d_scratch", "scratch"), ("d_stats", "stats")):
-        setattr(io, name, dev[key].data_ptr())
-    setattr(io, field, value)
-    breakout = models.MuZeroNetwork(configs.breakout())
-    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), be.stream()) == -1        # MZX_ERR_INVALID
-    assert be.lib.mzx_train_resnet_step(breakout.handle, ctypes.byref(io), be.stream()) == -1
-    torch.cuda.synchronize()
-    for key in host_tests.OUTPUTS:                                                                # nothing was launched
-        assert (dev[key] == 7.0).all(), key
+    common.check_abi_refusal(be, "resnet", cases, cases.BY_NAME["b_b3_k3"], field, value, device=be.device,
+                             sync=torch.cuda.synchronize, others=[models.MuZeroNetwork(configs.breakout())])
 
 
 def test_train_step_from_resident_rounds_then_search(be):

@@ -13,6 +13,7 @@ import torch
 import fc_train_cases
 import hostcheck
 import resnet_stem_train_cases as cases
+import train_cases_common as common
 from mzx import _lib, configs, models, trainer
 
 REFUSAL = "downsample stems (the strided convolutions and pools) are not trained natively"
@@ -40,48 +41,12 @@ def test_two_sgd_momentum_steps_weights_and_buffers(be, gold):
     cases.check_sgd(be, cases.BY_NAME["sc_b5_k2_stacked"], gold)
 
 
-def _io(be, case, net, keep, device="cpu"):
-    """A complete mzx_train_resnet_io over tensors on ``device``, outputs pre-filled with 7."""
-    observation, action, tv, tr, tp, weight, scale = cases.batch(case)
-    B, steps = case["B"], case["steps"]
-    nbytes = int(be.lib.mzx_train_resnet_scratch_bytes(net.handle, B, steps))
-    assert nbytes > 0
-    t = dict(observation=torch.from_numpy(observation).reshape(B, -1).contiguous(), action=torch.from_numpy(action).to(torch.int32),
-             tv=torch.from_numpy(tv), tr=torch.from_numpy(tr), tp=torch.from_numpy(tp), scale=torch.from_numpy(scale),
-             grad=torch.full((net.num_params,), 7.0), losses=torch.full((4,), 7.0), priorities=torch.full((B, steps), 7.0),
-             stats=torch.full((int(be.lib.mzx_train_resnet_stat_floats(net.handle)),), 7.0),
-             scratch=torch.full((nbytes // 4,), 7.0))
-    t = {k: v.to(device) for k, v in t.items()}
-    keep.append(t)
-    io = _lib.TrainResnetIO()
-    io.d_flat, io.d_observation, io.d_action = net.flat_weights().data_ptr(), t["observation"].data_ptr(), t["action"].data_ptr()
-    io.d_target_value, io.d_target_reward, io.d_target_policy = t["tv"].data_ptr(), t["tr"].data_ptr(), t["tp"].data_ptr()
-    io.d_gradient_scale = t["scale"].data_ptr()
-    io.batch, io.steps, io.value_loss_weight, io.per_alpha = B, steps, case["vlw"], case["alpha"]
-    io.d_grad_flat, io.d_losses, io.d_priorities = t["grad"].data_ptr(), t["losses"].data_ptr(), t["priorities"].data_ptr()
-    io.d_scratch, io.scratch_bytes, io.d_stats = t["scratch"].data_ptr(), nbytes, t["stats"].data_ptr()
-    return io, t
-
-
-OUTPUTS = ("grad", "losses", "priorities", "scratch", "stats")
 BAD = [("d_scratch", None), ("d_stats", None), ("steps", 0), ("scratch_bytes", 64)]
 
 
 def check_abi_refusal(be, field, value, device="cpu", sync=lambda: None):
-    case, keep = cases.BY_NAME["ca_b2_k2"], []
-    net = cases.network(be, case)
+    net = common.check_abi_refusal(be, "resnet", cases, cases.BY_NAME["ca_b2_k2"], field, value, device, sync)
     assert net.train_stem
-    io, t = _io(be, case, net, keep, device)
-    setattr(io, field, value)
-    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), be.stream()) == -1        # MZX_ERR_INVALID
-    assert be.lib.mzx_last_error()
-    sync()
-    for key in OUTPUTS:                                                                           # nothing was launched
-        assert (t[key] == 7.0).all(), key
-    io, t = _io(be, case, net, keep, device)                                                      # (the untouched struct is accepted)
-    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), be.stream()) == 0
-    sync()
-    assert not (t["losses"] == 7.0).any() and not (t["grad"] == 7.0).any() and not (t["stats"] == 7.0).any()
 
 
 @pytest.mark.parametrize("field,value", BAD, ids=[f"{f}={v}" for f, v in BAD])

@@ -13,7 +13,8 @@ import torch
 import fc_train_cases
 import hostcheck
 import resnet_train_cases as cases
-from mzx import _lib, configs, models, trainer
+import train_cases_common as common
+from mzx import configs, models, trainer
 from oracle import ref_shim
 
 
@@ -36,29 +37,8 @@ def test_two_sgd_momentum_steps_weights_and_buffers(be, gold):
     cases.check_sgd(be, cases.BY_NAME["c_b5_k4_stacked"], gold)
 
 
-def check_adam_bit_for_bit(be, case):
-    """Adam over the one flat parameter is Adam per tensor on the parameter spans, bit for bit; the spans of the running
-    statistics hold what the step committed, whatever Adam did to them."""
-    hp = dict(lr=0.02, weight_decay=1e-4)
-    net = cases.network(be, case)
-    before = net.flat_weights().clone()
-    optimizer = torch.optim.Adam(net.parameters(), **hp)
-    trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
-    grad = next(net.parameters()).grad
-    want = cases.adam_reference_step(net, grad, before, **hp)
-    state = net.state_dict()
-    committed = cases.run_native(be, case, cases.network(be, case))
-    for key, off, numel, shape in net._tensors:
-        got = state[key].cpu().numpy()
-        if cases.is_statistic(key):
-            assert numpy.array_equal(got.view(numpy.int32), committed["stat/" + key].view(numpy.int32)), key
-        else:
-            assert not torch.equal(state[key].cpu(), before[off:off + numel].reshape(shape).cpu()), key
-            assert numpy.array_equal(got.view(numpy.int32), want[key].cpu().numpy().view(numpy.int32)), key
-
-
 def test_adam_on_the_flat_parameter_is_adam_per_tensor(be):
-    check_adam_bit_for_bit(be, cases.BY_NAME["c_b5_k4_stacked"])
+    common.check_adam_bit_for_bit(be, cases, cases.BY_NAME["c_b5_k4_stacked"])
 
 
 def test_num_batches_tracked_and_train_returns_self(be):
@@ -75,30 +55,15 @@ def test_num_batches_tracked_and_train_returns_self(be):
         assert value == 3 * per_step, (key, value)
 
 
-def check_optimizer_state_round_trip(be, case, make):
-    net = cases.network(be, case)
-    optimizer = make(net.parameters())
-    for _ in range(2):
-        trainer.update_weights(net, optimizer, cases.batch(case), cases.config_of(case))
-    state = trainer.optimizer_state(optimizer, net)
+def parameter_table(net):
+    """The rows of the reference's ``parameters()``: the running statistics are buffers there."""
     table = [t for t in net._tensors if not cases.is_statistic(t[0])]
     assert len(table) < len(net._tensors)
-    assert sorted(state["state"]) == list(range(len(table)))
-    assert state["param_groups"][0]["params"] == list(range(len(table)))
-    for i, (_, _, _, shape) in enumerate(table):
-        for value in state["state"][i].values():
-            assert not torch.is_tensor(value) or value.dim() == 0 or tuple(value.shape) == tuple(shape)
-    twin_net = cases.network(be, case)
-    twin = make(twin_net.parameters())
-    trainer.load_optimizer_state(twin, twin_net, state)
-    again = trainer.optimizer_state(twin, twin_net)
-    assert again["param_groups"] == state["param_groups"] and sorted(again["state"]) == sorted(state["state"])
-    for i in state["state"]:
-        assert list(again["state"][i]) == list(state["state"][i])
-        for key, value in state["state"][i].items():
-            other = again["state"][i][key]
-            assert torch.equal(value, other) if torch.is_tensor(value) else value == other, (i, key)
-    return state
+    return table
+
+
+def check_optimizer_state_round_trip(be, case, make):
+    return common.check_optimizer_state_round_trip(be, cases, case, make, parameter_table)
 
 
 @pytest.mark.parametrize("kind", ["sgd", "adam"])
@@ -165,53 +130,20 @@ def test_the_board_games_of_the_reference_are_supported_at_their_shipped_shapes(
     assert not models.MuZeroNetwork(ref_shim.muzero_config("breakout"), _backend=be).train_resnet_supported(4, 3)
 
 
-def _io(be, case, net, keep):
-    """A complete mzx_train_resnet_io over host tensors, outputs pre-filled with 7."""
-    observation, action, tv, tr, tp, weight, scale = cases.batch(case)
-    B, steps = case["B"], case["steps"]
-    t = dict(observation=torch.from_numpy(observation).reshape(B, -1).contiguous(), action=torch.from_numpy(action).to(torch.int32),
-             tv=torch.from_numpy(tv), tr=torch.from_numpy(tr), tp=torch.from_numpy(tp), scale=torch.from_numpy(scale),
-             grad=torch.full((net.num_params,), 7.0), losses=torch.full((4,), 7.0), priorities=torch.full((B, steps), 7.0),
-             stats=torch.full((int(be.lib.mzx_train_resnet_stat_floats(net.handle)),), 7.0))
-    nbytes = int(be.lib.mzx_train_resnet_scratch_bytes(net.handle, B, steps))
-    t["scratch"] = torch.full((max(nbytes, 16) // 4,), 7.0)
-    keep.append(t)
-    io = _lib.TrainResnetIO()
-    io.d_flat, io.d_observation, io.d_action = net.flat_weights().data_ptr(), t["observation"].data_ptr(), t["action"].data_ptr()
-    io.d_target_value, io.d_target_reward, io.d_target_policy = t["tv"].data_ptr(), t["tr"].data_ptr(), t["tp"].data_ptr()
-    io.d_gradient_scale = t["scale"].data_ptr()
-    io.batch, io.steps, io.value_loss_weight, io.per_alpha = B, steps, case["vlw"], case["alpha"]
-    io.d_grad_flat, io.d_losses, io.d_priorities = t["grad"].data_ptr(), t["losses"].data_ptr(), t["priorities"].data_ptr()
-    io.d_scratch, io.scratch_bytes, io.d_stats = t["scratch"].data_ptr(), nbytes, t["stats"].data_ptr()
-    return io, t
-
-
-REQUIRED = ("d_flat", "d_observation", "d_action", "d_target_value", "d_target_reward", "d_target_policy", "d_gradient_scale",
-            "d_grad_flat", "d_losses", "d_priorities", "d_scratch", "d_stats")
-BAD = [(f, None) for f in REQUIRED] + [("batch", 0), ("batch", -1), ("steps", 0), ("steps", -2), ("scratch_bytes", 64),
-                                       ("d_scratch", "misaligned")]
-OUTPUTS = ("grad", "losses", "priorities", "scratch", "stats")
+BAD = [(f, None) for f in common.REQUIRED + ("d_stats",)] + [("batch", 0), ("batch", -1), ("steps", 0), ("steps", -2),
+                                                             ("scratch_bytes", 64), ("d_scratch", "misaligned")]
+OUTPUTS = common.OUTPUTS["resnet"]
 
 
 @pytest.mark.parametrize("field,value", BAD, ids=[f"{f}={v}" for f, v in BAD])
 def test_abi_refusals(be, field, value):
-    case, keep = cases.BY_NAME["b_b3_k3"], []
-    net = cases.network(be, case)
-    io, t = _io(be, case, net, keep)
-    setattr(io, field, t["scratch"].data_ptr() + 4 if value == "misaligned" else value)
-    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), None) == -1        # MZX_ERR_INVALID
-    assert be.lib.mzx_last_error()
-    for key in OUTPUTS:                                                                    # nothing was launched
-        assert (t[key] == 7.0).all(), key
-    io, t = _io(be, case, net, keep)                                                       # (the untouched struct is accepted)
-    assert be.lib.mzx_train_resnet_step(net.handle, ctypes.byref(io), None) == 0
-    assert not (t["losses"] == 7.0).any() and not (t["grad"] == 7.0).any() and not (t["stats"] == 7.0).any()
+    common.check_abi_refusal(be, "resnet", cases, cases.BY_NAME["b_b3_k3"], field, value)
 
 
 def test_abi_refuses_unsupported_networks_and_null_arguments(be):
     case, keep = cases.BY_NAME["b_b3_k3"], []
     net = cases.network(be, case)
-    io, t = _io(be, case, net, keep)
+    io, t = common.step_io(be, case, net, keep, "resnet")
     fc = fc_train_cases.network(be, fc_train_cases.CASES[1])
     assert be.lib.mzx_train_resnet_step(fc.handle, ctypes.byref(io), None) == -1
     assert "fully connected" in be.lib.mzx_last_error().decode()
