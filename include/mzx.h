@@ -123,7 +123,10 @@ int64_t mzx_net_workspace_floats(const mzx_net* net, int32_t max_batch);
 int64_t mzx_net_flops(const mzx_net* net, int32_t recurrent);
 
 /* AbstractNetwork.set_weights (models.py:72-73): bind the flat device buffer
- * (kept alive by the caller) and derive folded BatchNorm terms into d_derived. */
+ * (kept alive by the caller) and derive folded BatchNorm terms into d_derived.
+ * d_derived and every d_workspace / d_scratch below may come straight from hipMalloc: no call reads a word of them
+ * that it (or, for d_derived, this call) has not written; the padding words between the regions of d_derived are
+ * never read and keep whatever they held.  tests/poison_cases.py holds every entry to this on both builds. */
 int mzx_net_set_weights(mzx_net* net, const float* d_flat, int64_t n_floats,
                         float* d_derived, int64_t derived_floats, void* stream);
 

@@ -38,7 +38,22 @@ CASES = [
          A=18, S=41, per=False, alpha=1.0, vlw=1.0, seed=25),
 ]
 WIDE_UNSUPPORTED_S = 42
-BY_NAME = {c["name"]: c for c in CASES}
+# Shapes the fixture does not carry, held live to the restatement below in binary64 (check_live).
+LIVE_CASES = [
+    # wider than a wavefront everywhere: 72 inputs, an encoding of 70, 73 dynamics inputs with the action one-hot and hidden
+    # layers of 72 take the second `j += 64` pass of every row loop, not the logits alone.  72 is the width that stays inside
+    # the 160 KiB LDS budget: 37 530 floats of padded weights + 4 x 360 per wave of 40 960; hidden layers of 100 need 52 006
+    # floats for the weights alone and are refused (OVER64_UNSUPPORTED_WIDTH, tests/test_fc_train.py)
+    dict(name="b3_k3_over64", B=3, steps=3, obs=(1, 1, 72), stacked=0, enc=70, rep=[72], dyn=[72], rew=[72], val=[72],
+         pol=[72], A=3, S=2, per=False, alpha=0.5, vlw=1.0, seed=26),
+]
+OVER64_UNSUPPORTED_WIDTH = 100
+LIVE_CASES.append(
+    # every state has 0 < range < 1e-5 (the tiny_range recipe): the `scale += 1e-5` branch with arg-min != arg-max.  Nothing
+    # else has such a range, so a threshold of 1e-7 in place of 1e-5 passes every other case
+    dict(name="b3_k3_tiny_range", B=3, steps=3, obs=(1, 1, 4), stacked=0, enc=6, rep=[5], dyn=[5], rew=[5], val=[5], pol=[5], A=3,
+         S=2, per=False, alpha=0.5, vlw=1.0, seed=27, tiny_range=True))
+BY_NAME = {c["name"]: c for c in CASES + LIVE_CASES}
 
 
 def config_of(case, **kw):
@@ -83,7 +98,29 @@ def weights(case):
             out[key] = (rs.uniform(-1, 1, size=shape).astype(numpy.float32) * bound)
         else:
             out[key] = (rs.uniform(-1, 1, size=shape).astype(numpy.float32) * numpy.float32(0.5))
+    if case.get("tiny_range"):
+        tiny_range(out, len(case["rep"]), len(case["dyn"]))
     return out
+
+
+def amplified(case):
+    """The tensors whose gradient the tiny_range recipe amplifies by 1 / 1e-5 (train_cases_common.AMPLIFIED_ULPS)."""
+    if not case.get("tiny_range"):
+        return ()
+    return tuple(f"{name}.module.{2 * n}.{leaf}" for name, n in (("representation_network", len(case["rep"])),
+                                                                 ("dynamics_encoded_state_network", len(case["dyn"])))
+                 for leaf in ("weight", "bias"))
+
+
+def tiny_range(state, rep_layers, dyn_layers):
+    """The ``tiny_range`` recipe on a state_dict (numpy arrays or tensors, in place): the last layer of the representation
+    and dynamics networks gets weight x 1e-7 and bias 0, so every state is about 1e-7 to 3e-6, anchored at 0: 0 < range <
+    1e-5, the `scale += 1e-5` branch with arg-min != arg-max, which nothing else reaches (synthetic and trained states have
+    ranges of order 1 or exactly 0).  The gradients of those two layers are amplified by 1 / 1e-5: see ``amplified``."""
+    for name, n in (("representation_network", rep_layers), ("dynamics_encoded_state_network", dyn_layers)):
+        state[f"{name}.module.{2 * n}.weight"] *= 1e-7
+        state[f"{name}.module.{2 * n}.bias"] *= 0
+    return state
 
 
 batch = common.batch
@@ -174,6 +211,60 @@ def run_native(be, case, net=None):
     from mzx import trainer
     net = net if net is not None else network(be, case)
     return common.run_native(net, case, lambda logits: trainer.train_fc_gradients(net, batch(case), config_of(case), logits=logits))
+
+
+def is_bypassed(key):
+    return False
+
+
+def torch_step(case, dtype, device="cpu"):
+    """One training step of the restatement in ``dtype`` -> dict: the step-major logits, losses, decoded values and
+    ``grad/<key>`` per parameter (the layout of resnet_train_cases.torch_step)."""
+    model = load(FcNetwork(case), weights(case)).to(dtype).to(device)
+    observation, action, tv, tr, tp, weight, scale = batch(case)
+    t = lambda a: torch.tensor(a).to(dtype).to(device)
+    observation, tv, tr, tp, scale = t(observation), t(tv), t(tr), t(tp), t(scale)
+    weight = t(weight) if case["per"] else None
+    action = torch.tensor(action).long().to(device)
+    value, reward, policy, hidden = model.initial_inference(observation)
+    reward = reward.to(dtype)
+    values, rewards, policies = [value], [reward], [policy]
+    for i in range(1, action.shape[1]):
+        one_hot = torch.nn.functional.one_hot(action[:, i], model.A).to(dtype)
+        raw = model.dynamics_encoded_state_network(torch.cat((hidden, one_hot), dim=1))
+        reward = model.dynamics_reward_network(raw)
+        hidden = _unit_range(raw)
+        policy, value = model.prediction_policy_network(hidden), model.prediction_value_network(hidden)
+        hidden.register_hook(lambda grad: grad * 0.5)
+        values.append(value), rewards.append(reward), policies.append(policy)
+    loss, vl, rl, pl, _ = trainer_loss_cases.torch_loss_head(values, rewards, policies, tv, tr, tp, weight, scale, config_of(case))
+    loss.backward()
+    out = dict(loss=loss.item(), value_loss=vl.mean().item(), reward_loss=rl.mean().item(), policy_loss=pl.mean().item(),
+               value_logits=torch.stack(values).detach().cpu().numpy(), reward_logits=torch.stack(rewards).detach().cpu().numpy(),
+               policy_logits=torch.stack(policies).detach().cpu().numpy(),
+               pred=numpy.stack([trainer_loss_cases.torch_support_to_scalar(v.detach(), case["S"]).cpu().numpy().squeeze(-1)
+                                 for v in values], 1))
+    for key, p in model.named_parameters():
+        out["grad/" + key] = numpy.zeros(tuple(p.shape)) if p.grad is None else p.grad.detach().cpu().numpy().copy()
+    return out
+
+
+def check_live(be, case, report=print):
+    """The gates of ``check_case`` against the torch restatement run here in binary64 and float32 (shapes the fixture does
+    not carry), in the shape of resnet_train_cases.check_live; train_cases_common.check_against applies them with this module's floor."""
+    import sys
+    ref64, ref32 = torch_step(case, torch.float64), torch_step(case, torch.float32)
+    errors = {k: float(numpy.max(numpy.abs(ref32[k].astype(numpy.float64) - ref64[k]))) for k in ref64 if k.startswith("grad/")}
+    net = network(be, case)
+    got = run_native(be, case, net)
+    common.check_against(case, got, {h: ref32[f"{h}_logits"] for h in ("value", "reward", "policy")}, ref64, errors,
+                         {k: ref32[k] for k in LOSS_KEYS}, ref32["pred"], be, report, sys.modules[__name__],
+                         floor=PARAM_GRAD_ERROR_FLOOR, logit_gate=LOGIT_GATE)
+    again = run_native(be, case, net)
+    for key, value in got.items():
+        a, b = numpy.ascontiguousarray(value, numpy.float32), numpy.ascontiguousarray(again[key], numpy.float32)
+        assert numpy.array_equal(a.view(numpy.int32), b.view(numpy.int32)), key
+    return net, got
 
 
 LOGIT_GATE = 1e-4           # DESIGN.md section 2: the heads, against the reference's float32 results

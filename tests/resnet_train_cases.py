@@ -39,7 +39,15 @@ CASES = [
     dict(name="e_b3_k3_dead", B=3, steps=3, obs=(3, 3, 3), stacked=0, C=5, blocks=1, red=(2, 2, 2), rew=[4], val=[4], pol=[4], A=9,
          S=2, per=False, alpha=0.5, vlw=1.0, seed=32, dead_channel=3),
 ]
-BY_NAME = {c["name"]: c for c in CASES}
+# Shapes the fixture does not carry, held live to the restatement in binary64 (check_live).
+LIVE_CASES = [
+    # case b with one channel of the state between 0 and a few 1e-6 (the tiny_range recipe): 0 < range < 1e-5, the
+    # `scale += 1e-5` branch with arg-min != arg-max.  Nothing else has such a range -- planes are constant (range exactly
+    # 0) or of order 1 -- so a threshold of 1e-7 in place of 1e-5 passes every other case
+    dict(name="f_b3_k3_tiny_range", B=3, steps=3, obs=(3, 3, 3), stacked=0, C=5, blocks=1, red=(2, 2, 2), rew=[4], val=[4], pol=[4],
+         A=9, S=2, per=False, alpha=0.5, vlw=1.0, seed=32, tiny_channel=1),
+]
+BY_NAME = {c["name"]: c for c in CASES + LIVE_CASES}
 
 
 def config_of(case, **kw):
@@ -207,7 +215,33 @@ def weights(case):
         for net in ("representation_network", "dynamics_network"):
             out[f"{net}.module.resblocks.{last}.bn2.weight"][case["dead_channel"]] = 0.0
             out[f"{net}.module.resblocks.{last}.bn2.bias"][case["dead_channel"]] = -100.0
+    if "tiny_channel" in case:
+        tiny_range(out, case["blocks"], case["tiny_channel"])
     return out
+
+
+def amplified(case):
+    """The tensors whose gradient the tiny_range recipe amplifies by 1 / 1e-5 (train_cases_common.AMPLIFIED_ULPS)."""
+    if "tiny_channel" not in case:
+        return ()
+    return tuple(f"{net}.module.resblocks.0.bn2.{leaf}" for net in ("representation_network", "dynamics_network")
+                 for leaf in ("weight", "bias"))
+
+
+def tiny_range(state, blocks, channel):
+    """The ``tiny_range`` recipe on a state_dict (numpy arrays or tensors, in place): the first BatchNorm of the
+    representation and dynamics towers gets gamma 0, beta -1 on ``channel`` (0 behind the ReLU, so the blocks' residual adds
+    nothing), the last bn2 gamma 1e-6, beta 0: the channel of the state is relu(1e-6 x a normalised plane), 0 to a few 1e-6,
+    anchored at 0: 0 < range < 1e-5, the `scale += 1e-5` branch with arg-min != arg-max, which nothing else reaches.  One
+    block per tower (an earlier block's bn2 would put order-1 values into the channel).  The gradients of that bn2 are
+    amplified by 1 / 1e-5: see ``amplified``."""
+    assert blocks == 1
+    for net in ("representation_network", "dynamics_network"):
+        state[f"{net}.module.bn.weight"][channel] = 0.0
+        state[f"{net}.module.bn.bias"][channel] = -1.0
+        state[f"{net}.module.resblocks.0.bn2.weight"][channel] = 1e-6
+        state[f"{net}.module.resblocks.0.bn2.bias"][channel] = 0.0
+    return state
 
 
 batch = common.batch
@@ -333,60 +367,9 @@ def tensor_gate(ref_error):
 
 
 def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report=print, tables=THIS):
-    """The gates of one case.  ``ref64``: key -> binary64 arrays (losses, grad/<key>, stat/<key>); ``ref_errors``: key ->
-    the reference's own float32 error against binary64 on that tensor."""
-    name = case["name"]
-    failures = []
-    for head in ("value", "reward", "policy"):
-        ours, ref = got[f"{head}_logits"], want32_logits[head]
-        assert ours.shape == ref.shape, (head, ours.shape, ref.shape)
-        finite = numpy.isfinite(ref)
-        assert numpy.array_equal(ours[~finite], ref[~finite]), head
-        err = float(numpy.max(numpy.abs(ours[finite].astype(numpy.float64) - ref[finite]))) if finite.any() else 0.0
-        report(f"{name} {head} logits: error {err:.3e} against the reference float32, gate {LOGIT_GATE:.1e}")
-        if not err <= LOGIT_GATE:
-            failures.append(head)
-    for key in LOSS_KEYS:
-        mine, ref = abs(float(got[key]) - float(ref64[key])), abs(float(f32_losses[key]) - float(ref64[key]))
-        gate = max(4 * ref, trainer_loss_cases.LOSS_ERROR_FLOOR)
-        report(f"{name} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
-        if not mine <= gate:
-            failures.append(key)
-    logits = torch.from_numpy(got["value_logits"]).to(be.device).reshape(-1, 2 * case["S"] + 1)
-    pred = be.empty((logits.shape[0],), torch.float32)
-    be.lib.check(be.lib.mzx_support_to_scalar(be.ptr(logits), logits.shape[0], case["S"], be.ptr(pred), be.stream()))
-    pred = pred.cpu().numpy().reshape(case["steps"], case["B"]).T.copy()
-    want = numpy.abs(pred - tables.batch(case)[2]) ** case["alpha"]
-    assert want.dtype == numpy.float32
-    ulps = trainer_loss_cases.ulp_distance(want, got["priorities"])
-    report(f"{name} priorities: max ulp distance {ulps.max()} (alpha {case['alpha']})")
-    assert ulps.max() <= (0 if case["alpha"] == 1.0 else 1)
-    gap = numpy.abs(pred.astype(numpy.float64) - f32_pred)
-    report(f"{name} decoded value against the reference: {gap.max():.3e} (values up to {numpy.abs(pred).max():.2f})")
-    assert gap.max() <= trainer_loss_cases.DECODED_SCALAR_GATE
-    assert not numpy.isnan(got["grad_flat"]).any(), "d_grad_flat was not fully overwritten"
-    state = tables.weights(case)
-    worst = (0.0, None)
-    for key in tables.tensor_shapes(case):
-        if is_statistic(key):
-            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key      # exact zeros
-            kind, mine64 = "stat", got["stat/" + key]
-        else:
-            kind, mine64 = "grad", got["grad/" + key]
-        if tables.is_bypassed(key):        # never applied: exact-zero gradients, the statistics keep their bits
-            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
-            if is_statistic(key):
-                assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].reshape(-1).view(numpy.int32)), key
-        ref = float(ref_errors[f"{kind}/{key}"])
-        gate = tensor_gate(ref)
-        mine = float(numpy.max(numpy.abs(mine64.astype(numpy.float64).reshape(-1) - numpy.asarray(ref64[f"{kind}/{key}"]).reshape(-1))))
-        report(f"{name} {kind} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
-        if 4 * ref < PARAM_GRAD_ERROR_FLOOR and mine > worst[0]:
-            worst = (mine, key)
-        if not mine <= gate:
-            failures.append(key)
-    report(f"{name} largest error on a tensor that needs the floor: {worst[0]:.3e} ({worst[1]})")
-    assert not failures, failures
+    """The gates of one case (train_cases_common.check_against) with this module's floor and head gate."""
+    common.check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report, tables,
+                         floor=PARAM_GRAD_ERROR_FLOOR, logit_gate=LOGIT_GATE)
 
 
 def check_case(be, case, gold, report=print, tables=THIS):

@@ -32,6 +32,20 @@ def test_logits_losses_priorities_gradients(be, gold, case):
     cases.check_case(be, case, gold)
 
 
+@pytest.mark.parametrize("case", cases.LIVE_CASES, ids=lambda c: c["name"])
+def test_live_case_against_the_restatement(be, case):
+    """Shapes the fixture does not carry (wider than a wavefront in every row loop), against the restatement in binary64."""
+    cases.check_live(be, case)
+
+
+def test_over64_with_hidden_layers_of_100_is_beyond_the_lds_budget(be):
+    case = dict(cases.BY_NAME["b3_k3_over64"])
+    assert cases.network(be, case).train_fc_supported(case["B"], case["steps"])
+    for k in ("rep", "dyn", "rew", "val", "pol"):
+        case[k] = [cases.OVER64_UNSUPPORTED_WIDTH]
+    assert not cases.network(be, case).train_fc_supported(case["B"], case["steps"])
+
+
 def test_two_sgd_momentum_steps(be, gold):
     cases.check_sgd(be, cases.BY_NAME["b5_k4_stacked"], gold)
 

@@ -36,6 +36,11 @@ def test_logits_losses_priorities_gradients(be, gold, case):
     assert next(net.parameters()).grad.is_cuda
 
 
+@pytest.mark.parametrize("case", cases.LIVE_CASES, ids=lambda c: c["name"])
+def test_live_case_against_the_restatement(be, case):
+    cases.check_live(be, case)
+
+
 def test_two_sgd_momentum_steps(be, gold):
     cases.check_sgd(be, cases.BY_NAME["b5_k4_stacked"], gold)
 

@@ -94,6 +94,14 @@ def test_network_heads_within_tolerance(backend, name, engine):
         assert torch.equal(back[k], v)
 
 
+@pytest.mark.parametrize("kind,mode", [("fc", None), ("resnet", None), ("resnet", 0), ("resnet", 3)],
+                         ids=["fc", "resnet-fused", "resnet-per-operator", "resnet-streamed"])
+def test_tiny_range_states_within_tolerance(backend, kind, mode):
+    """States of range between 0 and 1e-5 (test_hostcheck_search.check_tiny_range): the `scale += 1e-5` branch of the
+    min-max scaling with a non-zero range, on every inference engine, against net_oracle within 1e-4."""
+    common.check_tiny_range(backend, kind, mode, TOL)
+
+
 @pytest.mark.parametrize("mode", ["generic", "fused"])
 @pytest.mark.parametrize("name", ["cartpole", "tictactoe", "connect4", "cartpole_ties", "tictactoe_custom",
                                   "cartpole_custom", "lunarlander_pretrained"])

@@ -39,6 +39,12 @@ def test_logits_losses_priorities_gradients_statistics(be, gold, case):
     assert next(net.parameters()).grad.is_cuda
 
 
+@pytest.mark.parametrize("case", cases.LIVE_CASES, ids=lambda c: c["name"])
+def test_live_case_against_the_restatement(be, case):
+    """Shapes the fixture does not carry (a state plane of range between 0 and 1e-5), against the restatement in binary64."""
+    cases.check_live(be, case)
+
+
 def test_two_sgd_momentum_steps_weights_and_buffers(be, gold):
     cases.check_sgd(be, cases.BY_NAME["c_b5_k4_stacked"], gold)
 

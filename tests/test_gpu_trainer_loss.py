@@ -43,6 +43,11 @@ def test_loss_gradients_priorities(be, gold, case):
         assert numpy.array_equal(numpy.asarray(plain[key]), numpy.asarray(got[key])), key
 
 
+@pytest.mark.parametrize("case", cases.LIVE_CASES, ids=lambda c: c["name"])
+def test_live_case_against_the_restatement(be, case):
+    cases.check_live_case(be, case)
+
+
 def test_muzero_loss_on_a_side_stream(be):
     case = cases.CASES[3]
     cfg = cases.config_of(case)

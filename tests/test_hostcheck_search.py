@@ -182,3 +182,75 @@ def test_arena_contents_need_not_persist(backend):
     second = run()
     assert numpy.array_equal(first.visit_counts, second.visit_counts)
     assert numpy.array_equal(first.root_values, second.root_values)
+
+
+# ---- states whose range lies between 0 and the 1e-5 of the min-max scaling (the `tiny_range` weight recipes of
+# fc_train_cases / resnet_train_cases): synthetic and trained weights give ranges of order 1 or exactly 0, never in between,
+# so nothing else tells `scale < 1e-5` from a smaller threshold.
+
+TINY_RANGE = {"fc": lambda: configs.cartpole(), "resnet": lambda: configs.tictactoe(blocks=1)}
+
+
+def tiny_range_weights(cfg, net, seed=17):
+    import fc_train_cases
+    import resnet_train_cases
+    sd = {k: v.clone() for k, v in synthetic.fill_state_dict(net.state_dict(), seed).items()}
+    if cfg.network == "resnet":
+        resnet_train_cases.tiny_range(sd, cfg.blocks, 1)
+        for tower in ("representation_network", "dynamics_network"):      # inference normalises with the running statistics:
+            sd[f"{tower}.module.resblocks.0.bn2.running_mean"][1] = 0.0    # centred, so that the ReLU keeps part of the plane
+            sd[f"{tower}.module.resblocks.0.bn2.running_var"][1] = 1.0
+            sd[f"{tower}.module.resblocks.0.bn2.weight"][1] = 1e-5         # (these convolutions give planes of order 0.1)
+    else:
+        fc_train_cases.tiny_range(sd, len(cfg.fc_representation_layers), len(cfg.fc_dynamics_layers))
+    return sd
+
+
+def check_tiny_range(backend, kind, mode=None, tolerance=1e-4):
+    """initial_inference and two recurrent steps of 5 samples against net_oracle in float32, every head and the hidden state
+    within ``tolerance``; the oracle's own float32 run is held to its binary64 run at the same bound first, and the states
+    are shown to have the ranges the recipe is for."""
+    from oracle import net_oracle
+    cfg = TINY_RANGE[kind]()
+    net = models.MuZeroNetwork(cfg, _backend=backend)
+    sd = tiny_range_weights(cfg, net)
+    net.set_weights(sd)
+    if mode is not None:
+        net.set_mode(mode)
+    o32, o64 = net_oracle.make_oracle_network(cfg, sd), net_oracle.make_oracle_network(cfg, sd, torch.float64)
+    B, A = 5, len(cfg.action_space)
+    obs = torch.tensor(numpy.asarray(synthetic.observations(B, net.input_shape, seed=2), numpy.float32))
+    acts = [torch.tensor(numpy.random.RandomState(s).randint(0, A, size=(B, 1))) for s in (3, 4)]
+    with torch.no_grad():
+        want, want64 = [o32.initial_inference(obs)], [o64.initial_inference(obs.double())]
+        for a in acts:
+            want.append(o32.recurrent_inference(want[-1][3], a))
+            want64.append(o64.recurrent_inference(want64[-1][3], a))
+    got = [net.initial_inference(obs)]
+    for a in acts:
+        got.append(net.recurrent_inference(got[-1][3], a.reshape(-1)))
+    # the recipe does what it is for: before the scaling, some row / plane of every state has 0 < range < 1e-5
+    with torch.no_grad():
+        if kind == "fc":
+            raw = net_oracle._mlp(o64.sd, "representation_network.module.", obs.double().view(B, -1))
+            span = raw.max(1)[0] - raw.min(1)[0]
+        else:
+            raw = o64.representation_unscaled(obs.double()).flatten(2)
+            span = (raw.max(2)[0] - raw.min(2)[0])[:, 1]
+    print("ranges before the scaling:", span.numpy())
+    assert (span < 1e-5).all() and (span > 1.2e-7).sum() >= 3, span      # (a plane the ReLU clears altogether has range 0)
+    for step, (g, w, w64) in enumerate(zip(got, want, want64)):
+        for key, a, b, c in zip(("value", "reward", "policy", "hidden"), g, w, w64):
+            a, b, c = a.cpu().numpy().reshape(B, -1), b.numpy().reshape(B, -1), c.numpy().reshape(B, -1)
+            finite = numpy.isfinite(b)
+            assert numpy.array_equal(a[~finite], b[~finite]), (kind, step, key)
+            own = numpy.abs(b[finite] - c[finite]).max()
+            err = numpy.abs(a[finite] - b[finite]).max()
+            print(f"tiny_range {kind} mode {mode} step {step} {key}: {err:.3e} (the oracle's float32 against binary64: {own:.3e})")
+            assert own < tolerance, (kind, step, key, own)
+            assert err < tolerance, (kind, mode, step, key, err)
+
+
+@pytest.mark.parametrize("kind", ["fc", "resnet"])
+def test_tiny_range_states_within_tolerance(backend, kind):
+    check_tiny_range(backend, kind)

@@ -58,6 +58,12 @@ def test_loss_gradients_priorities(be, gold, case):
         assert numpy.array_equal(numpy.asarray(plain[key]), numpy.asarray(got[key])), key
 
 
+@pytest.mark.parametrize("case", cases.LIVE_CASES, ids=lambda c: c["name"])
+def test_live_case_against_the_restatement(be, case):
+    """support_size 0 (one bin): target rows, losses and logit gradients against the loss head restated in torch."""
+    cases.check_live_case(be, case)
+
+
 def _tensors(x, device="cpu"):
     t = lambda a: None if a is None else torch.from_numpy(a).to(device)
     return {k: t(v) for k, v in x.items()}

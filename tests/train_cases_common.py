@@ -105,20 +105,34 @@ REQUIRED = ("d_flat", "d_observation", "d_action", "d_target_value", "d_target_r
 OUTPUTS = {"fc": ("grad", "losses", "priorities", "scratch"), "resnet": ("grad", "losses", "priorities", "scratch", "stats")}
 
 
-def step_io(be, case, net, keep, kind, device="cpu"):
+def step_io(be, case, net, keep, kind, device="cpu", fill=7.0, whole=False):
     """A complete mzx_train_fc_io / mzx_train_resnet_io over tensors on ``device``, outputs pre-filled with 7 -> (io, the
-    tensors by name; ``keep`` holds them alive)."""
+    tensors by name; ``keep`` holds them alive).  ``fill``: the number the outputs and the scratch start from, or a function
+    ``fill(name, tensor)`` that fills each of them in place on ``device`` (tests/poison_cases.py).  ``whole``: also the
+    optional members of the struct -- the three logit outputs and, for a case with PER, the weights."""
     observation, action, tv, tr, tp, weight, scale = batch(case)
     B, steps = case["B"], case["steps"]
     nbytes = int(getattr(be.lib, f"mzx_train_{kind}_scratch_bytes")(net.handle, B, steps))
     assert nbytes > 0
+    number = 7.0 if callable(fill) else fill
     t = dict(observation=torch.from_numpy(observation).reshape(B, -1).contiguous(), action=torch.from_numpy(action).to(torch.int32),
              tv=torch.from_numpy(tv), tr=torch.from_numpy(tr), tp=torch.from_numpy(tp), scale=torch.from_numpy(scale),
-             grad=torch.full((net.num_params,), 7.0), losses=torch.full((4,), 7.0), priorities=torch.full((B, steps), 7.0),
-             scratch=torch.full((nbytes // 4,), 7.0))
+             grad=torch.full((net.num_params,), number), losses=torch.full((4,), number), priorities=torch.full((B, steps), number),
+             scratch=torch.full((nbytes // 4,), number))
     if kind == "resnet":
-        t["stats"] = torch.full((int(be.lib.mzx_train_resnet_stat_floats(net.handle)),), 7.0)
+        t["stats"] = torch.full((int(be.lib.mzx_train_resnet_stat_floats(net.handle)),), number)
+    filled = OUTPUTS[kind]
+    if whole:
+        width = net.full_support_size
+        t.update(value_logits=torch.full((steps, B, width), number), reward_logits=torch.full((steps, B, width), number),
+                 policy_logits=torch.full((steps, B, case["A"]), number))
+        filled = filled + ("value_logits", "reward_logits", "policy_logits")
+        if weight is not None:
+            t["weight"] = torch.from_numpy(weight)
     t = {k: v.to(device) for k, v in t.items()}
+    if callable(fill):
+        for key in filled:
+            fill(key, t[key])
     keep.append(t)
     io = _lib.TrainFcIO() if kind == "fc" else _lib.TrainResnetIO()
     io.d_flat, io.d_observation, io.d_action = net.flat_weights().data_ptr(), t["observation"].data_ptr(), t["action"].data_ptr()
@@ -129,6 +143,9 @@ def step_io(be, case, net, keep, kind, device="cpu"):
     io.d_scratch, io.scratch_bytes = t["scratch"].data_ptr(), nbytes
     if kind == "resnet":
         io.d_stats = t["stats"].data_ptr()
+    if whole:
+        io.d_value_logits, io.d_reward_logits, io.d_policy_logits = (t[k + "_logits"].data_ptr() for k in ("value", "reward", "policy"))
+        io.d_weight = t["weight"].data_ptr() if "weight" in t else None
     return io, t
 
 
@@ -223,3 +240,85 @@ def check_bits(be, case, tables, section, family):
     have = bits.digests(tables.run_native(be, case), family)
     differs = [key for key in pinned if have[key] != want[key]]
     assert not differs, f"{case['name']}: {differs[0]} differs from the bits recorded at {section['commit']} (all: {differs})"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The gates of a step against a reference run, for both network kinds (fc_train_cases / resnet_train_cases pass their own
+# floor and head gate; ``tables`` is the case module: batch, weights, tensor_shapes, is_bypassed, LOSS_KEYS and, where a
+# case has them, amplified).
+
+# A tensor whose gradient a `tiny_range` recipe amplifies (``tables.amplified(case)``): the state is divided by range + 1e-5
+# with range << 1e-5, so the gradient of the layer that produces it is 1e5 times the gradient of the state -- values of order
+# 1e3 to 1e4, of which any float32 run gets a handful of units in the last place wrong: absolute errors of 1e-3, far above
+# the absolute floor, and the reference's own float32 error there is a draw from the same noise (zero when it rounds
+# luckily), no yardstick on its own.  For such a tensor the absolute floor is replaced by one from the precision of the
+# format: AMPLIFIED_ULPS float32 units in the last place of its largest element -- the sum runs over at most 81 rows x positions here, each term a chain of about ten
+# rounded operations behind the division, and rounding errors of such a sum grow with the square root of their number:
+# sqrt(81 x 10) = 28 half-units, rounded up to a power of two.  A threshold of 1e-7 in place of 1e-5 moves these gradients
+# by their own size, thousands of times this gate.
+AMPLIFIED_ULPS = 32
+
+
+def check_against(case, got, want32_logits, ref64, ref_errors, f32_losses, f32_pred, be, report, tables, floor, logit_gate):
+    """The gates of one case.  ``ref64``: key -> binary64 arrays (losses, grad/<key>, stat/<key>); ``ref_errors``: key ->
+    the reference's own float32 error against binary64 on that tensor."""
+    import trainer_loss_cases
+    name = case["name"]
+    failures = []
+    for head in ("value", "reward", "policy"):
+        ours, ref = got[f"{head}_logits"], want32_logits[head]
+        assert ours.shape == ref.shape, (head, ours.shape, ref.shape)
+        finite = numpy.isfinite(ref)
+        assert numpy.array_equal(ours[~finite], ref[~finite]), head
+        err = float(numpy.max(numpy.abs(ours[finite].astype(numpy.float64) - ref[finite]))) if finite.any() else 0.0
+        report(f"{name} {head} logits: error {err:.3e} against the reference float32, gate {logit_gate:.1e}")
+        if not err <= logit_gate:
+            failures.append(head)
+    for key in tables.LOSS_KEYS:
+        mine, ref = abs(float(got[key]) - float(ref64[key])), abs(float(f32_losses[key]) - float(ref64[key]))
+        gate = max(4 * ref, trainer_loss_cases.LOSS_ERROR_FLOOR)
+        report(f"{name} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
+        if not mine <= gate:
+            failures.append(key)
+    logits = torch.from_numpy(got["value_logits"]).to(be.device).reshape(-1, 2 * case["S"] + 1)
+    pred = be.empty((logits.shape[0],), torch.float32)
+    be.lib.check(be.lib.mzx_support_to_scalar(be.ptr(logits), logits.shape[0], case["S"], be.ptr(pred), be.stream()))
+    pred = pred.cpu().numpy().reshape(case["steps"], case["B"]).T.copy()
+    want = numpy.abs(pred - tables.batch(case)[2]) ** case["alpha"]
+    assert want.dtype == numpy.float32
+    ulps = trainer_loss_cases.ulp_distance(want, got["priorities"])
+    report(f"{name} priorities: max ulp distance {ulps.max()} (alpha {case['alpha']})")
+    assert ulps.max() <= (0 if case["alpha"] == 1.0 else 1)
+    gap = numpy.abs(pred.astype(numpy.float64) - f32_pred)
+    report(f"{name} decoded value against the reference: {gap.max():.3e} (values up to {numpy.abs(pred).max():.2f})")
+    assert gap.max() <= trainer_loss_cases.DECODED_SCALAR_GATE
+    assert not numpy.isnan(got["grad_flat"]).any(), "d_grad_flat was not fully overwritten"
+    state = tables.weights(case)
+    amplified = tables.amplified(case) if hasattr(tables, "amplified") else ()
+    worst = (0.0, None)
+    for key in tables.tensor_shapes(case):
+        if is_statistic(key):
+            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key      # exact zeros
+            kind, mine64 = "stat", got["stat/" + key]
+        else:
+            kind, mine64 = "grad", got["grad/" + key]
+        if tables.is_bypassed(key):        # never applied: exact-zero gradients, the statistics keep their bits
+            assert numpy.array_equal(got["grad/" + key], numpy.zeros_like(got["grad/" + key])), key
+            if is_statistic(key):
+                assert numpy.array_equal(got["stat/" + key].view(numpy.int32), state[key].reshape(-1).view(numpy.int32)), key
+        ref = float(ref_errors[f"{kind}/{key}"])
+        want64 = numpy.asarray(ref64[f"{kind}/{key}"]).reshape(-1)
+        gate = max(4 * ref, floor)
+        mine = float(numpy.max(numpy.abs(mine64.astype(numpy.float64).reshape(-1) - want64)))
+        if kind == "grad" and key in amplified:
+            gate = max(gate, AMPLIFIED_ULPS * 2.0 ** -23 * float(numpy.abs(want64).max()))
+            report(f"{name} grad {key}: error {mine:.3e}, reference float32 error {ref:.3e}, largest element "
+                   f"{numpy.abs(want64).max():.3e}, gate {gate:.3e} (floor: {AMPLIFIED_ULPS} units in its last place; amplified by 1 / 1e-5)")
+        else:
+            report(f"{name} {kind} {key}: error {mine:.3e}, reference float32 error {ref:.3e}, gate {gate:.3e}")
+            if 4 * ref < floor and mine > worst[0]:
+                worst = (mine, key)
+        if not mine <= gate:
+            failures.append(key)
+    report(f"{name} largest error on a tensor that needs the floor: {worst[0]:.3e} ({worst[1]})")
+    assert not failures, failures

@@ -20,6 +20,13 @@ CASES = [
     dict(name="b130_k6_s10_a7", B=130, steps=6, S=10, A=7, per=True, alpha=0.6, vlw=0.25, seed=16),
 ]
 
+# Cases with no rows in the fixture: held live to the restatement below (torch_loss_head, torch_scalar_to_support).
+#   support_size 0: one bin.  The reference's second scatter_ lands on the first one's bin and overwrites it with the masked
+#   (index 0, weight 0), so every target row is [0] and the value and reward losses and their gradients are exact zeros.
+LIVE_CASES = [
+    dict(name="b3_k3_s0_a3", B=3, steps=3, S=0, A=3, per=True, alpha=0.5, vlw=0.25, seed=17),
+]
+
 
 class ieee_sqrt:
     """
@@ -333,3 +340,48 @@ def check_case(be, case, gold, report=print):
     report(f"{name} decoded value against the reference: {gap.max():.3e} (values up to {numpy.abs(pred).max():.2f})")
     assert gap.max() <= DECODED_SCALAR_GATE
     return x, got
+
+
+def check_live_case(be, case, report=print):
+    """A case of LIVE_CASES: the target rows of mzx_scalar_to_support bit for bit against torch_scalar_to_support in float32
+    (correctly rounded square root), the loss head against torch_loss_head in binary64 with the yardstick of check_case --
+    4 x the error of the restatement's own float32 run, or the floors."""
+    from mzx import trainer
+    x = inputs(case)
+    S, steps = case["S"], case["steps"]
+    for key in ("value", "reward"):
+        t = torch.from_numpy(x[f"target_{key}"])
+        with ieee_sqrt():
+            want = torch_scalar_to_support(t, S).numpy()
+        rows = trainer.scalar_to_support(t.to(be.device), S, backend=be).cpu().numpy()
+        assert rows.shape == want.shape == t.shape + (2 * S + 1,) and rows.dtype == numpy.float32
+        assert numpy.array_equal(rows.view(numpy.int32), want.view(numpy.int32)), key
+        if S == 0:
+            assert not rows.any()
+
+    def restated(dtype):
+        t = {k: None if v is None else torch.from_numpy(v).to(dtype) for k, v in x.items()}
+        heads = [[t[k][i].clone().requires_grad_() for i in range(steps)] for k in ("value", "reward", "policy")]
+        loss, vl, rl, pl, _ = torch_loss_head(*heads, t["target_value"], t["target_reward"], t["target_policy"], t["weight"],
+                                              t["gradient_scale"], config_of(case))
+        loss.backward()
+        grads = [numpy.stack([numpy.zeros(h.shape) if h.grad is None else h.grad.numpy() for h in head]) for head in heads]
+        return dict(loss=loss.item(), value_loss=vl.mean().item(), reward_loss=rl.mean().item(), policy_loss=pl.mean().item(),
+                    grad_value=grads[0], grad_reward=grads[1], grad_policy=grads[2])
+    ref64, ref32 = restated(torch.float64), restated(torch.float32)
+    got = run_abi(be, case, x)
+    failures = []
+    for key in YARDSTICK_KEYS:
+        mine = float(numpy.max(numpy.abs(numpy.asarray(got[key], numpy.float64) - ref64[key])))
+        ref = float(numpy.max(numpy.abs(numpy.asarray(ref32[key], numpy.float64) - ref64[key])))
+        floor = GRAD_ERROR_FLOOR if key.startswith("grad") else LOSS_ERROR_FLOOR
+        report(f"{case['name']} {key}: error {mine:.3e}, restatement's float32 error {ref:.3e}, gate {max(4 * ref, floor):.3e}")
+        if not mine <= max(4 * ref, floor):
+            failures.append(key)
+    assert not failures, failures
+    if S == 0:
+        for key in ("value_loss", "reward_loss"):
+            assert got[key] == 0.0 and ref64[key] == 0.0, key
+        for key in ("grad_value", "grad_reward"):
+            assert not numpy.asarray(got[key]).any() and not ref64[key].any(), key
+    return got
