@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MZX_ABI_VERSION 7
+#define MZX_ABI_VERSION 8
 
 #define MZX_OK 0
 #define MZX_ERR_INVALID (-1)      /* bad argument / unsupported configuration */
@@ -994,6 +994,108 @@ int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, floa
  * ------------------------------------------------------------------------- */
 int mzx_net_set_train_stem(mzx_net* net, int on);
 int mzx_net_train_stem(const mzx_net* net);
+
+/* ------------------------------------------------------------------------- *
+ * The optimizer step over the flat parameter buffer (csrc/mzx_optim.h): torch.optim.Adam (no amsgrad, no maximize) and
+ * torch.optim.SGD (dampening 0, no nesterov) as ONE elementwise launch, no atomics: the same bits on every run.
+ * Only the LIVE SPANS of the buffer are visited: h_spans [num_spans][2] holds (offset, count) pairs in elements (count
+ * 0 is allowed).  Outside them the parameter, the gradient and the state arrays are neither read nor written (a network's
+ * running_mean / running_var, the tensors a downsample stem bypasses).  The spans are cut into chunks of at most
+ * MZX_OPTIM_CHUNK elements at absolute multiples of that size, one wavefront each: mzx_optim_chunks writes the chunk
+ * table (the same pairs) to HOST memory and returns how many chunks there are (h_chunks may be NULL or too short for
+ * cap pairs: then nothing is written beyond cap, the count is still returned; MZX_ERR_INVALID for a bad table).  The
+ * caller keeps a DEVICE copy of it, d_chunks [num_chunks][2], built once per network.
+ *
+ * The arithmetic is defined here.  Every operation is IEEE binary32 with gradual underflow, nothing is contracted, `/`
+ * and sqrt are correctly rounded.  The caller computes the scalars in binary64 as torch does; the library rounds each to
+ * binary32 once.  With g' = g + weight_decay * p (just g when weight_decay == 0):
+ *   Adam, step count t >= 1:   m = m + (g' - m) * one_minus_beta1
+ *                              v = v * beta2 + (one_minus_beta2 * g') * g'
+ *                              den = sqrt(v) / bias_correction2_sqrt + eps
+ *                              p = p + (-step_size) * (m / den)
+ *     with step_size = lr / (1 - beta1 ** t) and bias_correction2_sqrt = (1 - beta2 ** t) ** 0.5; d_state1 = exp_avg (m),
+ *     d_state2 = exp_avg_sq (v).
+ *   SGD:  momentum == 0:  p = p + (-lr) * g'  (no state array)
+ *         otherwise       buf = g' when first_step (torch: the buffer does not exist yet; it is written, never read),
+ *                         else buf = buf * momentum + g';  p = p + (-lr) * buf;  d_state1 = momentum_buffer.
+ * 16-byte loads and stores where the alignment of the arrays and of a chunk allows.  Adam moves 28 bytes per element,
+ * SGD with momentum 20.
+ * mzx_optim_step returns MZX_ERR_INVALID -- before anything is launched -- for a null required pointer, an unknown kind,
+ * a span outside [0, n) or two spans that overlap, t < 1, momentum != 0 without d_state1, and a num_chunks that is not
+ * what h_spans makes.
+ * ------------------------------------------------------------------------- */
+#define MZX_OPTIM_CHUNK 1024
+#define MZX_OPTIM_ADAM 0
+#define MZX_OPTIM_SGD 1
+typedef struct mzx_optim_io {
+  int32_t kind;                    /* MZX_OPTIM_ADAM / MZX_OPTIM_SGD */
+  int32_t first_step;              /* SGD with momentum: the first step */
+  int64_t t;                       /* the step count of this step, from 1 */
+  float* d_param;                  /* [n] */
+  const float* d_grad;             /* [n] */
+  float* d_state1;                 /* [n] exp_avg / momentum_buffer (nullable for SGD without momentum) */
+  float* d_state2;                 /* [n] exp_avg_sq (Adam) */
+  int64_t n;
+  const int64_t* h_spans;          /* host [num_spans][2] */
+  const int64_t* d_chunks;         /* device [num_chunks][2] (mzx_optim_chunks of h_spans) */
+  int32_t num_spans, num_chunks;
+  double weight_decay;
+  double lr, momentum;                                                             /* SGD */
+  double one_minus_beta1, beta2, one_minus_beta2, eps, step_size, bias_correction2_sqrt;      /* Adam */
+} mzx_optim_io;
+int64_t mzx_optim_chunks(const int64_t* h_spans, int32_t num_spans, int64_t n, int64_t* h_chunks, int64_t cap);
+int mzx_optim_step(const mzx_optim_io* io, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Whole training steps queued by ONE call (csrc/mzx_train_chain.h; mzx.trainer.train_steps): num_steps times, on the one
+ * stream and in this order,
+ *   mzx_replay_sample            call counter first_call + i; seed, total_samples and the slot table as the caller left them
+ *   mzx_replay_batch             observation and targets of the drawn samples
+ *   a conversion launch          value / reward / policy f64 -> f32, gradient scale i64 -> f32 (round-to-nearest-even),
+ *                                action i64 -> i32: what the Python path converts with torch
+ *   mzx_train_fc_step or mzx_train_resnet_step   (by the network's kind) reading d_flat, writing d_grad_flat, the four
+ *                                losses of step i to d_losses[i][0 .. 3]
+ *   the launch of mzx_optim_step   `optim` with t = optim.t + i, first_step only at i == 0, and lr = h_lr[i] (SGD) or
+ *                                step_size = h_step_size[i], bias_correction2_sqrt = h_bias_correction2_sqrt[i] (Adam):
+ *                                host arrays [num_steps] of binary64 scalars the CALLER computes (the library stays
+ *                                stateless); optim.d_param must be d_flat and optim.d_grad d_grad_flat
+ *   mzx_train_resnet_commit_stats   for a residual network
+ *   mzx_replay_update_priorities    with per
+ * and behind the last step mzx_net_set_weights(net, d_flat, ..., d_derived, ...) ONCE: the training kernels read the flat
+ * buffer, never the derived one, so a search running beside the chain sees re-folded BatchNorm terms at the granularity
+ * of a chain.  The chain calls the functions those entries call; it computes what calling them one by one computes, bit
+ * for bit.  No graph capture: plain back-to-back queueing.  Nothing synchronises.
+ * d_workspace: mzx_train_chain_scratch_bytes(net, batch, steps) bytes (steps = num_unroll_steps + 1), 256-byte aligned,
+ * the caller's, reusable from call to call; its contents mean nothing between calls.  0 bytes: the network's step does
+ * not run this shape (mzx_train_chain_supported: 1 / 0).  sampler->raw_capacity >= batch with per.
+ * MZX_ERR_INVALID before anything is queued: a null required pointer, num_steps / batch < 1, an unsupported network or
+ * shape, a pool whose stacked observation is not the network's input, a short or misaligned workspace, a short derived
+ * buffer, and every refusal of mzx_optim_step for each of the steps.
+ * ------------------------------------------------------------------------- */
+typedef struct mzx_train_chain_io {
+  const mzx_replay_pool* pool;
+  const mzx_replay_sampler* sampler;
+  uint64_t seed, first_call;
+  int64_t total_samples;
+  int32_t per, num_unroll_steps, stacked_observations, num_actions;
+  const int32_t* d_action_space;   /* nullable, as mzx_replay_sample_io */
+  int32_t batch, num_steps;
+  double value_loss_weight, per_alpha;
+  float* d_flat;
+  float* d_grad_flat;
+  mzx_optim_io optim;
+  const double* h_lr;                       /* [num_steps], SGD */
+  const double* h_step_size;                /* [num_steps], Adam */
+  const double* h_bias_correction2_sqrt;    /* [num_steps], Adam */
+  float* d_losses;                 /* [num_steps][4] */
+  float* d_derived;
+  int64_t derived_floats;
+  void* d_workspace;
+  int64_t workspace_bytes;
+} mzx_train_chain_io;
+int mzx_train_chain_supported(const mzx_net* net, int32_t batch, int32_t steps);
+int64_t mzx_train_chain_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps);
+int mzx_train_chain(mzx_net* net, const mzx_train_chain_io* io, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Games that step NATIVELY for a whole shard (host side, no GPU; csrc/mzx_games.h): the plugin surface of

@@ -12,6 +12,7 @@
 #include "mzx_draws.h"
 #include "mzx_games_device.h"
 #include "mzx_obs.h"
+#include "mzx_optim.h"
 #include "mzx_replay.h"
 #include "mzx_resident.h"
 #include "mzx_rng.h"
@@ -20,6 +21,7 @@
 #include "mzx_trainer.h"
 #include "mzx_train_fc.h"
 #include "mzx_train_resnet.h"
+#include "mzx_train_chain.h"
 #include "mzx_train_step.h"
 #include "mzx_tree_carry.h"
 #ifndef MZX_HOSTCHECK
@@ -1634,6 +1636,134 @@ int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, floa
     at += 2 * (int64_t)b.channels;
   }
   return MZX_OK;
+}
+
+// ------------------------------------------------------------- the optimizer step over the flat buffer (csrc/mzx_optim.h)
+
+int64_t mzx_optim_chunks(const int64_t* h_spans, int32_t num_spans, int64_t n, int64_t* h_chunks, int64_t cap) {
+  if (!optim_spans_ok("mzx_optim_chunks", h_spans, num_spans, n)) return MZX_ERR_INVALID;
+  int64_t at = 0;
+  return optim_cut_chunks(h_spans, num_spans, [&](int64_t off, int64_t count) {
+    if (h_chunks && at < cap) { h_chunks[2 * at] = off; h_chunks[2 * at + 1] = count; }
+    ++at;
+  });
+}
+
+int mzx_optim_step(const mzx_optim_io* io, void* stream) {
+  if (const int rc = optim_check(io)) return rc;
+  MZX_TRY_LAUNCH(optim_launch(io, (stream_t)stream));
+  return MZX_OK;
+}
+
+// ------------------------------------------------------------- whole training steps behind one call (csrc/mzx_train_chain.h)
+
+static int64_t chain_step_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps) {
+  if (!net) return 0;
+  return net->cfg.network == 1 ? mzx_train_resnet_scratch_bytes(net, batch, steps) : mzx_train_fc_scratch_bytes(net, batch, steps);
+}
+
+int mzx_train_chain_supported(const mzx_net* net, int32_t batch, int32_t steps) {
+  if (!net) return 0;
+  return net->cfg.network == 1 ? mzx_train_resnet_supported(net, batch, steps) : mzx_train_fc_supported(net, batch, steps);
+}
+
+int64_t mzx_train_chain_scratch_bytes(const mzx_net* net, int32_t batch, int32_t steps) {
+  const int64_t step_bytes = chain_step_scratch_bytes(net, batch, steps);
+  if (step_bytes <= 0) return 0;
+  return chain_plan(net, batch, steps, step_bytes, net->cfg.network == 1 ? rtn_stat_floats(net) : 0).total_bytes;
+}
+
+int mzx_train_chain(mzx_net* net, const mzx_train_chain_io* io, void* stream) {
+  const char* who = "mzx_train_chain";
+  if (!net || !io) { set_error("%s: null argument", who); return MZX_ERR_INVALID; }
+  if (io->num_steps < 1 || io->batch < 1 || io->num_unroll_steps < 0) {
+    set_error("%s: num_steps %d and batch %d must be positive, num_unroll_steps %d not negative", who, io->num_steps, io->batch, io->num_unroll_steps);
+    return MZX_ERR_INVALID;
+  }
+  if (!io->pool || !io->sampler || !io->d_flat || !io->d_grad_flat || !io->d_losses || !io->d_derived || !io->d_workspace) {
+    set_error("%s: missing buffer", who);
+    return MZX_ERR_INVALID;
+  }
+  const bool residual = net->cfg.network == 1, adam = io->optim.kind == MZX_OPTIM_ADAM;
+  const int32_t B = io->batch, steps = io->num_unroll_steps + 1;
+  if (!mzx_train_chain_supported(net, B, steps)) {
+    set_error("%s: mzx_train_%s_step does not run this network at batch %d x %d steps", who, residual ? "resnet" : "fc", B, steps);
+    return MZX_ERR_INVALID;
+  }
+  const mzx_replay_pool& pool = *io->pool;
+  const int64_t planes = (int64_t)pool.channels * (io->stacked_observations + 1) + io->stacked_observations;
+  if (io->stacked_observations < 0 || planes * pool.height * pool.width != net->input_size || pool.action_space_size != net->cfg.action_space_size ||
+      io->num_actions != pool.action_space_size) {
+    set_error("%s: the pool's stacked observation / action space is not the network's", who);
+    return MZX_ERR_INVALID;
+  }
+  ReplaySamplerTable table;
+  if (const int rc = replay_sampler_table(who, io->sampler, &table)) return rc;
+  if (!io->sampler->d_tile_prefix || (io->per && (!io->sampler->d_raw || io->sampler->raw_capacity < B))) {
+    set_error("%s: sampler workspace missing or short", who);
+    return MZX_ERR_INVALID;
+  }
+  const ChainPlan P = chain_plan(net, B, steps, chain_step_scratch_bytes(net, B, steps), residual ? rtn_stat_floats(net) : 0);
+  if (io->workspace_bytes < P.total_bytes || ((uintptr_t)io->d_workspace % 256) != 0) {
+    set_error("%s: workspace needs %lld bytes, 256-byte aligned", who, (long long)P.total_bytes);
+    return MZX_ERR_INVALID;
+  }
+  if (io->derived_floats < derived_total(net)) { set_error("%s: derived buffer too small", who); return MZX_ERR_INVALID; }
+  if (io->optim.d_param != io->d_flat || io->optim.d_grad != io->d_grad_flat || io->optim.n != net->num_params) {
+    set_error("%s: the optimizer must step d_flat with d_grad_flat (%lld elements)", who, (long long)net->num_params);
+    return MZX_ERR_INVALID;
+  }
+  if (adam ? (!io->h_step_size || !io->h_bias_correction2_sqrt) : !io->h_lr) { set_error("%s: missing per-step scalars", who); return MZX_ERR_INVALID; }
+  if (const int rc = optim_check(&io->optim)) return rc;      // (t only grows: the later steps pass what step 0 passes)
+
+  char* ws = (char*)io->d_workspace;
+  mzx_replay_sample_io sio;
+  memset(&sio, 0, sizeof(sio));
+  sio.seed = io->seed; sio.total_samples = io->total_samples; sio.num_samples = B; sio.per = io->per ? 1 : 0;
+  sio.num_unroll_steps = io->num_unroll_steps; sio.num_actions = io->num_actions; sio.d_action_space = io->d_action_space;
+  sio.d_base = (int64_t*)(ws + P.base); sio.d_len = (int32_t*)(ws + P.len); sio.d_pos = (int32_t*)(ws + P.pos);
+  sio.d_absorbing_actions = (int32_t*)(ws + P.tape); sio.d_game_id = (int64_t*)(ws + P.game_id);
+  sio.d_weight = io->per ? (float*)(ws + P.weight) : nullptr;
+  mzx_replay_batch_io bio;
+  memset(&bio, 0, sizeof(bio));
+  bio.d_base = sio.d_base; bio.d_len = sio.d_len; bio.d_pos = sio.d_pos; bio.d_absorbing_actions = sio.d_absorbing_actions;
+  bio.num_samples = B; bio.num_unroll_steps = io->num_unroll_steps; bio.stacked_observations = io->stacked_observations;
+  bio.d_observation = (float*)(ws + P.obs); bio.d_value = (double*)(ws + P.value64); bio.d_reward = (double*)(ws + P.reward64);
+  bio.d_policy = (double*)(ws + P.policy64); bio.d_action = (int64_t*)(ws + P.action64); bio.d_gradient_scale = (int64_t*)(ws + P.scale64);
+  ChainPrepOp prep;
+  prep.value = bio.d_value; prep.reward = bio.d_reward; prep.policy = bio.d_policy; prep.scale = bio.d_gradient_scale; prep.action = bio.d_action;
+  prep.value_out = (float*)(ws + P.value); prep.reward_out = (float*)(ws + P.reward); prep.policy_out = (float*)(ws + P.policy);
+  prep.scale_out = (float*)(ws + P.scale); prep.action_out = (int32_t*)(ws + P.action);
+  prep.rows = (int64_t)B * steps; prep.A = pool.action_space_size;
+  mzx_train_resnet_io tio;      // (its prefix is the mzx_train_fc_io of a fully connected step: csrc/mzx_train_step.h)
+  memset(&tio, 0, sizeof(tio));
+  tio.d_flat = io->d_flat; tio.d_observation = bio.d_observation; tio.d_action = prep.action_out;
+  tio.d_target_value = prep.value_out; tio.d_target_reward = prep.reward_out; tio.d_target_policy = prep.policy_out;
+  tio.d_gradient_scale = prep.scale_out; tio.d_weight = sio.d_weight;
+  tio.batch = B; tio.steps = steps; tio.value_loss_weight = io->value_loss_weight; tio.per_alpha = io->per_alpha;
+  tio.d_grad_flat = io->d_grad_flat; tio.d_priorities = (float*)(ws + P.priorities);
+  tio.d_scratch = ws + P.scratch; tio.scratch_bytes = P.step_scratch_bytes;
+  tio.d_stats = (float*)(ws + P.stats);
+  mzx_optim_io oio = io->optim;
+  for (int32_t i = 0; i < io->num_steps; ++i) {
+    sio.call_counter = io->first_call + (uint64_t)i;
+    if (const int rc = mzx_replay_sample(io->sampler, &sio, stream)) return rc;
+    if (const int rc = mzx_replay_batch(io->pool, &bio, stream)) return rc;
+    MZX_TRY_LAUNCH(launch<256>(prep, (stream_t)stream));
+    tio.d_losses = io->d_losses + 4 * (int64_t)i;
+    if (const int rc = residual ? mzx_train_resnet_step(net, &tio, stream)
+                                : mzx_train_fc_step(net, reinterpret_cast<const mzx_train_fc_io*>(&tio), stream)) return rc;
+    oio.t = io->optim.t + i;
+    oio.first_step = i == 0 ? io->optim.first_step : 0;
+    if (adam) { oio.step_size = io->h_step_size[i]; oio.bias_correction2_sqrt = io->h_bias_correction2_sqrt[i]; }
+    else oio.lr = io->h_lr[i];
+    MZX_TRY_LAUNCH(optim_launch(&oio, (stream_t)stream));
+    if (residual)
+      if (const int rc = mzx_train_resnet_commit_stats(net, tio.d_stats, io->d_flat, stream)) return rc;
+    if (io->per)
+      if (const int rc = mzx_replay_update_priorities(io->sampler, tio.d_priorities, sio.d_game_id, sio.d_pos, B, steps, stream)) return rc;
+  }
+  return mzx_net_set_weights(net, io->d_flat, net->num_params, io->d_derived, io->derived_floats, stream);
 }
 
 // ------------------------------------------------------------- natively stepped games + the round loop of a shard

@@ -14,7 +14,7 @@ import os
 import torch
 
 MZX_MAX_LAYERS = 8
-ABI_VERSION = 7
+ABI_VERSION = 8
 MOVE_NO_SYNC = 1
 PIECE_INFO_WORDS = 16
 
@@ -206,6 +206,29 @@ class TrainFcIO(ctypes.Structure):
     ]
 
 
+class OptimIO(ctypes.Structure):
+    """``mzx_optim_io``: one optimizer step over the live spans of a flat buffer (mzx.optim)."""
+    _fields_ = [("kind", c_i32), ("first_step", c_i32), ("t", c_i64), ("d_param", c_vp), ("d_grad", c_vp), ("d_state1", c_vp),
+                ("d_state2", c_vp), ("n", c_i64), ("h_spans", c_vp), ("d_chunks", c_vp), ("num_spans", c_i32), ("num_chunks", c_i32),
+                ("weight_decay", ctypes.c_double), ("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("one_minus_beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("one_minus_beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("step_size", ctypes.c_double), ("bias_correction2_sqrt", ctypes.c_double)]
+
+
+OPTIM_ADAM, OPTIM_SGD, OPTIM_CHUNK = 0, 1, 1024
+
+
+class TrainChainIO(ctypes.Structure):
+    """``mzx_train_chain_io``: num_steps whole training steps queued by one mzx_train_chain call (mzx.trainer.train_steps)."""
+    _fields_ = [("pool", ctypes.POINTER(ReplayPool)), ("sampler", ctypes.POINTER(ReplaySampler)), ("seed", ctypes.c_uint64),
+                ("first_call", ctypes.c_uint64), ("total_samples", c_i64), ("per", c_i32), ("num_unroll_steps", c_i32),
+                ("stacked_observations", c_i32), ("num_actions", c_i32), ("d_action_space", c_vp), ("batch", c_i32),
+                ("num_steps", c_i32), ("value_loss_weight", ctypes.c_double), ("per_alpha", ctypes.c_double), ("d_flat", c_vp),
+                ("d_grad_flat", c_vp), ("optim", OptimIO), ("h_lr", c_vp), ("h_step_size", c_vp),
+                ("h_bias_correction2_sqrt", c_vp), ("d_losses", c_vp), ("d_derived", c_vp), ("derived_floats", c_i64),
+                ("d_workspace", c_vp), ("workspace_bytes", c_i64)]
+
+
 class TrainResnetIO(ctypes.Structure):
     """``mzx_train_resnet_io``: ``mzx_train_fc_io`` plus the output of the running statistics after the step."""
     _fields_ = TrainFcIO._fields_ + [("d_stats", c_vp)]
@@ -315,6 +338,11 @@ PROTOTYPES = {
     "mzx_train_resnet_commit_stats": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mzx_net_set_train_stem": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mzx_net_train_stem": (ctypes.c_int, [c_vp]),
+    "mzx_optim_chunks": (c_i64, [c_vp, c_i32, c_i64, c_vp, c_i64]),
+    "mzx_optim_step": (ctypes.c_int, [ctypes.POINTER(OptimIO), c_vp]),
+    "mzx_train_chain_supported": (ctypes.c_int, [c_vp, c_i32, c_i32]),
+    "mzx_train_chain_scratch_bytes": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_train_chain": (ctypes.c_int, [c_vp, ctypes.POINTER(TrainChainIO), c_vp]),
     "mzx_game_create": (ctypes.c_int, [ctypes.c_char_p, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "mzx_game_destroy": (None, [c_vp]),
     "mzx_game_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32 * 8)]),

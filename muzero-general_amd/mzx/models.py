@@ -20,6 +20,7 @@ on batch statistics) for residual ones.  There is no autograd graph through
 import collections
 import ctypes
 import math
+import weakref
 
 import torch
 
@@ -233,6 +234,7 @@ class HipNetwork:
             self.hidden_shape = (self.hidden_size,)
         self._flat = self.backend.zeros((self.num_params,), torch.float32)
         self._param = torch.nn.Parameter(self._flat, requires_grad=True)   # the same storage, as an optimizer's leaf
+        self._param._mzx_network = weakref.ref(self)      # mzx.optim finds the network's span table through its parameter
         self._derived = self.backend.zeros((lib.mzx_net_derived_floats(handle),), torch.float32)
         self._workspace = None
         self._ws_batch = 0

@@ -34,11 +34,15 @@ the stem bypasses keep zero gradients, their statistics and their ``num_batches_
 convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """
 import collections
+import copy
 import ctypes
+import time
 
+import numpy
 import torch
 
-from . import _lib, models, replay
+from . import _lib, models, optim, replay
+from .replay import _remote
 
 
 def _backend(backend):
@@ -193,8 +197,9 @@ def _sgd_step(model, optimizer, batch, config, backend):
             # behind a downsample stem representation_network.module.conv / .bn are never applied: the reference's optimizer
             # skips them (their .grad is None), so weight decay and Adam's moments must not move them here either
             flat = model.flat_weights()
+            # (a native optimizer visits neither the statistics nor the bypassed tensors: nothing to keep)
             bypassed = [(off, numel, flat[off:off + numel].clone()) for key, off, numel, _ in model._tensors
-                        if key.startswith(_BYPASSED)] if model._cfg.downsample else []
+                        if key.startswith(_BYPASSED)] if model._cfg.downsample and not isinstance(optimizer, optim.NATIVE) else []
             optimizer.step()
             for off, numel, kept in bypassed:
                 flat[off:off + numel].copy_(kept)
@@ -247,7 +252,7 @@ _StepKind = collections.namedtuple("_StepKind", "name io limit")
 _FC = _StepKind("mzx_train_fc", _lib.TrainFcIO, _fc_limit)
 _RESNET = _StepKind("mzx_train_resnet", _lib.TrainResnetIO, _resnet_limit)
 TRAIN_SCRATCH_MAX_BYTES = 32 << 30
-_BYPASSED = ("representation_network.module.conv.", "representation_network.module.bn.")      # with config.downsample
+_BYPASSED = optim._BYPASSED      # with config.downsample
 
 
 def _train_gradients(kind, model, batch, config, logits, stats=None):
@@ -302,9 +307,7 @@ def _train_gradients(kind, model, batch, config, logits, stats=None):
     lib.check(getattr(lib, kind.name + "_step")(model.handle, ctypes.byref(io), be.stream()))
     if residual and stats is not None:
         stats["running"] = running
-        stats["applications"] = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
-        if model._cfg.downsample:      # the stem bypasses representation_network.module.conv / .bn (first match wins)
-            stats["applications"] = {"representation_network.module.bn.": 0, **stats["applications"]}
+        stats["applications"] = _applications(model, steps)
     return packed
 
 
@@ -340,11 +343,24 @@ def commit_running_stats(model, running, applications):
     raise every ``num_batches_tracked`` by its network's application count.  Call ``model.refresh_derived()`` after it."""
     be, lib = model.backend, model.backend.lib
     lib.check(lib.mzx_train_resnet_commit_stats(model.handle, be.ptr(running), be.ptr(model.flat_weights()), be.stream()))
+    _count_applications(model, applications)
+
+
+def _applications(model, steps):
+    """Per network prefix, how often a step of ``steps`` (= num_unroll_steps + 1) applies it; the first match counts."""
+    table = {"representation_network.": 1, "dynamics_network.": steps - 1, "prediction_network.": steps}
+    if model._cfg.downsample:      # the stem bypasses representation_network.module.conv / .bn (first match wins)
+        table = {"representation_network.module.bn.": 0, **table}
+    return table
+
+
+def _count_applications(model, applications, times=1):
+    """Raise every ``num_batches_tracked`` by ``times`` x its network's application count."""
     for key, *_ in model._tensors:
         if key.endswith(".running_var"):
             nbt = key[: -len("running_var")] + "num_batches_tracked"
             count = next(n for prefix, n in applications.items() if key.startswith(prefix))
-            model._num_batches_tracked[nbt] = model._num_batches_tracked.get(nbt, torch.zeros((), dtype=torch.int64)) + count
+            model._num_batches_tracked[nbt] = model._num_batches_tracked.get(nbt, torch.zeros((), dtype=torch.int64)) + times * count
 
 
 def update_lr(optimizer, config, training_step):
@@ -431,3 +447,253 @@ def train_step(model, optimizer, replay_buffer, config, backend=None):
     if config.PER:
         replay_buffer.update_priorities(packed[4:].view(batch_size, -1), index_batch)
     return packed[:4]
+
+
+def _lr_at(config, training_step):
+    return config.lr_init * config.lr_decay_rate ** (training_step / config.lr_decay_steps)
+
+
+def chain_refusal(model, optimizer, replay_buffer, config):
+    """What ``train_steps`` lacks to chain these four, by name, or None (``Trainer`` chooses its route with it)."""
+    if not isinstance(model, models.HipNetwork):
+        return "a torch model is not chained (a mzx.models.HipNetwork trains natively; use update_lr + train_step)"
+    if not isinstance(optimizer, optim.NATIVE):
+        return ("a torch optimizer is not chained (mzx.optim.Adam / mzx.optim.SGD run as the library's kernel; use update_lr + "
+                "train_step)")
+    store = getattr(replay_buffer, "_store", None)
+    if not getattr(replay_buffer, "_sampler", False) or store is None or store.sampler is None:
+        return ("the replay buffer has no device sampler (mzx.replay.ReplayBuffer(..., device_sampler=True) draws batches on "
+                "the device)")
+    lib = model.backend.lib
+    cfg = replay_buffer._stock.config
+    batch_size, steps = int(cfg.batch_size), int(cfg.num_unroll_steps) + 1
+    kind = _RESNET if model._cfg.network != 0 else _FC
+    if not lib.mzx_train_chain_supported(model.handle, batch_size, steps):
+        return f"{kind.name}_step does not run this network at batch {batch_size} x {steps} steps: {kind.limit(model)}"
+    nbytes = int(lib.mzx_train_chain_scratch_bytes(model.handle, batch_size, steps))
+    most = int(getattr(config, "train_scratch_max_bytes", TRAIN_SCRATCH_MAX_BYTES))
+    if nbytes > most:
+        return (f"the chain's scratch at batch {batch_size} x {steps} steps is {nbytes} bytes, more than "
+                f"config.train_scratch_max_bytes = {most}")
+    return None
+
+
+def train_steps(model, optimizer, replay_buffer, config, n, training_step):
+    """
+    ``n`` whole training steps queued by ONE library call (``mzx_train_chain``, csrc/mzx_train_chain.h).  By definition
+
+        for i in range(n):
+            update_lr(optimizer, config, training_step + i)
+            losses[i] = train_step(model, optimizer, replay_buffer, config)
+
+    and it leaves, bit for bit, what that loop leaves: the flat weights and the derived buffer, every optimizer state
+    tensor, ``state["step"]`` and ``param_groups[0]["lr"]`` (those of the last step), the store's priorities,
+    ``replay_buffer._sample_calls`` (advanced by ``n``) and every ``num_batches_tracked``.  Returns the losses as a device
+    tensor [n, 4] (loss, value / reward / policy loss per step); nothing is downloaded and nothing synchronises.  The
+    caller advances ``training_step``, as with ``train_step``.
+
+    Per step the library queues the sampler's draw (call counter ``_sample_calls + i``; ``total_samples`` and the slot
+    table as flushed once before the chain), the gather, the conversions ``trainer_tensors`` makes with torch, the native
+    step, the native optimizer's launch, for a residual network the commit of the running statistics and with PER the
+    priority scatter.  The BatchNorm re-fold (``mzx_net_set_weights``) runs ONCE, behind the last step: the training kernels
+    read the flat buffer, not the derived one -- a search running beside the chain sees folded terms at chunk granularity.
+    The per-step scalars (lr, Adam's step size and bias correction) are computed here in binary64, as torch computes
+    them.  The one workspace (``mzx_train_chain_scratch_bytes``) is allocated once per (network, batch, steps) and kept on
+    the network.
+
+    There is no fall-back: a torch optimizer, a torch model, a buffer without ``device_sampler=True``, a network the
+    native step refuses and a workspace above ``config.train_scratch_max_bytes`` raise ``NotImplementedError`` by name
+    before anything is queued; ``n < 1`` raises ``ValueError``.
+    """
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"train_steps: n = {n}, at least one step")
+    missing = chain_refusal(model, optimizer, replay_buffer, config)
+    if missing:
+        raise NotImplementedError("train_steps: " + missing)
+    store = replay_buffer._store
+    be, lib = model.backend, model.backend.lib
+    cfg = replay_buffer._stock.config
+    if bool(cfg.PER) != bool(config.PER):
+        raise ValueError("train_steps: config.PER differs from the replay buffer's")
+    batch_size, steps = int(cfg.batch_size), int(cfg.num_unroll_steps) + 1
+    kind = _RESNET if model._cfg.network != 0 else _FC
+    nbytes = int(lib.mzx_train_chain_scratch_bytes(model.handle, batch_size, steps))
+    if tuple(store.sample_shape) != tuple(model.input_shape) and int(numpy.prod(store.sample_shape)) != model.input_size:
+        raise ValueError("train_steps: the store's stacked observation is not the network's input")
+    if not store._with_positions:
+        raise ValueError("no game with a position is resident: nothing to draw from")
+    param = next(model.parameters())
+    if param.grad is None:
+        param.grad = torch.zeros_like(model.flat_weights())
+    io = _lib.TrainChainIO()
+    group, _, _, oio = optimizer._io(_lib.OPTIM_ADAM if isinstance(optimizer, optim.Adam) else _lib.OPTIM_SGD,
+                                     type(optimizer).__name__, optimizer._REFUSED)
+    lrs = [_lr_at(config, training_step + i) for i in range(n)]
+    h_lr = numpy.array(lrs, dtype=numpy.float64)
+    keep = [h_lr]
+    if isinstance(optimizer, optim.Adam):
+        step, exp_avg, exp_avg_sq = optimizer.native_state()
+        first_t = int(step.item()) + 1
+        beta1, beta2 = group["betas"]
+        oio.t, oio.d_state1, oio.d_state2 = first_t, exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+        oio.one_minus_beta1, oio.beta2, oio.one_minus_beta2, oio.eps = 1 - beta1, beta2, 1 - beta2, group["eps"]
+        scalars = numpy.array([optimizer.adam_scalars(first_t + i, lrs[i]) for i in range(n)], dtype=numpy.float64)
+        h_ss, h_bc = numpy.ascontiguousarray(scalars[:, 0]), numpy.ascontiguousarray(scalars[:, 1])
+        keep += [h_ss, h_bc]
+        io.h_step_size, io.h_bias_correction2_sqrt = h_ss.ctypes.data, h_bc.ctypes.data
+    else:
+        step = None
+        oio.t, oio.momentum = 1, float(group["momentum"])
+        if group["momentum"] != 0:
+            buf, first = optimizer.native_state()
+            oio.d_state1, oio.first_step = buf.data_ptr(), int(first)
+        io.h_lr = h_lr.ctypes.data
+    io.optim = oio
+    # the sampler's state as get_batch() leaves it before a draw (DeviceGameStore.sample)
+    store._flush_slots()
+    if cfg.PER and store._raw.numel() < batch_size:
+        store._raw = be.empty((batch_size,), torch.float64)
+        store.sampler.d_raw, store.sampler.raw_capacity = store._raw.data_ptr(), batch_size
+    io.pool, io.sampler = ctypes.pointer(store.pool), ctypes.pointer(store.sampler)
+    io.seed, io.first_call = int(cfg.seed) & (2 ** 64 - 1), int(replay_buffer._sample_calls) & (2 ** 64 - 1)
+    io.total_samples, io.per, io.num_unroll_steps = int(replay_buffer._stock.total_samples), int(bool(cfg.PER)), steps - 1
+    io.stacked_observations, io.num_actions = store.k, store.A
+    io.d_action_space = None if store._action_space is None else store._action_space.data_ptr()
+    io.batch, io.num_steps = batch_size, n
+    io.value_loss_weight, io.per_alpha = float(config.value_loss_weight), float(config.PER_alpha)
+    io.d_flat, io.d_grad_flat = model.flat_weights().data_ptr(), param.grad.data_ptr()
+    losses = be.empty((n, 4), torch.float32)
+    io.d_losses = losses.data_ptr()
+    io.d_derived, io.derived_floats = model._derived.data_ptr(), model._derived.numel()
+    key = (batch_size, steps)
+    workspace = getattr(model, "_chain_workspace", None)
+    if workspace is None or workspace[0] != key:
+        workspace = model._chain_workspace = (key, be.empty((nbytes + 256,), torch.uint8))
+    offset = -workspace[1].data_ptr() % 256
+    io.d_workspace, io.workspace_bytes = workspace[1].data_ptr() + offset, nbytes
+    lib.check(lib.mzx_train_chain(model.handle, ctypes.byref(io), be.stream()))
+    if step is not None:
+        step.fill_(float(first_t + n - 1))
+    group["lr"] = lrs[-1]
+    replay_buffer._sample_calls = replay_buffer._sample_calls + n
+    if kind is _RESNET:
+        _count_applications(model, _applications(model, steps), n)
+    return losses
+
+
+class Trainer:
+    """
+    trainer.py:13-123 -- the worker that trains the network and publishes it in the shared storage, under the reference's
+    names: ``Trainer(initial_checkpoint, config)``, ``continuous_update_weights(replay_buffer, shared_storage)``,
+    ``update_weights(batch)``, ``update_lr()``.  The network is ``models.MuZeroNetwork(config)``, the optimizer
+    ``mzx.optim.from_config`` (the library's kernel), the optimizer state travels in the reference's per-parameter format
+    (``optimizer_state`` / ``load_optimizer_state``).  ``_backend``: the serial build, for the tests.
+
+    The loop trains in chunks of ``min(config.train_steps_chunk (default 16), steps to the next multiple of
+    checkpoint_interval, steps left)``: one ``train_steps`` call and one download of the chunk's [chunk, 4] losses; then the
+    storage traffic of the reference's loop -- weights and optimizer state at every multiple of ``checkpoint_interval``,
+    the six logged entries (the last step's losses), ``training_delay``, the ``ratio`` wait, ``terminate``.  With
+    ``train_steps_chunk = 1`` the storage sees exactly the reference's sequence of ``set_info`` calls.  What ``train_steps``
+    refuses (``chain_refusal``) takes a per-step route, chosen once at the first chunk and readable as ``route``: "chain",
+    "step" (``update_lr`` + ``train_step`` with a device sampler) or "host" (``get_batch`` / ``update_weights`` /
+    ``update_priorities`` through the buffer's own methods, a Ray actor's included).
+    """
+
+    def __init__(self, initial_checkpoint, config, _backend=None):
+        self.config = config
+        # Fix random generator seed (trainer.py:21-23)
+        numpy.random.seed(self.config.seed)
+        torch.manual_seed(self.config.seed)
+        # the network lives on the GPU whatever config.train_on_gpu says: the engine has no CPU path
+        self.model = models.MuZeroNetwork(self.config, _backend=_backend)
+        self.model.set_weights(copy.deepcopy(initial_checkpoint["weights"]))
+        self.model.train()
+        self.training_step = initial_checkpoint["training_step"]
+        if "cuda" not in str(next(self.model.parameters()).device):
+            print("You are not training on GPU.\n")
+        self.optimizer = optim.from_config(self.model, self.config)
+        if initial_checkpoint["optimizer_state"] is not None:
+            print("Loading optimizer...\n")
+            load_optimizer_state(self.optimizer, self.model, copy.deepcopy(initial_checkpoint["optimizer_state"]))
+        self.route = None      # chosen at the first chunk of continuous_update_weights
+        self._backend = _backend
+
+    def _choose_route(self, replay_buffer):
+        self.route_reason = chain_refusal(self.model, self.optimizer, replay_buffer, self.config)
+        if self.route_reason is None:
+            return "chain"
+        return "step" if getattr(replay_buffer, "_sampler", False) else "host"
+
+    def _optimizer_state(self):
+        if isinstance(self.model, models.HipNetwork):
+            return optimizer_state(self.optimizer, self.model)
+        return copy.deepcopy(models.dict_to_cpu(self.optimizer.state_dict()))
+
+    def _train_chunk(self, replay_buffer, chunk):
+        """``chunk`` steps on the chosen route -> the last step's four losses as floats, after one download."""
+        if self.route == "chain":
+            losses = train_steps(self.model, self.optimizer, replay_buffer, self.config, chunk, self.training_step)
+            self.training_step += chunk
+            return [float(x) for x in losses.cpu().numpy()[-1]]
+        if self.route == "step":
+            for _ in range(chunk):
+                self.update_lr()
+                packed = train_step(self.model, self.optimizer, replay_buffer, self.config, backend=self._backend)
+                self.training_step += 1
+            return [float(x) for x in packed.cpu().numpy()]
+        for _ in range(chunk):
+            index_batch, batch = _remote(replay_buffer.get_batch)
+            self.update_lr()
+            priorities, *last = self.update_weights(batch)
+            if self.config.PER:
+                # Save new priorities in the replay buffer (See https://arxiv.org/abs/1803.00933)
+                _remote(replay_buffer.update_priorities, priorities, index_batch)
+        return last
+
+    def continuous_update_weights(self, replay_buffer, shared_storage):
+        cfg = self.config
+        # Wait for the replay buffer to be filled
+        while _remote(shared_storage.get_info, "num_played_games") < 1:
+            time.sleep(0.1)
+        # Training loop
+        while self.training_step < cfg.training_steps and not _remote(shared_storage.get_info, "terminate"):
+            if self.route is None:
+                self.route = self._choose_route(replay_buffer)
+            interval = int(cfg.checkpoint_interval)
+            chunk = min(max(1, int(getattr(cfg, "train_steps_chunk", 16))), interval - self.training_step % interval,
+                        cfg.training_steps - self.training_step)
+            total_loss, value_loss, reward_loss, policy_loss = self._train_chunk(replay_buffer, chunk)
+            # Save to the shared storage
+            if self.training_step % interval == 0:
+                _remote(shared_storage.set_info, {"weights": copy.deepcopy(self.model.get_weights()),
+                                                  "optimizer_state": self._optimizer_state()})
+                if cfg.save_model:
+                    _remote(shared_storage.save_checkpoint)
+            _remote(shared_storage.set_info, {
+                "training_step": self.training_step,
+                "lr": self.optimizer.param_groups[0]["lr"],
+                "total_loss": total_loss,
+                "value_loss": value_loss,
+                "reward_loss": reward_loss,
+                "policy_loss": policy_loss,
+            })
+            # Managing the self-play / training ratio
+            if cfg.training_delay:
+                time.sleep(cfg.training_delay)
+            if cfg.ratio:
+                while (self.training_step / max(1, _remote(shared_storage.get_info, "num_played_steps")) > cfg.ratio
+                       and self.training_step < cfg.training_steps
+                       and not _remote(shared_storage.get_info, "terminate")):
+                    time.sleep(0.5)
+
+    def update_weights(self, batch):
+        """One training step on ``batch`` (trainer.py:124-273): ``(priorities, total_loss, value_loss, reward_loss,
+        policy_loss)``; ``training_step`` advances."""
+        out = update_weights(self.model, self.optimizer, batch, self.config, backend=self._backend)
+        self.training_step += 1
+        return out
+
+    def update_lr(self):
+        """trainer.py:275-283"""
+        update_lr(self.optimizer, self.config, self.training_step)

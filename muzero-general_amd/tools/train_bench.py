@@ -9,6 +9,8 @@ One training step (Adam) of the shipped networks on the GPU, natively and throug
   call_us     (fc) mzx_train_fc_step alone (mzx.trainer.train_fc_gradients: five launches), HIP events around a block.
 
     python muzero-general_amd/tools/train_bench.py --family fc|resnet|stem [--out FILE] [--quick] [--shape NAME]
+    python muzero-general_amd/tools/train_bench.py --family chain [--out FILE] [--quick] [--shape NAME]   (whole steps: per-step loop
+              with torch.optim.Adam | with mzx.optim.Adam | mzx.trainer.train_steps in chunks of 16; the optimizer launch alone)
     python muzero-general_amd/tools/train_bench.py --family fc --trace a|b|c --trace-steps N   (under rocprofv3 --kernel-trace --stats)
     python muzero-general_amd/tools/train_bench.py --family fc --launches DIR_N1 N1 DIR_N2 N2  (kernel dispatches per step from two traces)
 
@@ -58,6 +60,14 @@ FAMILIES = {      # shapes: name -> (batch, steps) as shipped; warm-up calls, (b
                  what="one training step of the shipped residual networks with a downsample stem, Adam; torch_ms = update_weights "
                       "with the torch network (training mode), native_ms = update_weights with a HipNetwork, stem training on "
                       "(mzx_train_resnet_step); medians of alternating timed blocks [min, max], each call ends in one download"),
+    # whole training steps from a device replay store: (batch, unroll steps); see chain_measure / chain_optimizer_alone
+    "chain": dict(shapes={"cartpole": (128, 10), "tictactoe": (64, 20), "connect4": (64, 42)}, adam=dict(lr=0.003, weight_decay=1e-4),
+                  chunk=16, blocks=(7, 4), quick=(3, 1), log="train_chain_bench.log",
+                  what="whole training steps (device sampler, gather, native step, Adam, priority feedback) in ms per step; "
+                       "torch_adam = update_lr + train_step with torch.optim.Adam (the yardstick), native_adam = the same with "
+                       "mzx.optim.Adam, chain = mzx.trainer.train_steps in chunks of 16; one process, legs alternate block by "
+                       "block, medians of timed blocks [min, max], every block ends in ONE synchronise; then the optimizer launch "
+                       "alone (HIP events) against torch's Adam over the same flat parameter"),
 }
 
 
@@ -146,6 +156,105 @@ def measure(be, family, name, quick):
     return line
 
 
+def chain_setup(be, name, native):
+    """(config, network, Adam, buffer with a device sampler) of a shipped configuration: 48 games of 8 .. 40 positions."""
+    import numpy
+
+    import replay_sampler_cases
+    from mzx import configs, models, optim, replay, synthetic
+
+    fam = FAMILIES["chain"]
+    B, K = fam["shapes"][name]
+    cfg = getattr(configs, name)(PER=True, PER_alpha=0.5, batch_size=B, num_unroll_steps=K, td_steps=10, discount=0.997, seed=7, value_loss_weight=0.25,
+                                 replay_buffer_size=10 ** 6, lr_init=fam["adam"]["lr"], lr_decay_rate=0.9, lr_decay_steps=1000,
+                                 weight_decay=fam["adam"]["weight_decay"], optimizer="Adam")
+    rs = numpy.random.RandomState(5)
+    lengths = [int(T) for T in rs.randint(8, 41, size=48)]
+    store = replay.DeviceGameStore(cfg, be, sum(lengths) + len(lengths), max_games=64)
+    buffer = replay.ReplayBuffer(dict(replay_sampler_cases.CHECKPOINT), {}, cfg, stock=replay_sampler_cases.FeedbackStock,
+                                 device_store=store, device_sampler=True)
+    for k, T in enumerate(lengths):
+        buffer.save_game(replay_sampler_cases.game(cfg, T, 900 + k, priorities=0.1 + rs.random_sample(T)))
+    net = models.MuZeroNetwork(cfg, _backend=be)
+    net.set_weights(synthetic.fill_state_dict(net.state_dict(), 11))
+    make = optim.Adam if native else torch.optim.Adam
+    return cfg, net, make(net.parameters(), **fam["adam"]), buffer
+
+
+def chain_measure(be, name, quick):
+    from mzx import trainer
+
+    fam = FAMILIES["chain"]
+    blocks, chunks = fam["quick"] if quick else fam["blocks"]
+    chunk = fam["chunk"]
+    setups = dict(torch_adam=chain_setup(be, name, False), native_adam=chain_setup(be, name, True), chain=chain_setup(be, name, True))
+    at = dict.fromkeys(setups, 0)
+
+    def block(leg):
+        cfg, net, optimizer, buffer = setups[leg]
+        for _ in range(chunks):
+            if leg == "chain":
+                trainer.train_steps(net, optimizer, buffer, cfg, chunk, at[leg])
+            else:
+                for i in range(chunk):
+                    trainer.update_lr(optimizer, cfg, at[leg] + i)
+                    trainer.train_step(net, optimizer, buffer, cfg)
+            at[leg] += chunk
+
+    times = {leg: [] for leg in setups}
+    for leg in setups:
+        block(leg)
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for leg, ts in times.items():
+            t0 = time.perf_counter()
+            block(leg)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3 / (chunks * chunk))
+    B, K = fam["shapes"][name]
+    line = dict(shape=f"{name}_b{B}_k{K}", optimizer="Adam", blocks=blocks, steps_per_block=chunks * chunk, chunk=chunk)
+    for leg, ts in times.items():
+        line[f"{leg}_ms"] = round(statistics.median(ts), 4)
+        line[f"{leg}_ms_min_max"] = [round(min(ts), 4), round(max(ts), 4)]
+    line["torch_adam_over_chain"] = round(line["torch_adam_ms"] / line["chain_ms"], 3)
+    line["torch_adam_over_native_adam"] = round(line["torch_adam_ms"] / line["native_adam_ms"], 3)
+    flats = [setups[leg][1].flat_weights() for leg in ("native_adam", "chain")]
+    line["chain_equals_native_adam_loop"] = bool(torch.equal(*flats))      # (the same steps from the same start: the same bits)
+    return line
+
+
+def chain_optimizer_alone(be, name, quick):
+    """The optimizer launch alone over a shipped network's flat parameter: HIP events around runs of step() calls."""
+    from mzx import configs, models, optim
+
+    fam = FAMILIES["chain"]
+    blocks, iters = (3, 20) if quick else (7, 100)
+    net = models.MuZeroNetwork(getattr(configs, name)(), _backend=be)
+    param = next(net.parameters())
+    param.grad = torch.randn_like(net.flat_weights()) * 1e-3
+    live = sum(count for _, count in optim.live_spans(net))
+    line = dict(optimizer_alone=name, parameters=int(net.num_params), live=int(live))
+    for leg, make in (("torch", torch.optim.Adam), ("native", optim.Adam)):
+        optimizer = make(net.parameters(), **fam["adam"])
+        for _ in range(3):
+            optimizer.step()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(blocks):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(iters):
+                optimizer.step()
+            stop.record()
+            torch.cuda.synchronize()
+            ts.append(start.elapsed_time(stop) * 1e3 / iters)
+        line[f"{leg}_us"] = round(statistics.median(ts), 2)
+        line[f"{leg}_us_min_max"] = [round(min(ts), 2), round(max(ts), 2)]
+    line["native_bytes_per_s"] = round(28 * live / (line["native_us"] * 1e-6), 0)
+    line["native_fraction_of_8TBps"] = round(line["native_bytes_per_s"] / 8e12, 4)
+    return line
+
+
 def dispatches(directory):
     """{kernel name: calls} of a rocprofv3 --kernel-trace --stats output directory."""
     out = {}
@@ -183,6 +292,8 @@ def main():
     from mzx import _lib
 
     be = _lib.default_backend()
+    if args.family == "chain" and args.trace:
+        ap.error("--trace belongs to the step families")
     if args.trace:
         fn = legs(be, args.family, names[0])[0][args.trace]
         for _ in range(args.trace_steps):
@@ -193,6 +304,14 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     lines = [f"# {fam['log'][:-4]}: {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {fam['what']}"]
     print(lines[0], flush=True)
+    if args.family == "chain":
+        jobs = [(chain_measure, name) for name in names] + [(chain_optimizer_alone, name) for name in ("cartpole", "connect4", "atari")]
+        for fn, name in jobs:
+            lines.append(json.dumps(fn(be, name, args.quick)))
+            print(lines[-1], flush=True)
+            with open(out, "w") as log:
+                log.write("\n".join(lines) + "\n")
+        return
     for name in names:
         lines.append(json.dumps(measure(be, args.family, name, args.quick)))
         print(lines[-1], flush=True)
