@@ -996,6 +996,32 @@ int mzx_net_set_train_stem(mzx_net* net, int on);
 int mzx_net_train_stem(const mzx_net* net);
 
 /* ------------------------------------------------------------------------- *
+ * The GEMM body of mzx_train_resnet_step (and of mzx_train_chain and the trainer worker, which run it), per handle.  The
+ * forward, input-gradient and weight-gradient GEMMs of a step exist twice (csrc/mzx_train_resnet.h,
+ * csrc/mzx_train_gemm_tiled.h): a wavefront per 16 x 16 output tile with operands gathered from global memory, and a
+ * 256-thread workgroup per 64 x 64 output tile with operands staged once through LDS and shared by its four waves.  Both
+ * issue the same matrix instructions with the same operands in the same order per output element: EVERY output of the step
+ * has the same bits on either route, so the switch is a tuning decision only.
+ *   mzx_net_set_train_gemm(net, mode):
+ *     MZX_TRAIN_GEMM_WAVE       the default: every GEMM on the wave body
+ *     MZX_TRAIN_GEMM_TILED      the tiled body for the GEMMs the rule of csrc/mzx_tuning.h picks (at least 64 rows, 32
+ *                               columns, and 64 x 64 tiles x weight-gradient chunks >= 256 workgroups), the wave body for
+ *                               the rest
+ *     MZX_TRAIN_GEMM_TILED_ALL  the tiled body for every GEMM, ragged and tiny ones included (tests)
+ *     MZX_ERR_INVALID, with a text in mzx_last_error(), for a null handle, a fully connected network or another mode.
+ *   mzx_net_train_gemm(net): the mode (0 for null).
+ *   mzx_train_resnet_tiled_launches(net, batch, steps): how many GEMM launches of a step take the tiled body under the
+ *     handle's mode; 0 in mode 0 and where the step is unsupported.  mzx_train_resnet_launches and
+ *     mzx_train_resnet_scratch_bytes do not depend on the mode.
+ * ------------------------------------------------------------------------- */
+#define MZX_TRAIN_GEMM_WAVE 0
+#define MZX_TRAIN_GEMM_TILED 1
+#define MZX_TRAIN_GEMM_TILED_ALL 2
+int mzx_net_set_train_gemm(mzx_net* net, int mode);
+int mzx_net_train_gemm(const mzx_net* net);
+int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps);
+
+/* ------------------------------------------------------------------------- *
  * The optimizer step over the flat parameter buffer (csrc/mzx_optim.h): torch.optim.Adam (no amsgrad, no maximize) and
  * torch.optim.SGD (dampening 0, no nesterov) as ONE elementwise launch, no atomics: the same bits on every run.
  * Only the LIVE SPANS of the buffer are visited: h_spans [num_spans][2] holds (offset, count) pairs in elements (count

@@ -19,6 +19,11 @@ FLAGS = [
     "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
 ]
 
+# per translation unit, beyond FLAGS: the tiled training GEMMs are compiled without the packed binary32 instructions
+FILE_FLAGS = {
+    "mzx_train_gemm_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
 
 def sources():
     return sorted(
@@ -60,7 +65,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or not _object_up_to_date(obj, src):
-            cmd = [hipcc] + flags + extra + ["-x", "hip", "-c", src, "-o", obj]
+            cmd = [hipcc] + flags + FILE_FLAGS.get(os.path.basename(src), []) + extra + ["-x", "hip", "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             jobs.append((cmd, subprocess.Popen(cmd)))

@@ -6,8 +6,9 @@
 // tests/hostcheck: a serial loop (test infrastructure only).
 //
 // Wave bodies (mzx_wave.h) go through launch_waves: one work item per wavefront, WAVES items per workgroup, the body called
-// as body(item, lane); one-workgroup bodies through launch_block, called as body(thread).  tests/hostcheck: the serial loop
-// with lane 0 / the one call with thread 0.
+// as body(item, lane); one-workgroup bodies through launch_block, called as body(thread); tile bodies through launch_tiles:
+// one work item per THREADS-thread workgroup, called as body(item, thread), LDS declared in the body.  tests/hostcheck: the
+// serial loop with lane 0 / the one call with thread 0 / the serial loop with thread 0.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -39,6 +40,13 @@ inline int launch_waves(const Body& body, stream_t) {
 template <int BLOCK, class Body>
 inline int launch_block(const Body& body, stream_t) {
   body(0);
+  return 0;
+}
+
+template <int THREADS, class Body>
+inline int launch_tiles(const Body& body, stream_t) {
+  const size_t n = body.size();
+  for (size_t e = 0; e < n; ++e) body(e, 0);
   return 0;
 }
 
@@ -121,6 +129,21 @@ __global__ void __launch_bounds__(BLOCK) block_kernel(const Body body) {
 template <int BLOCK, class Body>
 inline int launch_block(const Body& body, stream_t stream) {
   hipLaunchKernelGGL((block_kernel<BLOCK, Body>), dim3(1), dim3(BLOCK), 0, stream, body);
+  return (int)hipGetLastError();
+}
+
+// every workgroup runs (a tile body has workgroup barriers and declares its own LDS)
+template <int THREADS, class Body>
+__global__ void __launch_bounds__(THREADS) tile_kernel(const Body body) {
+  body((size_t)blockIdx.x, (int)threadIdx.x);
+}
+
+template <int THREADS, class Body>
+inline int launch_tiles(const Body& body, stream_t stream) {
+  const size_t n = body.size();
+  if (n == 0) return 0;
+  if (n > 0x7fffffffu) return (int)hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL((tile_kernel<THREADS, Body>), dim3((unsigned)n), dim3(THREADS), 0, stream, body);
   return (int)hipGetLastError();
 }
 

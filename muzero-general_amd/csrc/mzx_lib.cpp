@@ -24,7 +24,9 @@
 #include "mzx_train_chain.h"
 #include "mzx_train_step.h"
 #include "mzx_tree_carry.h"
-#ifndef MZX_HOSTCHECK
+#ifdef MZX_HOSTCHECK
+#include "mzx_train_gemm_tiled.h"      // (the device build compiles the tiled GEMMs in mzx_train_gemm_tiled.hip)
+#else
 #include "mzx_fused_fc.h"
 #include "mzx_fused_fc2.h"
 #include "mzx_resnet_search.h"
@@ -1582,16 +1584,21 @@ int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_
 
 int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat_floats(net) : 0; }
 
-int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) {
-  return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [](const RtnPlan& plan) {
+// the dry run of a step: its launches (with the two of the loss head), or how many of its GEMMs take the LDS-tiled body
+static int64_t rtn_dry_run(const mzx_net* net, int32_t batch, int32_t steps, bool tiled) {
+  return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [&](const RtnPlan& plan) {
     RtnRun<false> run;      // (the launches of a step do not depend on its precision)
     memset((void*)&run, 0, sizeof(run));
-    run.P = &plan; run.dry = true;
+    run.P = &plan; run.dry = true; run.gemm_mode = net->train_gemm;
     run.forward();
     run.backward();
-    return run.launched + 2;      // (the two launches of the loss head)
+    return tiled ? run.tiled : run.launched + 2;
   });
 }
+
+int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, false); }
+
+int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, true); }
 
 // forward pass, loss head, backward pass of a planned step
 extern "C++" template <bool WIDE>
@@ -1601,6 +1608,7 @@ int rtn_step(const mzx_net* net, const mzx_train_resnet_io* io, const RtnPlan& P
   memset((void*)&run, 0, sizeof(run));
   run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
   run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
+  run.gemm_mode = net->train_gemm;
   const mzx_trainer_loss_io lio = train_head_io(reinterpret_cast<const mzx_train_fc_io*>(io), P, scratch, net->cfg.support_size,
                                                 run.vlog, run.rlog, run.plog);
   run.forward();
@@ -1626,6 +1634,16 @@ int mzx_net_set_train_stem(mzx_net* net, int on) {
 }
 
 int mzx_net_train_stem(const mzx_net* net) { return net ? net->train_stem : 0; }
+
+int mzx_net_set_train_gemm(mzx_net* net, int mode) {
+  if (!net) { set_error("mzx_net_set_train_gemm: null network handle"); return MZX_ERR_INVALID; }
+  if (net->cfg.network != 1) { set_error("mzx_net_set_train_gemm: fully connected networks do not train through the residual GEMMs"); return MZX_ERR_INVALID; }
+  if (mode < MZX_TRAIN_GEMM_WAVE || mode > MZX_TRAIN_GEMM_TILED_ALL) { set_error("mzx_net_set_train_gemm: unknown mode (0 wave, 1 tiled, 2 tiled_all)"); return MZX_ERR_INVALID; }
+  net->train_gemm = mode;
+  return MZX_OK;
+}
+
+int mzx_net_train_gemm(const mzx_net* net) { return net ? net->train_gemm : 0; }
 
 int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream) {
   if (!net || !d_stats || !d_flat_out) { set_error("mzx_train_resnet_commit_stats: null argument"); return MZX_ERR_INVALID; }

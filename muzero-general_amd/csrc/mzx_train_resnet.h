@@ -33,6 +33,12 @@
 // positions; chunk partials go to scratch and RtnWgradFinishOp sums them in increasing chunk order.  No atomics anywhere:
 // a second call reproduces every bit.  MFMA operand layout: lane l feeds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15],
 // and holds D[4 (l >> 4) + r][l & 15] in accumulator register r.
+// The tiled variant (RtnTileGemmBody<MODE, WIDE>, mzx_train_gemm_tiled.h; the handle's train_gemm switch and the rule of
+// mzx_tuning.h decide per GEMM): a 256-thread workgroup per (chunk, 64 x 64 output tile), four waves of 32 x 32 (four MFMA
+// tiles each); K in slabs of 32, A [32][64] and B [32][64] gathered once per workgroup along the operand's contiguous axis
+// into LDS as [k][column ^ (k >> 2)] with a row stride of 80 floats, two buffers, the next slab's loads in flight behind
+// this slab's MFMAs, one barrier per slab.  Same operand functions, same MFMAs per output element in the same order, same
+// chunks: the same bits as the wave body.
 //
 // One precision switch, bool WIDE: a template parameter of the step (RtnRun<WIDE>) and so of every GEMM and BatchNorm
 // kernel of it; true for a network with a downsample stem, false for every other.  WIDE = false: a GEMM keeps four binary32
@@ -84,6 +90,7 @@
 #include "mzx_net.h"
 #include "mzx_train_step.h"
 #include "mzx_trainer.h"
+#include "mzx_tuning.h"
 #include "mzx_wave.h"
 
 namespace mzx {
@@ -196,9 +203,45 @@ MZX_HD inline void rtn_store(const RtnGemm& p, int m, int n, int chunk, float v)
   p.out[at] = v;
 }
 
-#ifndef MZX_HOSTCHECK
+// the position of row m for the two modes whose rows are positions
+template <int MODE>
+MZX_HD inline RtnPos rtn_row(const RtnGemm& p, int m) {
+  if (MODE == RTN_WGRAD) return RtnPos{0, 0, 0, 0};
+  return MODE == RTN_DGRAD ? rtn_pos(m, p.Hin, p.Win) : rtn_pos(m, p.H, p.W);
+}
+
+#ifdef MZX_HOSTCHECK
+// the serial build's tile, of both GEMM bodies: rows m0 .. m0 + span, columns n0 .. n0 + span, k0 .. k1 of `chunk`
+template <int MODE, bool WIDE>
+inline void rtn_serial_tile(const RtnGemm& p, int m0, int n0, int span, int chunk, int k0, int k1) {
+  for (int i = 0; i < span; ++i) {
+    const int m = m0 + i;
+    if (m >= p.M) break;
+    const RtnPos row = rtn_row<MODE>(p, m);
+    for (int j = 0; j < span; ++j) {
+      const int n = n0 + j;
+      if (n >= p.N) break;
+      float acc = 0.f;
+      double wide = 0.0;
+      for (int k = k0; k < k1; k += 16) {
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < 4; ++c) {
+          float& sum = WIDE ? t[c] : acc;
+          for (int kc = k + 4 * c; kc < k + 4 * c + 4 && kc < k1; ++kc) sum = fmaf(rtn_a<MODE>(p, m, kc, row), rtn_b<MODE>(p, kc, n), sum);
+        }
+        if (WIDE) for (int c = 0; c < 4; ++c) wide += (double)t[c];
+      }
+      rtn_store<MODE>(p, m, n, chunk, WIDE ? (float)wide : acc);
+    }
+  }
+}
+#else
 typedef float rtn_f32x4 __attribute__((ext_vector_type(4)));
 #endif
+
+// The LDS-tiled variant of the GEMM below (mzx_train_gemm_tiled.h: RtnTileGemmBody<mode, wide>, the same bits); the device
+// build compiles it in a translation unit of its own.
+int rtn_launch_tiled(int mode, bool wide, const RtnGemm& g, stream_t stream);
 
 // a wavefront per (chunk, 16 x 16 tile).  WIDE = false: four binary32 accumulator chains over the whole of K, joined
 // (0 + 1) + (2 + 3): they hide the MFMA's dependent latency, and four short sums joined at the end round less than one long
@@ -219,26 +262,7 @@ struct RtnGemmBody {
     const int k0 = chunk * p.kchunk;
     const int k1 = (p.K - k0 < p.kchunk) ? p.K : k0 + p.kchunk;
 #ifdef MZX_HOSTCHECK
-    for (int i = 0; i < 16; ++i) {
-      const int m = m0 + i;
-      if (m >= p.M) break;
-      const RtnPos row = row_of(m);
-      for (int j = 0; j < 16; ++j) {
-        const int n = n0 + j;
-        if (n >= p.N) break;
-        float acc = 0.f;
-        double wide = 0.0;
-        for (int k = k0; k < k1; k += 16) {
-          float t[4] = {0.f, 0.f, 0.f, 0.f};
-          for (int c = 0; c < 4; ++c) {
-            float& sum = WIDE ? t[c] : acc;
-            for (int kc = k + 4 * c; kc < k + 4 * c + 4 && kc < k1; ++kc) sum = fmaf(rtn_a<MODE>(p, m, kc, row), rtn_b<MODE>(p, kc, n), sum);
-          }
-          if (WIDE) for (int c = 0; c < 4; ++c) wide += (double)t[c];
-        }
-        rtn_store<MODE>(p, m, n, chunk, WIDE ? (float)wide : acc);
-      }
-    }
+    rtn_serial_tile<MODE, WIDE>(p, m0, n0, 16, chunk, k0, k1);
 #else
     const int r = lane & 15, q = lane >> 4;
     const int m = m0 + r, n = n0 + r;
@@ -268,11 +292,7 @@ struct RtnGemmBody {
     for (int i = 0; i < 4; ++i) rtn_store<MODE>(p, m0 + 4 * q + i, n, chunk, WIDE ? (float)wide[i] : joined[i]);
 #endif
   }
-  // the position of row m for the two modes whose rows are positions
-  MZX_HD RtnPos row_of(int m) const {
-    if (MODE == RTN_WGRAD) return RtnPos{0, 0, 0, 0};
-    return MODE == RTN_DGRAD ? rtn_pos(m, p.Hin, p.Win) : rtn_pos(m, p.H, p.W);
-  }
+  MZX_HD RtnPos row_of(int m) const { return rtn_row<MODE>(p, m); }
 };
 
 // out[e] = sum over chunks, in increasing order
@@ -876,6 +896,8 @@ struct RtnRun {
   int rc = 0;
   int launched = 0;
   bool dry = false;            // count the launches of a step without making them (no pointer is read)
+  int gemm_mode = 0;           // the handle's train_gemm: which GEMMs take the LDS-tiled body (train_gemm_tiled, mzx_tuning.h)
+  int tiled = 0;               // how many did
 
   template <class F> void go(F f) {
     if (rc) return;
@@ -936,7 +958,14 @@ struct RtnRun {
     return g;
   }
   template <int MODE>
-  void launch_gemm(const RtnGemm& g) { go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<MODE, WIDE>{g}, stream); }); }
+  void launch_gemm(const RtnGemm& g) {
+    if (train_gemm_tiled(gemm_mode, g.M, g.N, g.nchunks)) {
+      ++tiled;
+      go([&] { return rtn_launch_tiled(MODE, WIDE, g, stream); });
+    } else {
+      go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<MODE, WIDE>{g}, stream); });
+    }
+  }
   RtnBn<S> bn(int n, size_t i, int app, int napps) const {
     const RtnPlan& p = *P;
     const RtnLayer& L = p.net[n].l[i];

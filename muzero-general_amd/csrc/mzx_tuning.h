@@ -68,6 +68,20 @@ inline int exp_int(const char* name, int dflt) {
 #endif
 }
 
+// Which GEMMs of a residual training step take the LDS-tiled body (mzx_train_gemm_tiled.h) instead of the wave body, under
+// the handle's switch (mzx_net_set_train_gemm: 0 none, 1 this rule, 2 all).  Both bodies return the same bits, so the rule
+// is a pure tuning decision: a 64 x 64 workgroup tile needs rows and columns to fill it, and enough workgroups
+// (tiles x weight-gradient chunks) to occupy the device's 256 compute units -- below that the wave body's four times as many,
+// smaller work items spread better.
+constexpr int TRAIN_GEMM_TILED_MIN_M = 64;
+constexpr int TRAIN_GEMM_TILED_MIN_N = 32;
+constexpr int TRAIN_GEMM_TILED_MIN_WORKGROUPS = 256;
+inline bool train_gemm_tiled(int mode, int64_t M, int64_t N, int64_t chunks) {
+  if (mode != 1) return mode == 2;
+  return M >= TRAIN_GEMM_TILED_MIN_M && N >= TRAIN_GEMM_TILED_MIN_N &&
+         ((M + 63) / 64) * ((N + 63) / 64) * chunks >= TRAIN_GEMM_TILED_MIN_WORKGROUPS;
+}
+
 inline int tuning_find(const char* name) {
   if (!name) return -1;
   TuningEntry* t = tuning_table();

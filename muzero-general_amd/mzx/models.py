@@ -241,6 +241,8 @@ class HipNetwork:
         self._num_batches_tracked = {}
         if config.network == "resnet" and getattr(config, "train_downsample", False):
             self.train_stem = True
+        if config.network == "resnet" and getattr(config, "train_gemm", "wave") != "wave":
+            self.train_gemm = config.train_gemm
         self.set_weights(self._initial_weights())
 
     def __del__(self):
@@ -293,6 +295,22 @@ class HipNetwork:
     @train_stem.setter
     def train_stem(self, on):
         self.backend.lib.check(self.backend.lib.mzx_net_set_train_stem(self.handle, int(bool(on))))
+
+    TRAIN_GEMM_MODES = ("wave", "tiled", "tiled_all")
+
+    @property
+    def train_gemm(self):
+        """The GEMM body of ``mzx_train_resnet_step`` on this handle (``mzx_net_set_train_gemm``): ``"wave"`` (the default,
+        a wavefront per 16 x 16 tile), ``"tiled"`` (a workgroup per 64 x 64 tile with operands staged through LDS, for the
+        GEMMs the library's rule picks) or ``"tiled_all"`` (for every GEMM).  Every route returns the same bits;
+        ``config.train_gemm`` sets it at construction.  Setting it on a fully connected network raises."""
+        return self.TRAIN_GEMM_MODES[self.backend.lib.mzx_net_train_gemm(self.handle)]
+
+    @train_gemm.setter
+    def train_gemm(self, mode):
+        if mode not in self.TRAIN_GEMM_MODES:
+            raise ValueError(f"train_gemm: {mode!r} is none of {self.TRAIN_GEMM_MODES}")
+        self.backend.lib.check(self.backend.lib.mzx_net_set_train_gemm(self.handle, self.TRAIN_GEMM_MODES.index(mode)))
 
     def state_dict(self):
         out = collections.OrderedDict()

@@ -30,6 +30,10 @@ A configuration with a downsample stem (``downsample = "resnet"`` / ``"CNN"``: b
 the stem's training on for that handle (``mzx_net_set_train_stem``); then the strided and biased convolutions, the stem's
 BatchNorm blocks and its three kinds of pool are trained as well, and the ``representation_network.module.conv`` / ``.bn``
 the stem bypasses keep zero gradients, their statistics and their ``num_batches_tracked``.
+``config.train_gemm`` / ``HipNetwork.train_gemm`` (``"wave"``, ``"tiled"``, ``"tiled_all"``; ``mzx_net_set_train_gemm``) picks
+the body of the step's GEMMs -- a wavefront per 16 x 16 tile, or a workgroup per 64 x 64 tile with operands staged through
+LDS (csrc/mzx_train_gemm_tiled.h); ``train_step``, ``train_steps`` and the ``Trainer`` worker pick it up through the handle,
+and every result has the same bits on either route.
 ``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
 convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """

@@ -11,6 +11,8 @@ One training step (Adam) of the shipped networks on the GPU, natively and throug
     python muzero-general_amd/tools/train_bench.py --family fc|resnet|stem [--out FILE] [--quick] [--shape NAME]
     python muzero-general_amd/tools/train_bench.py --family chain [--out FILE] [--quick] [--shape NAME]   (whole steps: per-step loop
               with torch.optim.Adam | with mzx.optim.Adam | mzx.trainer.train_steps in chunks of 16; the optimizer launch alone)
+    python muzero-general_amd/tools/train_bench.py --family tiled [--out FILE] [--quick] [--shape NAME]   (the GEMM routes of one handle:
+              train_gemm = "wave" (the yardstick) | "tiled" | "tiled_all"; --trace a|b|c runs one of them alone)
     python muzero-general_amd/tools/train_bench.py --family fc --trace a|b|c --trace-steps N   (under rocprofv3 --kernel-trace --stats)
     python muzero-general_amd/tools/train_bench.py --family fc --launches DIR_N1 N1 DIR_N2 N2  (kernel dispatches per step from two traces)
 
@@ -68,14 +70,26 @@ FAMILIES = {      # shapes: name -> (batch, steps) as shipped; warm-up calls, (b
                        "mzx.optim.Adam, chain = mzx.trainer.train_steps in chunks of 16; one process, legs alternate block by "
                        "block, medians of timed blocks [min, max], every block ends in ONE synchronise; then the optimizer launch "
                        "alone (HIP events) against torch's Adam over the same flat parameter"),
+    # the GEMM routes of mzx_net_set_train_gemm on ONE handle: name -> (case family, batch (halved until the scratch fits), steps,
+    # steps per timed block)
+    "tiled": dict(shapes={"tictactoe": ("resnet", 64, 21, 5), "connect4": ("resnet", 64, 43, 5), "gomoku": ("resnet", 1024, 6, 1),
+                          "breakout": ("stem", 16, 6, 5), "atari": ("stem", 256, 6, 1)},
+                  adam=dict(lr=0.003, weight_decay=1e-4), blocks=7, quick=3, log="resnet_train_tiled_bench.log",
+                  what="one training step (update_weights with a HipNetwork, Adam) per GEMM route of the SAME handle: wave_ms = "
+                       "train_gemm 'wave' (the yardstick: a wavefront per 16 x 16 tile), tiled_ms = 'tiled' (the LDS-tiled body where "
+                       "the rule of mzx_tuning.h picks it), tiled_all_ms = 'tiled_all'; legs alternate block by block, medians of "
+                       "the timed blocks [min, max], every call ends in a synchronise; a gain is claimed only beyond the larger of "
+                       "the two legs' spreads; tiled_equals_wave: gradients, statistics, logits and losses bit for bit at the timed "
+                       "size; tiled_launches: mzx_train_resnet_tiled_launches of 'tiled' / 'tiled_all'; torch_ms (stem shapes): "
+                       "update_weights with the torch network"),
 }
 
 
-def shape_of(be, name):
-    """(batch, steps) of a stem network: the shipped batch, halved until the native step's scratch fits train_scratch_max_bytes."""
+def shape_of(be, name, family="stem"):
+    """(batch, steps) of a network: the family's batch, halved until the native step's scratch fits train_scratch_max_bytes."""
     from mzx import configs, models, trainer
 
-    B, steps = FAMILIES["stem"]["shapes"][name]
+    B, steps = FAMILIES[family]["shapes"][name][-3:-1] if family == "tiled" else FAMILIES[family]["shapes"][name]
     probe = models.MuZeroNetwork(getattr(configs, name)(train_downsample=True), _backend=be)
     while B > 1:
         need = int(be.lib.mzx_train_resnet_scratch_bytes(probe.handle, B, steps))
@@ -153,6 +167,80 @@ def measure(be, family, name, quick):
         line[f"{leg}_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
     line["torch_over_native"] = round(line["torch_ms"] / line["native_ms"], 3)
     line.update(info)
+    return line
+
+
+def tiled_legs(be, name):
+    """({route: the step on that route} on one handle and one optimizer, the torch step or None, the case, its module)."""
+    from mzx import configs, trainer
+
+    family = FAMILIES["tiled"]["shapes"][name][0]
+    cases = importlib.import_module(FAMILIES[family]["cases"])
+    B, steps = shape_of(be, name, "tiled")
+    case = cases.case_of_config(getattr(configs, name)(), B, steps, name=name)
+    cfg = cases.config_of(case)
+    batch = tuple(None if x is None else torch.from_numpy(x).to(be.device) for x in cases.batch(case))
+    net = cases.network(be, case)
+    optimizer = torch.optim.Adam(net.parameters(), **FAMILIES["tiled"]["adam"])
+
+    def step(route):
+        net.train_gemm = route
+        trainer.update_weights(net, optimizer, batch, cfg)
+
+    fns = {route: (lambda route=route: step(route)) for route in ("wave", "tiled", "tiled_all")}
+    torch_step = None
+    if family == "stem":
+        model = cases.load(getattr(cases, FAMILIES[family]["torch_net"])(case), cases.weights(case)).to(be.device).train()
+        opt_torch = torch.optim.Adam(model.parameters(), **FAMILIES["tiled"]["adam"])
+        torch_step = lambda: trainer.update_weights(model, opt_torch, batch, cfg)
+    return fns, torch_step, case, cases, net
+
+
+def tiled_measure(be, name, quick):
+    import numpy
+
+    import resnet_train_cases
+
+    fam = FAMILIES["tiled"]
+    fns, torch_step, case, cases, net = tiled_legs(be, name)
+    size = (case["B"], case["steps"])
+    line = dict(shape=f"{name}_b{size[0]}_k{size[1]}", optimizer="Adam", launches=int(be.lib.mzx_train_resnet_launches(net.handle, *size)))
+    # the same bits on every route, at the timed size and before any weight moves
+    got, line["tiled_launches"] = {}, {}
+    for route in fns:
+        net.train_gemm = route
+        got[route] = resnet_train_cases.run_native(be, case, net, cases)
+        if route != "wave":
+            line["tiled_launches"][route] = int(be.lib.mzx_train_resnet_tiled_launches(net.handle, *size))
+    bits = lambda a: numpy.ascontiguousarray(a, numpy.float32).view(numpy.int32)
+    line["tiled_equals_wave"] = all(numpy.array_equal(bits(got[route][key]), bits(value))
+                                    for route in ("tiled", "tiled_all") for key, value in got["wave"].items())
+    assert line["tiled_equals_wave"], line
+    del got
+    blocks, iters = fam["quick"] if quick else fam["blocks"], fam["shapes"][name][3]
+    timed = dict(fns, **({"torch": torch_step} if torch_step else {}))
+    times = {leg: [] for leg in timed}
+    for fn in timed.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for leg, fn in timed.items():
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            times[leg].append((time.perf_counter() - t0) * 1e3 / iters)
+    line.update(blocks=blocks, steps_per_block=iters)
+    for leg, ts in times.items():
+        line[f"{leg}_ms"] = round(statistics.median(ts), 3)
+        line[f"{leg}_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+    spread = lambda leg: max(times[leg]) - min(times[leg])
+    for leg in ("tiled", "tiled_all"):
+        line[f"wave_over_{leg}"] = round(line["wave_ms"] / line[f"{leg}_ms"], 3)
+        beyond = abs(line["wave_ms"] - line[f"{leg}_ms"]) > max(spread("wave"), spread(leg))
+        line[f"{leg}_claim"] = "no gain claimed" if not beyond else "faster" if line[f"{leg}_ms"] < line["wave_ms"] else "slower"
+    if torch_step:
+        line["torch_over_tiled"] = round(line["torch_ms"] / line["tiled_ms"], 3)
     return line
 
 
@@ -295,7 +383,10 @@ def main():
     if args.family == "chain" and args.trace:
         ap.error("--trace belongs to the step families")
     if args.trace:
-        fn = legs(be, args.family, names[0])[0][args.trace]
+        if args.family == "tiled":
+            fn = tiled_legs(be, names[0])[0][dict(a="wave", b="tiled", c="tiled_all")[args.trace]]
+        else:
+            fn = legs(be, args.family, names[0])[0][args.trace]
         for _ in range(args.trace_steps):
             fn()
         torch.cuda.synchronize()
@@ -313,7 +404,8 @@ def main():
                 log.write("\n".join(lines) + "\n")
         return
     for name in names:
-        lines.append(json.dumps(measure(be, args.family, name, args.quick)))
+        line = tiled_measure(be, name, args.quick) if args.family == "tiled" else measure(be, args.family, name, args.quick)
+        lines.append(json.dumps(line))
         print(lines[-1], flush=True)
         with open(out, "w") as log:
             log.write("\n".join(lines) + "\n")
