@@ -1022,6 +1022,36 @@ int mzx_net_train_gemm(const mzx_net* net);
 int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps);
 
 /* ------------------------------------------------------------------------- *
+ * The matrix arithmetic of the LDS-tiled route above, per handle and orthogonal to mzx_net_set_train_gemm: which
+ * instructions multiply in the GEMMs that switch sends to the tiled route (csrc/mzx_train_gemm_split.h).  GEMMs on the wave
+ * body are never affected: under MZX_TRAIN_GEMM_WAVE this switch changes nothing.
+ *   MZX_TRAIN_MATRIX_F32     the default: v_mfma_f32_16x16x4_f32 on the binary32 operands, the bits of the wave body.
+ *   MZX_TRAIN_MATRIX_BF16X3  v_mfma_f32_16x16x32_bf16 on split operands.  Every binary32 operand x is split, once per
+ *                            workgroup and exactly, into three BF16 terms under round-to-nearest-even:
+ *                                h = bf16(x)    m = bf16(x - h)    l = bf16(x - h - m)        x == h + m + l
+ *                            and per 16 x 16 output tile and 32 values of k six of the nine partial products (each exact in
+ *                            binary32, accumulated in binary32) are issued in this order, written A-term.B-term:
+ *                                l.h  h.l  m.m  m.h  h.m  h.h
+ *                            The dropped terms m.l + l.m + l.l are below 2^-23 |a| |b|.  Without a downsample stem one
+ *                            binary32 accumulator per output element runs through all of K (a weight-gradient chunk); with
+ *                            one every instruction starts from zero and is added to a binary64 accumulator, rounded once.
+ *                            Deterministic (no atomics), but NOT the bits of the F32 arithmetic: its contract is the
+ *                            accuracy the binary32 routes are held to against a binary64 reference.
+ *   mzx_net_set_train_matrix(net, mode): MZX_ERR_INVALID, with a text in mzx_last_error(), for a null handle, a fully
+ *     connected network or another mode.
+ *   mzx_net_train_matrix(net): the mode (0 for null).
+ *   mzx_train_resnet_split_launches(net, batch, steps): how many GEMM launches of a step take the split body under the
+ *     handle's two modes: 0 under MZX_TRAIN_GEMM_WAVE or MZX_TRAIN_MATRIX_F32 and where the step is unsupported,
+ *     mzx_train_resnet_tiled_launches otherwise.  mzx_train_resnet_launches and mzx_train_resnet_scratch_bytes do not
+ *     depend on the mode.
+ * ------------------------------------------------------------------------- */
+#define MZX_TRAIN_MATRIX_F32 0
+#define MZX_TRAIN_MATRIX_BF16X3 1
+int mzx_net_set_train_matrix(mzx_net* net, int mode);
+int mzx_net_train_matrix(const mzx_net* net);
+int64_t mzx_train_resnet_split_launches(const mzx_net* net, int32_t batch, int32_t steps);
+
+/* ------------------------------------------------------------------------- *
  * The optimizer step over the flat parameter buffer (csrc/mzx_optim.h): torch.optim.Adam (no amsgrad, no maximize) and
  * torch.optim.SGD (dampening 0, no nesterov) as ONE elementwise launch, no atomics: the same bits on every run.
  * Only the LIVE SPANS of the buffer are visited: h_spans [num_spans][2] holds (offset, count) pairs in elements (count

@@ -22,6 +22,7 @@ FLAGS = [
 # per translation unit, beyond FLAGS: the tiled training GEMMs are compiled without the packed binary32 instructions
 FILE_FLAGS = {
     "mzx_train_gemm_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "mzx_train_gemm_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

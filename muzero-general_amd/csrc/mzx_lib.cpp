@@ -26,6 +26,7 @@
 #include "mzx_tree_carry.h"
 #ifdef MZX_HOSTCHECK
 #include "mzx_train_gemm_tiled.h"      // (the device build compiles the tiled GEMMs in mzx_train_gemm_tiled.hip)
+#include "mzx_train_gemm_split.h"      // (and their split-BF16 arithmetic in mzx_train_gemm_split.hip)
 #else
 #include "mzx_fused_fc.h"
 #include "mzx_fused_fc2.h"
@@ -1584,21 +1585,25 @@ int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_
 
 int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat_floats(net) : 0; }
 
-// the dry run of a step: its launches (with the two of the loss head), or how many of its GEMMs take the LDS-tiled body
-static int64_t rtn_dry_run(const mzx_net* net, int32_t batch, int32_t steps, bool tiled) {
+// the dry run of a step: its launches (with the two of the loss head), or how many of its GEMMs take the LDS-tiled route,
+// or how many of those the split-BF16 body
+enum RtnCount { RTN_COUNT_LAUNCHES, RTN_COUNT_TILED, RTN_COUNT_SPLIT };
+static int64_t rtn_dry_run(const mzx_net* net, int32_t batch, int32_t steps, RtnCount what) {
   return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [&](const RtnPlan& plan) {
     RtnRun<false> run;      // (the launches of a step do not depend on its precision)
     memset((void*)&run, 0, sizeof(run));
-    run.P = &plan; run.dry = true; run.gemm_mode = net->train_gemm;
+    run.P = &plan; run.dry = true; run.gemm_mode = net->train_gemm; run.matrix_mode = net->train_matrix;
     run.forward();
     run.backward();
-    return tiled ? run.tiled : run.launched + 2;
+    return what == RTN_COUNT_TILED ? run.tiled : what == RTN_COUNT_SPLIT ? run.split : run.launched + 2;
   });
 }
 
-int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, false); }
+int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_LAUNCHES); }
 
-int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, true); }
+int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_TILED); }
+
+int64_t mzx_train_resnet_split_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_SPLIT); }
 
 // forward pass, loss head, backward pass of a planned step
 extern "C++" template <bool WIDE>
@@ -1608,7 +1613,7 @@ int rtn_step(const mzx_net* net, const mzx_train_resnet_io* io, const RtnPlan& P
   memset((void*)&run, 0, sizeof(run));
   run.P = &P; run.flat = io->d_flat; run.obs = io->d_observation; run.action = io->d_action;
   run.scratch = scratch; run.grad = io->d_grad_flat; run.stats = io->d_stats; run.stream = (stream_t)stream;
-  run.gemm_mode = net->train_gemm;
+  run.gemm_mode = net->train_gemm; run.matrix_mode = net->train_matrix;
   const mzx_trainer_loss_io lio = train_head_io(reinterpret_cast<const mzx_train_fc_io*>(io), P, scratch, net->cfg.support_size,
                                                 run.vlog, run.rlog, run.plog);
   run.forward();
@@ -1644,6 +1649,16 @@ int mzx_net_set_train_gemm(mzx_net* net, int mode) {
 }
 
 int mzx_net_train_gemm(const mzx_net* net) { return net ? net->train_gemm : 0; }
+
+int mzx_net_set_train_matrix(mzx_net* net, int mode) {
+  if (!net) { set_error("mzx_net_set_train_matrix: null network handle"); return MZX_ERR_INVALID; }
+  if (net->cfg.network != 1) { set_error("mzx_net_set_train_matrix: fully connected networks do not train through the residual GEMMs"); return MZX_ERR_INVALID; }
+  if (mode < MZX_TRAIN_MATRIX_F32 || mode > MZX_TRAIN_MATRIX_BF16X3) { set_error("mzx_net_set_train_matrix: unknown mode (0 f32, 1 bf16x3)"); return MZX_ERR_INVALID; }
+  net->train_matrix = mode;
+  return MZX_OK;
+}
+
+int mzx_net_train_matrix(const mzx_net* net) { return net ? net->train_matrix : 0; }
 
 int mzx_train_resnet_commit_stats(const mzx_net* net, const float* d_stats, float* d_flat_out, void* stream) {
   if (!net || !d_stats || !d_flat_out) { set_error("mzx_train_resnet_commit_stats: null argument"); return MZX_ERR_INVALID; }

@@ -39,6 +39,9 @@
 // into LDS as [k][column ^ (k >> 2)] with a row stride of 80 floats, two buffers, the next slab's loads in flight behind
 // this slab's MFMAs, one barrier per slab.  Same operand functions, same MFMAs per output element in the same order, same
 // chunks: the same bits as the wave body.
+// The tiled route has a second arithmetic behind the handle's train_matrix switch (RtnSplitGemmBody<MODE, WIDE>,
+// mzx_train_gemm_split.h): every operand split once per workgroup into three BF16 terms, six v_mfma_f32_16x16x32_bf16 per
+// tile and 32 k.  Off by default; it is held to the reference gates, not to the wave body's bits.
 //
 // One precision switch, bool WIDE: a template parameter of the step (RtnRun<WIDE>) and so of every GEMM and BatchNorm
 // kernel of it; true for a network with a downsample stem, false for every other.  WIDE = false: a GEMM keeps four binary32
@@ -242,6 +245,9 @@ typedef float rtn_f32x4 __attribute__((ext_vector_type(4)));
 // The LDS-tiled variant of the GEMM below (mzx_train_gemm_tiled.h: RtnTileGemmBody<mode, wide>, the same bits); the device
 // build compiles it in a translation unit of its own.
 int rtn_launch_tiled(int mode, bool wide, const RtnGemm& g, stream_t stream);
+// The split-BF16 arithmetic of the tiled route (mzx_train_gemm_split.h: RtnSplitGemmBody<mode, wide>, six BF16 MFMAs per 32 k
+// on operands split into three BF16 terms; held to the reference gates, not to the bits above), likewise.
+int rtn_launch_split(int mode, bool wide, const RtnGemm& g, stream_t stream);
 
 // a wavefront per (chunk, 16 x 16 tile).  WIDE = false: four binary32 accumulator chains over the whole of K, joined
 // (0 + 1) + (2 + 3): they hide the MFMA's dependent latency, and four short sums joined at the end round less than one long
@@ -898,6 +904,8 @@ struct RtnRun {
   bool dry = false;            // count the launches of a step without making them (no pointer is read)
   int gemm_mode = 0;           // the handle's train_gemm: which GEMMs take the LDS-tiled body (train_gemm_tiled, mzx_tuning.h)
   int tiled = 0;               // how many did
+  int matrix_mode = 0;         // the handle's train_matrix: 1 = the tiled route runs the split-BF16 body (mzx_train_gemm_split.h)
+  int split = 0;               // how many GEMMs took it
 
   template <class F> void go(F f) {
     if (rc) return;
@@ -961,7 +969,12 @@ struct RtnRun {
   void launch_gemm(const RtnGemm& g) {
     if (train_gemm_tiled(gemm_mode, g.M, g.N, g.nchunks)) {
       ++tiled;
-      go([&] { return rtn_launch_tiled(MODE, WIDE, g, stream); });
+      if (matrix_mode == 1) {
+        ++split;
+        go([&] { return rtn_launch_split(MODE, WIDE, g, stream); });
+      } else {
+        go([&] { return rtn_launch_tiled(MODE, WIDE, g, stream); });
+      }
     } else {
       go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<MODE, WIDE>{g}, stream); });
     }

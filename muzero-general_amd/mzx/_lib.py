@@ -341,6 +341,9 @@ PROTOTYPES = {
     "mzx_net_set_train_gemm": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mzx_net_train_gemm": (ctypes.c_int, [c_vp]),
     "mzx_train_resnet_tiled_launches": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_net_set_train_matrix": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "mzx_net_train_matrix": (ctypes.c_int, [c_vp]),
+    "mzx_train_resnet_split_launches": (c_i64, [c_vp, c_i32, c_i32]),
     "mzx_optim_chunks": (c_i64, [c_vp, c_i32, c_i64, c_vp, c_i64]),
     "mzx_optim_step": (ctypes.c_int, [ctypes.POINTER(OptimIO), c_vp]),
     "mzx_train_chain_supported": (ctypes.c_int, [c_vp, c_i32, c_i32]),

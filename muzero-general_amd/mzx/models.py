@@ -243,6 +243,8 @@ class HipNetwork:
             self.train_stem = True
         if config.network == "resnet" and getattr(config, "train_gemm", "wave") != "wave":
             self.train_gemm = config.train_gemm
+        if config.network == "resnet" and getattr(config, "train_matrix", "f32") != "f32":
+            self.train_matrix = config.train_matrix
         self.set_weights(self._initial_weights())
 
     def __del__(self):
@@ -311,6 +313,23 @@ class HipNetwork:
         if mode not in self.TRAIN_GEMM_MODES:
             raise ValueError(f"train_gemm: {mode!r} is none of {self.TRAIN_GEMM_MODES}")
         self.backend.lib.check(self.backend.lib.mzx_net_set_train_gemm(self.handle, self.TRAIN_GEMM_MODES.index(mode)))
+
+    TRAIN_MATRIX_MODES = ("f32", "bf16x3")
+
+    @property
+    def train_matrix(self):
+        """The matrix arithmetic of the GEMMs that ``train_gemm`` sends to the tiled route (``mzx_net_set_train_matrix``):
+        ``"f32"`` (the default: FP32 matrix instructions, the wave body's bits) or ``"bf16x3"`` (every operand split into
+        three BF16 terms, six BF16 matrix instructions per 32 k: within the FP32 routes' accuracy gates, other bits).  Under
+        ``train_gemm = "wave"`` it changes nothing.  ``config.train_matrix`` sets it at construction.  Setting it on a fully
+        connected network raises."""
+        return self.TRAIN_MATRIX_MODES[self.backend.lib.mzx_net_train_matrix(self.handle)]
+
+    @train_matrix.setter
+    def train_matrix(self, mode):
+        if mode not in self.TRAIN_MATRIX_MODES:
+            raise ValueError(f"train_matrix: {mode!r} is none of {self.TRAIN_MATRIX_MODES}")
+        self.backend.lib.check(self.backend.lib.mzx_net_set_train_matrix(self.handle, self.TRAIN_MATRIX_MODES.index(mode)))
 
     def state_dict(self):
         out = collections.OrderedDict()

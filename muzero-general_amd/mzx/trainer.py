@@ -34,6 +34,10 @@ the stem bypasses keep zero gradients, their statistics and their ``num_batches_
 the body of the step's GEMMs -- a wavefront per 16 x 16 tile, or a workgroup per 64 x 64 tile with operands staged through
 LDS (csrc/mzx_train_gemm_tiled.h); ``train_step``, ``train_steps`` and the ``Trainer`` worker pick it up through the handle,
 and every result has the same bits on either route.
+``config.train_matrix`` / ``HipNetwork.train_matrix`` (``"f32"``, ``"bf16x3"``; ``mzx_net_set_train_matrix``) picks the matrix
+arithmetic of the GEMMs that take the tiled route, and is picked up through the handle in the same way: ``"bf16x3"`` splits
+every binary32 operand into three BF16 terms and multiplies on the BF16 matrix pipes (csrc/mzx_train_gemm_split.h).  That
+route is deterministic and meets the accuracy gates of the FP32 routes, but does not return their bits.
 ``update_lr`` is the reference's schedule; ``optimizer_state`` / ``load_optimizer_state``
 convert between the flat optimizer state and the reference's per-parameter ``state_dict`` (checkpoints round-trip).
 """

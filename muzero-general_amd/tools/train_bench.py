@@ -13,6 +13,8 @@ One training step (Adam) of the shipped networks on the GPU, natively and throug
               with torch.optim.Adam | with mzx.optim.Adam | mzx.trainer.train_steps in chunks of 16; the optimizer launch alone)
     python muzero-general_amd/tools/train_bench.py --family tiled [--out FILE] [--quick] [--shape NAME]   (the GEMM routes of one handle:
               train_gemm = "wave" (the yardstick) | "tiled" | "tiled_all"; --trace a|b|c runs one of them alone)
+    python muzero-general_amd/tools/train_bench.py --family split [--out FILE] [--quick] [--shape NAME]   (the matrix arithmetic of the
+              tiled route on one handle: 'wave' | 'tiled' + 'f32' (the yardstick) | 'tiled' + 'bf16x3'; --trace a|b|c likewise)
     python muzero-general_amd/tools/train_bench.py --family fc --trace a|b|c --trace-steps N   (under rocprofv3 --kernel-trace --stats)
     python muzero-general_amd/tools/train_bench.py --family fc --launches DIR_N1 N1 DIR_N2 N2  (kernel dispatches per step from two traces)
 
@@ -82,7 +84,23 @@ FAMILIES = {      # shapes: name -> (batch, steps) as shipped; warm-up calls, (b
                        "the two legs' spreads; tiled_equals_wave: gradients, statistics, logits and losses bit for bit at the timed "
                        "size; tiled_launches: mzx_train_resnet_tiled_launches of 'tiled' / 'tiled_all'; torch_ms (stem shapes): "
                        "update_weights with the torch network"),
+    # the matrix arithmetic of the tiled route (mzx_net_set_train_matrix) on ONE handle, at the shapes of "tiled"
+    "split": dict(adam=dict(lr=0.003, weight_decay=1e-4), blocks=7, quick=3, log="resnet_train_split_bench.log",
+                  what="one training step (update_weights with a HipNetwork, Adam) per route of the SAME handle: wave_ms = train_gemm "
+                       "'wave'; f32_ms = 'tiled' + train_matrix 'f32' (the yardstick: the LDS-tiled binary32 MFMA body where the rule "
+                       "of mzx_tuning.h picks it); bf16x3_ms = 'tiled' + 'bf16x3' (the same GEMMs on the split-BF16 body, "
+                       "csrc/mzx_train_gemm_split.h); legs alternate block by block, medians of the timed blocks [min, max], every "
+                       "call ends in a synchronise; bf16x3_claim: a gain (or loss) against f32_ms counts only beyond the larger of the "
+                       "two legs' spreads; f32_equals_wave: bit for bit at the timed size; split_meets_gates: every logit of the "
+                       "bf16x3 step within the case module's LOGIT_GATE of the wave step, and every gradient / statistic tensor "
+                       "within max(4 e, PARAM_GRAD_ERROR_FLOOR) of it, e = the distance of torch's float32 step on the device from "
+                       "the wave step on that tensor (the module's per-tensor gate with the wave step in the place of the binary64 "
+                       "reference); split_worst: the largest fraction of that gate reached, split_worst_distance the bf16x3 step's distance "
+                       "from the wave step on that key and torch_f32_distance_there that of torch's float32 step; split_launches: "
+                       "mzx_train_resnet_split_launches; torch_ms (stem shapes): update_weights with the torch network"),
 }
+FAMILIES["split"]["shapes"] = FAMILIES["tiled"]["shapes"]
+SPLIT_ROUTES = {"wave": ("wave", "f32"), "f32": ("tiled", "f32"), "bf16x3": ("tiled", "bf16x3")}
 
 
 def shape_of(be, name, family="stem"):
@@ -170,8 +188,9 @@ def measure(be, family, name, quick):
     return line
 
 
-def tiled_legs(be, name):
-    """({route: the step on that route} on one handle and one optimizer, the torch step or None, the case, its module)."""
+def tiled_legs(be, name, routes=None):
+    """({route: the step on that route} on one handle and one optimizer, the torch step or None, the case, its module);
+    ``routes``: name -> (train_gemm, train_matrix), by default the three values of train_gemm."""
     from mzx import configs, trainer
 
     family = FAMILIES["tiled"]["shapes"][name][0]
@@ -183,11 +202,13 @@ def tiled_legs(be, name):
     net = cases.network(be, case)
     optimizer = torch.optim.Adam(net.parameters(), **FAMILIES["tiled"]["adam"])
 
+    routes = routes or {route: (route, "f32") for route in ("wave", "tiled", "tiled_all")}
+
     def step(route):
-        net.train_gemm = route
+        net.train_gemm, net.train_matrix = routes[route]
         trainer.update_weights(net, optimizer, batch, cfg)
 
-    fns = {route: (lambda route=route: step(route)) for route in ("wave", "tiled", "tiled_all")}
+    fns = {route: (lambda route=route: step(route)) for route in routes}
     torch_step = None
     if family == "stem":
         model = cases.load(getattr(cases, FAMILIES[family]["torch_net"])(case), cases.weights(case)).to(be.device).train()
@@ -241,6 +262,72 @@ def tiled_measure(be, name, quick):
         line[f"{leg}_claim"] = "no gain claimed" if not beyond else "faster" if line[f"{leg}_ms"] < line["wave_ms"] else "slower"
     if torch_step:
         line["torch_over_tiled"] = round(line["torch_ms"] / line["tiled_ms"], 3)
+    return line
+
+
+def split_measure(be, name, quick):
+    import numpy
+
+    import resnet_train_cases
+
+    fam = FAMILIES["split"]
+    fns, torch_step, case, cases, net = tiled_legs(be, name, SPLIT_ROUTES)
+    size = (case["B"], case["steps"])
+    line = dict(shape=f"{name}_b{size[0]}_k{size[1]}", optimizer="Adam", launches=int(be.lib.mzx_train_resnet_launches(net.handle, *size)))
+    # before any weight moves, at the timed size: f32 = wave bit for bit; bf16x3 against wave within the module's gates
+    got = {}
+    for route, modes in SPLIT_ROUTES.items():
+        net.train_gemm, net.train_matrix = modes
+        got[route] = resnet_train_cases.run_native(be, case, net, cases)
+    line["tiled_launches"] = int(be.lib.mzx_train_resnet_tiled_launches(net.handle, *size))
+    line["split_launches"] = int(be.lib.mzx_train_resnet_split_launches(net.handle, *size))
+    bits = lambda a: numpy.ascontiguousarray(a, numpy.float32).view(numpy.int32)
+    line["f32_equals_wave"] = all(numpy.array_equal(bits(got["f32"][key]), bits(value)) for key, value in got["wave"].items())
+    assert line["f32_equals_wave"], line
+    other = cases.torch_step(case, torch.float32, device=be.device)
+    distance = lambda a, b: float(numpy.max(numpy.abs(numpy.asarray(a, numpy.float64).reshape(-1) - numpy.asarray(b, numpy.float64).reshape(-1))))
+    worst = (0.0, None)
+    for key, value in got["wave"].items():
+        if key.endswith("_logits"):
+            finite = numpy.isfinite(value)
+            fraction = distance(got["bf16x3"][key][finite], value[finite]) / cases.LOGIT_GATE
+        elif key[:5] in ("grad/", "stat/") and key in other:
+            gate = max(4 * distance(other[key], value), cases.PARAM_GRAD_ERROR_FLOOR)
+            fraction = distance(got["bf16x3"][key], value) / gate
+        else:
+            continue
+        if fraction > worst[0]:
+            worst = (fraction, key)
+    line["split_meets_gates"] = worst[0] <= 1.0
+    line["split_worst"] = [round(worst[0], 4), worst[1]]
+    if worst[1]:      # for scale, on that key: bf16x3 from wave, and torch's float32 step from wave
+        finite = numpy.isfinite(got["wave"][worst[1]])
+        line["split_worst_distance"] = distance(got["bf16x3"][worst[1]][finite], got["wave"][worst[1]][finite])
+        line["torch_f32_distance_there"] = distance(numpy.asarray(other[worst[1]])[finite], got["wave"][worst[1]][finite])
+    del got, other
+    blocks, iters = fam["quick"] if quick else fam["blocks"], fam["shapes"][name][3]
+    timed = dict(fns, **({"torch": torch_step} if torch_step else {}))
+    times = {leg: [] for leg in timed}
+    for fn in timed.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for leg, fn in timed.items():
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            times[leg].append((time.perf_counter() - t0) * 1e3 / iters)
+    line.update(blocks=blocks, steps_per_block=iters)
+    for leg, ts in times.items():
+        line[f"{leg}_ms"] = round(statistics.median(ts), 3)
+        line[f"{leg}_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+    spread = lambda leg: max(times[leg]) - min(times[leg])
+    line["f32_over_bf16x3"] = round(line["f32_ms"] / line["bf16x3_ms"], 3)
+    beyond = abs(line["f32_ms"] - line["bf16x3_ms"]) > max(spread("f32"), spread("bf16x3"))
+    line["bf16x3_claim"] = "no gain claimed" if not beyond else "faster" if line["bf16x3_ms"] < line["f32_ms"] else "slower"
+    if torch_step:
+        line["torch_over_bf16x3"] = round(line["torch_ms"] / line["bf16x3_ms"], 3)
     return line
 
 
@@ -385,6 +472,8 @@ def main():
     if args.trace:
         if args.family == "tiled":
             fn = tiled_legs(be, names[0])[0][dict(a="wave", b="tiled", c="tiled_all")[args.trace]]
+        elif args.family == "split":
+            fn = tiled_legs(be, names[0], SPLIT_ROUTES)[0][dict(a="wave", b="f32", c="bf16x3")[args.trace]]
         else:
             fn = legs(be, args.family, names[0])[0][args.trace]
         for _ in range(args.trace_steps):
@@ -404,7 +493,10 @@ def main():
                 log.write("\n".join(lines) + "\n")
         return
     for name in names:
-        line = tiled_measure(be, name, args.quick) if args.family == "tiled" else measure(be, args.family, name, args.quick)
+        if args.family in ("tiled", "split"):
+            line = (tiled_measure if args.family == "tiled" else split_measure)(be, name, args.quick)
+        else:
+            line = measure(be, args.family, name, args.quick)
         lines.append(json.dumps(line))
         print(lines[-1], flush=True)
         with open(out, "w") as log:
