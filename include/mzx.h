@@ -1013,13 +1013,35 @@ int mzx_net_train_stem(const mzx_net* net);
  *   mzx_train_resnet_tiled_launches(net, batch, steps): how many GEMM launches of a step take the tiled body under the
  *     handle's mode; 0 in mode 0 and where the step is unsupported.  mzx_train_resnet_launches and
  *     mzx_train_resnet_scratch_bytes do not depend on the mode.
+ *
+ * A third body, csrc/mzx_train_gemm_ksplit.h, serves the GEMMs that have too few output tiles to fill the device but a long
+ * K (the per-step dynamics convolutions): a 256-thread workgroup per 32 x 32 output tile whose four waves each own the whole
+ * tile and every fourth k-group of 16, with the next group's operands requested before this group's matrix instructions,
+ * and the four partial tiles joined through LDS in the fixed order (w0 + w1) + (w2 + w3) -- in binary64, rounded once, for a
+ * network with a downsample stem.  It sums K in another order than the two bodies above: deterministic (no atomics, a second
+ * call repeats every bit) but NOT their bits; its contract is the accuracy they are held to against a binary64 reference.
+ *   mzx_net_set_train_gemm_route(net, mode): the same switch over its whole range -- the three modes above, with their exact
+ *   behaviour, and
+ *     MZX_TRAIN_GEMM_KSPLIT      as MZX_TRAIN_GEMM_TILED for the GEMMs its rule picks (mzx_net_set_train_matrix included); of
+ *                                the rest, the split-K body for those the second rule of csrc/mzx_tuning.h picks (at least
+ *                                16 rows, 16 columns and four k-groups per weight-gradient chunk), the wave body otherwise
+ *     MZX_TRAIN_GEMM_KSPLIT_ALL  the split-K body for every GEMM, ragged, tiny and K < 64 included (tests)
+ *     MZX_ERR_INVALID as above.  mzx_net_set_train_gemm itself keeps its range: it refuses 3 and 4 as it always did.
+ *     mzx_net_set_train_matrix never affects a GEMM on the split-K body.
+ *   mzx_train_resnet_ksplit_launches(net, batch, steps): how many GEMM launches of a step take the split-K body under the
+ *     handle's mode; 0 in modes 0 - 2 and where the step is unsupported.  Under MZX_TRAIN_GEMM_KSPLIT
+ *     mzx_train_resnet_tiled_launches keeps counting the GEMMs of the tiled rule.
  * ------------------------------------------------------------------------- */
 #define MZX_TRAIN_GEMM_WAVE 0
 #define MZX_TRAIN_GEMM_TILED 1
 #define MZX_TRAIN_GEMM_TILED_ALL 2
+#define MZX_TRAIN_GEMM_KSPLIT 3
+#define MZX_TRAIN_GEMM_KSPLIT_ALL 4
 int mzx_net_set_train_gemm(mzx_net* net, int mode);
+int mzx_net_set_train_gemm_route(mzx_net* net, int mode);
 int mzx_net_train_gemm(const mzx_net* net);
 int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps);
+int64_t mzx_train_resnet_ksplit_launches(const mzx_net* net, int32_t batch, int32_t steps);
 
 /* ------------------------------------------------------------------------- *
  * The matrix arithmetic of the LDS-tiled route above, per handle and orthogonal to mzx_net_set_train_gemm: which

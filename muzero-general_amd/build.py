@@ -23,6 +23,7 @@ FLAGS = [
 FILE_FLAGS = {
     "mzx_train_gemm_tiled.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "mzx_train_gemm_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "mzx_train_gemm_ksplit.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

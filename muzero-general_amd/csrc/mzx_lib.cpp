@@ -27,6 +27,7 @@
 #ifdef MZX_HOSTCHECK
 #include "mzx_train_gemm_tiled.h"      // (the device build compiles the tiled GEMMs in mzx_train_gemm_tiled.hip)
 #include "mzx_train_gemm_split.h"      // (and their split-BF16 arithmetic in mzx_train_gemm_split.hip)
+#include "mzx_train_gemm_ksplit.h"     // (and the split-K GEMMs in mzx_train_gemm_ksplit.hip)
 #else
 #include "mzx_fused_fc.h"
 #include "mzx_fused_fc2.h"
@@ -1586,8 +1587,8 @@ int64_t mzx_train_resnet_scratch_bytes(const mzx_net* net, int32_t batch, int32_
 int64_t mzx_train_resnet_stat_floats(const mzx_net* net) { return net ? rtn_stat_floats(net) : 0; }
 
 // the dry run of a step: its launches (with the two of the loss head), or how many of its GEMMs take the LDS-tiled route,
-// or how many of those the split-BF16 body
-enum RtnCount { RTN_COUNT_LAUNCHES, RTN_COUNT_TILED, RTN_COUNT_SPLIT };
+// or how many of those the split-BF16 body, or how many take the split-K body
+enum RtnCount { RTN_COUNT_LAUNCHES, RTN_COUNT_TILED, RTN_COUNT_SPLIT, RTN_COUNT_KSPLIT };
 static int64_t rtn_dry_run(const mzx_net* net, int32_t batch, int32_t steps, RtnCount what) {
   return train_full_plan<RtnPlan>(rtn_plan, net, batch, steps, [&](const RtnPlan& plan) {
     RtnRun<false> run;      // (the launches of a step do not depend on its precision)
@@ -1595,7 +1596,7 @@ static int64_t rtn_dry_run(const mzx_net* net, int32_t batch, int32_t steps, Rtn
     run.P = &plan; run.dry = true; run.gemm_mode = net->train_gemm; run.matrix_mode = net->train_matrix;
     run.forward();
     run.backward();
-    return what == RTN_COUNT_TILED ? run.tiled : what == RTN_COUNT_SPLIT ? run.split : run.launched + 2;
+    return what == RTN_COUNT_TILED ? run.tiled : what == RTN_COUNT_SPLIT ? run.split : what == RTN_COUNT_KSPLIT ? run.ksplit : run.launched + 2;
   });
 }
 
@@ -1604,6 +1605,8 @@ int64_t mzx_train_resnet_launches(const mzx_net* net, int32_t batch, int32_t ste
 int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_TILED); }
 
 int64_t mzx_train_resnet_split_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_SPLIT); }
+
+int64_t mzx_train_resnet_ksplit_launches(const mzx_net* net, int32_t batch, int32_t steps) { return rtn_dry_run(net, batch, steps, RTN_COUNT_KSPLIT); }
 
 // forward pass, loss head, backward pass of a planned step
 extern "C++" template <bool WIDE>
@@ -1644,6 +1647,15 @@ int mzx_net_set_train_gemm(mzx_net* net, int mode) {
   if (!net) { set_error("mzx_net_set_train_gemm: null network handle"); return MZX_ERR_INVALID; }
   if (net->cfg.network != 1) { set_error("mzx_net_set_train_gemm: fully connected networks do not train through the residual GEMMs"); return MZX_ERR_INVALID; }
   if (mode < MZX_TRAIN_GEMM_WAVE || mode > MZX_TRAIN_GEMM_TILED_ALL) { set_error("mzx_net_set_train_gemm: unknown mode (0 wave, 1 tiled, 2 tiled_all)"); return MZX_ERR_INVALID; }
+  net->train_gemm = mode;
+  return MZX_OK;
+}
+
+// the same switch over its whole range: mzx_net_set_train_gemm keeps refusing what it always refused
+int mzx_net_set_train_gemm_route(mzx_net* net, int mode) {
+  if (!net) { set_error("mzx_net_set_train_gemm_route: null network handle"); return MZX_ERR_INVALID; }
+  if (net->cfg.network != 1) { set_error("mzx_net_set_train_gemm_route: fully connected networks do not train through the residual GEMMs"); return MZX_ERR_INVALID; }
+  if (mode < MZX_TRAIN_GEMM_WAVE || mode > MZX_TRAIN_GEMM_KSPLIT_ALL) { set_error("mzx_net_set_train_gemm_route: unknown mode (0 wave, 1 tiled, 2 tiled_all, 3 ksplit, 4 ksplit_all)"); return MZX_ERR_INVALID; }
   net->train_gemm = mode;
   return MZX_OK;
 }

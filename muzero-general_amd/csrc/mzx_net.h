@@ -72,7 +72,7 @@ struct mzx_net {
   int32_t rb_force = 0;    // 1: every program on the streamed engine (mzx_net_set_mode(3) / (4))
   int32_t rb_no_towers = 0;  // 1: the streamed engine runs layer by layer, no tower launches (mzx_net_set_mode(4): A/B)
   int32_t train_stem = 0;  // 1: mzx_train_resnet_* plan the downsample stem (mzx_net_set_train_stem); 0: they refuse it by name
-  int32_t train_gemm = 0;  // the GEMM body of mzx_train_resnet_*: 0 a wavefront per tile, 1 LDS-tiled where the rule of mzx_tuning.h picks it, 2 LDS-tiled always (mzx_net_set_train_gemm); the same bits
+  int32_t train_gemm = 0;  // the GEMM body of mzx_train_resnet_*: 0 a wavefront per tile, 1 LDS-tiled where the rule of mzx_tuning.h picks it, 2 LDS-tiled always (mzx_net_set_train_gemm); the same bits; 3 as 1 and split-K where its rule picks a GEMM that 1 leaves, 4 split-K always (mzx_net_set_train_gemm_route; other bits)
   int32_t train_matrix = 0;  // the matrix arithmetic of the LDS-tiled route: 0 binary32 MFMAs, 1 split-BF16 (mzx_net_set_train_matrix; mzx_train_gemm_split.h)
   mzx::RbPlan rb;          // streamed MFMA engine for residual networks the fused engine cannot hold (mzx_resnet_batched.h)
 };

@@ -42,6 +42,11 @@
 // The tiled route has a second arithmetic behind the handle's train_matrix switch (RtnSplitGemmBody<MODE, WIDE>,
 // mzx_train_gemm_split.h): every operand split once per workgroup into three BF16 terms, six v_mfma_f32_16x16x32_bf16 per
 // tile and 32 k.  Off by default; it is held to the reference gates, not to the wave body's bits.
+// The split-K variant (RtnKsplitGemmBody<MODE, WIDE>, mzx_train_gemm_ksplit.h; train_gemm modes 3 and 4 and the rule
+// train_gemm_ksplit of mzx_tuning.h) is for the GEMMs with too few tiles to fill the device: a workgroup per (chunk, 32 x 32
+// tile) whose four waves each own the whole tile and every fourth k-group of 16, the next group's operands requested before
+// this group's 16 MFMAs, the four partial tiles joined through LDS as (w0 + w1) + (w2 + w3).  Off by default; K is summed in
+// another order, so it too is held to the reference gates, not to the wave body's bits.
 //
 // One precision switch, bool WIDE: a template parameter of the step (RtnRun<WIDE>) and so of every GEMM and BatchNorm
 // kernel of it; true for a network with a downsample stem, false for every other.  WIDE = false: a GEMM keeps four binary32
@@ -248,6 +253,10 @@ int rtn_launch_tiled(int mode, bool wide, const RtnGemm& g, stream_t stream);
 // The split-BF16 arithmetic of the tiled route (mzx_train_gemm_split.h: RtnSplitGemmBody<mode, wide>, six BF16 MFMAs per 32 k
 // on operands split into three BF16 terms; held to the reference gates, not to the bits above), likewise.
 int rtn_launch_split(int mode, bool wide, const RtnGemm& g, stream_t stream);
+// The in-workgroup split-K body for GEMMs of few tiles and a long K (mzx_train_gemm_ksplit.h: RtnKsplitGemmBody<mode, wide>, a
+// workgroup per 32 x 32 tile, its four waves dividing K, joined through LDS in a fixed order; held to the reference gates),
+// likewise.
+int rtn_launch_ksplit(int mode, bool wide, const RtnGemm& g, stream_t stream);
 
 // a wavefront per (chunk, 16 x 16 tile).  WIDE = false: four binary32 accumulator chains over the whole of K, joined
 // (0 + 1) + (2 + 3): they hide the MFMA's dependent latency, and four short sums joined at the end round less than one long
@@ -906,6 +915,7 @@ struct RtnRun {
   int tiled = 0;               // how many did
   int matrix_mode = 0;         // the handle's train_matrix: 1 = the tiled route runs the split-BF16 body (mzx_train_gemm_split.h)
   int split = 0;               // how many GEMMs took it
+  int ksplit = 0;              // how many GEMMs took the split-K body (gemm_mode 3, 4: train_gemm_ksplit, mzx_train_gemm_ksplit.h)
 
   template <class F> void go(F f) {
     if (rc) return;
@@ -967,7 +977,7 @@ struct RtnRun {
   }
   template <int MODE>
   void launch_gemm(const RtnGemm& g) {
-    if (train_gemm_tiled(gemm_mode, g.M, g.N, g.nchunks)) {
+    if (train_gemm_tiled(gemm_mode == 3 ? 1 : gemm_mode, g.M, g.N, g.nchunks)) {      // (mode 3: the tiled rule first)
       ++tiled;
       if (matrix_mode == 1) {
         ++split;
@@ -975,6 +985,9 @@ struct RtnRun {
       } else {
         go([&] { return rtn_launch_tiled(MODE, WIDE, g, stream); });
       }
+    } else if (train_gemm_ksplit(gemm_mode, g.M, g.N, g.K, g.nchunks)) {
+      ++ksplit;
+      go([&] { return rtn_launch_ksplit(MODE, WIDE, g, stream); });
     } else {
       go([&] { return launch_waves<RTN_WAVES>(RtnGemmBody<MODE, WIDE>{g}, stream); });
     }

@@ -82,6 +82,23 @@ inline bool train_gemm_tiled(int mode, int64_t M, int64_t N, int64_t chunks) {
          ((M + 63) / 64) * ((N + 63) / 64) * chunks >= TRAIN_GEMM_TILED_MIN_WORKGROUPS;
 }
 
+// Which of the GEMMs the rule above leaves on the wave body take the in-workgroup split-K body (mzx_train_gemm_ksplit.h)
+// instead, under the handle's switch (3 this rule, 4 all, any other mode none).  The body cuts the dependent chain over K into
+// four, one per wave of a 32 x 32 workgroup tile, so a GEMM needs at least four k-groups of 16 per weight-gradient chunk --
+// below that a wave idles and the LDS join is pure overhead.  `chunks` chunks of RTN_KCHUNK = 512 positions: with more than
+// one, every chunk but the last is 512 long.  The rows and columns asked for started at one full 32 x 32 tile and were lowered
+// to one full MFMA tile each way by the first measurement (profiles/resnet_train_ksplit_bench_rule32.log): at 16
+// channels that rule picked 0 of 164 GEMMs at tic-tac-toe 64 x 21 and 0 of 159 at breakout 16 x 6, where sending EVERY GEMM to
+// the body took the step from 4.98 to 4.11 ms and from 9.96 to 8.85 ms (spreads below 0.06 ms): the body pays off with half of
+// its tile empty.  The heads' GEMMs of a few reduced channels stay on the wave body.
+constexpr int TRAIN_GEMM_KSPLIT_MIN_M = 16;
+constexpr int TRAIN_GEMM_KSPLIT_MIN_N = 16;
+constexpr int TRAIN_GEMM_KSPLIT_MIN_K = 64;
+inline bool train_gemm_ksplit(int mode, int64_t M, int64_t N, int64_t K, int64_t chunks) {
+  if (mode != 3) return mode == 4;
+  return M >= TRAIN_GEMM_KSPLIT_MIN_M && N >= TRAIN_GEMM_KSPLIT_MIN_N && (chunks > 1 || K >= TRAIN_GEMM_KSPLIT_MIN_K);
+}
+
 inline int tuning_find(const char* name) {
   if (!name) return -1;
   TuningEntry* t = tuning_table();

@@ -298,21 +298,26 @@ class HipNetwork:
     def train_stem(self, on):
         self.backend.lib.check(self.backend.lib.mzx_net_set_train_stem(self.handle, int(bool(on))))
 
-    TRAIN_GEMM_MODES = ("wave", "tiled", "tiled_all")
+    TRAIN_GEMM_MODES = ("wave", "tiled", "tiled_all")      # the range of mzx_net_set_train_gemm: the same bits on each
+    TRAIN_GEMM_ROUTES = TRAIN_GEMM_MODES + ("ksplit", "ksplit_all")      # the range of mzx_net_set_train_gemm_route
 
     @property
     def train_gemm(self):
-        """The GEMM body of ``mzx_train_resnet_step`` on this handle (``mzx_net_set_train_gemm``): ``"wave"`` (the default,
-        a wavefront per 16 x 16 tile), ``"tiled"`` (a workgroup per 64 x 64 tile with operands staged through LDS, for the
-        GEMMs the library's rule picks) or ``"tiled_all"`` (for every GEMM).  Every route returns the same bits;
-        ``config.train_gemm`` sets it at construction.  Setting it on a fully connected network raises."""
-        return self.TRAIN_GEMM_MODES[self.backend.lib.mzx_net_train_gemm(self.handle)]
+        """The GEMM body of ``mzx_train_resnet_step`` on this handle (``mzx_net_set_train_gemm_route``): ``"wave"`` (the
+        default, a wavefront per 16 x 16 tile), ``"tiled"`` (a workgroup per 64 x 64 tile with operands staged through LDS,
+        for the GEMMs the library's rule picks) or ``"tiled_all"`` (for every GEMM) -- these three return the same bits --
+        ``"ksplit"`` (as ``"tiled"``, and of the GEMMs that leaves, those a second rule picks on the split-K body: a
+        workgroup per 32 x 32 tile whose four waves divide K and join through LDS in a fixed order) or ``"ksplit_all"`` (the
+        split-K body for every GEMM).  The split-K body is deterministic and meets the accuracy gates of the other routes,
+        but does not return their bits.  ``config.train_gemm`` sets it at construction.  Setting it on a fully connected
+        network raises."""
+        return self.TRAIN_GEMM_ROUTES[self.backend.lib.mzx_net_train_gemm(self.handle)]
 
     @train_gemm.setter
     def train_gemm(self, mode):
-        if mode not in self.TRAIN_GEMM_MODES:
-            raise ValueError(f"train_gemm: {mode!r} is none of {self.TRAIN_GEMM_MODES}")
-        self.backend.lib.check(self.backend.lib.mzx_net_set_train_gemm(self.handle, self.TRAIN_GEMM_MODES.index(mode)))
+        if mode not in self.TRAIN_GEMM_ROUTES:
+            raise ValueError(f"train_gemm: {mode!r} is none of {self.TRAIN_GEMM_ROUTES}")
+        self.backend.lib.check(self.backend.lib.mzx_net_set_train_gemm_route(self.handle, self.TRAIN_GEMM_ROUTES.index(mode)))
 
     TRAIN_MATRIX_MODES = ("f32", "bf16x3")
 

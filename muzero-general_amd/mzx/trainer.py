@@ -33,7 +33,10 @@ the stem bypasses keep zero gradients, their statistics and their ``num_batches_
 ``config.train_gemm`` / ``HipNetwork.train_gemm`` (``"wave"``, ``"tiled"``, ``"tiled_all"``; ``mzx_net_set_train_gemm``) picks
 the body of the step's GEMMs -- a wavefront per 16 x 16 tile, or a workgroup per 64 x 64 tile with operands staged through
 LDS (csrc/mzx_train_gemm_tiled.h); ``train_step``, ``train_steps`` and the ``Trainer`` worker pick it up through the handle,
-and every result has the same bits on either route.
+and every result has the same bits on either route.  Two further values, ``"ksplit"`` and ``"ksplit_all"``
+(``mzx_net_set_train_gemm_route``), send the GEMMs of few tiles and a long K -- the per-step dynamics convolutions -- or every
+GEMM to a third body, a workgroup per 32 x 32 tile whose four waves divide K and join their partial tiles through LDS in a
+fixed order (csrc/mzx_train_gemm_ksplit.h): deterministic and within the same accuracy gates, but not the same bits.
 ``config.train_matrix`` / ``HipNetwork.train_matrix`` (``"f32"``, ``"bf16x3"``; ``mzx_net_set_train_matrix``) picks the matrix
 arithmetic of the GEMMs that take the tiled route, and is picked up through the handle in the same way: ``"bf16x3"`` splits
 every binary32 operand into three BF16 terms and multiplies on the BF16 matrix pipes (csrc/mzx_train_gemm_split.h).  That

@@ -15,6 +15,8 @@ One training step (Adam) of the shipped networks on the GPU, natively and throug
               train_gemm = "wave" (the yardstick) | "tiled" | "tiled_all"; --trace a|b|c runs one of them alone)
     python muzero-general_amd/tools/train_bench.py --family split [--out FILE] [--quick] [--shape NAME]   (the matrix arithmetic of the
               tiled route on one handle: 'wave' | 'tiled' + 'f32' (the yardstick) | 'tiled' + 'bf16x3'; --trace a|b|c likewise)
+    python muzero-general_amd/tools/train_bench.py --family ksplit [--out FILE] [--quick] [--shape NAME]  (the split-K body on one handle:
+              'wave' | 'tiled' (the better of the two is the yardstick) | 'ksplit' | 'ksplit_all'; --trace a|b|c|d likewise)
     python muzero-general_amd/tools/train_bench.py --family fc --trace a|b|c --trace-steps N   (under rocprofv3 --kernel-trace --stats)
     python muzero-general_amd/tools/train_bench.py --family fc --launches DIR_N1 N1 DIR_N2 N2  (kernel dispatches per step from two traces)
 
@@ -98,9 +100,25 @@ FAMILIES = {      # shapes: name -> (batch, steps) as shipped; warm-up calls, (b
                        "reference); split_worst: the largest fraction of that gate reached, split_worst_distance the bf16x3 step's distance "
                        "from the wave step on that key and torch_f32_distance_there that of torch's float32 step; split_launches: "
                        "mzx_train_resnet_split_launches; torch_ms (stem shapes): update_weights with the torch network"),
+    # the split-K body (mzx_net_set_train_gemm_route modes 3 and 4) on ONE handle, at four shapes of "tiled"
+    "ksplit": dict(adam=dict(lr=0.003, weight_decay=1e-4), blocks=7, quick=3, log="resnet_train_ksplit_bench.log",
+                   what="one training step (update_weights with a HipNetwork, Adam) per GEMM route of the SAME handle: wave_ms = "
+                        "train_gemm 'wave', tiled_ms = 'tiled', ksplit_ms = 'ksplit' (as 'tiled', and the split-K body of "
+                        "csrc/mzx_train_gemm_ksplit.h where the second rule of mzx_tuning.h picks a GEMM that leaves), ksplit_all_ms = "
+                        "'ksplit_all'; legs alternate block by block, medians of the timed blocks [min, max], every call ends in a "
+                        "synchronise; yardstick: the better of wave_ms and tiled_ms of the same run; ksplit_claim: a gain (or loss) "
+                        "against the yardstick counts only beyond the larger of the two legs' spreads; gemms: per leg the GEMM launches "
+                        "of a step on the wave / tiled / split-K body; gate_fraction: per split-K leg, before any weight moves and at "
+                        "the timed size, the largest fraction reached of the case module's gates with the wave step in the place of "
+                        "the binary64 reference (logits: LOGIT_GATE; gradient / statistic tensors: max(4 e, PARAM_GRAD_ERROR_FLOOR), "
+                        "e = the distance of torch's float32 step on the device from the wave step on that tensor), its key, the "
+                        "leg's distance from the wave step there and torch's float32 step's; the wave step's own fraction is 0 by "
+                        "construction"),
 }
 FAMILIES["split"]["shapes"] = FAMILIES["tiled"]["shapes"]
+FAMILIES["ksplit"]["shapes"] = {name: FAMILIES["tiled"]["shapes"][name] for name in ("tictactoe", "connect4", "breakout", "gomoku")}
 SPLIT_ROUTES = {"wave": ("wave", "f32"), "f32": ("tiled", "f32"), "bf16x3": ("tiled", "bf16x3")}
+KSPLIT_ROUTES = {route: (route, "f32") for route in ("wave", "tiled", "ksplit", "ksplit_all")}
 
 
 def shape_of(be, name, family="stem"):
@@ -331,6 +349,70 @@ def split_measure(be, name, quick):
     return line
 
 
+def ksplit_measure(be, name, quick):
+    import numpy
+
+    import resnet_train_cases
+
+    fam = FAMILIES["ksplit"]
+    fns, _, case, cases, net = tiled_legs(be, name, KSPLIT_ROUTES)
+    size = (case["B"], case["steps"])
+    line = dict(shape=f"{name}_b{size[0]}_k{size[1]}", optimizer="Adam", launches=int(be.lib.mzx_train_resnet_launches(net.handle, *size)))
+    net.train_gemm = "tiled_all"
+    gemms = int(be.lib.mzx_train_resnet_tiled_launches(net.handle, *size))
+    # before any weight moves, at the timed size: tiled = wave bit for bit; the split-K legs against wave within the module's gates
+    got, line["gemms"] = {}, {}
+    for route in KSPLIT_ROUTES:
+        net.train_gemm = route
+        got[route] = resnet_train_cases.run_native(be, case, net, cases)
+        tiled, ksplit = (int(count(net.handle, *size)) for count in (be.lib.mzx_train_resnet_tiled_launches, be.lib.mzx_train_resnet_ksplit_launches))
+        line["gemms"][route] = dict(wave=gemms - tiled - ksplit, tiled=tiled, ksplit=ksplit)
+    bits = lambda a: numpy.ascontiguousarray(a, numpy.float32).view(numpy.int32)
+    assert all(numpy.array_equal(bits(got["tiled"][key]), bits(value)) for key, value in got["wave"].items()), line
+    other = cases.torch_step(case, torch.float32, device=be.device)
+    distance = lambda a, b: float(numpy.max(numpy.abs(numpy.asarray(a, numpy.float64).reshape(-1) - numpy.asarray(b, numpy.float64).reshape(-1))))
+    line["gate_fraction"] = {}
+    for route in ("ksplit", "ksplit_all"):
+        worst = (0.0, None, 0.0, 0.0)
+        for key, value in got["wave"].items():
+            finite = numpy.isfinite(value)
+            if key.endswith("_logits"):
+                gate = cases.LOGIT_GATE
+            elif key[:5] in ("grad/", "stat/") and key in other:
+                gate = max(4 * distance(other[key], value), cases.PARAM_GRAD_ERROR_FLOOR)
+            else:
+                continue
+            d = distance(got[route][key][finite], value[finite])
+            if d / gate > worst[0]:
+                worst = (d / gate, key, d, distance(numpy.asarray(other[key])[finite], value[finite]) if key in other else None)
+        line["gate_fraction"][route] = dict(worst=round(worst[0], 4), key=worst[1], distance=worst[2], torch_f32_distance_there=worst[3])
+    del got, other
+    blocks, iters = fam["quick"] if quick else fam["blocks"], fam["shapes"][name][3]
+    times = {leg: [] for leg in fns}
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for leg, fn in fns.items():
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            times[leg].append((time.perf_counter() - t0) * 1e3 / iters)
+    line.update(blocks=blocks, steps_per_block=iters)
+    for leg, ts in times.items():
+        line[f"{leg}_ms"] = round(statistics.median(ts), 3)
+        line[f"{leg}_ms_min_max"] = [round(min(ts), 3), round(max(ts), 3)]
+    spread = lambda leg: max(times[leg]) - min(times[leg])
+    line["yardstick"] = "wave" if line["wave_ms"] <= line["tiled_ms"] else "tiled"
+    base = line[f"{line['yardstick']}_ms"]
+    for leg in ("ksplit", "ksplit_all"):
+        line[f"yardstick_over_{leg}"] = round(base / line[f"{leg}_ms"], 3)
+        beyond = abs(base - line[f"{leg}_ms"]) > max(spread(line["yardstick"]), spread(leg))
+        line[f"{leg}_claim"] = "no gain claimed" if not beyond else "faster" if line[f"{leg}_ms"] < base else "slower"
+    return line
+
+
 def chain_setup(be, name, native):
     """(config, network, Adam, buffer with a device sampler) of a shipped configuration: 48 games of 8 .. 40 positions."""
     import numpy
@@ -453,7 +535,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--shape", action="append")
-    ap.add_argument("--trace", choices=["a", "b", "c"])
+    ap.add_argument("--trace", choices=["a", "b", "c", "d"])
     ap.add_argument("--trace-steps", type=int, default=10)
     ap.add_argument("--launches", nargs=4, metavar=("DIR1", "N1", "DIR2", "N2"))
     args = ap.parse_args()
@@ -474,6 +556,8 @@ def main():
             fn = tiled_legs(be, names[0])[0][dict(a="wave", b="tiled", c="tiled_all")[args.trace]]
         elif args.family == "split":
             fn = tiled_legs(be, names[0], SPLIT_ROUTES)[0][dict(a="wave", b="f32", c="bf16x3")[args.trace]]
+        elif args.family == "ksplit":
+            fn = tiled_legs(be, names[0], KSPLIT_ROUTES)[0][dict(a="wave", b="tiled", c="ksplit", d="ksplit_all")[args.trace]]
         else:
             fn = legs(be, args.family, names[0])[0][args.trace]
         for _ in range(args.trace_steps):
@@ -493,8 +577,8 @@ def main():
                 log.write("\n".join(lines) + "\n")
         return
     for name in names:
-        if args.family in ("tiled", "split"):
-            line = (tiled_measure if args.family == "tiled" else split_measure)(be, name, args.quick)
+        if args.family in ("tiled", "split", "ksplit"):
+            line = dict(tiled=tiled_measure, split=split_measure, ksplit=ksplit_measure)[args.family](be, name, args.quick)
         else:
             line = measure(be, args.family, name, args.quick)
         lines.append(json.dumps(line))
