@@ -63,6 +63,9 @@ int mzx_is_device_build(void);
  *                  searches of a small network run side by side); 0 = all on the caller's stream (the A/B)
  *   wave_select    per-simulation launches, more than 16 actions: 1 = the selection walk by a wavefront per tree (lane l scores
  *                  child slots l, l + 64, ...), 0 = by a 16-lane row per tree (the A/B); the same walks either way
+ *   fcs_tm         streamed engine for fully connected networks (mzx_net_set_fc_engine): rows per workgroup -- the largest of
+ *                  16 | 32 | 64 that fits LDS and is not above the value (values below 16 count as 16); 0 = the largest that
+ *                  fits and leaves a workgroup per compute unit (256), else the smallest; the same bits either way
  * mzx_tuning_set / _get return MZX_ERR_INVALID for an unknown name or a value out of range; mzx_tuning_name /
  * _help enumerate the table (NULL past its end).
  * ------------------------------------------------------------------------- */
@@ -1042,6 +1045,47 @@ int mzx_net_set_train_gemm_route(mzx_net* net, int mode);
 int mzx_net_train_gemm(const mzx_net* net);
 int64_t mzx_train_resnet_tiled_launches(const mzx_net* net, int32_t batch, int32_t steps);
 int64_t mzx_train_resnet_ksplit_launches(const mzx_net* net, int32_t batch, int32_t steps);
+
+/* ------------------------------------------------------------------------- *
+ * The inference engine of a FULLY CONNECTED network outside the whole-search kernel, per handle, off by default.  A fully
+ * connected network runs its searches in fc2_search_kernel where that kernel's plan takes it (layers up to 64 wide, 16
+ * actions, a support of 64 values, 64 KiB of parameters); every other search of such a network, and every batched
+ * mzx_net_initial_inference / mzx_net_recurrent_inference, runs one element kernel per operator.
+ *   mzx_net_set_fc_engine(net, engine):
+ *     MZX_FC_ENGINE_OPS       the default: one kernel per operator
+ *     MZX_FC_ENGINE_STREAMED  a whole inference in ONE launch of csrc/mzx_fc_streamed.hip: a 256-thread workgroup per tile
+ *                             of 16 / 32 / 64 rows, activations resident in LDS, every Linear on v_mfma_f32_16x16x4_f32 with
+ *                             the weights streamed from L2 into registers.  Both inferences of the handle take it, with or
+ *                             without hidden-state indices; a search that fc2_search_kernel does not take runs the
+ *                             row-per-tree kernels around it (mzx_search_route reports route 2), fresh, continued and from
+ *                             given roots, and leaves the node store mzx_search_advance reads.  Searches that
+ *                             fc2_search_kernel takes keep it.  Deterministic, independent of the batch and of the tile
+ *                             size, but NOT the per-operator kernels' bits (K is summed in another order): its contract is
+ *                             their 1e-4 gate against a binary64 reference.
+ *     MZX_ERR_INVALID, with a text in mzx_last_error(), for a null handle, another value, and for MZX_FC_ENGINE_STREAMED on
+ *     a residual network, a layer wider than 1024, an observation of more than 4096 values, or activations beyond the
+ *     160 KiB of LDS at 16 rows.  The serial test build accepts the setter and keeps running the per-operator program.
+ *   mzx_net_fc_engine(net): the engine (0 for null).
+ * The tuning entry "fcs_tm" forces the tile size (tests); mzx_net_set_mode is independent of this switch.
+ * ------------------------------------------------------------------------- */
+#define MZX_FC_ENGINE_OPS 0
+#define MZX_FC_ENGINE_STREAMED 1
+int mzx_net_set_fc_engine(mzx_net* net, int engine);
+int mzx_net_fc_engine(const mzx_net* net);
+
+/* ------------------------------------------------------------------------- *
+ * recurrent_inference through a hidden-state NODE STORE, the form the searches use between their tree kernels: sample b reads
+ * node d_in_node[b] of d_hidden_nodes [batch][in_nodes][hidden] and writes its next state to node d_out_node[b] of
+ * d_next_hidden_nodes [batch][out_nodes][hidden]; no other node is touched.  The logits are dense, as in
+ * mzx_net_recurrent_inference, and every output has that call's bits on the gathered rows.  The two stores may be one
+ * buffer when no sample reads a node that another one writes.  Node numbers are not range-checked (device memory).  Only an
+ * MFMA engine takes indices: the fused or streamed engine of a residual network, or MZX_FC_ENGINE_STREAMED; otherwise, and
+ * in the serial test build, MZX_ERR_INVALID ("indexed inference needs an MFMA engine").
+ * ------------------------------------------------------------------------- */
+int mzx_net_recurrent_inference_indexed(mzx_net* net, const float* d_hidden_nodes, const int32_t* d_in_node, int32_t in_nodes,
+                                        const int32_t* d_action, int32_t batch, float* d_value_logits, float* d_reward_logits,
+                                        float* d_policy_logits, float* d_next_hidden_nodes, const int32_t* d_out_node,
+                                        int32_t out_nodes, float* d_workspace, int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * The matrix arithmetic of the LDS-tiled route above, per handle and orthogonal to mzx_net_set_train_gemm: which

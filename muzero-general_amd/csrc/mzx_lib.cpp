@@ -274,6 +274,22 @@ int mzx_net_set_mode(mzx_net* net, int32_t mode) {
   return MZX_OK;
 }
 
+int mzx_net_set_fc_engine(mzx_net* net, int engine) {
+  if (!net) { set_error("mzx_net_set_fc_engine: null network handle"); return MZX_ERR_INVALID; }
+  if (engine != MZX_FC_ENGINE_OPS && engine != MZX_FC_ENGINE_STREAMED) { set_error("mzx_net_set_fc_engine: unknown engine (0 ops, 1 streamed)"); return MZX_ERR_INVALID; }
+  FcsPlan P;
+  if (engine == MZX_FC_ENGINE_STREAMED) {
+    P = fcs_plan(net);
+    if (!P.ok) { set_error("mzx_net_set_fc_engine: %s", P.why); return MZX_ERR_INVALID; }
+    if (!fcs_choose_tm(P, false, 1, 16) || !fcs_choose_tm(P, true, 1, 16)) { set_error("mzx_net_set_fc_engine: activations beyond 160 KiB of LDS at 16 rows per workgroup"); return MZX_ERR_INVALID; }
+  }
+  net->fc_engine = engine;
+  net->fcs = P;      // (ok = 0 with the switch off)
+  return MZX_OK;
+}
+
+int mzx_net_fc_engine(const mzx_net* net) { return net ? net->fc_engine : 0; }
+
 int64_t mzx_net_flops(const mzx_net* net, int32_t recurrent) {
   if (!net) return 0;
   int64_t macs = 0;
@@ -329,9 +345,11 @@ int mzx_net_initial_inference(mzx_net* net, const float* d_observation, int32_t 
   NetBuffers nb;
   nb.in = d_observation; nb.action = nullptr; nb.hidden = d_hidden; nb.value = d_value_logits;
   nb.reward = nullptr; nb.policy = d_policy_logits; nb.workspace = d_workspace;
+  const bool fills_reward = fcs_enabled(net, false);      // (the streamed fully connected engine writes the constant row itself)
+  if (fills_reward) nb.reward = d_reward_logits;
   rc = run_network(net, false, nb, batch, (stream_t)stream);
   if (rc) return rc;
-  if (d_reward_logits) {
+  if (d_reward_logits && !fills_reward) {
     RewardFillOp f;
     f.y = d_reward_logits; f.batch = batch; f.full_support = net->full_support;
     MZX_TRY_LAUNCH(launch<256>(f, (stream_t)stream));
@@ -352,6 +370,26 @@ int mzx_net_recurrent_inference(mzx_net* net, const float* d_hidden, const int32
   nb.in = d_hidden; nb.action = d_action; nb.hidden = d_next_hidden; nb.value = d_value_logits;
   nb.reward = d_reward_logits; nb.policy = d_policy_logits; nb.workspace = d_workspace;
   return run_network(net, true, nb, batch, (stream_t)stream);
+}
+
+int mzx_net_recurrent_inference_indexed(mzx_net* net, const float* d_hidden_nodes, const int32_t* d_in_node, int32_t in_nodes,
+                                        const int32_t* d_action, int32_t batch, float* d_value_logits, float* d_reward_logits,
+                                        float* d_policy_logits, float* d_next_hidden_nodes, const int32_t* d_out_node,
+                                        int32_t out_nodes, float* d_workspace, int64_t workspace_floats, void* stream) {
+  int rc = check_net_call(net, batch, workspace_floats);
+  if (rc) return rc;
+  if (!d_hidden_nodes || !d_in_node || !d_out_node || !d_action || !d_value_logits || !d_reward_logits || !d_policy_logits ||
+      !d_next_hidden_nodes || in_nodes < 1 || out_nodes < 1) {
+    set_error("mzx_net_recurrent_inference_indexed: null buffer / node counts below 1");
+    return MZX_ERR_INVALID;
+  }
+  if (!rz_enabled(net, true) && !rb_enabled(net, true) && !fcs_enabled(net, true)) { set_error("indexed inference needs an MFMA engine"); return MZX_ERR_INVALID; }
+  NetBuffers nb;
+  nb.in = d_hidden_nodes; nb.action = d_action; nb.hidden = d_next_hidden_nodes; nb.value = d_value_logits;
+  nb.reward = d_reward_logits; nb.policy = d_policy_logits; nb.workspace = d_workspace;
+  NetIndex ix;
+  ix.in_node = d_in_node; ix.out_node = d_out_node; ix.in_nodes = in_nodes; ix.out_nodes = out_nodes;
+  return run_network(net, true, nb, batch, (stream_t)stream, &ix);
 }
 
 int mzx_net_debug_prefix(mzx_net* net, int32_t recurrent, int32_t fused, int32_t n_ops, const float* d_input,
@@ -468,6 +506,10 @@ const char* mzx_tuning_help(int32_t index) { return (index >= 0 && index < TUNE_
 static SearchChoice search_choice(const mzx_search* s, SearchStart::Kind kind) {
   SearchChoice c;
 #ifndef MZX_HOSTCHECK
+  // a fully connected network on its streamed engine (mzx_net_set_fc_engine) that fc2_search_kernel does not take: the
+  // row-per-tree kernels around it, for every kind of start and with or without spare capacity (the row route keeps the node
+  // store); wider action spaces than the row kernels take stay on the per-operator path
+  if (s->net && s->fused_ok != 1 && fcs_enabled(s->net, true) && row_search_supported(s->p)) { c.path = PATH_ROWS; c.fc_streamed = true; return c; }
   if (!s->net || !(s->mode & 1)) return c;
   const bool spare = s->max_nodes > 0;
   const bool from_roots = kind == SearchStart::OVERRIDE;
@@ -583,7 +625,7 @@ static int search_simulate(mzx_search* s, const mzx_search_io* io, void* d_arena
       break;
     case PATH_ROWS:
     case PATH_RT:
-      s->last_kernel = c.path == PATH_RT ? KERNEL_RT : KERNEL_ROWS;
+      s->last_kernel = c.path == PATH_RT ? KERNEL_RT : c.fc_streamed ? KERNEL_ROWS_FCS : KERNEL_ROWS;
       rc = search_run_rows(s, io, d_arena, stream, start, c.force_streamed, c.path == PATH_RT);
       break;
 #endif

@@ -51,6 +51,26 @@ struct OpDesc {
 
 struct LayerSpec { int32_t n; const int32_t* sizes; };
 
+// The plan of the streamed engine for fully connected networks (mzx_fc_streamed.h: fcs_plan fills it, the handle keeps it)
+struct FcsLayer {
+  int32_t w, b;            // flat offsets of weight [N][w_stride] and bias [N]
+  int32_t K, N, w_stride;  // K: columns multiplied (w_stride - A for the dynamics network's first layer)
+  int32_t elu, onehot, vec;  // vec: the weight rows allow 128-bit loads
+};
+struct FcsMlp {
+  int32_t n;
+  FcsLayer l[MZX_MAX_LAYERS + 1];
+};
+
+struct FcsPlan {
+  int ok = 0;
+  const char* why = "";    // what the plan refuses, by name
+  FcsMlp rep, dyn, rew, pol, val;
+  int32_t E = 0, A = 0, F = 0, in_size = 0;
+  int32_t width[2] = {0, 0};     // widest LDS-resident row of the initial / recurrent chain
+  int32_t ks_tiles[2] = {0, 0};  // most column tiles of a split-K layer of the chain
+};
+
 }  // namespace mzx
 
 struct mzx_net {
@@ -74,6 +94,8 @@ struct mzx_net {
   int32_t train_stem = 0;  // 1: mzx_train_resnet_* plan the downsample stem (mzx_net_set_train_stem); 0: they refuse it by name
   int32_t train_gemm = 0;  // the GEMM body of mzx_train_resnet_*: 0 a wavefront per tile, 1 LDS-tiled where the rule of mzx_tuning.h picks it, 2 LDS-tiled always (mzx_net_set_train_gemm); the same bits; 3 as 1 and split-K where its rule picks a GEMM that 1 leaves, 4 split-K always (mzx_net_set_train_gemm_route; other bits)
   int32_t train_matrix = 0;  // the matrix arithmetic of the LDS-tiled route: 0 binary32 MFMAs, 1 split-BF16 (mzx_net_set_train_matrix; mzx_train_gemm_split.h)
+  int32_t fc_engine = 0;   // fully connected networks: 0 one kernel per operator outside the whole-search kernel, 1 the streamed MFMA engine (mzx_net_set_fc_engine; mzx_fc_streamed.h)
+  mzx::FcsPlan fcs;        // its plan, kept while the switch is on (ok = 0 otherwise)
   mzx::RbPlan rb;          // streamed MFMA engine for residual networks the fused engine cannot hold (mzx_resnet_batched.h)
 };
 

@@ -51,6 +51,7 @@
 #include "mzx_net.h"
 #include "mzx_pack.h"
 #include "mzx_resnet_batched.h"
+#include "mzx_fc_streamed.h"
 
 namespace mzx {
 
@@ -1591,6 +1592,7 @@ inline int run_network(const mzx_net* net, bool recurrent, const NetBuffers& nb,
     return rz_launch(net, R, in, nb, batch, ix, stream);
   }
   if (rb_enabled(net, recurrent)) return rb_run_program(net, recurrent, nb, batch, stream, ix);
+  if (fcs_enabled(net, recurrent)) return fcs_run(net, recurrent, nb, batch, stream, ix);
 #endif
   if (ix && (ix->in_nodes != 1 || ix->out_nodes != 1)) { set_error("indexed inference needs an MFMA engine"); return MZX_ERR_INVALID; }
   return run_program(net, prog, nb, batch, stream);

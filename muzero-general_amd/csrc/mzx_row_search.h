@@ -337,7 +337,7 @@ inline int search_run_rows(mzx_search* s, const mzx_search_io* io, void* d_arena
         return rb_run_program(n, recurrent, b, batch, st, ixp);
       };
   int rc = search_prepare_roots(s, io, d_arena, stream, start, run_network,
-                                force_streamed || rz_enabled(net, false) || rb_enabled(net, false));
+                                force_streamed || rz_enabled(net, false) || rb_enabled(net, false) || fcs_enabled(net, false));
   if (rc) return rc;
   // ---- the simulations, all of them in one launch (rt_search_kernel, mzx_tower_search.inc) ...
   if (whole_search) {

@@ -168,6 +168,7 @@ enum SearchPath { PATH_GENERIC = 0, PATH_RZ, PATH_ROWS, PATH_RT, PATH_FC2, PATH_
 struct SearchChoice {
   int path = PATH_GENERIC;
   bool force_streamed = false;   // a network the LDS-resident engine would run: the streamed engine for this search
+  bool fc_streamed = false;      // PATH_ROWS around the streamed engine of a fully connected network (mzx_fc_streamed.h)
 };
 #define MZX_STREAMED_BETWEEN "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between "
 constexpr const char* KERNEL_GENERIC = "one kernel per step of a simulation (select / network / expand + back-propagate)";
@@ -176,6 +177,7 @@ constexpr const char* KERNEL_GENERIC_STREAMED = MZX_STREAMED_BETWEEN "one-thread
 constexpr const char* KERNEL_ROWS = MZX_ROW_KERNELS;
 constexpr const char* KERNEL_ROWS_SPLIT = MZX_ROW_KERNELS ", two half-shards on two streams";
 #undef MZX_ROW_KERNELS
+constexpr const char* KERNEL_ROWS_FCS = "mzx::fcs_recurrent_kernel (streamed FP32-MFMA fully connected network, one launch per inference) between mzx::row_select_kernel / mzx::row_expand_backprop_kernel";
 #undef MZX_STREAMED_BETWEEN
 constexpr const char* KERNEL_RT = "mzx::rt_search_kernel";
 constexpr const char* KERNEL_FC2 = "mzx::fc2_search_kernel";
@@ -230,7 +232,8 @@ inline int search_run_generic(mzx_search* s, const mzx_search_io* io, void* d_ar
   const int B = s->p.num_trees;
   // With the fused network engine the per-node hidden states are read from / written to the arena
   // store [B][N][Hf] directly (NetIndex); the per-operator engine goes through dense staging copies.
-  const bool ix_init = rz_enabled(net, false) || rb_enabled(net, false), ix_rec = rz_enabled(net, true) || rb_enabled(net, true);
+  const bool ix_init = rz_enabled(net, false) || rb_enabled(net, false) || fcs_enabled(net, false);
+  const bool ix_rec = rz_enabled(net, true) || rb_enabled(net, true) || fcs_enabled(net, true);
   int rc = search_prepare_roots(s, io, d_arena, stream, start, &run_network, ix_init);
   if (rc) return rc;
 

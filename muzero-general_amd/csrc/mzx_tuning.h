@@ -31,6 +31,7 @@ enum TuningKey {
   TUNE_RT_SHORT,              // 1: a last row group of MT - 1 row tiles runs the short K loop (0: every wave multiplies MT tiles, A/B)
   TUNE_ROUNDS_STREAMS,        // mzx_selfplay_rounds: 1 = every slot group behind the first searches on a stream of its own (0: one stream, A/B)
   TUNE_WAVE_SELECT,           // per-simulation launches, wide child records: 1 = a wavefront per tree walks (wave_select_kernel), 0 = a 16-lane row (row_select_kernel<0>, A/B); same walks
+  TUNE_FCS_TM,                // streamed engine for fully connected networks: rows per workgroup, 16 / 32 / 64 (0: the rule fcs_choose_tm)
   TUNE_COUNT
 };
 
@@ -49,6 +50,7 @@ inline TuningEntry* tuning_table() {
       {"rt_short", 1, 1, 0, 1, "tower whole-search kernel: waves of a row group one tile short skip that tile's products (0 = multiply it, A/B)"},
       {"rounds_streams", 1, 1, 0, 1, "mzx_selfplay_rounds: slot groups behind the first search on streams of their own (0 = the caller's stream for all)"},
       {"wave_select", 1, 1, 0, 1, "per-simulation launches, more than 16 actions: the selection walk by a wavefront per tree (0 = a 16-lane row per tree, A/B; same walks)"},
+      {"fcs_tm", 0, 0, 0, 64, "streamed engine for fully connected networks: rows per workgroup, the largest of 16 / 32 / 64 that fits LDS and is not above the value, values below 16 count as 16 (0 = the largest that fits and leaves a workgroup per compute unit; same bits)"},
   };
   return t;
 }
@@ -97,6 +99,24 @@ constexpr int TRAIN_GEMM_KSPLIT_MIN_K = 64;
 inline bool train_gemm_ksplit(int mode, int64_t M, int64_t N, int64_t K, int64_t chunks) {
   if (mode != 3) return mode == 4;
   return M >= TRAIN_GEMM_KSPLIT_MIN_M && N >= TRAIN_GEMM_KSPLIT_MIN_N && (chunks > 1 || K >= TRAIN_GEMM_KSPLIT_MIN_K);
+}
+
+// Rows per workgroup (TM = 16, 32 or 64) of the streamed engine for fully connected networks (mzx_fc_streamed.h).  fits[i]: the
+// LDS plan of TM = 16 << i fits.  The largest TM that fits and still gives every compute unit a workgroup -- 256 of them, the
+// MI355X's count, a constant as TRAIN_GEMM_TILED_MIN_WORKGROUPS above -- else the smallest that fits: below 256 workgroups
+// more, smaller tiles spread better.  forced (the tuning entry "fcs_tm", tests): the largest TM that fits and is not above
+// it; a value below 16 counts as 16.  A row's bits do not depend on TM, so this is a pure tuning decision.  0: nothing fits.
+constexpr int FCS_MIN_WORKGROUPS = 256;
+inline int fcs_tm_rule(int batch, int forced, const bool fits[3]) {
+  if (forced > 0 && forced < 16) forced = 16;
+  int smallest = 0;
+  for (int i = 2; i >= 0; --i) {
+    const int TM = 16 << i;
+    if (!fits[i] || (forced > 0 && TM > forced)) continue;
+    if (forced > 0 || (batch + TM - 1) / TM >= FCS_MIN_WORKGROUPS) return TM;
+    smallest = TM;
+  }
+  return smallest;
 }
 
 inline int tuning_find(const char* name) {

@@ -343,6 +343,10 @@ PROTOTYPES = {
     "mzx_train_resnet_tiled_launches": (c_i64, [c_vp, c_i32, c_i32]),
     "mzx_net_set_train_gemm_route": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mzx_train_resnet_ksplit_launches": (c_i64, [c_vp, c_i32, c_i32]),
+    "mzx_net_set_fc_engine": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "mzx_net_fc_engine": (ctypes.c_int, [c_vp]),
+    "mzx_net_recurrent_inference_indexed": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                           c_vp, c_i64, c_vp]),
     "mzx_net_set_train_matrix": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mzx_net_train_matrix": (ctypes.c_int, [c_vp]),
     "mzx_train_resnet_split_launches": (c_i64, [c_vp, c_i32, c_i32]),

@@ -245,6 +245,8 @@ class HipNetwork:
             self.train_gemm = config.train_gemm
         if config.network == "resnet" and getattr(config, "train_matrix", "f32") != "f32":
             self.train_matrix = config.train_matrix
+        if getattr(config, "fc_engine", "ops") != "ops":
+            self.fc_engine = config.fc_engine
         self.set_weights(self._initial_weights())
 
     def __del__(self):
@@ -335,6 +337,25 @@ class HipNetwork:
         if mode not in self.TRAIN_MATRIX_MODES:
             raise ValueError(f"train_matrix: {mode!r} is none of {self.TRAIN_MATRIX_MODES}")
         self.backend.lib.check(self.backend.lib.mzx_net_set_train_matrix(self.handle, self.TRAIN_MATRIX_MODES.index(mode)))
+
+    FC_ENGINES = ("ops", "streamed")
+
+    @property
+    def fc_engine(self):
+        """The inference engine of a fully connected network outside the whole-search kernel (``mzx_net_set_fc_engine``):
+        ``"ops"`` (the default, one kernel per operator) or ``"streamed"`` (a whole inference in one launch of
+        ``csrc/mzx_fc_streamed.hip``: activations in LDS, every Linear on FP32 matrix instructions).  With ``"streamed"`` both
+        inferences of this handle, and every search the whole-search kernel does not take (``BatchedMCTS``, ``SelfPlay``,
+        Reanalyse, the replay sweeps), run on it; within the 1e-4 gate of the per-operator kernels, other bits.
+        ``config.fc_engine`` sets it at construction.  ``"streamed"`` raises on a residual network, a layer wider than 1024
+        or an observation of more than 4096 values."""
+        return self.FC_ENGINES[self.backend.lib.mzx_net_fc_engine(self.handle)]
+
+    @fc_engine.setter
+    def fc_engine(self, engine):
+        if engine not in self.FC_ENGINES:
+            raise ValueError(f"fc_engine: {engine!r} is none of {self.FC_ENGINES}")
+        self.backend.lib.check(self.backend.lib.mzx_net_set_fc_engine(self.handle, self.FC_ENGINES.index(engine)))
 
     def state_dict(self):
         out = collections.OrderedDict()
@@ -505,3 +526,25 @@ class HipNetwork:
         lib.check(lib.mzx_net_recurrent_inference(self.handle, b.ptr(state), b.ptr(act), n, b.ptr(value), b.ptr(reward),
                                                   b.ptr(policy), b.ptr(hidden), b.ptr(ws), ws.numel(), b.stream()))
         return value, reward, policy, hidden
+
+    def recurrent_inference_indexed(self, nodes, in_node, action, out_nodes, out_node):
+        """``recurrent_inference`` through hidden-state node stores (``mzx_net_recurrent_inference_indexed``, what the searches
+        run between their tree kernels): sample b reads ``nodes[b, in_node[b]]`` and its next state is written to node
+        ``out_node[b]`` of ``out_nodes`` [batch, nodes, hidden...], in place; no other node is touched.  Returns the dense
+        value, reward and policy logits.  Needs an MFMA engine (``fc_engine = "streamed"`` for a fully connected network)."""
+        b, lib = self.backend, self.backend.lib
+        n = nodes.shape[0]
+        if nodes.dtype != torch.float32 or out_nodes.dtype != torch.float32 or not (nodes.is_contiguous() and out_nodes.is_contiguous()) \
+                or out_nodes.shape[0] != n or nodes[0, 0].numel() != self.hidden_size or out_nodes[0, 0].numel() != self.hidden_size:
+            raise ValueError("node stores are contiguous float32 [batch, nodes, hidden] tensors of one batch")
+        idx = [t.to(b.device).reshape(-1).to(torch.int32).contiguous() for t in (in_node, out_node, action)]
+        if any(t.numel() != n for t in idx):
+            raise ValueError("one node pair and one action per sample")
+        value = b.empty((n, self.full_support_size), torch.float32)
+        reward = b.empty((n, self.full_support_size), torch.float32)
+        policy = b.empty((n, self.action_space_size), torch.float32)
+        ws = self._ws(n)
+        lib.check(lib.mzx_net_recurrent_inference_indexed(self.handle, b.ptr(nodes), b.ptr(idx[0]), nodes.shape[1], b.ptr(idx[2]), n,
+                                                          b.ptr(value), b.ptr(reward), b.ptr(policy), b.ptr(out_nodes),
+                                                          b.ptr(idx[1]), out_nodes.shape[1], b.ptr(ws), ws.numel(), b.stream()))
+        return value, reward, policy
