@@ -1058,7 +1058,11 @@ int64_t mzx_train_resnet_ksplit_launches(const mzx_net* net, int32_t batch, int3
  *                             the weights streamed from L2 into registers.  Both inferences of the handle take it, with or
  *                             without hidden-state indices; a search that fc2_search_kernel does not take runs the
  *                             row-per-tree kernels around it (mzx_search_route reports route 2), fresh, continued and from
- *                             given roots, and leaves the node store mzx_search_advance reads.  Searches that
+ *                             given roots, and leaves the node store mzx_search_advance reads.  Bit 0 of the search mode
+ *                             stands for that route: a search handle created while the engine is on has it set by
+ *                             default, and search mode 0 (mzx_search_set_mode) keeps the one-thread-per-tree kernels,
+ *                             with the network still on the engine (route 0); a handle created before the switch was
+ *                             turned on stays in mode 0 until mzx_search_set_mode(s, 1).  Searches that
  *                             fc2_search_kernel takes keep it.  Deterministic, independent of the batch and of the tile
  *                             size, but NOT the per-operator kernels' bits (K is summed in another order): its contract is
  *                             their 1e-4 gate against a binary64 reference.

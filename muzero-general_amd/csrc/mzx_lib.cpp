@@ -410,6 +410,18 @@ int mzx_net_debug_prefix(mzx_net* net, int32_t recurrent, int32_t fused, int32_t
 
 // ----------------------------------------------------------------- search
 
+// The row route around the streamed engine of a fully connected network (the first rule of search_choice).  Such a handle
+// has no whole-search kernel (fused_ok 0), so bit 0 of its mode stands for this route alone: set by default where the engine
+// is on when the handle is created, and accepted by mzx_search_set_mode while it is on.
+static bool fcs_row_route(const mzx_search* s) {
+#ifndef MZX_HOSTCHECK
+  return s->net && s->fused_ok != 1 && fcs_enabled(s->net, true) && row_search_supported(s->p);
+#else
+  (void)s;
+  return false;
+#endif
+}
+
 int mzx_search_create(const mzx_search_config* cfg, mzx_net* net, mzx_search** out) {
   if (!cfg || !out) { set_error("mzx_search_create: null argument"); return MZX_ERR_INVALID; }
   if (cfg->num_trees < 1 || cfg->num_simulations < 0 || cfg->action_space_size < 1) {
@@ -442,7 +454,7 @@ int mzx_search_create(const mzx_search_config* cfg, mzx_net* net, mzx_search** o
   // network that runs layer by layer on the streamed MFMA engine
   s->fused_ok = fc2_plan(s).ok ? 1 : (rz_search_supported(s) ? 2 : ((net && net->rb.ok && net->rb.recurrent.ok && row_search_supported(s->p)) ? 3 : 0));
 #endif
-  s->mode = s->fused_ok ? 1 : 0;
+  s->mode = (s->fused_ok || fcs_row_route(s)) ? 1 : 0;
   *out = s;
   return MZX_OK;
 }
@@ -506,11 +518,12 @@ const char* mzx_tuning_help(int32_t index) { return (index >= 0 && index < TUNE_
 static SearchChoice search_choice(const mzx_search* s, SearchStart::Kind kind) {
   SearchChoice c;
 #ifndef MZX_HOSTCHECK
+  if (!s->net || !(s->mode & 1)) return c;
   // a fully connected network on its streamed engine (mzx_net_set_fc_engine) that fc2_search_kernel does not take: the
   // row-per-tree kernels around it, for every kind of start and with or without spare capacity (the row route keeps the node
-  // store); wider action spaces than the row kernels take stay on the per-operator path
-  if (s->net && s->fused_ok != 1 && fcs_enabled(s->net, true) && row_search_supported(s->p)) { c.path = PATH_ROWS; c.fc_streamed = true; return c; }
-  if (!s->net || !(s->mode & 1)) return c;
+  // store); wider action spaces than the row kernels take stay on the per-operator path.  As every rule below, only with
+  // bit 0 of the mode: mode 0 keeps the one-thread-per-tree kernels, whose network calls still go to the engine
+  if (fcs_row_route(s)) { c.path = PATH_ROWS; c.fc_streamed = true; return c; }
   const bool spare = s->max_nodes > 0;
   const bool from_roots = kind == SearchStart::OVERRIDE;
   if (s->fused_ok == 1 && !spare) {
@@ -572,7 +585,7 @@ int mzx_net_search_route(const mzx_net* net, int32_t num_trees, int32_t num_simu
 #ifndef MZX_HOSTCHECK
   tmp.fused_ok = fc2_plan(&tmp).ok ? 1 : (rz_search_supported(&tmp) ? 2 : ((net->rb.ok && net->rb.recurrent.ok && row_search_supported(tmp.p)) ? 3 : 0));
 #endif
-  tmp.mode = tmp.fused_ok ? 1 : 0;
+  tmp.mode = (tmp.fused_ok || fcs_row_route(&tmp)) ? 1 : 0;
   search_route_of(&tmp, out);
   return MZX_OK;
 }
@@ -585,7 +598,7 @@ int mzx_search_set_mode(mzx_search* s, int32_t mode) {
 #else
   if (mode & 16) { set_error("flag 16 (the first-generation fully connected kernel) needs an instrumented build (-DMZX_EXPERIMENT)"); return MZX_ERR_INVALID; }
 #endif
-  if ((mode & 1) && !s->fused_ok) { set_error("fused search kernel does not support this configuration"); return MZX_ERR_INVALID; }
+  if ((mode & 1) && !s->fused_ok && !fcs_row_route(s)) { set_error("fused search kernel does not support this configuration"); return MZX_ERR_INVALID; }
   s->mode = mode;
   return MZX_OK;
 }

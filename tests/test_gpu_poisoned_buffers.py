@@ -73,6 +73,11 @@ def _networks():
     nets.update({"parity-" + k: v for k, v in RESNET_CASES.items()})
     nets.update({"streamed-" + k: STREAMED_CASES[k][0] for k in ("tictactoe", "connect4", "breakout", "breakout_cnn", "cnn_small",
                                                                   "odd", "wide144")})
+    # fully connected networks on mzx_net_set_fc_engine's streamed engine (the config carries the switch): ragged column
+    # tiles and k on both routes, E = 24, A = 18 / F = 601 output columns straight to the tensors
+    from test_gpu_fc_streamed import SHAPES
+    nets.update({"fc-streamed-" + k: (lambda k=k: configs.cartpole(**SHAPES[k][0], fc_engine="streamed"))
+                 for k in ("w72-ragged", "support300")})
     return nets
 
 

@@ -9,7 +9,8 @@ cell, and this table is what says where.
 EXPECTED was recorded by running observe() of this file against the library built from commit 91618a8 ("Run continued searches
 in fc2_search_kernel and rt_search_kernel"), the last one whose mzx_search_run_from_roots chose its route with a chain of its
 own -- not from the code under test; every cell of it passes against that library too.  Mode flag 16 (the first-generation fully connected kernel) exists in instrumented builds
-only and is not part of the table.  Toy sizes: 4 trees x 3 simulations, synthetic weights.
+only and is not part of the table.  The rows of "fc-streamed" (a fully connected network on mzx_net_set_fc_engine's streamed
+engine, newer than that commit) are not recorded at all: they restate include/mzx.h, see the comment in EXPECTED.  Toy sizes: 4 trees x 3 simulations, synthetic weights.
 """
 import numpy
 import pytest
@@ -27,6 +28,8 @@ PER_OP = "one kernel per step of a simulation (select / network / expand + back-
 _STREAMED = "mzx::rb_tower_kernel / mzx::rb_gemm_kernel / mzx::rb_gemm_multi_kernel (streamed FP32-MFMA trunks, layers, head MLP levels) between "
 ROWS = _STREAMED + "mzx::row_select_kernel / mzx::row_expand_backprop_kernel"
 PER_OP_STREAMED = _STREAMED + "one-thread-per-tree kernels"
+ROWS_FCS = ("mzx::fcs_recurrent_kernel (streamed FP32-MFMA fully connected network, one launch per inference) between "
+            "mzx::row_select_kernel / mzx::row_expand_backprop_kernel")
 
 
 def _tile_3x6():
@@ -35,10 +38,18 @@ def _tile_3x6():
                              resnet_fc_reward_layers=[16], resnet_fc_value_layers=[16], resnet_fc_policy_layers=[16])
 
 
+def _fc_streamed():
+    width = dict.fromkeys(("fc_representation_layers", "fc_dynamics_layers", "fc_reward_layers", "fc_value_layers",
+                           "fc_policy_layers"), [128])
+    return configs.cartpole(**width, action_space=list(range(18)), fc_engine="streamed")
+
+
 # network class: (configuration, tuning entries moved for the whole cell, network mode: None = the default engine)
 CLASSES = {
     "fc-small": (configs.cartpole, {}, None),             # fully connected, SmallNet (register-resident weights)
     "fc-lds": (configs.lunarlander, {}, None),            # fully connected, LdsNet
+    # fully connected, outside fc2_search_kernel's plan (128 wide, 18 actions), on its streamed engine: the config carries the switch
+    "fc-streamed": (_fc_streamed, {}, None),
     "res-wave": (configs.tictactoe, {}, None),            # narrow residual network, a wave per tree
     "res-tile": (_tile_3x6, {}, None),                    # narrow residual network, a row tile per wave
     "tower": (configs.connect4, {}, None),                # connect4 class: the tower arithmetic at every shard size
@@ -66,6 +77,15 @@ EXPECTED = {
     ("fc-lds", 0, "none"): (PER_OP, PER_OP),
     ("fc-lds", 0, "spare"): (PER_OP, PER_OP, PER_OP, "accepted"),
     ("fc-lds", 0, "beyond-fc2"): (PER_OP, PER_OP, PER_OP, "accepted"),
+    # fc-streamed: not recorded but stated.  Default mode, from include/mzx.h (MZX_FC_ENGINE_STREAMED): "the row-per-tree
+    # kernels around it ..., fresh, continued and from given roots, and leaves the node store mzx_search_advance reads", at
+    # every capacity.  Mode 0, the rule of every other class: the one-thread-per-tree kernels, the network engine as set.
+    ("fc-streamed", None, "none"): (ROWS_FCS, ROWS_FCS),
+    ("fc-streamed", None, "spare"): (ROWS_FCS, ROWS_FCS, ROWS_FCS, "accepted"),
+    ("fc-streamed", None, "beyond-fc2"): (ROWS_FCS, ROWS_FCS, ROWS_FCS, "accepted"),
+    ("fc-streamed", 0, "none"): (PER_OP, PER_OP),
+    ("fc-streamed", 0, "spare"): (PER_OP, PER_OP, PER_OP, "accepted"),
+    ("fc-streamed", 0, "beyond-fc2"): (PER_OP, PER_OP, PER_OP, "accepted"),
     ("res-wave", None, "none"): (WAVE, WAVE),
     ("res-wave", None, "spare"): (PER_OP, PER_OP, PER_OP, "accepted"),
     ("res-wave", 0, "none"): (PER_OP, PER_OP),
